@@ -90,7 +90,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-size", type=int, default=128)
     ap.add_argument("--cpu-sample-iterations", type=int, default=24)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of voxels when the arrays exceed 64 MB in all; see dump_outputs())")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.size is None:
         args.size = 512 if args.workload in ("multiframe", "hier2d") else 256
     # a step of a few milliseconds: 20 of them are over before the card's clocks have settled (20 timed steps 1.74-1.75 ms
@@ -163,6 +168,42 @@ def timed_steps(step, args, fence, max_over_ranks=None):
     return total, elapsed
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: every file of one run together, .npy headers included
+
+
+def dump_outputs(directory, grid, arrays, rank=0, world=1, seed=0):
+    """--dump-outputs: what the timed path's last step returned, as DIR/<name>.npy in float32 (float64 stays float64), so
+    that two builds can be compared output for output on identical inputs.  `arrays` maps names to tensors shaped `grid`
+    or `grid` + (components,).  Whole arrays while they fit in DUMP_BYTES; otherwise the same seeded sample of voxels from
+    every array, shaped (samples,) or (samples, components), and the samples' flat C-order indices into `grid` as
+    sample_voxel_index.npy (float64, ascending) -- the sample depends on `grid` and `seed` alone.  N > 1: every rank
+    writes its own part as <name>_rank<r>.npy, within DUMP_BYTES / N."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    grid = tuple(int(g) for g in grid)
+    voxels = int(np.prod(grid))
+    flat, shapes = {}, {}
+    for name, a in arrays.items():
+        a = torch.as_tensor(a).detach()
+        assert tuple(a.shape[:len(grid)]) == grid, (name, tuple(a.shape), grid)
+        flat[name] = a.reshape(voxels, -1)
+        shapes[name] = tuple(a.shape)
+    item = {name: 8 if a.dtype == torch.float64 else 4 for name, a in flat.items()}
+    per_voxel = sum(a.shape[1] * item[name] for name, a in flat.items())
+    budget = DUMP_BYTES // world - 4096 * (len(flat) + 1)  # room for the .npy headers
+    if voxels * per_voxel > budget:
+        samples = budget // (per_voxel + 8)
+        index = np.sort(np.random.default_rng(seed).choice(voxels, samples, replace=False))
+        np.save(os.path.join(directory, "sample_voxel_index%s.npy" % suffix), index.astype(np.float64))
+        index = torch.from_numpy(index)
+        for name, a in flat.items():
+            flat[name] = a[index.to(a.device)]
+            shapes[name] = (samples,) + shapes[name][len(grid):]
+    for name, a in flat.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"),
+                a.cpu().numpy().astype(np.float64 if item[name] == 8 else np.float32).reshape(shapes[name]))
+
+
 def hier_finest_level_kernels(n, full, taps, device, reps=20):
     """HIP events around the launches ONE finest-level iteration of the hierarchical optimizer makes, on buffers of the
     level's size (the engine's own launches carry the same kernels plus the record bookkeeping): hier_iteration_kernel
@@ -221,6 +262,7 @@ def extra_workload(args, device, world, rank, dist):
     k7 = lsf.generate_1d_sobolev_kernel(7, 0.1)
     extra = {}
     comm = None
+    last = {}  # what the latest step returned (--dump-outputs)
 
     def fence():
         torch.cuda.synchronize()
@@ -244,7 +286,7 @@ def extra_workload(args, device, world, rank, dist):
         per_pair = iters * sum((n >> k) ** 2 for k in range(3))
 
         def step():
-            opt.optimize(canonical, live0)
+            last["warp_field"] = opt.optimize(canonical, live0)
             return per_pair, per_pair
         b_alg = 48
         name = "2D %d^2 HierarchicalOptimizer2d, 3 levels (maximum_chunk_size 4), Tikhonov (tikhonov_strength 0.05), %d " \
@@ -298,7 +340,7 @@ def extra_workload(args, device, world, rank, dist):
 
             def step():
                 for k in range(args.frames - 1):  # live_frame_index = canonical_frame_index + 1
-                    opt.optimize(frames[k], frames[k + 1])
+                    last["warp_field_pair%d" % k] = opt.optimize(frames[k], frames[k + 1])
                 done = (args.frames - 1) * per_pair
                 return (done // world, done // world) if slab else (done, done)
             name = "3D %d^3 multi-frame sequence, %d frames (%d pairs per step), HierarchicalOptimizer3d: 4 levels, " \
@@ -311,13 +353,18 @@ def extra_workload(args, device, world, rank, dist):
             canonical, live0 = sphere_pair(n, 3, device)
 
             def step():
-                opt.optimize(canonical, live0)
+                last["warp_field"] = opt.optimize(canonical, live0)
                 return per_pair, per_pair
             name = "3D %d^3 HierarchicalOptimizer3d, 4 levels, Tikhonov (tikhonov_strength 0.05)%s, %d iterations per " \
                    "level" % (n, " + 7-tap kernel" if full else "", iters)
         b_alg = 104 if full else 68
         note = "whole-step rate x B_alg (%d B/voxel-update), all kernels of the iteration together" % b_alg
     (updates, visited), elapsed = timed_steps(step, args, fence, max_over_ranks if world > 1 else None)
+    if args.dump_outputs:
+        if args.workload == "sobolev":  # warp_field is built on first read, from the last call's state
+            last.update(live_field=live, warp_field=opt.warp_field)
+        grid = next(v for k, v in last.items() if k.startswith("warp_field")).shape[:-1]  # a warp is [.., D]
+        dump_outputs(args.dump_outputs, grid, last, rank, world)
     updates, visited = updates * world, visited * world
     value = updates / elapsed
     achieved = visited / elapsed * b_alg / 1e9 / world  # per GPU
@@ -470,6 +517,7 @@ def secondary_measurements(args, device):
             size = max(size, 64)  # its coarsest level (size / 8) must hold the 7-tap kernel
         a.workload, a.size, a.steps, a.warmup, a.iterations = workload, size, steps, warmup, iterations
         a.no_cpu_baseline, a.frames, a.parallelism, a.halo = True, 8, "replicas", None
+        a.dump_outputs = None  # --dump-outputs holds the primary workload's results alone
         for k, v in more.items():
             setattr(a, k, v)
         row = dict(workload=workload, size=size, steps=steps, iterations=iterations)
@@ -719,6 +767,11 @@ def killing_workload(args, device, world, rank, local_rank, dist, dense_walk=Tru
     if world > 1:
         elapsed = max_over_ranks(elapsed)
     assert executed == iters, "expected %d fixed iterations, the gate closed after %d" % (iters, executed)
+    if args.dump_outputs:  # the last timed step's results (warp_field is built on first read), before the next call
+        outputs = dict(live_field=live, warp_field=opt.warp_field)
+        if world > 1:  # a rank's own slab, halos dropped
+            outputs = {k: layout.owned_of(v) if v.shape[:3] == live.shape else v for k, v in outputs.items()}
+        dump_outputs(args.dump_outputs, outputs["live_field"].shape, outputs, rank, world)
     # The same K steps under the conditions of the PRODUCT's pair loop (experiment/multipair.run_pairs ->
     # hostloop.parked_collector(): torch's objects parked, the cyclic collector left ON; caller shape
     # run_hierarchical_optimizer3d_multipair.py:403-432) -- reported next to ms_per_step as ms_per_step_gc_on

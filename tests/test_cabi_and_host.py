@@ -493,3 +493,38 @@ def test_bench_scaling_modes_parse():
                                                   "multiframe", "sobolev", "hier2d"]
     finally:
         sys.argv = old
+
+
+def test_bench_dump_outputs_fits_and_samples_the_same_voxels(tmp_path):
+    """bench.py --dump-outputs: whole arrays while they fit; above 64 MB in all a seeded voxel sample, the same from run to
+    run and across the arrays, with its flat indices; float64 stays float64; N > 1 ranks write files of their own"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch = bench.torch
+    small = {"live_field": torch.rand(8, 8, 8), "warp_field": torch.rand(8, 8, 8, 3)}
+    bench.dump_outputs(str(tmp_path / "small"), (8, 8, 8), small)
+    assert sorted(os.listdir(str(tmp_path / "small"))) == ["live_field.npy", "warp_field.npy"]
+    for name, a in small.items():
+        got = np.load(str(tmp_path / "small" / (name + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, a.numpy())
+    n = 200  # 32 MB of live field + 96 MB of warp
+    big = {"live_field": torch.rand(n, n, n), "warp_field": torch.rand(n, n, n, 3)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), (n, n, n), big)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["live_field.npy", "sample_voxel_index.npy", "warp_field.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64 * 10 ** 6
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))), f
+    index = np.load(str(tmp_path / "a" / "sample_voxel_index.npy"))
+    assert index.dtype == np.float64 and np.all(np.diff(index) > 0) and index[-1] < n ** 3
+    index = index.astype(np.int64)
+    live, warp = np.load(str(tmp_path / "a" / "live_field.npy")), np.load(str(tmp_path / "a" / "warp_field.npy"))
+    assert live.shape == (len(index),) and warp.shape == (len(index), 3) and len(index) > 10 ** 6
+    assert np.array_equal(live, big["live_field"].numpy().reshape(-1)[index])
+    assert np.array_equal(warp, big["warp_field"].numpy().reshape(-1, 3)[index])
+    bench.dump_outputs(str(tmp_path / "ranks"), (4, 4), {"warp_field": torch.rand(4, 4, 2, dtype=torch.float64)}, 1, 2)
+    assert os.listdir(str(tmp_path / "ranks")) == ["warp_field_rank1.npy"]
+    assert np.load(str(tmp_path / "ranks" / "warp_field_rank1.npy")).dtype == np.float64

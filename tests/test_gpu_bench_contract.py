@@ -189,3 +189,56 @@ def test_plain_form_launches_its_own_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "z-slab x2" in d["config"]["parallelism"]
     assert abs(d["value"] - 2 * 64 ** 3 * 6 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+
+
+def test_dump_outputs_are_the_timed_path_s_results(tmp_path):
+    """--dump-outputs: the last timed step's live field and warp, the same from run to run (with or without the secondary
+    measurements behind it) and equal to the numpy oracle on the same input; --steps sets the timed steps; N > 1 ranks
+    write their own slabs"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    from levelsetfusion_python_amd.synthetic import sphere_pair
+    from oracle import lsf_oracle as O
+    n, iters = 64, 4
+    for run, more in (("a", ("--secondary-divisor", "4")), ("b", ("--no-secondary",))):  # secondaries dump nothing
+        d = _run("--size", str(n), "--iterations", str(iters), "--steps", "3", "--no-cpu-baseline", *more,
+                 "--dump-outputs", str(tmp_path / run))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and ("secondary" in d) == (run == "a")
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["live_field.npy", "warp_field.npy"]
+    for name in ("live_field", "warp_field"):
+        a, b = (np.load(str(tmp_path / run / (name + ".npy"))) for run in ("a", "b"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    canonical, live = (t.cpu().numpy() for t in sphere_pair(n, 3, "cpu"))
+    ref = O.SlavchevaOracle(compute_method=O.DIRECT, level_set_term_enabled=True, smoothing_term_method=O.KILLING,
+                            maximum_warp_length_lower_threshold=0.0, max_iterations=iters, min_iterations=iters)
+    ref.optimize(live, canonical)
+    assert np.abs(np.load(str(tmp_path / "a" / "live_field.npy")) - live).max() <= 1e-5
+    assert np.abs(np.load(str(tmp_path / "a" / "warp_field.npy")) - ref.warp_field).max() <= 1e-5
+    _run_ranks(2, "--size", str(n), "--iterations", str(iters), "--halo", "2", "--dump-outputs", str(tmp_path / "ranks"))
+    for r in range(2):
+        live_r = np.load(str(tmp_path / "ranks" / ("live_field_rank%d.npy" % r)))
+        warp_r = np.load(str(tmp_path / "ranks" / ("warp_field_rank%d.npy" % r)))
+        assert live_r.shape == (n, n, n) and warp_r.shape == (n, n, n, 3)
+
+
+@pytest.mark.parametrize("workload, flags, shapes", [
+    ("hier2d", ("--size", "64", "--iterations", "4"), {"warp_field": (64, 64, 2)}),
+    ("hier-tik", ("--size", "64", "--iterations", "3"), {"warp_field": (64, 64, 64, 3)}),
+    ("sobolev", ("--size", "64", "--iterations", "3"), {"live_field": (64, 64, 64), "warp_field": (64, 64, 64, 3)}),
+    ("multiframe", ("--size", "64", "--frames", "3", "--iterations", "2"),
+     {"warp_field_pair0": (64, 64, 64, 3), "warp_field_pair1": (64, 64, 64, 3)}),
+])
+def test_dump_outputs_of_the_other_workloads(tmp_path, workload, flags, shapes):
+    """--dump-outputs on every --workload: what its optimize() calls returned in the last timed step"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    d = _run("--workload", workload, *flags, "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 2
+    assert sorted(os.listdir(str(tmp_path))) == sorted(name + ".npy" for name in shapes)
+    for name, shape in shapes.items():
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.shape == shape and a.dtype == np.float32 and np.isfinite(a).all(), name
+        if name.startswith("warp_field"):
+            assert np.abs(a).max() > 0, name
