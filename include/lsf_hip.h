@@ -732,6 +732,67 @@ int lsf_slavcheva_update_rewarp(const float *live, const float *canonical, float
                                 lsf_iteration_record *record, const int32_t *band_list /* may be NULL */,
                                 int64_t band_count, void *stream);
 
+/* ---- one energy term on its own: the term-level functions of nonrigid_opt/slavcheva/{data_term,smoothing_term,
+ * level_set_term}.py, which the reference's tests, focus-point debugging and visualiser call one by one.  One launch
+ * evaluates ONE term (below) at the selected voxels and writes any of: its gradient (float32), its per-voxel energy
+ * contribution (float64, the float32 local value widened) and the sum of those contributions (float64, ADDED to
+ * *energy_total by block reductions -- the caller zeroes it; the order of the additions varies between launches).
+ *   term                           reference                                   reads
+ *   LSF_TERM_DATA_BASIC            data_term.py:169-187, :334-349               live, canonical, live_gradient_x/y[/z]
+ *   LSF_TERM_DATA_THRESHOLDED_FDM  data_term.py:190-227 (OOB neighbours read 1) the same
+ *   LSF_TERM_TIKHONOV              smoothing_term.py:155-159 (-scipy laplace)   warp
+ *   LSF_TERM_TIKHONOV_LOCAL        smoothing_term.py:103-139                    warp
+ *   LSF_TERM_KILLING               smoothing_term.py:50-100                     warp
+ *   LSF_TERM_LEVEL_SET             level_set_term.py:28-64                      live
+ * live_gradient_* (caller's planes, data terms) are read only when gradient_out is given.
+ * Energies: data terms 0.5*diff^2; Killing and level set their local form; the Tikhonov terms the per-location form of
+ * smoothing_term.py:134-139 (energy_form LSF_TERM_ENERGY_LOCAL) or the np.gradient form of smoothing_term.py:162-177
+ * (LSF_TERM_ENERGY_NP_GRADIENT; Tikhonov terms only).
+ * selection: LSF_SELECT_ALL every voxel; LSF_SELECT_BAND every voxel, those outside the narrow-band union (|live| ==
+ * |canonical| == 1, tsdf_set_routines.py:19-52) get gradient 0 and energy 0 (needs live and canonical);
+ * LSF_SELECT_LIST the index_count flat voxel indices `indices` (device): outputs are then compact, entry k for indices[k]
+ * (an index outside the array gets zeros).
+ * Layout of warp and gradient_out: planar [c][voxel] (planes of nz*ny*nx entries, or index_count with a list), or
+ * interleaved [voxel][c] with LSF_TERM_INTERLEAVED -- the reference's (..., D) arrays, no conversion launch.
+ * LSF_TERM_COPY_IF_ZERO (TIKHONOV_LOCAL, KILLING): a neighbour outside the array or with norm 0 reads the centre value
+ * (utils/sampling.py:91-96); without it a neighbour outside the array reads the centre (sampling.py:84-88).
+ * LSF_TERM_IGNORE_IF_ZERO (TIKHONOV_LOCAL; KILLING accepts and ignores it, as the reference does): gradient and
+ * energy 0 where a component of an existing 4-neighbour is 0.  Both flags have 2-D semantics only: LSF_ERR_BAD_ARGUMENT
+ * in 3-D.  The grid must cover the whole array (z_begin 0, z_end nz). */
+#define LSF_TERM_DATA_BASIC 0
+#define LSF_TERM_DATA_THRESHOLDED_FDM 1
+#define LSF_TERM_TIKHONOV 2
+#define LSF_TERM_TIKHONOV_LOCAL 3
+#define LSF_TERM_KILLING 4
+#define LSF_TERM_LEVEL_SET 5
+#define LSF_TERM_COPY_IF_ZERO 1
+#define LSF_TERM_IGNORE_IF_ZERO 2
+#define LSF_TERM_INTERLEAVED 4
+#define LSF_SELECT_ALL 0
+#define LSF_SELECT_BAND 1
+#define LSF_SELECT_LIST 2
+#define LSF_TERM_ENERGY_LOCAL 0
+#define LSF_TERM_ENERGY_NP_GRADIENT 1
+
+typedef struct lsf_term_params {
+    double isomorphic_enforcement_factor_f64; /* Killing lambda as given: -2(1+lambda) is formed in double */
+    float isomorphic_enforcement_factor;      /* float32(lambda) */
+    float epsilon;                            /* level set, level_set_term.py:28 */
+    float scaling_factor;                     /* data terms, data_term.py:182 / :335 */
+    int32_t term;                             /* LSF_TERM_* */
+    int32_t flags;                            /* LSF_TERM_COPY_IF_ZERO | LSF_TERM_IGNORE_IF_ZERO | LSF_TERM_INTERLEAVED */
+    int32_t reserved;
+} lsf_term_params;
+
+/* replaces data_term.compute_data_term_gradient_vectorized / _direct / compute_data_term_energy_contribution /
+ * compute_local_data_term* / data_term_at_location (data_term.py:169-237, 334-384), smoothing_term.compute_*
+ * (smoothing_term.py:50-201) and level_set_term.level_set_term_at_location (level_set_term.py:28-64) */
+int lsf_term_gradient(const float *live, const float *canonical, const float *live_gradient_x,
+                      const float *live_gradient_y, const float *live_gradient_z, const float *warp,
+                      float *gradient_out, double *energy_out, double *energy_total, const lsf_grid *grid,
+                      const lsf_term_params *params, int32_t selection, int32_t energy_form, const int32_t *indices,
+                      int64_t index_count, void *stream);
+
 /* ---- a20: convergence statistics ---------------------------------------------------------------------
  * replaces cpp.build_warp_delta_statistics_2d / build_tsdf_difference_statistics_2d
  * (slavcheva_optimizer2d.py:394-398; known answer tests/test_slavcheva_optimizer.py:141-145).

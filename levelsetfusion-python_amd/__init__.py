@@ -19,7 +19,8 @@ from .nonrigid_opt.slavcheva.slavcheva_optimizer3d import SlavchevaOptimizer3d
 from .nonrigid_opt.slavcheva.data_term import DataTermMethod
 from .nonrigid_opt.slavcheva.smoothing_term import SmoothingTermMethod
 from .nonrigid_opt.slavcheva.sobolev_filter import generate_1d_sobolev_kernel
+from .nonrigid_opt.slavcheva import data_term, level_set_term, smoothing_term
 
 __all__ = ["HierarchicalOptimizer2d", "HierarchicalOptimizer3d", "SlavchevaOptimizer2d", "SlavchevaOptimizer3d",
            "ComputeMethod", "AdaptiveLearningRateMethod", "DataTermMethod", "SmoothingTermMethod",
-           "generate_1d_sobolev_kernel"]
+           "generate_1d_sobolev_kernel", "data_term", "smoothing_term", "level_set_term"]

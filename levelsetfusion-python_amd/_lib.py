@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "2b52a5b7ac923a65"
+HEADER_ABI_HASH = "588721031b87b4cd"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -97,6 +97,19 @@ class StateRun(ctypes.Structure):
                 ("totals_host", ctypes.c_void_p), ("grid", Grid), ("sparse_reach", ctypes.c_int32),
                 ("second_state_late", ctypes.c_int32), ("box_scratch", ctypes.c_void_p), ("box_all", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+# one energy term on its own (lsf_term_gradient)
+TERM_DATA_BASIC, TERM_DATA_THRESHOLDED_FDM, TERM_TIKHONOV, TERM_TIKHONOV_LOCAL, TERM_KILLING, TERM_LEVEL_SET = range(6)
+TERM_COPY_IF_ZERO, TERM_IGNORE_IF_ZERO, TERM_INTERLEAVED = 1, 2, 4
+SELECT_ALL, SELECT_BAND, SELECT_LIST = 0, 1, 2
+TERM_ENERGY_LOCAL, TERM_ENERGY_NP_GRADIENT = 0, 1
+
+
+class TermParams(ctypes.Structure):
+    _fields_ = [("isomorphic_enforcement_factor_f64", ctypes.c_double), ("isomorphic_enforcement_factor", ctypes.c_float),
+                ("epsilon", ctypes.c_float), ("scaling_factor", ctypes.c_float), ("term", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class StateRunResult(ctypes.Structure):
@@ -245,6 +258,8 @@ PROTOTYPES = {
                                                       _P(ctypes.c_double), _i32, _P(Gate), _vp, _vp, _i64, _vp]),
     "lsf_slavcheva_update_rewarp": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(Grid), _P(SlavchevaParams),
                                                    _P(Gate), _vp, _vp, _i64, _vp]),
+    "lsf_term_gradient": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Grid), _P(TermParams), _i32, _i32,
+                                         _vp, _i64, _vp]),
     "lsf_warp_statistics": (ctypes.c_int, [_vp, _vp, _vp, _P(Grid), _f32, _vp, _vp]),
     "lsf_tsdf_difference_statistics": (ctypes.c_int, [_vp, _vp, _P(Grid), _vp, _vp]),
     "lsf_tsdf_generate_nearest": (ctypes.c_int, [_vp, _vp, _P(Grid), _P(TsdfParams), _vp]),

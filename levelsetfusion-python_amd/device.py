@@ -3,8 +3,8 @@
 torch is plumbing here: it owns device memory and the HIP stream.  Every wrapper validates dtype, device,
 contiguity and element counts on the host BEFORE the launch (a hand-written kernel that reads past a buffer can
 take the whole GPU down), then passes raw device pointers + the current HIP stream to the library.
-The common helpers live in device_core.py, the field operations (warps, pyramids, filters) in device_fields.py; this module
-re-exports both and holds the optimizers' kernels.
+The common helpers live in device_core.py, the field operations (warps, pyramids, filters) in device_fields.py, one energy
+term on its own in device_terms.py; this module re-exports them and holds the optimizers' kernels.
 """
 import ctypes
 
@@ -16,6 +16,7 @@ from ._lib import Gate, Grid, HierParams, SlavchevaParams, check, lib
 from .device_core import *  # noqa: F401,F403
 from .device_core import _PINNED, _gate_ref, _ptr, _record_ptr  # noqa: F401
 from .device_fields import *  # noqa: F401,F403
+from .device_terms import term_gradient  # noqa: F401
 
 # ------------------------------------------------------------------------------------- optimizer kernels
 def hier_iteration(packed, canonical, warp, g_prev, g_out, grid, params, gate, records, index):
