@@ -846,6 +846,78 @@ typedef struct lsf_ewa_params {
 int lsf_tsdf_generate_ewa(const uint16_t *depth_image, float *field, const lsf_grid *grid,
                           const lsf_tsdf_params *params, const lsf_ewa_params *ewa, void *stream);
 
+/* nearest pixel on the inputs lsf_tsdf_generate_nearest refuses: the same reference functions (tsdf/generation.py:130-207,
+ * :356-437), with the dtypes the reference's own arithmetic takes under numpy >= 2.
+ * depth_image: DEVICE [image_height][image_width] of depth_dtype (LSF_DEPTH_*).  inf gives +1 like any depth beyond
+ *   the band; d <= 0 leaves default_value.  float32 depth is scaled in float32 (depth * float32(depth_unit_ratio)),
+ *   uint16 and float64 depth in float64.
+ * array_offset: HOST, 3 doubles (x, y, z voxels, fractional allowed); params->array_offset is ignored.
+ * extrinsic_f64: HOST, 16 doubles row-major: the product is evaluated in float64 and so is the projection.  NULL: the
+ *   float32 params->extrinsic and the float32 product, as lsf_tsdf_generate_nearest.
+ * The signed distance is taken in the promoted dtype of depth and camera-space point; a float32 distance is compared
+ * with and divided by float32(narrow_band_half_width).  On uint16 depth, integral offsets and a float32 extrinsic the
+ * result equals lsf_tsdf_generate_nearest's bit for bit; lsf_tsdf_params.array_offset is int32, so a fractional offset
+ * needs this entry point. */
+#define LSF_DEPTH_U16 0
+#define LSF_DEPTH_F32 1
+#define LSF_DEPTH_F64 2
+int lsf_tsdf_generate_nearest_typed(const void *depth_image, int32_t depth_dtype, float *field, const lsf_grid *grid,
+                                    const lsf_tsdf_params *params, const double *array_offset,
+                                    const double *extrinsic_f64, void *stream);
+
+/* ---- SDF-2-SDF rigid 2-D tracker ----------------------------------------------------------------------------------
+ * replaces rigid_opt/sdf_gradient_field.py:13-38 (calculate_gradient_wrt_twist) and rigid_opt/sdf_2_sdf_optimizer2d.py:
+ * 60-137 (Sdf2SdfOptimizer2d.optimize) on a square or rectangular 2-D field [height][width] (row = depth axis).
+ * Per voxel, as the reference evaluates it:
+ *   point      (x + offset_x) * voxel_size, (y + offset_z) * voxel_size in float64, rounded to float32
+ *   twist^-1   twist_vector_to_matrix2d(-twist) (math_utils/transformation.py:11-23) -- not the true inverse
+ *   trans      twist^-1 (float64) . point
+ *   grad       np.gradient of the live field: central in the interior, one-sided at the edges (float32)
+ *   g          ([grad_x, grad_y] . [[1, 0, trans_1], [0, 1, -trans_0]]) in float64, rounded to float32, then divided
+ *              by float32(voxel_size)
+ * The run (lsf_rigid_run) regenerates the live field every iteration from the live depth image under
+ * twist_vector_to_matrix3d([t0, 0, t1, 0, t2, 0]) -- the float32-rounded twist, rotation about y by Rodrigues in float64
+ * rounded to float32, float64 product (lsf_tsdf_generate_nearest_typed's arithmetic) -- then accumulates in float64
+ *   A += g g^T (products float32), b += ((c - l) (float32) + g . twist) g, energy += (c [c > -eta] - l [l > -eta])^2
+ * and updates twist += rate (A^-1 b - twist) (sdf_2_sdf_optimizer2d.py:92-126).  The update is skipped ("SINGULAR
+ * MATRIX!", skipped = 1) when A holds a non-finite entry or its float64 LU with partial pivoting meets an exact zero
+ * pivot: A == 0, a zero row and column (a twist-gradient component 0 at every voxel), any A found exactly singular --
+ * where the reference's np.linalg.cond(A) is inf or NaN and it skips too.  A nearly singular A is inverted, as there. */
+typedef struct lsf_rigid_params {
+    lsf_tsdf_params tsdf;      /* intrinsics, ratio, voxel size, band, image extents and row, default value; its
+                                  extrinsic and array_offset are ignored */
+    double array_offset[3];    /* voxels (x, y, z), fractional allowed */
+    double voxel_size;         /* calculate_gradient_wrt_twist's voxel_size (optimize()'s argument): the voxel points
+                                  and the final division; tsdf.voxel_size is the generator's */
+    double twist[3];           /* lsf_rigid_gradient: the twist (t_x, t_z, theta), float64 */
+    double rate;               /* lsf_rigid_run: step of the update */
+    float eta;                 /* lsf_rigid_run: float32(eta), weight threshold c > -eta */
+    int32_t depth_dtype;       /* lsf_rigid_run: LSF_DEPTH_* of the live depth image */
+    int32_t height, width;     /* field extents, >= 2 each */
+    int32_t iterations;        /* lsf_rigid_run: >= 0 */
+    int32_t reserved;
+} lsf_rigid_params;
+
+/* one record per iteration, LSF_RIGID_RECORD_DOUBLES doubles, written by the launch after it (lsf_rigid_run):
+ *   [0, 3) twist* = A^-1 b (0 when skipped)   [3, 6) twist after the update   [6] energy   [7, 16) A row-major
+ *   [16, 19) b   [19] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)   [20, 24) reserved */
+#define LSF_RIGID_RECORD_DOUBLES 24
+/* the launches of lsf_rigid_run use at most LSF_RIGID_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of
+ * 10 float64 partial sums per workgroup (6 of A, 3 of b, energy) */
+#define LSF_RIGID_MAX_BLOCKS 256
+#define LSF_RIGID_SCRATCH_BYTES (2 * LSF_RIGID_MAX_BLOCKS * 10 * 8)
+
+/* the gradient of live (DEVICE float32 [height][width]) with respect to params->twist: gradient_out DEVICE float32
+ * [height][width][3].  One launch. */
+int lsf_rigid_gradient(const float *live, float *gradient_out, const lsf_rigid_params *params, void *stream);
+
+/* the whole optimize(): iterations launches of the fused iteration kernel, then one finishing launch, back to back on
+ * stream with no host synchronisation.  canonical: DEVICE float32 [height][width]; live_depth: DEVICE depth image of
+ * params->depth_dtype; twist_inout: DEVICE 3 doubles, read at the start, the final twist written by the finishing
+ * launch; records: DEVICE iterations * LSF_RIGID_RECORD_DOUBLES doubles; scratch: DEVICE, LSF_RIGID_SCRATCH_BYTES. */
+int lsf_rigid_run(const float *canonical, const void *live_depth, double *twist_inout, double *records,
+                  void *scratch, const lsf_rigid_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "588721031b87b4cd"
+HEADER_ABI_HASH = "fd8a75f4092536e2"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -161,6 +161,21 @@ class TsdfParams(ctypes.Structure):
                 ("intrinsics_are_f32", ctypes.c_int32)]
 
 
+DEPTH_U16, DEPTH_F32, DEPTH_F64 = 0, 1, 2
+RIGID_RECORD_DOUBLES = 24
+RIGID_MAX_BLOCKS = 256
+RIGID_SCRATCH_BYTES = 2 * RIGID_MAX_BLOCKS * 10 * 8
+
+
+class RigidParams(ctypes.Structure):
+    """lsf_rigid_params: the SDF-2-SDF rigid tracker (lsf_rigid_gradient, lsf_rigid_run)"""
+    _fields_ = [("tsdf", TsdfParams), ("array_offset", ctypes.c_double * 3), ("voxel_size", ctypes.c_double),
+                ("twist", ctypes.c_double * 3),
+                ("rate", ctypes.c_double), ("eta", ctypes.c_float), ("depth_dtype", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -265,6 +280,10 @@ PROTOTYPES = {
     "lsf_tsdf_generate_nearest": (ctypes.c_int, [_vp, _vp, _P(Grid), _P(TsdfParams), _vp]),
     "lsf_tsdf_generate_bilinear": (ctypes.c_int, [_vp, _vp, _P(Grid), _P(TsdfParams), _i32, _vp]),
     "lsf_tsdf_generate_ewa": (ctypes.c_int, [_vp, _vp, _P(Grid), _P(TsdfParams), _P(EwaParams), _vp]),
+    "lsf_tsdf_generate_nearest_typed": (ctypes.c_int, [_vp, _i32, _vp, _P(Grid), _P(TsdfParams), _P(ctypes.c_double),
+                                                       _P(ctypes.c_double), _vp]),
+    "lsf_rigid_gradient": (ctypes.c_int, [_vp, _vp, _P(RigidParams), _vp]),
+    "lsf_rigid_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(RigidParams), _vp]),
 }
 
 

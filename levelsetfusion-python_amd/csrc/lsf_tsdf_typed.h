@@ -1,0 +1,65 @@
+// Nearest-pixel TSDF value of one voxel on the typed inputs of lsf_tsdf_generate_nearest_typed (reference
+// tsdf/generation.py:130-207, :356-437; tsdf/common.py:34-47): uint16 / float32 / float64 depth, fractional array
+// offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip and the live-field stage of lsf_rigid.hip.
+// The dtypes are those numpy >= 2 gives the reference's expressions (oracle: tests/rigid_restatement.py):
+//   voxel point     ((index + offset) * voxel_size) in float64, rounded to float32 (np.array(..., dtype=float32))
+//   camera point    extrinsic.dot(point): float32 or float64 as the extrinsic, ((e0 x + e1 y) + e2 z) + e3
+//   projection      promote(intrinsic dtype, camera point dtype); int() truncates
+//   depth           uint16 * ratio and float64 * ratio in float64; float32 * ratio in float32 (a Python float is weak)
+//   signed distance promote(depth dtype, camera point dtype); a float32 one meets float32(half width)
+#pragma once
+
+#include "lsf_device.h"
+
+namespace lsf {
+
+struct TypedTsdf {
+    double fx, fy, cx, cy;
+    double depth_unit_ratio, voxel_size, half_width;
+    double off[3];
+    int width, height, image_y;
+    float default_value;
+};
+
+__device__ inline double scaled_depth(const unsigned short* d, long long i, double ratio) { return (double)d[i] * ratio; }
+__device__ inline float scaled_depth(const float* d, long long i, double ratio) { return d[i] * (float)ratio; }
+__device__ inline double scaled_depth(const double* d, long long i, double ratio) { return d[i] * ratio; }
+
+template <typename S>
+__device__ inline float typed_tsdf_value(S sd, double half) {
+    const S h = (S)half;
+    return sd < -h ? -1.0f : (sd > h ? 1.0f : (float)(sd / h));
+}
+
+template <typename Q>
+__device__ inline long long typed_project(Q f, Q pc, Q z, Q c) {
+    const Q v = ((f * pc) / z + c) + (Q)0.5;
+    // int() of the reference truncates toward zero; saturate so that wild values stay out of range
+    if (!(v > (Q)-2147483000.0 && v < (Q)2147483000.0)) return -1;
+    return (long long)v;
+}
+
+// D = 2: field[y][x], x from the x index, the depth axis from the y index, y_voxel = 0, depth row p.image_y.
+// D = 3: field[z][y][x].  E = float or double: the extrinsic's dtype (e: first three rows, row-major); P = the
+// intrinsic matrix's dtype; DT = the depth image's element type.
+template <int D, typename E, typename P, typename DT>
+__device__ inline float typed_tsdf_voxel(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x, int y,
+                                         int z) {
+    using Q = decltype(E() + P());
+    const float xv = (float)(((double)x + p.off[0]) * p.voxel_size);
+    const float yv = D == 3 ? (float)(((double)y + p.off[1]) * p.voxel_size) : 0.0f;
+    const float zv = (float)(((double)(D == 3 ? z : y) + p.off[2]) * p.voxel_size);
+    const E pcx = ((e[0] * (E)xv + e[1] * (E)yv) + e[2] * (E)zv) + e[3] * (E)1;
+    const E pcy = ((e[4] * (E)xv + e[5] * (E)yv) + e[6] * (E)zv) + e[7] * (E)1;
+    const E pcz = ((e[8] * (E)xv + e[9] * (E)yv) + e[10] * (E)zv) + e[11] * (E)1;
+    if (!(pcz > (E)0)) return p.default_value;
+    const long long ix = typed_project<Q>((Q)(P)p.fx, (Q)pcx, (Q)pcz, (Q)(P)p.cx);
+    const long long iy = D == 3 ? typed_project<Q>((Q)(P)p.fy, (Q)pcy, (Q)pcz, (Q)(P)p.cy) : (long long)p.image_y;
+    if (ix < 0 || ix >= p.width || iy < 0 || iy >= p.height) return p.default_value;
+    const auto d = scaled_depth(depth, iy * p.width + ix, p.depth_unit_ratio);
+    if (d <= 0) return p.default_value;  // NaN goes on, as in the reference
+    using S = decltype(d + pcz);
+    return typed_tsdf_value<S>((S)d - (S)pcz, p.half_width);
+}
+
+}  // namespace lsf
