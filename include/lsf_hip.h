@@ -918,6 +918,67 @@ int lsf_rigid_gradient(const float *live, float *gradient_out, const lsf_rigid_p
 int lsf_rigid_run(const float *canonical, const void *live_depth, double *twist_inout, double *records,
                   void *scratch, const lsf_rigid_params *params, void *stream);
 
+/* ---- SDF-2-SDF rigid 3-D tracker (6-DoF) ----------------------------------------------------------------------------
+ * The reference has no 3-D tracker; this is its 2-D algorithm (rigid_opt/sdf_gradient_field.py:13-38,
+ * rigid_opt/sdf_2_sdf_optimizer2d.py:60-137) lifted to a volume [depth][height][width] = [z][y][x], with the 2-D
+ * kernel's dtypes.  The twist is (t_x, t_y, t_z, r_x, r_y, r_z) in twist_vector_to_matrix3d's layout
+ * (math_utils/transformation.py:26-34); a 2-D twist (t0, t1, t2) is (t0, 0, t1, 0, t2, 0).  Per voxel:
+ *   point      (index + offset) * voxel_size per axis in float64, rounded to float32
+ *   p          twist_vector_to_matrix3d(-twist) (Rodrigues in float64) . (point, 1) in float64 -- the negated twist,
+ *              not the inverse, as the 2-D reference's twist_vector_to_matrix2d(-twist)
+ *   grad       np.gradient of the live volume: central inside, one-sided at all six faces (float32)
+ *   g          [grad ; p x grad] in float64, rounded to float32, then divided by float32(voxel_size).  At r = 0 on a
+ *              y-constant volume, (g_tx, g_tz, g_ry) is the 2-D g term for term; at r_y != 0 the 2-D matrix turns the
+ *              x-z plane the other way from Rodrigues about y, and the two differ.
+ * The run (lsf_rigid3d_run) regenerates the live volume every iteration under twist_vector_to_matrix3d of the
+ * float32-rounded twist (Rodrigues in float64 rounded to float32, float64 product: lsf_tsdf_generate_nearest_typed's
+ * arithmetic), then accumulates in float64
+ *   A += g g^T (6 x 6, products float32), b += ((c - l) (float32) + g . twist) g, energy += (c [c > -eta] - l [l > -eta])^2
+ * and updates twist += rate (A^-1 b - twist), the 2-D loop's step (sdf_2_sdf_optimizer2d.py:92-126).  The update is
+ * skipped (skipped = 1) when A holds a non-finite entry or its float64 LU with partial pivoting meets an exact zero
+ * pivot -- the 2-D rule; a wall facing the camera leaves the t_x, t_y and r_z columns zero.  A nearly singular A is
+ * inverted. */
+typedef struct lsf_rigid3d_params {
+    lsf_tsdf_params tsdf;      /* intrinsics, ratio, voxel size, band, image extents, default value; its extrinsic,
+                                  array_offset and image_y_coordinate are ignored */
+    double array_offset[3];    /* voxels (x, y, z), fractional allowed */
+    double voxel_size;         /* the gradient's voxel size (optimize()'s argument); tsdf.voxel_size is the generator's */
+    double twist[6];           /* lsf_rigid3d_gradient: the twist, float64 */
+    double rate;               /* lsf_rigid3d_run: step of the update */
+    float eta;                 /* lsf_rigid3d_run: float32(eta), weight threshold c > -eta */
+    int32_t depth_dtype;       /* LSF_DEPTH_* of the live depth image (the run; the gradient when live is NULL) */
+    int32_t depth, height, width;  /* volume extents z, y, x, >= 2 each */
+    int32_t iterations;        /* lsf_rigid3d_run: >= 0 */
+} lsf_rigid3d_params;
+
+/* one record per iteration, LSF_RIGID3D_RECORD_DOUBLES doubles, written by the launch after it (lsf_rigid3d_run);
+ * each entry is the 6-DoF form of the 2-D record's (LSF_RIGID_RECORD_DOUBLES), which holds the values the reference's
+ * loop prints or tests (sdf_2_sdf_optimizer2d.py:111 twist_star, :117 twist, :104-105 energy, :96-101 A and b, :110
+ * the singular branch):
+ *   [0, 6) twist* = A^-1 b (0 when skipped)   [6, 12) twist after the update   [12] energy   [13, 49) A row-major
+ *   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)   [56, 64) reserved */
+#define LSF_RIGID3D_RECORD_DOUBLES 64
+/* the launches of lsf_rigid3d_run use at most LSF_RIGID3D_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of
+ * 28 float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy) */
+#define LSF_RIGID3D_MAX_BLOCKS 256
+#define LSF_RIGID3D_SCRATCH_BYTES (2 * LSF_RIGID3D_MAX_BLOCKS * 28 * 8)
+
+/* the gradient with respect to params->twist of a live volume, one launch.  live: DEVICE float32 [depth][height][width];
+ * or NULL, and then the live volume is generated from live_depth (DEVICE depth image of params->depth_dtype) under
+ * params->twist exactly as an iteration of lsf_rigid3d_run generates it.  live_out: NULL, or DEVICE float32
+ * [depth][height][width] that receives the live volume used; gradient_out: NULL, or DEVICE float32
+ * [depth][height][width][6].  At least one of the two outputs is given. */
+int lsf_rigid3d_gradient(const float *live, const void *live_depth, float *live_out, float *gradient_out,
+                         const lsf_rigid3d_params *params, void *stream);
+
+/* the whole 6-DoF optimize(): iterations launches of the fused iteration kernel, then one finishing launch, back to back
+ * on stream with no host synchronisation.  canonical: DEVICE float32 [depth][height][width]; live_depth: DEVICE depth
+ * image of params->depth_dtype; twist_inout: DEVICE 6 doubles, read at the start, the final twist written by the
+ * finishing launch; records: DEVICE iterations * LSF_RIGID3D_RECORD_DOUBLES doubles; scratch: DEVICE,
+ * LSF_RIGID3D_SCRATCH_BYTES. */
+int lsf_rigid3d_run(const float *canonical, const void *live_depth, double *twist_inout, double *records,
+                    void *scratch, const lsf_rigid3d_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 Drop-in for the numpy path of Algomorph/LevelSetFusion-Python's warp-field gradient descent:
     SlavchevaOptimizer2d(...).optimize(live_field, canonical_field)
     HierarchicalOptimizer2d(...).optimize(canonical_field, live_field)
-plus their 3-D generalisations, and the SDF-2-SDF rigid 2-D tracker rigid_opt.Sdf2SdfOptimizer2d.  Host code is Python; device buffers are PyTorch-ROCm tensors; every per-voxel
+plus their 3-D generalisations, the SDF-2-SDF rigid 2-D tracker rigid_opt.Sdf2SdfOptimizer2d and its 6-DoF 3-D
+form rigid_opt.Sdf2SdfOptimizer3d.  Host code is Python; device buffers are PyTorch-ROCm tensors; every per-voxel
 operation is a hand-written HIP kernel (gfx950) behind the C ABI in include/lsf_hip.h.  There is no CPU
 execution path: importing the package without liblsf_hip.so raises.
 
@@ -22,10 +23,12 @@ from .nonrigid_opt.slavcheva.sobolev_filter import generate_1d_sobolev_kernel
 from .nonrigid_opt.slavcheva import data_term, level_set_term, smoothing_term
 from . import rigid_opt
 from .math_utils import transformation
-from .rigid_opt import sdf_2_sdf_optimizer2d, sdf_2_sdf_visualizer, sdf_generation, sdf_gradient_field
+from .rigid_opt import (sdf_2_sdf_optimizer2d, sdf_2_sdf_optimizer3d, sdf_2_sdf_visualizer, sdf_generation,
+                        sdf_gradient_field)
 from .rigid_opt.sdf_2_sdf_optimizer2d import Sdf2SdfOptimizer2d
+from .rigid_opt.sdf_2_sdf_optimizer3d import Sdf2SdfOptimizer3d
 
 __all__ = ["HierarchicalOptimizer2d", "HierarchicalOptimizer3d", "SlavchevaOptimizer2d", "SlavchevaOptimizer3d",
            "ComputeMethod", "AdaptiveLearningRateMethod", "DataTermMethod", "SmoothingTermMethod",
            "generate_1d_sobolev_kernel", "data_term", "smoothing_term", "level_set_term", "rigid_opt",
-           "transformation", "Sdf2SdfOptimizer2d"]
+           "transformation", "Sdf2SdfOptimizer2d", "Sdf2SdfOptimizer3d"]

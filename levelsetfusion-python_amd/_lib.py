@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "fd8a75f4092536e2"
+HEADER_ABI_HASH = "021fd30fe4013820"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -176,6 +176,20 @@ class RigidParams(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+RIGID3D_RECORD_DOUBLES = 64
+RIGID3D_MAX_BLOCKS = 256
+RIGID3D_SCRATCH_BYTES = 2 * RIGID3D_MAX_BLOCKS * 28 * 8
+
+
+class Rigid3dParams(ctypes.Structure):
+    """lsf_rigid3d_params: the 6-DoF SDF-2-SDF rigid tracker (lsf_rigid3d_gradient, lsf_rigid3d_run)"""
+    _fields_ = [("tsdf", TsdfParams), ("array_offset", ctypes.c_double * 3), ("voxel_size", ctypes.c_double),
+                ("twist", ctypes.c_double * 6),
+                ("rate", ctypes.c_double), ("eta", ctypes.c_float), ("depth_dtype", ctypes.c_int32),
+                ("depth", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("iterations", ctypes.c_int32)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -284,6 +298,8 @@ PROTOTYPES = {
                                                        _P(ctypes.c_double), _vp]),
     "lsf_rigid_gradient": (ctypes.c_int, [_vp, _vp, _P(RigidParams), _vp]),
     "lsf_rigid_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(RigidParams), _vp]),
+    "lsf_rigid3d_gradient": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
+    "lsf_rigid3d_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
 }
 
 

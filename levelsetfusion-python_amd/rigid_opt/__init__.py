@@ -1,2 +1,3 @@
-"""SDF-2-SDF rigid 2-D tracking (reference rigid_opt/): Sdf2SdfOptimizer2d, its datasets and
-calculate_gradient_wrt_twist.  The optimizer's whole loop runs on the GPU (csrc/lsf_rigid.hip)."""
+"""SDF-2-SDF rigid tracking (reference rigid_opt/): Sdf2SdfOptimizer2d, its datasets and calculate_gradient_wrt_twist,
+and their 6-DoF 3-D generalisation Sdf2SdfOptimizer3d and calculate_gradient_wrt_twist_3d.  The optimizers' whole loops
+run on the GPU (csrc/lsf_rigid.hip, csrc/lsf_rigid3d.hip)."""

@@ -15,3 +15,12 @@ def calculate_gradient_wrt_twist(live_field, twist, array_offset, voxel_size=0.0
     (3, 1), fractional allowed.  as_tensor=True keeps it on the GPU."""
     g = device_rigid.gradient_wrt_twist(live_field, twist, array_offset, voxel_size)
     return g if as_tensor else g.cpu().numpy()
+
+
+def calculate_gradient_wrt_twist_3d(live_field, twist, array_offset, voxel_size=0.004, as_tensor=False):
+    """(Z, Y, X, 6) float32 gradient of the live volume (Z, Y, X) with respect to the 6-DoF twist (t_x, t_y, t_z, r_x,
+    r_y, r_z): [grad ; p x grad] / voxel_size with p = twist_vector_to_matrix3d(-twist) . (point, 1), the 3-D form of
+    calculate_gradient_wrt_twist.  One launch of csrc/lsf_rigid3d.hip, mode GRADIENT.
+    as_tensor=True keeps it on the GPU."""
+    g = device_rigid.gradient_wrt_twist_3d(live_field, twist, array_offset, voxel_size)
+    return g if as_tensor else g.cpu().numpy()
