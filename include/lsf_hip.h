@@ -979,6 +979,45 @@ int lsf_rigid3d_gradient(const float *live, const void *live_depth, float *live_
 int lsf_rigid3d_run(const float *canonical, const void *live_depth, double *twist_inout, double *records,
                     void *scratch, const lsf_rigid3d_params *params, void *stream);
 
+/* ---- fusion of aligned frames into a canonical TSDF volume (KillingFusion / SobolevFusion's model update) -----------
+ * The reference has no fusion code; the rule is this project's ("Fusion").  The model is two
+ * float32 arrays of one shape, tsdf (starts at 1) and weight (starts at 0).  A voxel is observed when its live value l
+ * satisfies -1 < l < 1 strictly (+-1 and NaN are not fused); there, in float32 with separately rounded operations,
+ *   W1 = W + w,  tsdf = (W t + w l) / W1,  weight = min(W1, max_weight)
+ * -- the average takes the uncapped W1.  A voxel that is not observed keeps its tsdf and weight bit for bit.
+ * Each call writes a record of LSF_FUSION_RECORD_DOUBLES doubles: [0] fused (observed voxels), [1] first_seen (observed
+ * voxels whose weight was 0), [2] sum over observed voxels of |t1 - t| (each term float32, summed in float64 in a fixed
+ * order: reruns are bit-identical), [3] max |t1 - t|, [4..7] 0.  Voxels are taken four to a lane in flat order; the
+ * per-workgroup partials (at most LSF_FUSION_MAX_BLOCKS) go to scratch and a finishing one-workgroup launch combines
+ * them in a fixed order.  No host synchronisation. */
+typedef struct lsf_fusion_params {
+    lsf_tsdf_params tsdf;      /* depth mode: intrinsics, ratio, generator voxel size, band, image extents, default
+                                  value; its extrinsic, array_offset and image_y_coordinate are ignored */
+    double twist[6];           /* depth mode: the frame's twist (t_x, t_y, t_z, r_x, r_y, r_z), float64 */
+    double array_offset[3];    /* depth mode: voxels (x, y, z), fractional allowed */
+    int32_t depth, height, width; /* extents z, y, x, >= 1 each; volume mode fuses depth * height * width voxels */
+    float weight;              /* w of the rule: finite, > 0 */
+    float max_weight;          /* the cap: > 0, +inf allowed */
+    int32_t depth_dtype;       /* depth mode: LSF_DEPTH_* of the depth image */
+} lsf_fusion_params;
+#define LSF_FUSION_RECORD_DOUBLES 8
+#define LSF_FUSION_MAX_BLOCKS 2048
+/* per-workgroup partials: fused, first_seen, sum, max */
+#define LSF_FUSION_SCRATCH_BYTES (LSF_FUSION_MAX_BLOCKS * 4 * 8)
+
+/* volume mode: fuse a given live field.  tsdf, weight: DEVICE float32, in/out, depth * height * width voxels each, two
+ * distinct buffers; live: DEVICE float32 of the same count, aliasing neither (any contiguous shape: the index is flat);
+ * record: DEVICE LSF_FUSION_RECORD_DOUBLES doubles; scratch: DEVICE, LSF_FUSION_SCRATCH_BYTES. */
+int lsf_fusion_integrate_volume(float *tsdf, float *weight, const float *live, double *record, void *scratch,
+                                const lsf_fusion_params *params, void *stream);
+
+/* depth mode: the live value of every voxel of a [depth][height][width] volume generated from depth_image (DEVICE, of
+ * params->depth_dtype) under params->twist exactly as lsf_rigid3d_gradient generates it (twist_vector_to_matrix3d of
+ * the float32-rounded twist, nearest pixel), fused in the same pass; no live volume is written.  The result and the
+ * record equal lsf_rigid3d_gradient's live_out followed by lsf_fusion_integrate_volume, bit for bit. */
+int lsf_fusion_integrate_depth(float *tsdf, float *weight, const void *depth_image, double *record, void *scratch,
+                               const lsf_fusion_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "021fd30fe4013820"
+HEADER_ABI_HASH = "bc02ed0838831b36"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -190,6 +190,18 @@ class Rigid3dParams(ctypes.Structure):
                 ("iterations", ctypes.c_int32)]
 
 
+FUSION_RECORD_DOUBLES = 8
+FUSION_MAX_BLOCKS = 2048
+FUSION_SCRATCH_BYTES = FUSION_MAX_BLOCKS * 4 * 8
+
+
+class FusionParams(ctypes.Structure):
+    """lsf_fusion_params: fusion into a canonical TSDF volume (lsf_fusion_integrate_volume, lsf_fusion_integrate_depth)"""
+    _fields_ = [("tsdf", TsdfParams), ("twist", ctypes.c_double * 6), ("array_offset", ctypes.c_double * 3),
+                ("depth", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("weight", ctypes.c_float), ("max_weight", ctypes.c_float), ("depth_dtype", ctypes.c_int32)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -300,6 +312,8 @@ PROTOTYPES = {
     "lsf_rigid_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(RigidParams), _vp]),
     "lsf_rigid3d_gradient": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
     "lsf_rigid3d_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
+    "lsf_fusion_integrate_volume": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
+    "lsf_fusion_integrate_depth": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
 }
 
 

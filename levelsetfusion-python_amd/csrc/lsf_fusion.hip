@@ -1,0 +1,270 @@
+// Fusion of aligned frames into a canonical TSDF volume (include/lsf_hip.h, lsf_fusion_*): the model update of
+// KillingFusion / SobolevFusion, which the reference does not have; the rule is this project's (INTEGRATION.md
+// section 3, "Fusion"; tests/fusion_restatement.py restates it).  One kernel, two live sources, one update:
+//   VOLUME  the live value of a voxel is read from a given float32 field (flat index, 16-byte accesses per lane)
+//   DEPTH   the live value is generated from a depth image under a twist by the rigid 3-D tracker's own code
+//           (live_extrinsic + typed_tsdf_voxel, lsf_tsdf_typed.h) and fused in the same pass; no live volume is written
+// Every lane takes four consecutive voxels per step of a grid-stride loop; the grid depends on the voxel count alone,
+// so both sources visit the voxels in one order and sum the record identically.  Per-workgroup partials go to
+// scratch; a finishing one-workgroup launch combines them in a fixed order: no atomics, reruns are bit-identical.
+// -ffp-contract=off keeps W t + w l two roundings and an add, as numpy computes it.
+#include "lsf_device.h"
+#include "lsf_tsdf_typed.h"
+
+using namespace lsf;
+
+namespace {
+
+constexpr int kParts = 4;  // fused, first_seen, sum |t1 - t|, max |t1 - t|
+constexpr int kMaxBlocks = LSF_FUSION_MAX_BLOCKS;
+constexpr int kRec = LSF_FUSION_RECORD_DOUBLES;
+static_assert(kRec >= kParts, "the record holds the four results");
+
+enum Source { VOLUME = 0, DEPTH = 1 };
+
+struct FusionDev {
+    TypedTsdf t;        // DEPTH
+    double twist[6];    // DEPTH
+    long long n;        // voxels
+    long long groups;   // n / 4: the four-voxel steps; the n % 4 voxels after them are the tail
+    int ny, nx;         // DEPTH: the flat index's y and x extents
+    float w, max_weight;
+    int aligned;        // every buffer read or written with 16-byte accesses is 16-byte aligned
+    int nblocks;        // the grid: min(ceil(groups / kBlock), kMaxBlocks), at least 1; the number of partials
+};
+
+struct Acc {
+    int fused, first;
+    double sum;
+    float max;
+};
+
+// the rule at one voxel; true when the voxel was observed (and its tsdf and weight may have changed)
+__device__ inline bool fuse_voxel(float l, float& t, float& W, const FusionDev& p, Acc& a) {
+    if (!(l > -1.0f && l < 1.0f)) return false;  // +-1 and NaN are not fused
+    const float W1 = W + p.w;
+    const float t1 = (W * t + p.w * l) / W1;
+    const float d = fabsf(t1 - t);
+    a.fused += 1;
+    a.first += W == 0.0f ? 1 : 0;
+    a.sum += (double)d;
+    a.max = d > a.max ? d : a.max;
+    t = t1;
+    W = W1 > p.max_weight ? p.max_weight : W1;
+    return true;
+}
+
+__device__ inline void load4(const float* __restrict__ f, long long i, float (&v)[4], bool aligned) {
+    if (aligned) {
+        const float4 q = *reinterpret_cast<const float4*>(f + i);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = f[i + k];
+    }
+}
+
+__device__ inline void store4(float* __restrict__ f, long long i, const float (&v)[4], bool aligned) {
+    if (aligned) {
+        *reinterpret_cast<float4*>(f + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[i + k] = v[k];
+    }
+}
+
+// the live value of voxel i (flat [z][y][x] index) under extrinsic e: lsf_rigid3d_gradient's generation
+template <typename DT, typename PT>
+__device__ inline float depth_voxel(const DT* __restrict__ depth, const FusionDev& p, const double* e, long long i) {
+    const long long row = i / p.nx;
+    const int x = (int)(i - row * p.nx);
+    const int z = (int)(row / p.ny);
+    const int y = (int)(row - (long long)z * p.ny);
+    return typed_tsdf_voxel<3, double, PT, DT>(depth, p.t, e, x, y, z);
+}
+
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ inline float wave_max(float v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const float u = __shfl_xor(v, o);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+
+// the block's totals of v[] (counts and sum added, max taken) in a fixed order; they land in thread 0's v[]
+__device__ inline void block_combine(double (&v)[kParts], double (*red)[kParts]) {
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = wave_sum(v[c]);
+    v[3] = (double)wave_max((float)v[3]);
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < kParts; ++c) red[wave][c] = v[c];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int q = 1; q < kBlock / kWave; ++q) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] += red[q][c];
+            v[3] = red[q][3] > v[3] ? red[q][3] : v[3];
+        }
+}
+
+template <int SOURCE, typename DT, typename PT>
+__global__ __launch_bounds__(kBlock) void fusion_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
+                                                        const float* __restrict__ live,
+                                                        const DT* __restrict__ depth, double* __restrict__ scratch,
+                                                        FusionDev p) {
+    __shared__ double e[12];
+    __shared__ double red[kBlock / kWave][kParts];
+    if (SOURCE == DEPTH) {
+        if (threadIdx.x == 0) live_extrinsic(p.twist, e);
+        __syncthreads();
+    }
+    const bool aligned = p.aligned != 0;
+    Acc a = {0, 0, 0.0, 0.0f};
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
+        const long long i = g * 4;
+        float l[4], t[4], W[4];
+        if (SOURCE == VOLUME) {
+            load4(live, i, l, aligned);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) l[k] = depth_voxel<DT, PT>(depth, p, e, i + k);
+        }
+        load4(tsdf, i, t, aligned);
+        load4(weight, i, W, aligned);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) any = fuse_voxel(l[k], t[k], W[k], p, a) || any;
+        if (any) {  // a step without an observed voxel stores nothing; the stored values would equal the loaded ones
+            store4(tsdf, i, t, aligned);
+            store4(weight, i, W, aligned);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
+        for (long long i = p.groups * 4; i < p.n; ++i) {
+            const float l = SOURCE == VOLUME ? live[i] : depth_voxel<DT, PT>(depth, p, e, i);
+            float t = tsdf[i], W = weight[i];
+            if (fuse_voxel(l, t, W, p, a)) {
+                tsdf[i] = t;
+                weight[i] = W;
+            }
+        }
+    double v[kParts] = {(double)a.fused, (double)a.first, a.sum, (double)a.max};
+    block_combine(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < kParts; ++c) scratch[(size_t)blockIdx.x * kParts + c] = v[c];
+}
+
+// one workgroup: lane q combines partials q, q + kBlock, ... in order, then the block in a fixed order
+__global__ __launch_bounds__(kBlock) void fusion_finish_kernel(const double* __restrict__ scratch,
+                                                               double* __restrict__ record, int nblocks) {
+    __shared__ double red[kBlock / kWave][kParts];
+    double v[kParts] = {0.0, 0.0, 0.0, 0.0};
+    for (int q = threadIdx.x; q < nblocks; q += kBlock) {
+        const double* s = scratch + (size_t)q * kParts;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] += s[c];
+        v[3] = s[3] > v[3] ? s[3] : v[3];
+    }
+    block_combine(v, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < kParts; ++c) record[c] = v[c];
+        for (int c = kParts; c < kRec; ++c) record[c] = 0.0;
+    }
+}
+
+bool aligned16(const void* ptr) { return ptr == nullptr || ((uintptr_t)ptr & 15) == 0; }
+
+int convert(const lsf_fusion_params* params, FusionDev& p) {
+    if (!params) return LSF_ERR_BAD_ARGUMENT;
+    if (params->depth < 1 || params->height < 1 || params->width < 1) return LSF_ERR_BAD_ARGUMENT;
+    const float w = params->weight, cap = params->max_weight;
+    if (!(w > 0.0f) || !std::isfinite(w) || !(cap > 0.0f)) return LSF_ERR_BAD_ARGUMENT;
+    const lsf_tsdf_params& t = params->tsdf;
+    p.t.fx = t.intrinsics[0]; p.t.fy = t.intrinsics[1]; p.t.cx = t.intrinsics[2]; p.t.cy = t.intrinsics[3];
+    p.t.depth_unit_ratio = t.depth_unit_ratio;
+    p.t.voxel_size = t.voxel_size;
+    p.t.half_width = t.narrow_band_half_width;
+    for (int i = 0; i < 3; ++i) p.t.off[i] = params->array_offset[i];
+    p.t.width = t.image_width; p.t.height = t.image_height; p.t.image_y = 0;
+    p.t.default_value = t.default_value;
+    for (int i = 0; i < 6; ++i) p.twist[i] = params->twist[i];
+    p.n = (long long)params->depth * params->height * params->width;
+    p.groups = p.n / 4;
+    p.ny = params->height;
+    p.nx = params->width;
+    p.w = w;
+    p.max_weight = cap;
+    const long long want = (p.groups + kBlock - 1) / kBlock;
+    p.nblocks = want < 1 ? 1 : (want > kMaxBlocks ? kMaxBlocks : (int)want);
+    return 0;
+}
+
+template <int SOURCE, typename DT, typename PT>
+int launch(float* tsdf, float* weight, const float* live, const void* depth, double* record, double* scratch,
+           const FusionDev& p, hipStream_t s) {
+    hipLaunchKernelGGL((fusion_kernel<SOURCE, DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, live,
+                       reinterpret_cast<const DT*>(depth), scratch, p);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(fusion_finish_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record, p.nblocks);
+    return launch_status();
+}
+
+int check_buffers(const float* tsdf, const float* weight, const void* source, const double* record,
+                  const void* scratch) {
+    if (!tsdf || !weight || !source || !record || !scratch) return LSF_ERR_BAD_ARGUMENT;
+    if ((const void*)tsdf == (const void*)weight || source == (const void*)tsdf || source == (const void*)weight)
+        return LSF_ERR_BAD_ARGUMENT;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int lsf_fusion_integrate_volume(float* tsdf, float* weight, const float* live, double* record,
+                                           void* scratch, const lsf_fusion_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (int e = check_buffers(tsdf, weight, live, record, scratch)) return e;
+    FusionDev p;
+    if (int e = convert(params, p)) return e;
+    p.aligned = aligned16(tsdf) && aligned16(weight) && aligned16(live);
+    return launch<VOLUME, float, double>(tsdf, weight, live, nullptr, record, reinterpret_cast<double*>(scratch), p,
+                                         as_stream(stream));
+}
+
+extern "C" int lsf_fusion_integrate_depth(float* tsdf, float* weight, const void* depth_image, double* record,
+                                          void* scratch, const lsf_fusion_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
+    FusionDev p;
+    if (int e = convert(params, p)) return e;
+    const lsf_tsdf_params& t = params->tsdf;
+    const int32_t dt = params->depth_dtype;
+    if (dt != LSF_DEPTH_U16 && dt != LSF_DEPTH_F32 && dt != LSF_DEPTH_F64) return LSF_ERR_BAD_ARGUMENT;
+    if (!(t.image_width > 0 && t.image_height > 0 && t.narrow_band_half_width > 0.0 &&
+          (long long)t.image_width * t.image_height <= 0x7fffffffll))
+        return LSF_ERR_BAD_ARGUMENT;
+    p.aligned = aligned16(tsdf) && aligned16(weight);
+    hipStream_t s = as_stream(stream);
+    double* sc = reinterpret_cast<double*>(scratch);
+    // one instantiation per (depth dtype, intrinsics dtype), as lsf_rigid3d.hip
+    const float* none = nullptr;
+    if (t.intrinsics_are_f32) {
+        if (dt == LSF_DEPTH_U16) return launch<DEPTH, unsigned short, float>(tsdf, weight, none, depth_image, record, sc, p, s);
+        if (dt == LSF_DEPTH_F32) return launch<DEPTH, float, float>(tsdf, weight, none, depth_image, record, sc, p, s);
+        return launch<DEPTH, double, float>(tsdf, weight, none, depth_image, record, sc, p, s);
+    }
+    if (dt == LSF_DEPTH_U16) return launch<DEPTH, unsigned short, double>(tsdf, weight, none, depth_image, record, sc, p, s);
+    if (dt == LSF_DEPTH_F32) return launch<DEPTH, float, double>(tsdf, weight, none, depth_image, record, sc, p, s);
+    return launch<DEPTH, double, double>(tsdf, weight, none, depth_image, record, sc, p, s);
+}

@@ -157,30 +157,11 @@ __device__ void combine_and_update(const Rigid3dDev& p, int k, const double* __r
     __syncthreads();
 }
 
-// cv2.Rodrigues of a float64 rotation vector (math_utils/transformation.py::rodrigues), row-major
-__device__ inline void rodrigues(const double r[3], double rot[9]) {
-    const double theta = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
-    for (int i = 0; i < 9; ++i) rot[i] = i % 4 == 0 ? 1.0 : 0.0;
-    if (theta < 2.220446049250313e-16) return;
-    const double c = cos(theta), s = sin(theta), c1 = 1.0 - c, itheta = 1.0 / theta;
-    const double u[3] = {r[0] * itheta, r[1] * itheta, r[2] * itheta};
-    const double rx[9] = {0.0, -u[2], u[1], u[2], 0.0, -u[0], -u[1], u[0], 0.0};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            rot[i * 3 + j] = (c * (i == j ? 1.0 : 0.0) + c1 * (u[i] * u[j])) + s * rx[i * 3 + j];
-}
-
 // the pose of one launch from the twist, rows 0..2 row-major: m = twist_vector_to_matrix3d(-twist) in float64 (the
-// gradient's p), e = twist_vector_to_matrix3d of the float32-rounded twist (the live volume: Rodrigues in float64
-// rounded to float32, as cv2.Rodrigues on a float32 vector)
+// gradient's p), e = the live volume's extrinsic (live_extrinsic, lsf_tsdf_typed.h)
 __device__ inline void make_pose(const double* tw, double* m, double* e) {
     double r[3], rot[9];
-    for (int i = 0; i < 3; ++i) r[i] = (double)(float)tw[3 + i];
-    rodrigues(r, rot);
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) e[i * 4 + j] = (double)(float)rot[i * 3 + j];
-        e[i * 4 + 3] = (double)(float)tw[i];
-    }
+    live_extrinsic(tw, e);
     for (int i = 0; i < 3; ++i) r[i] = -tw[3 + i];
     rodrigues(r, rot);
     for (int i = 0; i < 3; ++i) {

@@ -1,6 +1,7 @@
 // Nearest-pixel TSDF value of one voxel on the typed inputs of lsf_tsdf_generate_nearest_typed (reference
 // tsdf/generation.py:130-207, :356-437; tsdf/common.py:34-47): uint16 / float32 / float64 depth, fractional array
-// offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip and the live-field stage of lsf_rigid.hip.
+// offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip, the live-field stages of lsf_rigid.hip
+// and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip).
 // The dtypes are those numpy >= 2 gives the reference's expressions (oracle: tests/rigid_restatement.py):
 //   voxel point     ((index + offset) * voxel_size) in float64, rounded to float32 (np.array(..., dtype=float32))
 //   camera point    extrinsic.dot(point): float32 or float64 as the extrinsic, ((e0 x + e1 y) + e2 z) + e3
@@ -60,6 +61,32 @@ __device__ inline float typed_tsdf_voxel(const DT* __restrict__ depth, const Typ
     if (d <= 0) return p.default_value;  // NaN goes on, as in the reference
     using S = decltype(d + pcz);
     return typed_tsdf_value<S>((S)d - (S)pcz, p.half_width);
+}
+
+// cv2.Rodrigues of a float64 rotation vector (math_utils/transformation.py::rodrigues), row-major
+__device__ inline void rodrigues(const double r[3], double rot[9]) {
+    const double theta = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    for (int i = 0; i < 9; ++i) rot[i] = i % 4 == 0 ? 1.0 : 0.0;
+    if (theta < 2.220446049250313e-16) return;
+    const double c = cos(theta), s = sin(theta), c1 = 1.0 - c, itheta = 1.0 / theta;
+    const double u[3] = {r[0] * itheta, r[1] * itheta, r[2] * itheta};
+    const double rx[9] = {0.0, -u[2], u[1], u[2], 0.0, -u[0], -u[1], u[0], 0.0};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            rot[i * 3 + j] = (c * (i == j ? 1.0 : 0.0) + c1 * (u[i] * u[j])) + s * rx[i * 3 + j];
+}
+
+// the live volume's extrinsic under a 6-DoF twist, rows 0..2 row-major: twist_vector_to_matrix3d of the float32-rounded
+// twist (Rodrigues in float64 rounded to float32, as cv2.Rodrigues on a float32 vector), held in float64.  The rigid 3-D
+// tracker (lsf_rigid3d.hip) and depth-mode fusion (lsf_fusion.hip) generate their live volumes under it.
+__device__ inline void live_extrinsic(const double* tw, double* e) {
+    double r[3], rot[9];
+    for (int i = 0; i < 3; ++i) r[i] = (double)(float)tw[3 + i];
+    rodrigues(r, rot);
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) e[i * 4 + j] = (double)(float)rot[i * 3 + j];
+        e[i * 4 + 3] = (double)(float)tw[i];
+    }
 }
 
 }  // namespace lsf

@@ -1,0 +1,126 @@
+"""Torch-facing wrapper of the fusion entry points (include/lsf_hip.h: lsf_fusion_integrate_volume,
+lsf_fusion_integrate_depth).  Every argument is checked on the host before a launch; a call enqueues two launches and
+returns the record as a device tensor without waiting for it -- the caller decides when to copy it back.  The public
+interface is fusion.CanonicalVolume / fusion.SequenceFusion3d."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import FusionParams, check, lib
+from .device_core import require_gpu, stream_ptr
+from .device_rigid import _tsdf3d, twist6
+from .tsdf.generation import offsets_of
+
+RECORD = _lib.FUSION_RECORD_DOUBLES
+RECORD_FIELDS = ("fused", "first_seen", "sum_abs_change", "max_abs_change")
+
+
+def fusion_weights(weight, max_weight):
+    """(w, max_weight) as float32 values after the rule's checks: w finite and > 0, max_weight > 0 (inf allowed)"""
+    with np.errstate(over="ignore"):
+        w, cap = np.float32(weight), np.float32(max_weight)
+    if not (np.isfinite(w) and w > 0):
+        raise ValueError("weight must be finite and > 0 as a float32, got %r" % (weight,))
+    if not cap > 0:
+        raise ValueError("max_weight must be > 0 (inf allowed), got %r" % (max_weight,))
+    return float(w), float(cap)
+
+
+def _overlap(a, b):
+    sa = a.untyped_storage().data_ptr(), a.untyped_storage().nbytes()
+    sb = b.untyped_storage().data_ptr(), b.untyped_storage().nbytes()
+    if sa[0] == sb[0]:
+        lo_a, lo_b = a.data_ptr(), b.data_ptr()
+        return lo_a < lo_b + b.numel() * b.element_size() and lo_b < lo_a + a.numel() * a.element_size()
+    return False
+
+
+def check_model(tsdf, weight, live=None):
+    """the model buffers (and a live field): float32, contiguous, on the GPU, one device, one shape, no aliasing"""
+    named = [("tsdf", tsdf), ("weight", weight)] + ([("live", live)] if live is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (name, t.dtype))
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    for name, t in named[1:]:
+        if t.device != tsdf.device:
+            raise ValueError("%s is on %s, tsdf on %s: all buffers must be on one device" % (name, t.device,
+                                                                                             tsdf.device))
+        if tuple(t.shape) != tuple(tsdf.shape):
+            raise ValueError("%s has shape %s, tsdf %s: they must have one shape" % (name, tuple(t.shape),
+                                                                                    tuple(tsdf.shape)))
+    if tsdf.numel() == 0:
+        raise ValueError("the volume is empty")
+    if _overlap(tsdf, weight):
+        raise ValueError("tsdf and weight must be distinct buffers")
+    if live is not None and (_overlap(live, tsdf) or _overlap(live, weight)):
+        raise ValueError("live must not alias tsdf or weight")
+
+
+def _params(shape, weight, max_weight):
+    p = FusionParams()
+    w, cap = fusion_weights(weight, max_weight)
+    p.weight, p.max_weight = w, cap
+    n = int(np.prod(shape))
+    if len(shape) == 3:
+        p.depth, p.height, p.width = (int(s) for s in shape)
+    else:  # the volume mode's index is flat: any shape is one run of voxels
+        p.depth, p.height, p.width = 1, 1, n
+    return p
+
+
+def _launch(fn, name, tsdf, weight, source, p, record):
+    record = torch.empty(RECORD, dtype=torch.float64, device=tsdf.device) if record is None else record
+    scratch = torch.empty(_lib.FUSION_SCRATCH_BYTES // 8, dtype=torch.float64, device=tsdf.device)
+    check(fn(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(source.data_ptr()),
+             ctypes.c_void_p(record.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()),
+          name)
+    return record
+
+
+def integrate_volume(tsdf, weight, live, w=1.0, max_weight=math.inf, record=None):
+    """fuse the live field into (tsdf, weight) in place, one launch and a finishing one; returns the record, a float64
+    device tensor of RECORD doubles (unpack_record once it is on the host)"""
+    require_gpu()
+    check_model(tsdf, weight, live)
+    p = _params(tuple(tsdf.shape), w, max_weight)
+    return _launch(lib.lsf_fusion_integrate_volume, "lsf_fusion_integrate_volume", tsdf, weight, live, p, record)
+
+
+def integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                    narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, default_value=1, record=None):
+    """generate the live volume of the device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*) under
+    twist exactly as device_rigid.live_and_gradient_3d does, and fuse it into the (Z, Y, X) model in the same pass;
+    returns the record as integrate_volume does"""
+    require_gpu()
+    check_model(tsdf, weight)
+    if tsdf.dim() != 3:
+        raise ValueError("depth mode fuses a 3-D (Z, Y, X) volume, got shape %s" % (tuple(tsdf.shape),))
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() != 2 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 2-D device tensor (tsdf.generation.device_depth)")
+    if depth.device != tsdf.device:
+        raise ValueError("depth is on %s, tsdf on %s: all buffers must be on one device" % (depth.device, tsdf.device))
+    if not voxel_size > 0:
+        raise ValueError("voxel_size must be positive")
+    p = _params(tuple(tsdf.shape), w, max_weight)
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    p.tsdf = _tsdf3d(P, camera, depth, voxel_size, narrow_band_width_voxels, default_value)
+    p.twist[:] = list(twist6(twist))
+    p.array_offset[:] = list(offsets_of(array_offset))
+    p.depth_dtype = int(depth_code)
+    return _launch(lib.lsf_fusion_integrate_depth, "lsf_fusion_integrate_depth", tsdf, weight, depth, p, record)
+
+
+def unpack_record(r):
+    """the host record (RECORD float64) as a dict: exact counts as ints, the float64 sum and the max"""
+    r = np.asarray(r, dtype=np.float64).reshape(-1)
+    return {"fused": int(r[0]), "first_seen": int(r[1]), "sum_abs_change": float(r[2]),
+            "max_abs_change": float(r[3])}

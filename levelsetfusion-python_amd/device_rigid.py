@@ -165,6 +165,21 @@ def live_and_gradient_3d(live_depth, depth_code, camera, shape, array_offset, tw
     return live, grad
 
 
+def live_volume_3d(live_depth, depth_code, camera, shape, array_offset, twist, voxel_size=0.004,
+                   narrow_band_width_voxels=20., default_value=1):
+    """(Z, Y, X) float32 device tensor: the live volume of live_and_gradient_3d alone (one launch, no gradient)"""
+    require_gpu()
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    p = _params3d(shape, array_offset, voxel_size)
+    p.tsdf = _tsdf3d(P, camera, live_depth, voxel_size, narrow_band_width_voxels, default_value)
+    p.twist[:] = list(twist6(twist))
+    p.depth_dtype = int(depth_code)
+    live = torch.empty((p.depth, p.height, p.width), dtype=torch.float32, device="cuda")
+    check(lib.lsf_rigid3d_gradient(None, ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(live.data_ptr()),
+                                   None, ctypes.byref(p), stream_ptr()), "lsf_rigid3d_gradient")
+    return live
+
+
 def rigid_run_3d(canonical, live_depth, depth_code, camera, array_offset, iterations, rate, eta, voxel_size,
                  generator_voxel_size, narrow_band_width_voxels, default_value=1, twist=None):
     """the whole 6-DoF optimize() enqueued: iterations + 1 launches and one copy back.  canonical: float32 volume

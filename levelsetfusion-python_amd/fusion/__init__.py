@@ -1,0 +1,143 @@
+"""Fusion of tracked depth frames into a canonical TSDF volume: the model update of KillingFusion / SobolevFusion, which
+the reference does not have.  INTEGRATION.md section 3 ("Fusion") defines the rule; tests/fusion_restatement.py
+restates it in numpy.
+
+CanonicalVolume holds the model, two float32 device arrays of one shape: `tsdf` (starts at 1) and `weight` (starts at
+0).  A frame's live value l at a voxel is fused when -1 < l < 1, strictly:
+    W1 = W + w,  tsdf = (W t + w l) / W1,  weight = min(W1, max_weight)
+in float32, the average taken with the uncapped W1; every other voxel keeps its tsdf and weight bit for bit.  Each
+integrate_* call is two launches of csrc/lsf_fusion.hip and returns the call's record as a float64 device tensor
+(unpack_record turns a host copy into {fused, first_seen, sum_abs_change, max_abs_change}); nothing waits for the GPU.
+
+SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
+first tracked against the model by the 6-DoF rigid tracker, started from the previous frame's twist
+(device_rigid.rigid_run_3d, `rigid_iterations` iterations; 0 keeps the previous twist).  Without a non-rigid optimizer
+the frame is then fused in depth mode under its twist: one launch pair, no live volume.  With one (a
+SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is generated,
+warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
+
+Host synchronisations per frame: the rigid run's one copy back (frames >= 1 with rigid_iterations > 0), the non-rigid
+optimize()'s own (when one is given), and one read of the fusion record.
+
+Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
+field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
+fusion, a 2-D depth-mode row generator, and HierarchicalOptimizer3d as the non-rigid step."""
+import math
+
+import numpy as np
+import torch
+
+from .. import device_fusion, device_rigid
+from ..device_core import require_gpu
+from ..device_fusion import RECORD_FIELDS, unpack_record
+from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
+from ..tsdf.generation import device_depth
+
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS"]
+
+
+def _model_shape(shape):
+    s = (int(shape),) * 3 if np.ndim(shape) == 0 else tuple(int(v) for v in shape)
+    if len(s) not in (2, 3) or min(s) < 1:
+        raise ValueError("a canonical volume has two or three extents >= 1, got %s" % (s,))
+    return s
+
+
+def _live(live):
+    if isinstance(live, torch.Tensor):
+        return live if live.is_cuda else live.to("cuda")
+    a = np.asarray(live)
+    if a.dtype.kind not in "fiub":
+        raise ValueError("live must be numeric, got %s" % a.dtype)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda")
+
+
+class CanonicalVolume:
+    """the weighted canonical TSDF: `tsdf` and `weight`, float32 device tensors of `shape` ((Z, Y, X), (H, W) or an
+    int for a cube).  Depth mode needs a 3-D volume."""
+
+    def __init__(self, shape, max_weight=math.inf):
+        require_gpu()
+        self.shape = _model_shape(shape)
+        device_fusion.fusion_weights(1.0, max_weight)
+        self.max_weight = max_weight
+        self.tsdf = torch.ones(self.shape, dtype=torch.float32, device="cuda")
+        self.weight = torch.zeros(self.shape, dtype=torch.float32, device="cuda")
+
+    def reset(self):
+        """back to the empty model: tsdf 1, weight 0 everywhere"""
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+
+    def integrate_volume(self, live, weight=1.0):
+        """fuse a live field of the model's shape (numpy or a float32 device tensor); returns the device record"""
+        return device_fusion.integrate_volume(self.tsdf, self.weight, _live(live), weight, self.max_weight)
+
+    def integrate_depth(self, depth_image, camera, twist, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
+                        weight=1.0):
+        """generate the live volume of depth_image (uint16 / float32 / float64, numpy or device) under twist, as the
+        rigid tracker does, and fuse it in the same pass; returns the device record"""
+        depth, code = device_depth(depth_image)
+        return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
+                                             voxel_size, narrow_band_width_voxels, weight, self.max_weight)
+
+
+class SequenceFusion3d:
+    """track each depth frame against the model and fuse it (module docstring).  Keeps `canonical` (the
+    CanonicalVolume), `twists` (one float64 (6,) per frame) and `frame_records` (one dict per frame: frame, twist,
+    rigid_records, nonrigid, fusion)."""
+
+    def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
+                 max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
+                 initial_twist=None):
+        self.camera = camera
+        self.field_shape = device_rigid.volume_shape(field_shape)
+        self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
+        if self.array_offset.size != 3:
+            raise ValueError("array_offset must have 3 entries, got %d" % self.array_offset.size)
+        if not voxel_size > 0 or not narrow_band_width_voxels > 0:
+            raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
+        if int(rigid_iterations) < 0:
+            raise ValueError("rigid_iterations must be >= 0")
+        self.voxel_size = voxel_size
+        self.narrow_band_width_voxels = narrow_band_width_voxels
+        self.rigid_iterations = int(rigid_iterations)
+        self.rigid_rate = rigid_rate
+        self.eta = eta
+        self.nonrigid_optimizer = nonrigid_optimizer
+        self.initial_twist = np.zeros(6) if initial_twist is None else device_rigid.twist6(initial_twist).copy()
+        self.canonical = CanonicalVolume(self.field_shape, max_weight)
+        self.twists = []
+        self.frame_records = []
+
+    def integrate(self, depth_image):
+        """track and fuse one frame; returns its record (also appended to frame_records)"""
+        k = len(self.twists)
+        depth, code = device_depth(depth_image)
+        model = self.canonical
+        rigid_records, nonrigid = [], None
+        gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
+        if k == 0:
+            twist = self.initial_twist.copy()
+        else:
+            twist = self.twists[-1].copy()
+            if self.rigid_iterations > 0:
+                twist, records = device_rigid.rigid_run_3d(
+                    model.tsdf, depth, code, self.camera, self.array_offset, self.rigid_iterations, self.rigid_rate,
+                    self.eta, self.voxel_size, self.voxel_size, self.narrow_band_width_voxels, twist=twist)
+                rigid_records = [unpack_rigid_record(r) for r in records]
+        if k == 0 or self.nonrigid_optimizer is None:
+            record = device_fusion.integrate_depth(model.tsdf, model.weight, depth, code, self.camera,
+                                                   self.array_offset, twist, w=1.0, max_weight=model.max_weight, **gen)
+        else:
+            live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
+                                               **gen)
+            self.nonrigid_optimizer.optimize(live, model.tsdf)
+            nonrigid = self.nonrigid_optimizer.engine.last_call
+            record = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0, model.max_weight)
+        frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
+                 "rigid_records": rigid_records, "nonrigid": nonrigid,
+                 "fusion": unpack_record(record.cpu().numpy())}
+        self.twists.append(frame["twist"].copy())
+        self.frame_records.append(frame)
+        return frame
