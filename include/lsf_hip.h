@@ -1018,6 +1018,39 @@ int lsf_fusion_integrate_volume(float *tsdf, float *weight, const float *live, d
 int lsf_fusion_integrate_depth(float *tsdf, float *weight, const void *depth_image, double *record, void *scratch,
                                const lsf_fusion_params *params, void *stream);
 
+/* ---- ray-casting the canonical TSDF into a depth (and normal) image -------------------------------------------------
+ * The reference has no ray-caster; the arithmetic is this project's ("Ray-casting"), every
+ * step one float64 operation.  The camera is the generator's: E = twist_vector_to_matrix3d of the float32-rounded
+ * twist (lsf_fusion_integrate_depth's), world -> camera.  Pixel (u, v) casts the ray s ((u - cx) / fx, (v - cy) / fy, 1)
+ * from the camera centre; voxel (i, j, k) of the [z][y][x] volume sits at ((k, j, i) + offset) * voxel_size.  The ray
+ * is clipped to the box of valid sample positions and sampled at s = m * voxel_size / LSF_RAYCAST_STEPS_PER_VOXEL
+ * (camera z, m >= 1 an integer).  A sample is trilinear in tsdf and valid only when all 8 corner weights are > 0.  The
+ * surface is the first step whose previous sample is valid and > 0 and whose own sample is valid and <= 0; the depth is
+ * refined linearly between the two.  One lane per pixel; a workgroup covers LSF_RAYCAST_TILE x LSF_RAYCAST_TILE pixels,
+ * each wave an 8 x 8 block of them.  No host synchronisation. */
+typedef struct lsf_raycast_params {
+    double fx, fy, cx, cy;             /* intrinsics, pixels; finite, fx and fy non-zero */
+    double depth_unit_ratio;           /* metres per unit of the fallback image (ignored without one) */
+    double voxel_size;                 /* metres, finite and > 0 */
+    double offset_x, offset_y, offset_z; /* array offset, voxels, fractional allowed */
+    double t_x, t_y, t_z, r_x, r_y, r_z; /* the camera's twist, float64 (rounded to float32 as the generator does) */
+    int32_t depth, height, width;      /* volume extents z, y, x, >= 2 each */
+    int32_t image_height, image_width; /* output extents, >= 1 each, at most 2^31 - 1 pixels */
+    int32_t fallback_dtype;            /* LSF_DEPTH_* of fallback_depth (ignored when it is NULL) */
+} lsf_raycast_params;
+#define LSF_RAYCAST_STEPS_PER_VOXEL 2
+#define LSF_RAYCAST_TILE 16
+
+/* tsdf, weight: DEVICE float32 [depth][height][width], two distinct buffers, read only.  depth_out: DEVICE float32
+ * [image_height][image_width], camera z of the hit in metres, 0 where a ray hits nothing.  normals_out: NULL, or DEVICE
+ * float32 [image_height][image_width][3], the unit normal in camera coordinates (central differences of trilinear
+ * samples one voxel apart), 0 where there is no hit or a difference sample is invalid.  fallback_depth: NULL, or DEVICE
+ * [image_height][image_width] of fallback_dtype; where a ray hits nothing its value times depth_unit_ratio is written
+ * (float32 depth scaled in float32, uint16 and float64 in float64).  hit_count: NULL, or DEVICE one uint64 to which the
+ * number of hit pixels is ADDED (exact).  No output may alias an input or another output. */
+int lsf_raycast(const float *tsdf, const float *weight, const void *fallback_depth, float *depth_out, float *normals_out,
+                uint64_t *hit_count, const lsf_raycast_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

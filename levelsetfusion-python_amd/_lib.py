@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "bc02ed0838831b36"
+HEADER_ABI_HASH = "3f118f4bbd4896fa"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -202,6 +202,18 @@ class FusionParams(ctypes.Structure):
                 ("weight", ctypes.c_float), ("max_weight", ctypes.c_float), ("depth_dtype", ctypes.c_int32)]
 
 
+RAYCAST_STEPS_PER_VOXEL = 2
+RAYCAST_TILE = 16
+
+
+class RaycastParams(ctypes.Structure):
+    """lsf_raycast_params: ray-casting the canonical TSDF (lsf_raycast)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_unit_ratio", "voxel_size", "offset_x",
+                                               "offset_y", "offset_z", "t_x", "t_y", "t_z", "r_x", "r_y", "r_z")] + \
+               [(n, ctypes.c_int32) for n in ("depth", "height", "width", "image_height", "image_width",
+                                              "fallback_dtype")]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -314,6 +326,7 @@ PROTOTYPES = {
     "lsf_rigid3d_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
     "lsf_fusion_integrate_volume": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
     "lsf_fusion_integrate_depth": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
+    "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
 }
 
 

@@ -1,0 +1,82 @@
+"""Torch-facing wrapper of the ray-caster (include/lsf_hip.h: lsf_raycast).  Every argument is checked on the host
+before the launch; a call enqueues one launch and returns device tensors without waiting.  The public interface is
+fusion.CanonicalVolume.raycast; fusion.SequenceFusion3d(tracking_reference="raycast") tracks against its output."""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import RaycastParams, check, lib
+from .device_core import require_gpu, stream_ptr
+from .device_fusion import check_model
+from .device_rigid import twist6
+from .tsdf.generation import offsets_of
+
+
+def image_extents(image_shape):
+    s = tuple(int(v) for v in image_shape)
+    if len(s) != 2 or min(s) < 1 or s[0] * s[1] > 0x7fffffff:
+        raise ValueError("image_shape must be (height, width) with extents >= 1, got %s" % (tuple(image_shape),))
+    return s
+
+
+def params(shape, camera, twist, array_offset, voxel_size, image_shape, fallback_code=None):
+    """the lsf_raycast_params of a call, after the host checks"""
+    if len(shape) != 3 or min(shape) < 2:
+        raise ValueError("ray-casting needs a 3-D (Z, Y, X) volume of extents >= 2, got shape %s" % (tuple(shape),))
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    p = RaycastParams()
+    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
+    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
+        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    p.depth_unit_ratio = float(camera.depth_unit_ratio)
+    p.voxel_size = float(voxel_size)
+    if not (np.isfinite(p.voxel_size) and p.voxel_size > 0):
+        raise ValueError("voxel_size must be finite and positive")
+    p.offset_x, p.offset_y, p.offset_z = (float(v) for v in offsets_of(array_offset))
+    p.t_x, p.t_y, p.t_z, p.r_x, p.r_y, p.r_z = (float(v) for v in twist6(twist))
+    if not np.all(np.isfinite([p.offset_x, p.offset_y, p.offset_z, p.t_x, p.t_y, p.t_z, p.r_x, p.r_y, p.r_z])):
+        raise ValueError("array_offset and twist must be finite")
+    p.depth, p.height, p.width = (int(v) for v in shape)
+    p.image_height, p.image_width = image_extents(image_shape)
+    if fallback_code is not None:
+        if not np.isfinite(p.depth_unit_ratio):
+            raise ValueError("the camera's depth_unit_ratio must be finite")
+        p.fallback_dtype = int(fallback_code)
+    return p
+
+
+def raycast(tsdf, weight, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
+            fallback_depth=None, fallback_code=None, hit_count=None):
+    """one launch of lsf_raycast on the (Z, Y, X) model.  fallback_depth: a contiguous device depth image of
+    image_shape (tsdf.generation.device_depth) and its LSF_DEPTH_* code, scaled by camera.depth_unit_ratio where a ray
+    hits nothing.  hit_count: a device int64 tensor of one element the hit count is added to, or None for a fresh
+    one.  Returns (depth (H, W), normals (H, W, 3) or None, hit_count) as device tensors; nothing waits."""
+    require_gpu()
+    check_model(tsdf, weight)
+    p = params(tuple(tsdf.shape), camera, twist, array_offset, voxel_size, image_shape,
+               None if fallback_depth is None else fallback_code)
+    h, w = p.image_height, p.image_width
+    if fallback_depth is not None:
+        if fallback_code is None:
+            raise ValueError("fallback_depth needs its LSF_DEPTH_* code (tsdf.generation.device_depth)")
+        if not isinstance(fallback_depth, torch.Tensor) or not fallback_depth.is_cuda or \
+                not fallback_depth.is_contiguous():
+            raise ValueError("fallback_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+        if tuple(fallback_depth.shape) != (h, w):
+            raise ValueError("fallback_depth has shape %s, the image %s" % (tuple(fallback_depth.shape), (h, w)))
+        if fallback_depth.device != tsdf.device:
+            raise ValueError("fallback_depth is on %s, tsdf on %s" % (fallback_depth.device, tsdf.device))
+    if hit_count is None:
+        hit_count = torch.zeros(1, dtype=torch.int64, device=tsdf.device)
+    elif not (isinstance(hit_count, torch.Tensor) and hit_count.is_cuda and hit_count.dtype == torch.int64 and
+              hit_count.numel() == 1):
+        raise ValueError("hit_count must be a device int64 tensor of one element")
+    depth = torch.empty((h, w), dtype=torch.float32, device=tsdf.device)
+    out_normals = torch.empty((h, w, 3), dtype=torch.float32, device=tsdf.device) if normals else None
+    check(lib.lsf_raycast(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()),
+                          None if fallback_depth is None else ctypes.c_void_p(fallback_depth.data_ptr()),
+                          ctypes.c_void_p(depth.data_ptr()),
+                          None if out_normals is None else ctypes.c_void_p(out_normals.data_ptr()),
+                          ctypes.c_void_p(hit_count.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_raycast")
+    return depth, out_normals, hit_count

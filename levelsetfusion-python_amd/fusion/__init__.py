@@ -8,32 +8,45 @@ CanonicalVolume holds the model, two float32 device arrays of one shape: `tsdf` 
 in float32, the average taken with the uncapped W1; every other voxel keeps its tsdf and weight bit for bit.  Each
 integrate_* call is two launches of csrc/lsf_fusion.hip and returns the call's record as a float64 device tensor
 (unpack_record turns a host copy into {fused, first_seen, sum_abs_change, max_abs_change}); nothing waits for the GPU.
+CanonicalVolume.raycast renders the model into a depth (and normal) image seen from a camera at a twist: one launch of
+csrc/lsf_raycast.hip ("Ray-casting"; tests/raycast_restatement.py restates it).
 
 SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
-first tracked against the model by the 6-DoF rigid tracker, started from the previous frame's twist
-(device_rigid.rigid_run_3d, `rigid_iterations` iterations; 0 keeps the previous twist).  Without a non-rigid optimizer
-the frame is then fused in depth mode under its twist: one launch pair, no live volume.  With one (a
-SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is generated,
-warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
+first tracked by the 6-DoF rigid tracker, started from the previous frame's twist (device_rigid.rigid_run_3d,
+`rigid_iterations` iterations; 0 keeps the previous twist), against a reference volume chosen by `tracking_reference`:
+    "model"    the model's tsdf itself (the default)
+    "raycast"  the live volume, under the previous twist, of the model ray-cast at the previous twist with the holes
+               filled from the previous frame's depth -- KillingFusion-style tracking against the model's prediction.
+               Voxels behind the fused band keep the model's initial +1, where a frame has -1; tracking against the
+               model itself meets that residual at every band's back edge, and the prediction does not have it.
+Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
+With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
+generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
 
-Host synchronisations per frame: the rigid run's one copy back (frames >= 1 with rigid_iterations > 0), the non-rigid
-optimize()'s own (when one is given), and one read of the fusion record.
+Host synchronisations per frame: the rigid run's one copy back (frames >= 1 with rigid_iterations > 0; in "raycast"
+mode it also brings the prediction's hit count), the non-rigid optimize()'s own (when one is given), and one read of
+the fusion record.
 
 Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
 field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
-fusion, a 2-D depth-mode row generator, and HierarchicalOptimizer3d as the non-rigid step."""
+fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, frame-to-model tracking with
+the prediction's normals (point-to-plane ICP), an adaptive ray-casting step, and a colour or confidence image in the
+prediction."""
 import math
 
 import numpy as np
 import torch
 
-from .. import device_fusion, device_rigid
+from .. import device_fusion, device_raycast, device_rigid
 from ..device_core import require_gpu
 from ..device_fusion import RECORD_FIELDS, unpack_record
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
-from ..tsdf.generation import device_depth
+from .._lib import DEPTH_F32
+from ..tsdf.generation import DepthCamera, device_depth
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS"]
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS", "TRACKING_REFERENCES"]
+
+TRACKING_REFERENCES = ("model", "raycast")
 
 
 def _model_shape(shape):
@@ -81,15 +94,32 @@ class CanonicalVolume:
         return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
                                              voxel_size, narrow_band_width_voxels, weight, self.max_weight)
 
+    def raycast(self, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
+                fallback_depth=None, as_tensor=False):
+        """the model seen from a pinhole camera at twist (the generator's convention: twist_vector_to_matrix3d of the
+        float32-rounded twist maps world to camera): float32 depth (H, W) in metres, 0 where a ray hits nothing, and
+        with normals=True the unit normals (H, W, 3) in camera coordinates.  fallback_depth (uint16 / float32 /
+        float64, numpy or device, scaled by camera.depth_unit_ratio) fills the pixels without a hit.  Returns depth or
+        (depth, normals): device tensors with as_tensor=True, enqueued without waiting; numpy copies otherwise."""
+        fb, code = (None, None) if fallback_depth is None else device_depth(fallback_depth)
+        depth, out_normals, _ = device_raycast.raycast(self.tsdf, self.weight, camera, twist, array_offset, voxel_size,
+                                                       image_shape, normals, fb, code)
+        out = (depth, out_normals) if normals else (depth,)
+        if not as_tensor:
+            out = tuple(t.cpu().numpy() for t in out)
+        return out if normals else out[0]
+
 
 class SequenceFusion3d:
-    """track each depth frame against the model and fuse it (module docstring).  Keeps `canonical` (the
-    CanonicalVolume), `twists` (one float64 (6,) per frame) and `frame_records` (one dict per frame: frame, twist,
-    rigid_records, nonrigid, fusion)."""
+    """track each depth frame against the model (tracking_reference "model") or its ray-cast prediction ("raycast")
+    and fuse it (module docstring).  Keeps `canonical` (the CanonicalVolume), `twists` (one float64 (6,) per frame),
+    `frame_records` (one dict per frame: frame, twist, rigid_records, nonrigid, fusion, prediction_hits -- the pixels
+    of the prediction that hit the model, None without a prediction) and, in "raycast" mode, `prediction` (the last
+    predicted depth image, a float32 device tensor in metres)."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
-                 initial_twist=None):
+                 initial_twist=None, tracking_reference="model"):
         self.camera = camera
         self.field_shape = device_rigid.volume_shape(field_shape)
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
@@ -99,6 +129,8 @@ class SequenceFusion3d:
             raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
         if int(rigid_iterations) < 0:
             raise ValueError("rigid_iterations must be >= 0")
+        if tracking_reference not in TRACKING_REFERENCES:
+            raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_REFERENCES, tracking_reference))
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -106,26 +138,48 @@ class SequenceFusion3d:
         self.eta = eta
         self.nonrigid_optimizer = nonrigid_optimizer
         self.initial_twist = np.zeros(6) if initial_twist is None else device_rigid.twist6(initial_twist).copy()
+        self.tracking_reference = tracking_reference
         self.canonical = CanonicalVolume(self.field_shape, max_weight)
         self.twists = []
         self.frame_records = []
+        self.prediction = None  # "raycast": the last prediction, a float32 device depth image in metres
+        self._previous = None  # "raycast": the previous frame's (device depth, LSF_DEPTH_* code)
+        P = camera.intrinsics.intrinsic_matrix
+        # the prediction is in metres: its live volume is generated with ratio 1
+        self._metric_camera = DepthCamera(intrinsics=DepthCamera.Intrinsics(intrinsic_matrix=P), depth_unit_ratio=1.0)
+
+    def _prediction_volume(self, twist):
+        """the live volume under twist of the model ray-cast at twist, holes filled from the previous frame; and the
+        prediction's device hit count"""
+        previous, code = self._previous
+        model = self.canonical
+        self.prediction, _, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
+                                                          self.array_offset, self.voxel_size, tuple(previous.shape),
+                                                          fallback_depth=previous, fallback_code=code)
+        live = device_rigid.live_volume_3d(self.prediction, DEPTH_F32, self._metric_camera, self.field_shape,
+                                           self.array_offset, twist, self.voxel_size, self.narrow_band_width_voxels)
+        return live, hits
 
     def integrate(self, depth_image):
         """track and fuse one frame; returns its record (also appended to frame_records)"""
         k = len(self.twists)
         depth, code = device_depth(depth_image)
         model = self.canonical
-        rigid_records, nonrigid = [], None
+        rigid_records, nonrigid, hits = [], None, None
         gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
         if k == 0:
             twist = self.initial_twist.copy()
         else:
             twist = self.twists[-1].copy()
             if self.rigid_iterations > 0:
+                reference = model.tsdf
+                if self.tracking_reference == "raycast":
+                    reference, hits = self._prediction_volume(twist)
                 twist, records = device_rigid.rigid_run_3d(
-                    model.tsdf, depth, code, self.camera, self.array_offset, self.rigid_iterations, self.rigid_rate,
+                    reference, depth, code, self.camera, self.array_offset, self.rigid_iterations, self.rigid_rate,
                     self.eta, self.voxel_size, self.voxel_size, self.narrow_band_width_voxels, twist=twist)
                 rigid_records = [unpack_rigid_record(r) for r in records]
+                del reference
         if k == 0 or self.nonrigid_optimizer is None:
             record = device_fusion.integrate_depth(model.tsdf, model.weight, depth, code, self.camera,
                                                    self.array_offset, twist, w=1.0, max_weight=model.max_weight, **gen)
@@ -137,7 +191,10 @@ class SequenceFusion3d:
             record = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0, model.max_weight)
         frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
-                 "fusion": unpack_record(record.cpu().numpy())}
+                 "fusion": unpack_record(record.cpu().numpy()),
+                 "prediction_hits": None if hits is None else int(hits.item())}
+        if self.tracking_reference == "raycast":
+            self._previous = (depth, code)
         self.twists.append(frame["twist"].copy())
         self.frame_records.append(frame)
         return frame
