@@ -13,7 +13,7 @@ SOURCES = ["lsf_fields.hip", "lsf_hierarchical.hip", "lsf_slavcheva.hip", "lsf_s
            "lsf_terms.hip", "lsf_rigid.hip", "lsf_rigid3d.hip", "lsf_fusion.hip",
            "lsf_raycast.hip"]
 HEADERS = ["lsf_device.h", "lsf_slavcheva_terms.h", "lsf_slavcheva_state_taps.h", "lsf_tsdf_typed.h",
-           os.path.join("..", "..", "include", "lsf_hip.h")]
+           "lsf_rigid_solve.h", os.path.join("..", "..", "include", "lsf_hip.h")]
 ABI_HEADER = os.path.join(PKG_DIR, "..", "include", "lsf_hip.h")
 # -ffp-contract=off: multiply and add stay separately rounded so that results are bit-identical to the numpy
 # oracle (numpy never fuses); the path is HBM/L1-bound, the lost FMAs do not show.

@@ -3,12 +3,15 @@
 // section 3, "Fusion"; tests/fusion_restatement.py restates it).  One kernel, two live sources, one update:
 //   VOLUME  the live value of a voxel is read from a given float32 field (flat index, 16-byte accesses per lane)
 //   DEPTH   the live value is generated from a depth image under a twist by the rigid 3-D tracker's own code
-//           (live_extrinsic + typed_tsdf_voxel, lsf_tsdf_typed.h) and fused in the same pass; no live volume is written
+//           (live_extrinsic + typed_tsdf_voxel, lsf_tsdf_typed.h, with its host setup and dispatch) and fused in the
+//           same pass; no live volume is written
 // Every lane takes four consecutive voxels per step of a grid-stride loop; the grid depends on the voxel count alone,
 // so both sources visit the voxels in one order and sum the record identically.  Per-workgroup partials go to
-// scratch; a finishing one-workgroup launch combines them in a fixed order: no atomics, reruns are bit-identical.
+// scratch; a finishing one-workgroup launch combines them in a fixed order (the sums by the trackers' butterfly,
+// wave_sum_xor in lsf_rigid_solve.h): no atomics, reruns are bit-identical.
 // -ffp-contract=off keeps W t + w l two roundings and an add, as numpy computes it.
 #include "lsf_device.h"
+#include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
 
 using namespace lsf;
@@ -83,12 +86,6 @@ __device__ inline float depth_voxel(const DT* __restrict__ depth, const FusionDe
     return typed_tsdf_voxel<3, double, PT, DT>(depth, p.t, e, x, y, z);
 }
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __device__ inline float wave_max(float v) {
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {
@@ -102,7 +99,7 @@ __device__ inline float wave_max(float v) {
 __device__ inline void block_combine(double (&v)[kParts], double (*red)[kParts]) {
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = wave_sum(v[c]);
+    for (int c = 0; c < 3; ++c) v[c] = wave_sum_xor(v[c]);
     v[3] = (double)wave_max((float)v[3]);
     if (lane == 0)
 #pragma unroll
@@ -191,14 +188,7 @@ int convert(const lsf_fusion_params* params, FusionDev& p) {
     if (params->depth < 1 || params->height < 1 || params->width < 1) return LSF_ERR_BAD_ARGUMENT;
     const float w = params->weight, cap = params->max_weight;
     if (!(w > 0.0f) || !std::isfinite(w) || !(cap > 0.0f)) return LSF_ERR_BAD_ARGUMENT;
-    const lsf_tsdf_params& t = params->tsdf;
-    p.t.fx = t.intrinsics[0]; p.t.fy = t.intrinsics[1]; p.t.cx = t.intrinsics[2]; p.t.cy = t.intrinsics[3];
-    p.t.depth_unit_ratio = t.depth_unit_ratio;
-    p.t.voxel_size = t.voxel_size;
-    p.t.half_width = t.narrow_band_half_width;
-    for (int i = 0; i < 3; ++i) p.t.off[i] = params->array_offset[i];
-    p.t.width = t.image_width; p.t.height = t.image_height; p.t.image_y = 0;
-    p.t.default_value = t.default_value;
+    p.t = typed_tsdf(params->tsdf, params->array_offset, 0);
     for (int i = 0; i < 6; ++i) p.twist[i] = params->twist[i];
     p.n = (long long)params->depth * params->height * params->width;
     p.groups = p.n / 4;
@@ -248,23 +238,12 @@ extern "C" int lsf_fusion_integrate_depth(float* tsdf, float* weight, const void
     if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
     FusionDev p;
     if (int e = convert(params, p)) return e;
-    const lsf_tsdf_params& t = params->tsdf;
-    const int32_t dt = params->depth_dtype;
-    if (dt != LSF_DEPTH_U16 && dt != LSF_DEPTH_F32 && dt != LSF_DEPTH_F64) return LSF_ERR_BAD_ARGUMENT;
-    if (!(t.image_width > 0 && t.image_height > 0 && t.narrow_band_half_width > 0.0 &&
-          (long long)t.image_width * t.image_height <= 0x7fffffffll))
+    if (!depth_dtype_ok(params->depth_dtype) || !typed_tsdf_ok(params->tsdf, false, true))
         return LSF_ERR_BAD_ARGUMENT;
     p.aligned = aligned16(tsdf) && aligned16(weight);
     hipStream_t s = as_stream(stream);
     double* sc = reinterpret_cast<double*>(scratch);
-    // one instantiation per (depth dtype, intrinsics dtype), as lsf_rigid3d.hip
-    const float* none = nullptr;
-    if (t.intrinsics_are_f32) {
-        if (dt == LSF_DEPTH_U16) return launch<DEPTH, unsigned short, float>(tsdf, weight, none, depth_image, record, sc, p, s);
-        if (dt == LSF_DEPTH_F32) return launch<DEPTH, float, float>(tsdf, weight, none, depth_image, record, sc, p, s);
-        return launch<DEPTH, double, float>(tsdf, weight, none, depth_image, record, sc, p, s);
-    }
-    if (dt == LSF_DEPTH_U16) return launch<DEPTH, unsigned short, double>(tsdf, weight, none, depth_image, record, sc, p, s);
-    if (dt == LSF_DEPTH_F32) return launch<DEPTH, float, double>(tsdf, weight, none, depth_image, record, sc, p, s);
-    return launch<DEPTH, double, double>(tsdf, weight, none, depth_image, record, sc, p, s);
+    return dispatch_typed(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch<DEPTH, decltype(dt), decltype(pt)>(tsdf, weight, nullptr, depth_image, record, sc, p, s);
+    });
 }

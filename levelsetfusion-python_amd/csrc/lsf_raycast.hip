@@ -183,11 +183,8 @@ int convert(const lsf_raycast_params* q, bool with_fallback, RayDev& p) {
     for (double x : all)
         if (!finite(x)) return LSF_ERR_BAD_ARGUMENT;
     if (q->fx == 0.0 || q->fy == 0.0 || !(q->voxel_size > 0.0)) return LSF_ERR_BAD_ARGUMENT;
-    if (with_fallback) {
-        const int32_t dt = q->fallback_dtype;
-        if (dt != LSF_DEPTH_U16 && dt != LSF_DEPTH_F32 && dt != LSF_DEPTH_F64) return LSF_ERR_BAD_ARGUMENT;
-        if (!finite(q->depth_unit_ratio)) return LSF_ERR_BAD_ARGUMENT;
-    }
+    if (with_fallback && (!depth_dtype_ok(q->fallback_dtype) || !finite(q->depth_unit_ratio)))
+        return LSF_ERR_BAD_ARGUMENT;
     p.fx = q->fx; p.fy = q->fy; p.cx = q->cx; p.cy = q->cy;
     p.ratio = q->depth_unit_ratio;
     p.voxel = q->voxel_size;
@@ -243,9 +240,7 @@ extern "C" int lsf_raycast(const float* tsdf, const float* weight, const void* f
     const Volume vol{tsdf, weight, params->width, params->height, params->depth};
     hipStream_t s = as_stream(stream);
     if (!fallback_depth) return launch<float>(vol, nullptr, depth_out, normals_out, hit_count, p, s);
-    if (params->fallback_dtype == LSF_DEPTH_U16)
-        return launch<unsigned short>(vol, fallback_depth, depth_out, normals_out, hit_count, p, s);
-    if (params->fallback_dtype == LSF_DEPTH_F32)
-        return launch<float>(vol, fallback_depth, depth_out, normals_out, hit_count, p, s);
-    return launch<double>(vol, fallback_depth, depth_out, normals_out, hit_count, p, s);
+    return dispatch_depth(params->fallback_dtype, [&](auto dt) {
+        return launch<decltype(dt)>(vol, fallback_depth, depth_out, normals_out, hit_count, p, s);
+    });
 }

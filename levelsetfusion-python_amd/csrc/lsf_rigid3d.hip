@@ -1,17 +1,18 @@
 // SDF-2-SDF rigid 3-D tracker, 6-DoF (include/lsf_hip.h, lsf_rigid3d_*): the reference's 2-D algorithm
 // (rigid_opt/sdf_2_sdf_optimizer2d.py:60-137, rigid_opt/sdf_gradient_field.py:13-38) lifted to a volume, with the dtypes
-// of lsf_rigid.hip.  One kernel, three modes, as the 2-D one:
+// of lsf_rigid.hip.  One kernel, three modes, as the 2-D one (RigidMode, lsf_rigid_solve.h):
 //   GRADIENT  the twist gradient of a given live volume, or of the live volume generated under a given twist (one launch)
-//   ITERATE   iteration k of optimize(): prologue = combine iteration k-1's per-block partial sums (fixed order, the
-//             same in every block), singular test, 6x6 solve and update -- every block computes the same twist bit for
-//             bit, block 0 writes record k-1; body = march a 16 x 16 x-y tile plus a one-voxel halo along z through a
-//             ring of planes in LDS, generating one new live plane per step under the pose, np.gradient, twist
-//             gradient, and the 28 float64 sums of A, b and the energy kept in registers; one wave / block reduction at
-//             the end into this block's partial (ping-pong buffer k & 1)
+//   ITERATE   iteration k of optimize(): prologue = rigid_prologue<6> (combine iteration k-1's per-block partial sums,
+//             singular test, 6x6 solve and update -- every block computes the same twist bit for bit, block 0 writes
+//             record k-1); body = march a 16 x 16 x-y tile plus a one-voxel halo along z through a ring of planes in
+//             LDS, generating one new live plane per step under the pose, np.gradient, twist gradient, and the 28
+//             float64 sums of A, b and the energy kept in registers; one wave / block reduction at the end into this
+//             block's partial (ping-pong buffer k & 1)
 //   FINISH    the prologue alone for the last iteration, one block; writes the final twist
-// The partials cross a launch boundary only: no atomics, no in-launch hand-off, so a run is bit-reproducible.  Per-voxel
-// arithmetic is bit-identical to tests/rigid3d_restatement.py under -ffp-contract=off; the sums are tree reductions.
+// Per-voxel arithmetic is bit-identical to tests/rigid3d_restatement.py under -ffp-contract=off; the sums are tree
+// reductions.
 #include "lsf_device.h"
+#include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
 
 using namespace lsf;
@@ -21,15 +22,11 @@ namespace {
 constexpr int kRT = 16;          // tile edge: 16 x 16 voxels = one thread each
 constexpr int kRH = kRT + 2;     // with the one-voxel halo
 constexpr int kSlots = 4;        // ring of live planes: z - 1, z, z + 1 and the one being generated
-constexpr int kSums = 28;        // A's upper triangle (21, row by row), b (6), energy
-constexpr int kRec = LSF_RIGID3D_RECORD_DOUBLES;
-constexpr int kMaxBlocks = LSF_RIGID3D_MAX_BLOCKS;
+constexpr int kSums = RigidLayout<6>::kSums;  // A's upper triangle (21, row by row), b (6), energy
+constexpr int kMaxBlocks = RigidLayout<6>::kMaxBlocks;
 constexpr int kMinChunk = 4;     // the shortest z run of one work item (2 halo planes per run)
 static_assert(kBlock == kRT * kRT, "one thread per tile voxel");
-static_assert(kMaxBlocks <= kBlock, "the prologue gives every partial one thread");
 static_assert(kRH * kRH <= 2 * kBlock, "a plane with its halo is generated in two passes");
-
-enum Mode { GRADIENT = 0, ITERATE = 1, FINISH = 2 };
 
 struct Rigid3dDev {
     TypedTsdf t;
@@ -44,118 +41,6 @@ struct Rigid3dDev {
     int items;              // tiles_xy * ceil(nz / zc): (tile, z-chunk) pairs, item = chunk * tiles_xy + tile
     int nblocks;            // the grid: min(items, kMaxBlocks), the number of partials
 };
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sums of v[] over the block in a fixed order; the totals land in thread 0's v[]
-__device__ inline void block_sum(double (&v)[kSums], double (*red)[kSums]) {
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int c = 0; c < kSums; ++c) v[c] = wave_sum(v[c]);
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < kSums; ++c) red[wave][c] = v[c];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int c = 0; c < kSums; ++c) {
-            double s = red[0][c];
-            for (int q = 1; q < kBlock / kWave; ++q) s += red[q][c];
-            v[c] = s;
-        }
-    __syncthreads();
-}
-
-// 6x6 inverse by LU with partial pivoting (LAPACK getrf's pivot rule: first largest magnitude); false on an exact zero
-// pivot -- lsf_rigid.hip's invert3 at n = 6
-__device__ inline bool invert6(const double a[36], double inv[36]) {
-    double m[6][6];
-    int perm[6];
-    for (int i = 0; i < 6; ++i) {
-        perm[i] = i;
-        for (int j = 0; j < 6; ++j) m[i][j] = a[i * 6 + j];
-    }
-    for (int c = 0; c < 6; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 6; ++r)
-            if (fabs(m[r][c]) > fabs(m[piv][c])) piv = r;
-        if (m[piv][c] == 0.0) return false;
-        if (piv != c) {
-            for (int j = 0; j < 6; ++j) { const double t = m[c][j]; m[c][j] = m[piv][j]; m[piv][j] = t; }
-            const int t = perm[c]; perm[c] = perm[piv]; perm[piv] = t;
-        }
-        for (int r = c + 1; r < 6; ++r) {
-            m[r][c] = m[r][c] / m[c][c];
-            for (int j = c + 1; j < 6; ++j) m[r][j] = m[r][j] - m[r][c] * m[c][j];
-        }
-    }
-    for (int col = 0; col < 6; ++col) {  // solve L U x = P e_col
-        double y[6];
-        for (int i = 0; i < 6; ++i) {
-            double s = perm[i] == col ? 1.0 : 0.0;
-            for (int j = 0; j < i; ++j) s = s - m[i][j] * y[j];
-            y[i] = s;
-        }
-        for (int i = 5; i >= 0; --i) {
-            double s = y[i];
-            for (int j = i + 1; j < 6; ++j) s = s - m[i][j] * inv[j * 6 + col];
-            inv[i * 6 + col] = s / m[i][i];
-        }
-    }
-    return true;
-}
-
-// combine iteration k-1 (partials in scratch buffer (k-1) & 1, twist before it in `prev`), update, write record k-1
-// (block 0); the new twist goes to tw_out (LDS) for every thread
-__device__ void combine_and_update(const Rigid3dDev& p, int k, const double* __restrict__ prev,
-                                   double* __restrict__ records, const double* __restrict__ scratch,
-                                   double (*red)[kSums], double* tw_out, double* twist_final) {
-    double v[kSums];
-    const double* part = scratch + (size_t)((k - 1) & 1) * kMaxBlocks * kSums;
-#pragma unroll
-    for (int c = 0; c < kSums; ++c) v[c] = 0.0;
-    if ((int)threadIdx.x < p.nblocks)
-#pragma unroll
-        for (int c = 0; c < kSums; ++c) v[c] = part[threadIdx.x * kSums + c];
-    block_sum(v, red);
-    if (threadIdx.x == 0) {
-        double a[36], b[6];
-        for (int i = 0, q = 0; i < 6; ++i)
-            for (int j = i; j < 6; ++j, ++q) a[i * 6 + j] = a[j * 6 + i] = v[q];
-        for (int i = 0; i < 6; ++i) b[i] = v[21 + i];
-        const double energy = 0.5 * v[27];
-        double tw[6], ts[6];
-        for (int i = 0; i < 6; ++i) { tw[i] = prev[i]; ts[i] = 0.0; }
-        bool finite = true;
-        for (int i = 0; i < 36; ++i) finite = finite && isfinite(a[i]);
-        double inv[36];
-        const int skipped = finite && invert6(a, inv) ? 0 : 1;
-        if (skipped == 0) {
-            for (int i = 0; i < 6; ++i) {
-                double s = inv[i * 6] * b[0];
-                for (int j = 1; j < 6; ++j) s = s + inv[i * 6 + j] * b[j];
-                ts[i] = s;
-            }
-            for (int i = 0; i < 6; ++i) tw[i] = tw[i] + p.rate * (ts[i] - tw[i]);
-        }
-        for (int i = 0; i < 6; ++i) tw_out[i] = tw[i];
-        if (blockIdx.x == 0) {
-            double* r = records + (size_t)(k - 1) * kRec;
-            for (int i = 0; i < 6; ++i) { r[i] = ts[i]; r[6 + i] = tw[i]; r[49 + i] = b[i]; }
-            r[12] = energy;
-            for (int i = 0; i < 36; ++i) r[13 + i] = a[i];
-            r[55] = (double)skipped;
-            for (int i = 56; i < kRec; ++i) r[i] = 0.0;
-            if (twist_final)
-                for (int i = 0; i < 6; ++i) twist_final[i] = tw[i];
-        }
-    }
-    __syncthreads();
-}
 
 // the pose of one launch from the twist, rows 0..2 row-major: m = twist_vector_to_matrix3d(-twist) in float64 (the
 // gradient's p), e = the live volume's extrinsic (live_extrinsic, lsf_tsdf_typed.h)
@@ -181,18 +66,7 @@ __global__ __launch_bounds__(kBlock) void rigid3d_kernel(const float* __restrict
     __shared__ double red[kBlock / kWave][kSums];
     __shared__ double tw[6], m[12], e[12];
 
-    if (MODE == GRADIENT) {
-        if (threadIdx.x == 0)
-            for (int i = 0; i < 6; ++i) tw[i] = p.twist[i];
-    } else if (k == 0) {
-        if (threadIdx.x == 0)
-            for (int i = 0; i < 6; ++i) tw[i] = twist_io[i];
-    } else {
-        // the twist before iteration k-1: record k-2's, or the initial one.  The finishing launch has one block, which
-        // reads twist_io before it writes it.
-        const double* prev = k >= 2 ? records + (size_t)(k - 2) * kRec + 6 : twist_io;
-        combine_and_update(p, k, prev, records, scratch, red, tw, MODE == FINISH ? twist_io : nullptr);
-    }
+    rigid_prologue<MODE, 6>(p, k, twist_io, records, scratch, red, tw);
     if (MODE == FINISH) return;
     if (threadIdx.x == 0) make_pose(tw, m, e);
     __syncthreads();
@@ -280,21 +154,7 @@ __global__ __launch_bounds__(kBlock) void rigid3d_kernel(const float* __restrict
         }
         __syncthreads();  // the next item's first planes overwrite slots this item's last steps read
     }
-    if (MODE == ITERATE) {
-        block_sum(acc, red);
-        if (threadIdx.x == 0) {
-            double* part = scratch + (size_t)(k & 1) * kMaxBlocks * kSums + (size_t)blockIdx.x * kSums;
-#pragma unroll
-            for (int c = 0; c < kSums; ++c) part[c] = acc[c];
-        }
-    }
-}
-
-bool depth_dtype_ok(int32_t dt) { return dt == LSF_DEPTH_U16 || dt == LSF_DEPTH_F32 || dt == LSF_DEPTH_F64; }
-
-bool tsdf_ok(const lsf_tsdf_params& t) {
-    return t.image_width > 0 && t.image_height > 0 && t.narrow_band_half_width > 0.0 &&
-           (long long)t.image_width * t.image_height <= 0x7fffffffll;
+    if (MODE == ITERATE) rigid_store_partial<6>(acc, red, scratch, k);
 }
 
 int convert(const lsf_rigid3d_params* params, Rigid3dDev& p) {
@@ -304,14 +164,8 @@ int convert(const lsf_rigid3d_params* params, Rigid3dDev& p) {
         (long long)params->depth * params->height * params->width > 0x7fffffffll)
         return LSF_ERR_BAD_ARGUMENT;
     if (!(params->voxel_size > 0.0)) return LSF_ERR_BAD_ARGUMENT;
-    p.t.fx = t.intrinsics[0]; p.t.fy = t.intrinsics[1]; p.t.cx = t.intrinsics[2]; p.t.cy = t.intrinsics[3];
-    p.t.depth_unit_ratio = t.depth_unit_ratio;
-    p.t.voxel_size = t.voxel_size;
-    p.t.half_width = t.narrow_band_half_width;
-    for (int i = 0; i < 3; ++i) p.t.off[i] = params->array_offset[i];
+    p.t = typed_tsdf(t, params->array_offset, 0);
     for (int i = 0; i < 6; ++i) p.twist[i] = params->twist[i];
-    p.t.width = t.image_width; p.t.height = t.image_height; p.t.image_y = 0;
-    p.t.default_value = t.default_value;
     p.rate = params->rate;
     p.eta = params->eta;
     p.voxel_size = params->voxel_size;
@@ -339,12 +193,6 @@ int launch(const Rigid3dDev& p, unsigned blocks, const float* live, const float*
 }
 
 template <typename DT, typename PT>
-int launch_gradient(const Rigid3dDev& p, const void* depth, float* live_out, float* gradient_out, hipStream_t s) {
-    return launch<GRADIENT, DT, PT>(p, p.nblocks, nullptr, nullptr, depth, live_out, gradient_out, nullptr, nullptr,
-                                    nullptr, 0, s);
-}
-
-template <typename DT, typename PT>
 int launch_run(const float* canonical, const void* live_depth, double* twist, double* records, double* scratch,
                const Rigid3dDev& p, int iterations, hipStream_t s) {
     for (int k = 0; k < iterations; ++k)
@@ -354,34 +202,6 @@ int launch_run(const float* canonical, const void* live_depth, double* twist, do
     return launch<FINISH, DT, PT>(p, 1, nullptr, canonical, live_depth, nullptr, nullptr, twist, records, scratch,
                                   iterations, s);
 }
-
-// one instantiation per (depth dtype, intrinsics dtype)
-template <template <typename, typename> class F, typename... A>
-int dispatch(int32_t depth_dtype, bool intrinsics_f32, A... a) {
-    if (intrinsics_f32) {
-        if (depth_dtype == LSF_DEPTH_U16) return F<unsigned short, float>::run(a...);
-        if (depth_dtype == LSF_DEPTH_F32) return F<float, float>::run(a...);
-        return F<double, float>::run(a...);
-    }
-    if (depth_dtype == LSF_DEPTH_U16) return F<unsigned short, double>::run(a...);
-    if (depth_dtype == LSF_DEPTH_F32) return F<float, double>::run(a...);
-    return F<double, double>::run(a...);
-}
-
-template <typename DT, typename PT>
-struct GradientOp {
-    static int run(const Rigid3dDev& p, const void* depth, float* live_out, float* gradient_out, hipStream_t s) {
-        return launch_gradient<DT, PT>(p, depth, live_out, gradient_out, s);
-    }
-};
-
-template <typename DT, typename PT>
-struct RunOp {
-    static int run(const float* canonical, const void* live_depth, double* twist, double* records, double* scratch,
-                   const Rigid3dDev& p, int iterations, hipStream_t s) {
-        return launch_run<DT, PT>(canonical, live_depth, twist, records, scratch, p, iterations, s);
-    }
-};
 
 }  // namespace
 
@@ -395,9 +215,12 @@ extern "C" int lsf_rigid3d_gradient(const float* live, const void* live_depth, f
     if (live)
         return launch<GRADIENT, float, double>(p, p.nblocks, live, nullptr, nullptr, live_out, gradient_out, nullptr,
                                                nullptr, nullptr, 0, s);
-    if (!depth_dtype_ok(params->depth_dtype) || !tsdf_ok(params->tsdf)) return LSF_ERR_BAD_ARGUMENT;
-    return dispatch<GradientOp>(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, (const Rigid3dDev&)p,
-                                live_depth, live_out, gradient_out, s);
+    if (!depth_dtype_ok(params->depth_dtype) || !typed_tsdf_ok(params->tsdf, false, true))
+        return LSF_ERR_BAD_ARGUMENT;
+    return dispatch_typed(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch<GRADIENT, decltype(dt), decltype(pt)>(
+            p, p.nblocks, nullptr, nullptr, live_depth, live_out, gradient_out, nullptr, nullptr, nullptr, 0, s);
+    });
 }
 
 extern "C" int lsf_rigid3d_run(const float* canonical, const void* live_depth, double* twist_inout, double* records,
@@ -408,9 +231,12 @@ extern "C" int lsf_rigid3d_run(const float* canonical, const void* live_depth, d
     if (int e = convert(params, p)) return e;
     const int it = params->iterations;
     if (it < 0 || (it > 0 && !records)) return LSF_ERR_BAD_ARGUMENT;
-    if (!depth_dtype_ok(params->depth_dtype) || !tsdf_ok(params->tsdf)) return LSF_ERR_BAD_ARGUMENT;
+    if (!depth_dtype_ok(params->depth_dtype) || !typed_tsdf_ok(params->tsdf, false, true))
+        return LSF_ERR_BAD_ARGUMENT;
     if (it == 0) return 0;
-    return dispatch<RunOp>(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, (const float*)canonical,
-                           live_depth, twist_inout, records, reinterpret_cast<double*>(scratch), (const Rigid3dDev&)p,
-                           it, as_stream(stream));
+    double* sc = reinterpret_cast<double*>(scratch);
+    hipStream_t s = as_stream(stream);
+    return dispatch_typed(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch_run<decltype(dt), decltype(pt)>(canonical, live_depth, twist_inout, records, sc, p, it, s);
+    });
 }

@@ -335,21 +335,14 @@ __global__ __launch_bounds__(kBlock) void tsdf_nearest_typed_kernel(const DT* __
 }
 
 template <typename E, typename P, typename DT>
-void launch_typed(const void* depth, float* field, const Grid& g, const TypedTsdf& p, const Extrinsic<E>& x, int dims,
-                  unsigned blocks, hipStream_t s) {
+int launch_typed(const void* depth, float* field, const Grid& g, const TypedTsdf& p, const Extrinsic<E>& x, int dims,
+                 unsigned blocks, hipStream_t s) {
     const DT* d = reinterpret_cast<const DT*>(depth);
     if (dims == 2)
         hipLaunchKernelGGL((tsdf_nearest_typed_kernel<2, E, P, DT>), dim3(blocks), dim3(kBlock), 0, s, d, field, g, p, x);
     else
         hipLaunchKernelGGL((tsdf_nearest_typed_kernel<3, E, P, DT>), dim3(blocks), dim3(kBlock), 0, s, d, field, g, p, x);
-}
-
-template <typename E, typename P>
-void launch_typed_depth(const void* depth, int32_t depth_dtype, float* field, const Grid& g, const TypedTsdf& p,
-                        const Extrinsic<E>& x, int dims, unsigned blocks, hipStream_t s) {
-    if (depth_dtype == LSF_DEPTH_U16) launch_typed<E, P, unsigned short>(depth, field, g, p, x, dims, blocks, s);
-    else if (depth_dtype == LSF_DEPTH_F32) launch_typed<E, P, float>(depth, field, g, p, x, dims, blocks, s);
-    else launch_typed<E, P, double>(depth, field, g, p, x, dims, blocks, s);
+    return launch_status();
 }
 
 }  // namespace
@@ -359,36 +352,25 @@ extern "C" int lsf_tsdf_generate_nearest_typed(const void* depth_image, int32_t 
                                                const double* array_offset, const double* extrinsic_f64, void* stream) {
     if (int e = check_grid(grid)) return e;
     if (!depth_image || !field || !params || !array_offset) return LSF_ERR_BAD_ARGUMENT;
-    if (depth_dtype != LSF_DEPTH_U16 && depth_dtype != LSF_DEPTH_F32 && depth_dtype != LSF_DEPTH_F64)
-        return LSF_ERR_BAD_ARGUMENT;
-    if (params->image_width <= 0 || params->image_height <= 0 || !(params->narrow_band_half_width > 0.0))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (grid->dims == 2 && (params->image_y_coordinate < 0 || params->image_y_coordinate >= params->image_height))
-        return LSF_ERR_BAD_ARGUMENT;
+    // the depth row is checked in 2-D only; width x height is not bounded here
+    if (!depth_dtype_ok(depth_dtype) || !typed_tsdf_ok(*params, grid->dims == 2, false)) return LSF_ERR_BAD_ARGUMENT;
     Grid g = make_grid(grid);
     Tiling t = make_tiling(g);
     if (t.total == 0) return 0;
-    TypedTsdf p;
-    p.fx = params->intrinsics[0]; p.fy = params->intrinsics[1]; p.cx = params->intrinsics[2]; p.cy = params->intrinsics[3];
-    p.depth_unit_ratio = params->depth_unit_ratio;
-    p.voxel_size = params->voxel_size;
-    p.half_width = params->narrow_band_half_width;
-    for (int k = 0; k < 3; ++k) p.off[k] = array_offset[k];
-    p.width = params->image_width; p.height = params->image_height; p.image_y = params->image_y_coordinate;
-    p.default_value = params->default_value;
+    const TypedTsdf p = typed_tsdf(*params, array_offset, params->image_y_coordinate);
     const unsigned blocks = launch_blocks(t.total);
     hipStream_t s = as_stream(stream);
-    const bool p32 = params->intrinsics_are_f32 != 0;
+    const int dims = grid->dims;
     if (extrinsic_f64) {
         Extrinsic<double> x;
         for (int k = 0; k < 12; ++k) x.e[k] = extrinsic_f64[k];
-        if (p32) launch_typed_depth<double, float>(depth_image, depth_dtype, field, g, p, x, grid->dims, blocks, s);
-        else launch_typed_depth<double, double>(depth_image, depth_dtype, field, g, p, x, grid->dims, blocks, s);
-    } else {
-        Extrinsic<float> x;
-        for (int k = 0; k < 12; ++k) x.e[k] = params->extrinsic[k];
-        if (p32) launch_typed_depth<float, float>(depth_image, depth_dtype, field, g, p, x, grid->dims, blocks, s);
-        else launch_typed_depth<float, double>(depth_image, depth_dtype, field, g, p, x, grid->dims, blocks, s);
+        return dispatch_typed(depth_dtype, params->intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+            return launch_typed<double, decltype(pt), decltype(dt)>(depth_image, field, g, p, x, dims, blocks, s);
+        });
     }
-    return launch_status();
+    Extrinsic<float> x;
+    for (int k = 0; k < 12; ++k) x.e[k] = params->extrinsic[k];
+    return dispatch_typed(depth_dtype, params->intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch_typed<float, decltype(pt), decltype(dt)>(depth_image, field, g, p, x, dims, blocks, s);
+    });
 }

@@ -1,7 +1,8 @@
 // Nearest-pixel TSDF value of one voxel on the typed inputs of lsf_tsdf_generate_nearest_typed (reference
 // tsdf/generation.py:130-207, :356-437; tsdf/common.py:34-47): uint16 / float32 / float64 depth, fractional array
 // offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip, the live-field stages of lsf_rigid.hip
-// and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip).
+// and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip), as is the host-side setup at the end of this file
+// (lsf_tsdf_params -> TypedTsdf, the depth-dtype and image checks, the (depth dtype, intrinsics dtype) dispatch).
 // The dtypes are those numpy >= 2 gives the reference's expressions (oracle: tests/rigid_restatement.py):
 //   voxel point     ((index + offset) * voxel_size) in float64, rounded to float32 (np.array(..., dtype=float32))
 //   camera point    extrinsic.dot(point): float32 or float64 as the extrinsic, ((e0 x + e1 y) + e2 z) + e3
@@ -87,6 +88,44 @@ __device__ inline void live_extrinsic(const double* tw, double* e) {
         for (int j = 0; j < 3; ++j) e[i * 4 + j] = (double)(float)rot[i * 3 + j];
         e[i * 4 + 3] = (double)(float)tw[i];
     }
+}
+
+// ---- host: the typed-TSDF setup of every entry point that generates from depth ------------------------------------
+
+inline bool depth_dtype_ok(int32_t dt) { return dt == LSF_DEPTH_U16 || dt == LSF_DEPTH_F32 || dt == LSF_DEPTH_F64; }
+
+// the image and band checks of a typed-TSDF entry point.  image_y: the depth row must lie in the image (2-D);
+// pixels: width x height must fit an int32.  Each entry point keeps the set of checks it has always made.
+inline bool typed_tsdf_ok(const lsf_tsdf_params& t, bool image_y, bool pixels) {
+    if (!(t.image_width > 0 && t.image_height > 0 && t.narrow_band_half_width > 0.0)) return false;
+    if (image_y && (t.image_y_coordinate < 0 || t.image_y_coordinate >= t.image_height)) return false;
+    return !pixels || (long long)t.image_width * t.image_height <= 0x7fffffffll;
+}
+
+inline TypedTsdf typed_tsdf(const lsf_tsdf_params& t, const double off[3], int image_y) {
+    TypedTsdf p;
+    p.fx = t.intrinsics[0]; p.fy = t.intrinsics[1]; p.cx = t.intrinsics[2]; p.cy = t.intrinsics[3];
+    p.depth_unit_ratio = t.depth_unit_ratio;
+    p.voxel_size = t.voxel_size;
+    p.half_width = t.narrow_band_half_width;
+    for (int i = 0; i < 3; ++i) p.off[i] = off[i];
+    p.width = t.image_width; p.height = t.image_height; p.image_y = image_y;
+    p.default_value = t.default_value;
+    return p;
+}
+
+// f(DT()) with DT the element type of a checked LSF_DEPTH_* code; the argument carries its type only (decltype)
+template <typename F>
+inline int dispatch_depth(int32_t depth_dtype, F&& f) {
+    if (depth_dtype == LSF_DEPTH_U16) return f((unsigned short)0);
+    if (depth_dtype == LSF_DEPTH_F32) return f(float());
+    return f(double());
+}
+
+// f(DT(), PT()), PT the intrinsics' type: one instantiation per (depth dtype, intrinsics dtype)
+template <typename F>
+inline int dispatch_typed(int32_t depth_dtype, bool intrinsics_f32, F&& f) {
+    return dispatch_depth(depth_dtype, [&](auto dt) { return intrinsics_f32 ? f(dt, float()) : f(dt, double()); });
 }
 
 }  // namespace lsf

@@ -14,7 +14,11 @@ from .tsdf.generation import offsets_of, tsdf_params
 RECORD = _lib.RIGID_RECORD_DOUBLES
 
 
-def _field(x, name):
+TWIST_NAMES = {3: "t_x, t_z, theta", 6: "t_x, t_y, t_z, r_x, r_y, r_z"}
+
+
+def _device_f32(x, name, rank):
+    """x as a contiguous float32 device tensor of `rank` extents >= 2: a 2-D field or a 3-D volume"""
     if isinstance(x, torch.Tensor):
         t = (x if x.is_cuda else x.to("cuda")).to(torch.float32).contiguous()
     else:
@@ -22,22 +26,49 @@ def _field(x, name):
         if a.dtype.kind not in "fiub":
             raise ValueError("%s must be numeric, got %s" % (name, a.dtype))
         t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda")
-    if t.dim() != 2 or t.shape[0] < 2 or t.shape[1] < 2:
-        raise ValueError("%s must be a 2-D field of at least 2 x 2, got shape %s" % (name, tuple(t.shape)))
+    if t.dim() != rank or min(t.shape) < 2:
+        raise ValueError("%s must be a %d-D %s of at least %s, got shape %s" % (
+            name, rank, "field" if rank == 2 else "volume", " x ".join(["2"] * rank), tuple(t.shape)))
+    return t
+
+
+def twist_n(twist, n):
+    """the twist as a flat float64 n-vector: n = 3 (2-D tracker) or 6 (6-DoF)"""
+    t = np.asarray(twist, dtype=np.float64).reshape(-1)
+    if t.size != n:
+        raise ValueError("twist must have %d entries (%s), got %d" % (n, TWIST_NAMES[n], t.size))
     return t
 
 
 def twist3(twist):
-    t = np.asarray(twist, dtype=np.float64).reshape(-1)
-    if t.size != 3:
-        raise ValueError("twist must have 3 entries (t_x, t_z, theta), got %d" % t.size)
-    return t
+    return twist_n(twist, 3)
+
+
+def twist6(twist):
+    return twist_n(twist, 6)
+
+
+def _enqueue_run(entry, name, canonical, live_depth, p, twist, n, head, record, scratch_bytes):
+    """the whole optimize() enqueued by `entry` (lsf_rigid_run / lsf_rigid3d_run): p.iterations + 1 launches into one
+    buffer [twist (n)][pad to head][records (iterations x record)], and one copy back.  Returns (final twist float64
+    (n,), records float64 (iterations, record))."""
+    iterations = p.iterations
+    out = torch.zeros(head + iterations * record, dtype=torch.float64, device="cuda")
+    if twist is not None:
+        out[:n] = torch.from_numpy(twist_n(twist, n))
+    scratch = torch.empty(scratch_bytes // 8, dtype=torch.float64, device="cuda")
+    base = out.data_ptr()
+    check(entry(ctypes.c_void_p(canonical.data_ptr()), ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(base),
+                ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()),
+          name)
+    host = out.cpu().numpy()
+    return host[:n].copy(), host[head:].reshape(iterations, record).copy()
 
 
 def gradient_wrt_twist(live_field, twist, array_offset, voxel_size=0.004):
     """(H, W, 3) float32 device tensor: calculate_gradient_wrt_twist of live_field (H, W) in one launch"""
     require_gpu()
-    live = _field(live_field, "live_field")
+    live = _device_f32(live_field, "live_field", 2)
     p = RigidParams()
     p.array_offset[:] = list(offsets_of(array_offset))
     p.voxel_size = float(voxel_size)
@@ -57,7 +88,7 @@ def rigid_run(canonical, live_depth, depth_code, camera, image_y_coordinate, arr
     (H, W); live_depth: device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*).  Returns (final twist
     float64 (3,), records float64 (iterations, RIGID_RECORD_DOUBLES))."""
     require_gpu()
-    canonical = _field(canonical, "canonical_field")
+    canonical = _device_f32(canonical, "canonical_field", 2)
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError("iteration must be >= 0")
@@ -72,42 +103,13 @@ def rigid_run(canonical, live_depth, depth_code, camera, image_y_coordinate, arr
     p.depth_dtype = int(depth_code)
     p.height, p.width = int(canonical.shape[0]), int(canonical.shape[1])
     p.iterations = iterations
-    # one buffer: [twist (3)][records (iterations x RECORD)] -- one copy back
-    out = torch.zeros(3 + iterations * RECORD, dtype=torch.float64, device="cuda")
-    if twist is not None:
-        out[:3] = torch.from_numpy(twist3(twist))
-    scratch = torch.empty(_lib.RIGID_SCRATCH_BYTES // 8, dtype=torch.float64, device="cuda")
-    base = out.data_ptr()
-    check(lib.lsf_rigid_run(ctypes.c_void_p(canonical.data_ptr()), ctypes.c_void_p(live_depth.data_ptr()),
-                            ctypes.c_void_p(base), ctypes.c_void_p(base + 3 * 8), ctypes.c_void_p(scratch.data_ptr()),
-                            ctypes.byref(p), stream_ptr()), "lsf_rigid_run")
-    host = out.cpu().numpy()
-    return host[:3].copy(), host[3:].reshape(iterations, RECORD).copy()
+    return _enqueue_run(lib.lsf_rigid_run, "lsf_rigid_run", canonical, live_depth, p, twist, 3, 3, RECORD,
+                        _lib.RIGID_SCRATCH_BYTES)
 
 
 # ---- the 6-DoF 3-D tracker (lsf_rigid3d_gradient, lsf_rigid3d_run) ----------------------------------------------------
 
 RECORD3D = _lib.RIGID3D_RECORD_DOUBLES
-
-
-def _volume(x, name):
-    if isinstance(x, torch.Tensor):
-        t = (x if x.is_cuda else x.to("cuda")).to(torch.float32).contiguous()
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "fiub":
-            raise ValueError("%s must be numeric, got %s" % (name, a.dtype))
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda")
-    if t.dim() != 3 or min(t.shape) < 2:
-        raise ValueError("%s must be a 3-D volume of at least 2 x 2 x 2, got shape %s" % (name, tuple(t.shape)))
-    return t
-
-
-def twist6(twist):
-    t = np.asarray(twist, dtype=np.float64).reshape(-1)
-    if t.size != 6:
-        raise ValueError("twist must have 6 entries (t_x, t_y, t_z, r_x, r_y, r_z), got %d" % t.size)
-    return t
 
 
 def volume_shape(shape):
@@ -131,7 +133,7 @@ def _params3d(shape, array_offset, voxel_size):
 def gradient_wrt_twist_3d(live, twist, array_offset, voxel_size=0.004):
     """(Z, Y, X, 6) float32 device tensor: the 6-DoF twist gradient of the live volume (Z, Y, X) in one launch"""
     require_gpu()
-    live = _volume(live, "live_field")
+    live = _device_f32(live, "live_field", 3)
     p = _params3d(live.shape, array_offset, voxel_size)
     p.twist[:] = list(twist6(twist))
     out = torch.empty(tuple(live.shape) + (6,), dtype=torch.float32, device="cuda")
@@ -147,9 +149,10 @@ def _tsdf3d(P, camera, live_depth, generator_voxel_size, narrow_band_width_voxel
 
 
 def live_and_gradient_3d(live_depth, depth_code, camera, shape, array_offset, twist, voxel_size=0.004,
-                         generator_voxel_size=0.004, narrow_band_width_voxels=20., default_value=1):
+                         generator_voxel_size=0.004, narrow_band_width_voxels=20., default_value=1, gradient=True):
     """(live (Z, Y, X), gradient (Z, Y, X, 6)) float32 device tensors: the live volume an iteration of rigid_run_3d
-    generates under twist, and its twist gradient -- one launch of the run's own generation and gradient code"""
+    generates under twist, and its twist gradient -- one launch of the run's own generation and gradient code.
+    gradient=False: the live volume alone, and None"""
     require_gpu()
     P = np.asarray(camera.intrinsics.intrinsic_matrix)
     p = _params3d(shape, array_offset, voxel_size)
@@ -158,26 +161,19 @@ def live_and_gradient_3d(live_depth, depth_code, camera, shape, array_offset, tw
     p.depth_dtype = int(depth_code)
     s = (p.depth, p.height, p.width)
     live = torch.empty(s, dtype=torch.float32, device="cuda")
-    grad = torch.empty(s + (6,), dtype=torch.float32, device="cuda")
+    grad = torch.empty(s + (6,), dtype=torch.float32, device="cuda") if gradient else None
     check(lib.lsf_rigid3d_gradient(None, ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(live.data_ptr()),
-                                   ctypes.c_void_p(grad.data_ptr()), ctypes.byref(p), stream_ptr()),
-          "lsf_rigid3d_gradient")
+                                   ctypes.c_void_p(grad.data_ptr()) if gradient else None, ctypes.byref(p),
+                                   stream_ptr()), "lsf_rigid3d_gradient")
     return live, grad
 
 
 def live_volume_3d(live_depth, depth_code, camera, shape, array_offset, twist, voxel_size=0.004,
                    narrow_band_width_voxels=20., default_value=1):
-    """(Z, Y, X) float32 device tensor: the live volume of live_and_gradient_3d alone (one launch, no gradient)"""
-    require_gpu()
-    P = np.asarray(camera.intrinsics.intrinsic_matrix)
-    p = _params3d(shape, array_offset, voxel_size)
-    p.tsdf = _tsdf3d(P, camera, live_depth, voxel_size, narrow_band_width_voxels, default_value)
-    p.twist[:] = list(twist6(twist))
-    p.depth_dtype = int(depth_code)
-    live = torch.empty((p.depth, p.height, p.width), dtype=torch.float32, device="cuda")
-    check(lib.lsf_rigid3d_gradient(None, ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(live.data_ptr()),
-                                   None, ctypes.byref(p), stream_ptr()), "lsf_rigid3d_gradient")
-    return live
+    """(Z, Y, X) float32 device tensor: the live volume of live_and_gradient_3d alone (one launch, no gradient),
+    generated at voxel_size"""
+    return live_and_gradient_3d(live_depth, depth_code, camera, shape, array_offset, twist, voxel_size, voxel_size,
+                                narrow_band_width_voxels, default_value, gradient=False)[0]
 
 
 def rigid_run_3d(canonical, live_depth, depth_code, camera, array_offset, iterations, rate, eta, voxel_size,
@@ -187,7 +183,7 @@ def rigid_run_3d(canonical, live_depth, depth_code, camera, array_offset, iterat
     twist: the starting 6-vector (zero by default).  Returns (final twist float64 (6,), records float64
     (iterations, RIGID3D_RECORD_DOUBLES))."""
     require_gpu()
-    canonical = _volume(canonical, "canonical_field")
+    canonical = _device_f32(canonical, "canonical_field", 3)
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError("iteration must be >= 0")
@@ -198,14 +194,5 @@ def rigid_run_3d(canonical, live_depth, depth_code, camera, array_offset, iterat
     p.eta = float(np.float32(eta))
     p.depth_dtype = int(depth_code)
     p.iterations = iterations
-    # one buffer: [twist (6)][pad (2)][records (iterations x RECORD3D)] -- one copy back
-    out = torch.zeros(8 + iterations * RECORD3D, dtype=torch.float64, device="cuda")
-    if twist is not None:
-        out[:6] = torch.from_numpy(twist6(twist))
-    scratch = torch.empty(_lib.RIGID3D_SCRATCH_BYTES // 8, dtype=torch.float64, device="cuda")
-    base = out.data_ptr()
-    check(lib.lsf_rigid3d_run(ctypes.c_void_p(canonical.data_ptr()), ctypes.c_void_p(live_depth.data_ptr()),
-                              ctypes.c_void_p(base), ctypes.c_void_p(base + 8 * 8),
-                              ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_rigid3d_run")
-    host = out.cpu().numpy()
-    return host[:6].copy(), host[8:].reshape(iterations, RECORD3D).copy()
+    return _enqueue_run(lib.lsf_rigid3d_run, "lsf_rigid3d_run", canonical, live_depth, p, twist, 6, 8, RECORD3D,
+                        _lib.RIGID3D_SCRATCH_BYTES)

@@ -31,12 +31,19 @@ RESET = "\033[0m"
 SKIP_NONE, SKIP_SINGULAR = 0, 1
 
 
-def unpack_record(r):
-    return {"twist_star": r[0:3].reshape(3, 1).copy(), "twist": r[3:6].reshape(3, 1).copy(), "energy": float(r[6]),
-            "matrix_a": r[7:16].reshape(3, 3).copy(), "vector_b": r[16:19].reshape(3, 1).copy(), "skipped": int(r[19])}
+def unpack_record(r, n=3):
+    """one host record of an n-DoF tracker (n = 3 here, 6 in sdf_2_sdf_optimizer3d) as a dict; the layout of
+    csrc/lsf_rigid_solve.h: [twist* (n)][twist (n)][energy][A (n x n)][b (n)][skipped]"""
+    a = 2 * n + 1
+    b = a + n * n
+    return {"twist_star": r[0:n].reshape(n, 1).copy(), "twist": r[n:2 * n].reshape(n, 1).copy(),
+            "energy": float(r[2 * n]), "matrix_a": r[a:b].reshape(n, n).copy(),
+            "vector_b": r[b:b + n].reshape(n, 1).copy(), "skipped": int(r[b + n])}
 
 
-class Sdf2SdfOptimizer2d:
+class Sdf2SdfOptimizerBase:
+    """what the 2-D and the 6-DoF optimizer share: the constructor and the verbosity prints from the records"""
+
     class VerbosityParameters:
         """what optimize() prints per iteration"""
 
@@ -49,27 +56,11 @@ class Sdf2SdfOptimizer2d:
 
     def __init__(self, rate=0.5, verbosity_parameters=None, visualization_parameters=None):
         self.rate = rate
-        self.verbosity_parameters = verbosity_parameters if verbosity_parameters else \
-            Sdf2SdfOptimizer2d.VerbosityParameters()
+        self.verbosity_parameters = verbosity_parameters if verbosity_parameters else self.VerbosityParameters()
         self.visualization_parameters = visualization_parameters if visualization_parameters else \
             Sdf2SdfVisualizer.Parameters()
         self.visualizer = None
         self.last_records = []
-
-    def optimize(self, data_to_use, voxel_size=0.004, narrow_band_width_voxels=20., iteration=60, eta=.01):
-        """the (3, 1) float64 twist aligning data_to_use's live depth row to its canonical one"""
-        canonical_field = data_to_use.generate_2d_canonical_field(narrow_band_width_voxels=narrow_band_width_voxels,
-                                                                  method=FilteringMethod.NONE, as_tensor=True)
-        depth, depth_code = device_depth(data_to_use.live_depth_image())
-        self.visualizer = Sdf2SdfVisualizer(parameters=self.visualization_parameters,
-                                            field_size=canonical_field.shape[0])
-        twist, records = device_rigid.rigid_run(
-            canonical_field, depth, depth_code, data_to_use.depth_camera, data_to_use.image_pixel_row,
-            data_to_use.offset, iteration, self.rate, eta, voxel_size, 0.004, narrow_band_width_voxels)
-        self.last_records = [unpack_record(r) for r in records]
-        self._report(self.last_records)
-        del self.visualizer
-        return twist.reshape(3, 1)
 
     def _report(self, records):
         v = self.verbosity_parameters
@@ -84,7 +75,23 @@ class Sdf2SdfOptimizer2d:
                 continue
             if v.print_max_warp_update:
                 ts, tw = rec["twist_star"].reshape(-1), rec["twist"].reshape(-1)
-                print("optimal twist: %f, %f, %f, twist: %f, %f, %f" % (ts[0], ts[1], ts[2], tw[0], tw[1], tw[2]),
-                      end="")
+                print("optimal twist: %s, twist: %s" % (", ".join("%f" % x for x in ts),
+                                                         ", ".join("%f" % x for x in tw)), end="")
                 print("")
 
+
+class Sdf2SdfOptimizer2d(Sdf2SdfOptimizerBase):
+    def optimize(self, data_to_use, voxel_size=0.004, narrow_band_width_voxels=20., iteration=60, eta=.01):
+        """the (3, 1) float64 twist aligning data_to_use's live depth row to its canonical one"""
+        canonical_field = data_to_use.generate_2d_canonical_field(narrow_band_width_voxels=narrow_band_width_voxels,
+                                                                  method=FilteringMethod.NONE, as_tensor=True)
+        depth, depth_code = device_depth(data_to_use.live_depth_image())
+        self.visualizer = Sdf2SdfVisualizer(parameters=self.visualization_parameters,
+                                            field_size=canonical_field.shape[0])
+        twist, records = device_rigid.rigid_run(
+            canonical_field, depth, depth_code, data_to_use.depth_camera, data_to_use.image_pixel_row,
+            data_to_use.offset, iteration, self.rate, eta, voxel_size, 0.004, narrow_band_width_voxels)
+        self.last_records = [unpack_record(r) for r in records]
+        self._report(self.last_records)
+        del self.visualizer
+        return twist.reshape(3, 1)

@@ -19,28 +19,17 @@ components; the records stay on the optimizer as `last_records` (a list of dicts
 vector_b, skipped)."""
 from .. import device_rigid
 from ..tsdf.generation import FilteringMethod, device_depth
-from .sdf_2_sdf_optimizer2d import BOLD_LIGHT_CYAN, BOLD_YELLOW, RESET, SKIP_SINGULAR, Sdf2SdfOptimizer2d
+from . import sdf_2_sdf_optimizer2d
+from .sdf_2_sdf_optimizer2d import (BOLD_LIGHT_CYAN, BOLD_YELLOW, RESET, SKIP_SINGULAR,  # noqa: F401
+                                    Sdf2SdfOptimizerBase)
 from .sdf_2_sdf_visualizer import Sdf2SdfVisualizer
 
 
 def unpack_record(r):
-    return {"twist_star": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
-            "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
-            "skipped": int(r[55])}
+    return sdf_2_sdf_optimizer2d.unpack_record(r, 6)
 
 
-class Sdf2SdfOptimizer3d:
-    VerbosityParameters = Sdf2SdfOptimizer2d.VerbosityParameters
-
-    def __init__(self, rate=0.5, verbosity_parameters=None, visualization_parameters=None):
-        self.rate = rate
-        self.verbosity_parameters = verbosity_parameters if verbosity_parameters else \
-            Sdf2SdfOptimizer3d.VerbosityParameters()
-        self.visualization_parameters = visualization_parameters if visualization_parameters else \
-            Sdf2SdfVisualizer.Parameters()
-        self.visualizer = None
-        self.last_records = []
-
+class Sdf2SdfOptimizer3d(Sdf2SdfOptimizerBase):
     def optimize(self, data_to_use, voxel_size=0.004, narrow_band_width_voxels=20., iteration=60, eta=.01):
         """the (6, 1) float64 twist aligning data_to_use's live depth frame to its canonical one"""
         canonical_field = data_to_use.generate_3d_canonical_field(narrow_band_width_voxels=narrow_band_width_voxels,
@@ -55,21 +44,3 @@ class Sdf2SdfOptimizer3d:
         self._report(self.last_records)
         del self.visualizer
         return twist.reshape(6, 1)
-
-    def _report(self, records):
-        v = self.verbosity_parameters
-        for iteration_count, rec in enumerate(records):
-            if v.print_per_iteration_info:
-                print("%s[ITERATION %d COMPLETED]%s" % (BOLD_LIGHT_CYAN, iteration_count, RESET), end="")
-                if v.print_iteration_energy:
-                    print(" energy: %f" % rec["energy"], end="")
-                    print("")
-            if rec["skipped"] == SKIP_SINGULAR:
-                print("%sSINGULAR MATRIX!%s" % (BOLD_YELLOW, RESET))
-                continue
-            if v.print_max_warp_update:
-                ts, tw = rec["twist_star"].reshape(-1), rec["twist"].reshape(-1)
-                print("optimal twist: %s, twist: %s" % (", ".join("%f" % x for x in ts),
-                                                         ", ".join("%f" % x for x in tw)), end="")
-                print("")
-

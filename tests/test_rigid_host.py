@@ -226,3 +226,38 @@ def test_host_argument_checks():
         lsf.transformation.twist_vector_to_matrix3d(np.zeros(3))
     with pytest.raises(ValueError, match="3 entries"):
         lsf.transformation.rodrigues(np.zeros(4))
+
+
+def test_report_text_of_both_optimizers(capsys):
+    """the verbosity prints of Sdf2SdfOptimizer2d and Sdf2SdfOptimizer3d, from host-built records: the reference's 2-D
+    text, and the 6-DoF text with the same format, which at three components is the 2-D text byte for byte"""
+    from levelsetfusion_python_amd.rigid_opt import sdf_2_sdf_optimizer2d as O2, sdf_2_sdf_optimizer3d as O3
+
+    def records(n, size):
+        out = []
+        for k, skipped in enumerate((0, 1, 0)):
+            r = np.zeros(size)
+            r[:2 * n] = 0.125 * (np.arange(2 * n) + 1) * (-1) ** k
+            r[2 * n] = 1234.5 / (k + 1)
+            r[2 * n + 1 + n * n + n] = skipped
+            out.append(r)
+        return out
+
+    def report(cls, recs):
+        verbose = cls.VerbosityParameters(print_max_warp_update=True, print_iteration_energy=True)
+        cls(verbosity_parameters=verbose)._report(recs)
+        return capsys.readouterr().out
+
+    text2 = report(O2.Sdf2SdfOptimizer2d, [O2.unpack_record(r) for r in records(3, 24)])
+    c, y, z = "\033[36;1;m", "\033[33;1;m", "\033[0m"
+    assert text2 == (
+        c + "[ITERATION 0 COMPLETED]" + z + " energy: 1234.500000\n"
+        "optimal twist: 0.125000, 0.250000, 0.375000, twist: 0.500000, 0.625000, 0.750000\n" +
+        c + "[ITERATION 1 COMPLETED]" + z + " energy: 617.250000\n" + y + "SINGULAR MATRIX!" + z + "\n" +
+        c + "[ITERATION 2 COMPLETED]" + z + " energy: 411.500000\n"
+        "optimal twist: 0.125000, 0.250000, 0.375000, twist: 0.500000, 0.625000, 0.750000\n")
+    assert report(O3.Sdf2SdfOptimizer3d, [O2.unpack_record(r) for r in records(3, 24)]) == text2
+    text3 = report(O3.Sdf2SdfOptimizer3d, [O3.unpack_record(r) for r in records(6, 64)])
+    assert text3.splitlines()[1] == ("optimal twist: 0.125000, 0.250000, 0.375000, 0.500000, 0.625000, 0.750000, "
+                                     "twist: 0.875000, 1.000000, 1.125000, 1.250000, 1.375000, 1.500000")
+    assert text3.splitlines()[2:4] == text2.splitlines()[2:4]
