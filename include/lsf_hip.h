@@ -1051,6 +1051,44 @@ typedef struct lsf_raycast_params {
 int lsf_raycast(const float *tsdf, const float *weight, const void *fallback_depth, float *depth_out, float *normals_out,
                 uint64_t *hit_count, const lsf_raycast_params *params, void *stream);
 
+/* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
+ * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):
+ * marching cubes over the cells whose 8 corners have weight > min_weight and a finite tsdf, with the generated case
+ * table of csrc/lsf_mesh_tables.h, one vertex per crossing grid edge, every float step one float64 operation.  The
+ * output order is fixed (vertices by owning voxel, then axis x, y, z; faces by cell, then table order), so reruns are
+ * bit-identical.  A call is lsf_mesh_count (3 launches), one host read of the two totals, then lsf_mesh_emit (2
+ * launches) into outputs of exactly that size.  No inter-workgroup waits, no float atomics.
+ * Workspaces (DEVICE, the caller's; voxels = depth * height * width, blocks = ceil(voxels / LSF_MESH_TILE)):
+ *   cell_code      uint8 [voxels]      per cell (named by its lowest voxel): its case when valid, else 0
+ *   edge_mask      uint8 [voxels]      per voxel: bit a set when its grid edge along axis a (x, y, z) has a vertex
+ *   block_offsets  int32 [2][blocks]   after lsf_mesh_count: the exclusive offsets of each block's vertices ([0])
+ *                                      and faces ([1])
+ *   vertex_base    int32 [voxels]      lsf_mesh_emit: the index of a voxel's first vertex (where edge_mask != 0) */
+typedef struct lsf_mesh_params {
+    double voxel_size;                   /* metres, finite and > 0 */
+    double offset_x, offset_y, offset_z; /* array offset, voxels, finite, fractional allowed */
+    double iso;                          /* the level, finite; a corner is inside when (double)tsdf < iso */
+    double min_weight;                   /* a voxel counts when (double)weight > min_weight; not NaN */
+    int32_t depth, height, width;        /* volume extents z, y, x, >= 2 each; 3 * voxels and
+                                            5 * (depth - 1)(height - 1)(width - 1) at most 2^31 - 1 */
+} lsf_mesh_params;
+#define LSF_MESH_TILE 2048
+
+/* tsdf, weight: DEVICE float32 [depth][height][width], two distinct buffers, read only.  Writes cell_code, edge_mask
+ * and block_offsets, and totals: DEVICE int64 [2] = (vertex count V, face count F), exact.  No buffer may alias
+ * another. */
+int lsf_mesh_count(const float *tsdf, const float *weight, uint8_t *cell_code, uint8_t *edge_mask,
+                   int32_t *block_offsets, int64_t *totals, const lsf_mesh_params *params, void *stream);
+
+/* After lsf_mesh_count on the same inputs and workspaces, with vertex_count and face_count its totals.  vertices: DEVICE
+ * float32 [vertex_count][3], world (x, y, z) in metres.  normals: NULL, or DEVICE float32 [vertex_count][3], unit
+ * normals towards larger tsdf (0 where the interpolated gradient is 0).  faces: DEVICE int32 [face_count][3], vertex
+ * indices, right-hand normal towards larger tsdf.  With both counts 0 nothing is launched and the outputs may be NULL.
+ * No output may alias an input or another output. */
+int lsf_mesh_emit(const float *tsdf, const float *weight, const uint8_t *cell_code, const uint8_t *edge_mask,
+                  const int32_t *block_offsets, int32_t *vertex_base, float *vertices, float *normals, int32_t *faces,
+                  int64_t vertex_count, int64_t face_count, const lsf_mesh_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

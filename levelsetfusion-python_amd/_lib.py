@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "3f118f4bbd4896fa"
+HEADER_ABI_HASH = "acacf271da7966a1"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -214,6 +214,17 @@ class RaycastParams(ctypes.Structure):
                                               "fallback_dtype")]
 
 
+MESH_TILE = 2048
+MESH_MAX_TRIANGLES = 5
+
+
+class MeshParams(ctypes.Structure):
+    """lsf_mesh_params: a triangle mesh of the canonical TSDF (lsf_mesh_count, lsf_mesh_emit)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("voxel_size", "offset_x", "offset_y", "offset_z", "iso",
+                                               "min_weight")] + \
+               [(n, ctypes.c_int32) for n in ("depth", "height", "width")]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -327,6 +338,8 @@ PROTOTYPES = {
     "lsf_fusion_integrate_volume": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
     "lsf_fusion_integrate_depth": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
+    "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
+    "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
 }
 
 

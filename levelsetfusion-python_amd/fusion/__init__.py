@@ -10,6 +10,11 @@ integrate_* call is two launches of csrc/lsf_fusion.hip and returns the call's r
 (unpack_record turns a host copy into {fused, first_seen, sum_abs_change, max_abs_change}); nothing waits for the GPU.
 CanonicalVolume.raycast renders the model into a depth (and normal) image seen from a camera at a twist: one launch of
 csrc/lsf_raycast.hip ("Ray-casting"; tests/raycast_restatement.py restates it).
+CanonicalVolume.extract_mesh takes the model's surface out as a triangle mesh: marching cubes over the cells whose 8
+corners have weight > min_weight, with a generated case table whose meshes are watertight, in a fixed output order
+("Mesh extraction"; tests/mesh_restatement.py restates it).  It is five launches of
+csrc/lsf_mesh.hip with one host read of the vertex and face totals between the counting and the emitting launches;
+mesh_io.write_ply writes the result.  SequenceFusion3d.extract_mesh passes the sequence's array_offset and voxel_size.
 
 SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
 first tracked by the 6-DoF rigid tracker, started from the previous frame's twist (device_rigid.rigid_run_3d,
@@ -25,19 +30,21 @@ generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsd
 
 Host synchronisations per frame: the rigid run's one copy back (frames >= 1 with rigid_iterations > 0; in "raycast"
 mode it also brings the prediction's hit count), the non-rigid optimize()'s own (when one is given), and one read of
-the fusion record.
+the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
+vertex and face totals.
 
 Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
 field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
 fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, frame-to-model tracking with
-the prediction's normals (point-to-plane ICP), an adaptive ray-casting step, and a colour or confidence image in the
-prediction."""
+the prediction's normals (point-to-plane ICP), an adaptive ray-casting step, a colour or confidence image in the
+prediction, marching squares for 2-D models, vertex attributes beyond normals, welding vertices by position,
+decimation, and a mesh extracted without the host read of its totals."""
 import math
 
 import numpy as np
 import torch
 
-from .. import device_fusion, device_raycast, device_rigid
+from .. import device_fusion, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
 from ..device_fusion import RECORD_FIELDS, unpack_record
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
@@ -108,6 +115,22 @@ class CanonicalVolume:
         if not as_tensor:
             out = tuple(t.cpu().numpy() for t in out)
         return out if normals else out[0]
+
+    def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False):
+        """the level set iso of the model as a triangle mesh, with raycast's conventions (voxel (i, j, k) at
+        ((k, j, i) + array_offset) * voxel_size): float32 vertices (V, 3) in world metres, (x, y, z); int32 faces
+        (F, 3), their right-hand normal towards larger tsdf; with normals=True also the float32 unit normals (V, 3).
+        Only cells whose 8 corners have weight > min_weight draw.  Returns (vertices, faces) or (vertices, faces,
+        normals): device tensors with as_tensor=True, numpy copies otherwise.  One host synchronisation: the read of
+        the two totals."""
+        if len(self.shape) != 3:
+            raise ValueError("mesh extraction needs a 3-D model, this one has shape %s" % (self.shape,))
+        verts, faces, out_normals = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso,
+                                                             min_weight, normals)
+        out = (verts, faces, out_normals) if normals else (verts, faces)
+        if not as_tensor:
+            out = tuple(t.cpu().numpy() for t in out)
+        return out
 
 
 class SequenceFusion3d:
@@ -198,3 +221,7 @@ class SequenceFusion3d:
         self.twists.append(frame["twist"].copy())
         self.frame_records.append(frame)
         return frame
+
+    def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False):
+        """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size"""
+        return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor)
