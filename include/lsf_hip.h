@@ -1051,6 +1051,57 @@ typedef struct lsf_raycast_params {
 int lsf_raycast(const float *tsdf, const float *weight, const void *fallback_depth, float *depth_out, float *normals_out,
                 uint64_t *hit_count, const lsf_raycast_params *params, void *stream);
 
+/* ---- projective point-to-plane ICP against the ray-cast prediction -------------------------------------------------
+ * The KinectFusion tracker; the reference has none, the arithmetic is this project's (INTEGRATION.md section 3,
+ * "Projective ICP"), every step one float64 operation.  The prediction is lsf_raycast's depth and normals at twist_p
+ * (camera E_p = twist_vector_to_matrix3d of the float32-rounded twist_p); a prediction pixel is usable when its depth is
+ * > 0 and its normal non-zero.  The estimate is the float64 twist xi, its pose [Rodrigues(xi_r), xi_t] built from the
+ * unrounded twist.  A live pixel (u, v) with depth d > 0 has the vertex v = d ((u - cx) / fx, (v - cy) / fy, 1), the
+ * world point g = R^T (v - xi_t) and the prediction camera point q = R_p g + t_p; it associates with the prediction
+ * pixel (rint(fx q_x / q_z + cx), rint(fy q_y / q_z + cy)) when q_z > 0, that pixel is in the image and usable, and
+ * |g - V_w| <= max_distance, V_w the prediction vertex in world coordinates.  Residual r = N_w . (g - V_w), Jacobian
+ * J = (N_w, g x N_w); each iteration sums A = sum J J^T, b = -sum J r, the energy sum r^2 and the correspondence count,
+ * solves delta = A^-1 b (skipped as in the rigid trackers) and composes R' = R Rodrigues(delta_w)^T,
+ * t' = xi_t - R' delta_t, xi' = (t', log R').  Levels run coarse first; a level of stride s uses the live pixels
+ * (s i, s j) and associates into the full-resolution prediction.  One lane per strided live pixel, a wave per 8 x 8
+ * block of them, a grid-stride loop over at most LSF_ICP_MAX_BLOCKS workgroups.  The partial sums cross launch
+ * boundaries only: no float atomics, and a rerun is bit-identical. */
+#define LSF_ICP_MAX_LEVELS 4
+typedef struct lsf_icp_params {
+    double fx, fy, cx, cy;             /* intrinsics, pixels; finite, fx and fy non-zero */
+    double depth_unit_ratio;           /* metres per unit of the live depth image, finite */
+    double max_distance;               /* metres, > 0 (inf allowed) */
+    double twist_p[6];                 /* the prediction's twist, float64 (rounded to float32 as the ray-cast does) */
+    int32_t height, width;             /* image extents of the live frame and the prediction, >= 1 each, at most
+                                          2^31 - 1 pixels */
+    int32_t depth_dtype;               /* LSF_DEPTH_* of the live depth image */
+    int32_t levels;                    /* 1 .. LSF_ICP_MAX_LEVELS */
+    int32_t iterations[LSF_ICP_MAX_LEVELS]; /* per level, coarse first, >= 0 */
+    int32_t strides[LSF_ICP_MAX_LEVELS];    /* per level, >= 1 */
+} lsf_icp_params;
+
+/* one record per iteration, LSF_ICP_RECORD_DOUBLES doubles, written by the launch after it:
+ *   [0, 6) delta = A^-1 b (0 when skipped)   [6, 12) twist after the update   [12] energy (sum r^2)   [13, 49) A
+ *   row-major   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)
+ *   [56] correspondence count   [57] level   [58, 64) reserved */
+#define LSF_ICP_RECORD_DOUBLES 64
+/* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
+ * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
+#define LSF_ICP_MAX_BLOCKS 256
+#define LSF_ICP_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 29 * 8)
+
+/* the whole pyramid: sum(iterations) launches of the fused iteration kernel, then one finishing launch, back to back
+ * on stream with no host synchronisation.  live_depth: DEVICE [height][width] of params->depth_dtype (float32 depth
+ * scaled in float32, uint16 and float64 in float64); pred_depth: DEVICE float32 [height][width] in metres;
+ * pred_normals: DEVICE float32 [height][width][3] in camera coordinates (lsf_raycast's outputs at twist_p);
+ * twist_inout: DEVICE 6 doubles, read at the start, the final twist written by the finishing launch; records: DEVICE
+ * sum(iterations) * LSF_ICP_RECORD_DOUBLES doubles; scratch: DEVICE, LSF_ICP_SCRATCH_BYTES; residuals_out: NULL, or
+ * DEVICE float32 [height][width] that receives the last iteration's r, NaN where a pixel has no correspondence (or is
+ * not on the last level's stride).  With sum(iterations) == 0 nothing is launched.  No output may alias an input or
+ * another output. */
+int lsf_icp_run(const void *live_depth, const float *pred_depth, const float *pred_normals, double *twist_inout,
+                double *records, void *scratch, float *residuals_out, const lsf_icp_params *params, void *stream);
+
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):
  * marching cubes over the cells whose 8 corners have weight > min_weight and a finite tsdf, with the generated case

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "acacf271da7966a1"
+HEADER_ABI_HASH = "328469b091d8b5a3"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -225,6 +225,20 @@ class MeshParams(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("depth", "height", "width")]
 
 
+ICP_MAX_LEVELS = 4
+ICP_RECORD_DOUBLES = 64
+ICP_MAX_BLOCKS = 256
+ICP_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 29 * 8
+
+
+class IcpParams(ctypes.Structure):
+    """lsf_icp_params: projective point-to-plane ICP against the ray-cast prediction (lsf_icp_run)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_unit_ratio", "max_distance")] + \
+               [("twist_p", ctypes.c_double * 6)] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "depth_dtype", "levels")] + \
+               [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS), ("strides", ctypes.c_int32 * ICP_MAX_LEVELS)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -340,6 +354,7 @@ PROTOTYPES = {
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
+    "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
 }
 
 

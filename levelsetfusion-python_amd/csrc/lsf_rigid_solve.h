@@ -2,6 +2,8 @@
 // N = 6): the layouts of the per-block partial sums and of the per-iteration record, the fixed-order reductions of
 // the partials, the N x N inverse, and the kernel prologue that turns iteration k-1's partials into the twist of
 // launch k.  Each tracker keeps its own per-voxel body; everything from the partial sums on is decided here once.
+// Projective ICP (lsf_icp.hip) shares the reductions, the normal equations' layout and the solve; its update (a
+// composition, not the SDF-2-SDF blend) and its record are its own.
 // The partials cross a launch boundary only (cdna_hip_programming.md, split-K item 2, the launch-boundary reduce): no
 // atomics, no in-launch hand-off, and the reductions add in one fixed order, so a run is bit-reproducible.
 // The prologue and the update are forced inline: a template of a header has vague linkage and is otherwise kept out
@@ -102,6 +104,56 @@ __device__ inline bool invert(const double a[N * N], double inv[N * N]) {
         }
     }
     return true;
+}
+
+// the fixed-order sum of nblocks partials of K sums each, part[block * K + c]: one partial per thread, then block_sum;
+// the totals land in thread 0's v[]
+template <int K>
+__device__ __forceinline__ void combine_partials(const double* __restrict__ part, int nblocks, double (&v)[K],
+                                                 double (*red)[K]) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) v[c] = 0.0;
+    if ((int)threadIdx.x < nblocks)
+#pragma unroll
+        for (int c = 0; c < K; ++c) v[c] = part[threadIdx.x * K + c];
+    block_sum(v, red);
+}
+
+// the normal equations from their sums: A (N x N, row-major) from its upper triangle stored row by row at v[0], b (N)
+// after it
+template <int N>
+__device__ __forceinline__ void normal_equations(const double* v, double a[N * N], double b[N]) {
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) {
+            const int r = i < j ? i : j, c = i < j ? j : i;  // the upper triangle's entry
+            a[i * N + j] = v[r * N - r * (r - 1) / 2 + (c - r)];
+        }
+    for (int i = 0; i < N; ++i) b[i] = v[N * (N + 1) / 2 + i];
+}
+
+// x = A^-1 b (x[i] = inv[i][0] b[0] + inv[i][1] b[1] + ..., left to right); 1 and x untouched when A holds a non-finite
+// entry or invert<N> meets an exact zero pivot (the update is skipped), else 0
+template <int N>
+__device__ __forceinline__ int solve(const double a[N * N], const double b[N], double x[N]) {
+    bool finite = true;
+    for (int i = 0; i < N * N; ++i) finite = finite && isfinite(a[i]);
+    double inv[N * N];
+    if (!(finite && invert<N>(a, inv))) return 1;
+    for (int i = 0; i < N; ++i) {
+        double s = inv[i * N] * b[0];
+        for (int j = 1; j < N; ++j) s = s + inv[i * N + j] * b[j];
+        x[i] = s;
+    }
+    return 0;
+}
+
+// this block's K sums: reduced over the block (block_sum), thread 0 writes them to part[blockIdx.x * K + c]
+template <int K>
+__device__ __forceinline__ void store_partial(double (&acc)[K], double (*red)[K], double* __restrict__ part) {
+    block_sum(acc, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < K; ++c) part[(size_t)blockIdx.x * K + c] = acc[c];
 }
 
 // combine iteration k-1 (partials in scratch buffer (k-1) & 1, twist before it in `prev`), singular test, update

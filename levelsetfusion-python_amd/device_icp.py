@@ -1,0 +1,102 @@
+"""Torch-facing wrapper of projective point-to-plane ICP (include/lsf_hip.h: lsf_icp_run).  Every argument is checked on
+the host before the launches; a call enqueues sum(iterations) + 1 launches with no host wait and copies the twist and
+the records back once.  The public interfaces are rigid_opt.ProjectiveIcp3d and
+fusion.SequenceFusion3d(tracking_reference="icp")."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import IcpParams, check, lib
+from .device_core import require_gpu, stream_ptr
+from .device_raycast import image_extents
+from .device_rigid import twist6
+
+RECORD = _lib.ICP_RECORD_DOUBLES
+ITERATIONS, STRIDES, MAX_DISTANCE = (4, 4, 6), (4, 2, 1), 0.02
+
+
+def levels(iterations, strides):
+    """the pyramid as two tuples of ints, coarse first: iterations >= 0 and strides >= 1 per level, at most
+    ICP_MAX_LEVELS levels"""
+    it = tuple(int(v) for v in np.atleast_1d(iterations))
+    st = tuple(int(v) for v in np.atleast_1d(strides))
+    if not 1 <= len(it) <= _lib.ICP_MAX_LEVELS or len(it) != len(st):
+        raise ValueError("iterations and strides need one entry per level, 1 to %d levels, got %s and %s"
+                         % (_lib.ICP_MAX_LEVELS, it, st))
+    if min(it) < 0 or min(st) < 1:
+        raise ValueError("iterations must be >= 0 and strides >= 1, got %s and %s" % (it, st))
+    return it, st
+
+
+def params(camera, image_shape, twist_p, depth_code, iterations=ITERATIONS, strides=STRIDES,
+           max_distance=MAX_DISTANCE):
+    """the lsf_icp_params of a call, after the host checks"""
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    p = IcpParams()
+    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
+    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
+        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    p.depth_unit_ratio = float(camera.depth_unit_ratio)
+    if not np.isfinite(p.depth_unit_ratio):
+        raise ValueError("the camera's depth_unit_ratio must be finite")
+    p.max_distance = float(max_distance)
+    if not p.max_distance > 0:
+        raise ValueError("max_distance must be positive")
+    tp = twist6(twist_p)
+    if not np.all(np.isfinite(tp)):
+        raise ValueError("twist_p must be finite")
+    p.twist_p[:] = list(tp)
+    p.height, p.width = image_extents(image_shape)
+    p.depth_dtype = int(depth_code)
+    it, st = levels(iterations, strides)
+    p.levels = len(it)
+    p.iterations[:len(it)] = list(it)
+    p.strides[:len(st)] = list(st)
+    return p
+
+
+def _prediction(x, name, shape):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise ValueError("%s must be a contiguous float32 device tensor (device_raycast.raycast)" % name)
+    if tuple(x.shape) != shape:
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(x.shape), shape))
+    return x
+
+
+def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, twist=None, iterations=ITERATIONS,
+            strides=STRIDES, max_distance=MAX_DISTANCE, residuals=False):
+    """the whole pyramid enqueued: sum(iterations) + 1 launches and one copy back.  live_depth: device depth image
+    (uint16 / float32 / float64, depth_code LSF_DEPTH_*, scaled by camera.depth_unit_ratio); pred_depth (H, W) and
+    pred_normals (H, W, 3): device_raycast.raycast's float32 outputs at twist_p; twist: the starting 6-vector (twist_p
+    by default).  Returns (final twist float64 (6,), records float64 (sum(iterations), ICP_RECORD_DOUBLES), and the
+    last iteration's residual image (H, W) as a float32 device tensor with residuals=True, else None)."""
+    require_gpu()
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
+        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+    h, w = (int(v) for v in live_depth.shape)
+    p = params(camera, (h, w), twist_p, depth_code, iterations, strides, max_distance)
+    _prediction(pred_depth, "pred_depth", (h, w))
+    _prediction(pred_normals, "pred_normals", (h, w, 3))
+    total = sum(p.iterations[:p.levels])
+    head = 8
+    out = torch.zeros(head + total * RECORD, dtype=torch.float64, device=live_depth.device)
+    out[:6] = torch.from_numpy(twist6(twist_p if twist is None else twist).copy())
+    scratch = torch.empty(_lib.ICP_SCRATCH_BYTES // 8, dtype=torch.float64, device=live_depth.device)
+    res = torch.empty((h, w), dtype=torch.float32, device=live_depth.device) if residuals else None
+    base = out.data_ptr()
+    check(lib.lsf_icp_run(ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(pred_depth.data_ptr()),
+                          ctypes.c_void_p(pred_normals.data_ptr()), ctypes.c_void_p(base),
+                          ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr()),
+                          None if res is None else ctypes.c_void_p(res.data_ptr()), ctypes.byref(p), stream_ptr()),
+          "lsf_icp_run")
+    host = out.cpu().numpy()
+    return host[:6].copy(), host[head:].reshape(total, RECORD).copy(), res
+
+
+def unpack_record(r):
+    """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES)"""
+    return {"delta": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
+            "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
+            "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57])}

@@ -17,26 +17,32 @@ csrc/lsf_mesh.hip with one host read of the vertex and face totals between the c
 mesh_io.write_ply writes the result.  SequenceFusion3d.extract_mesh passes the sequence's array_offset and voxel_size.
 
 SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
-first tracked by the 6-DoF rigid tracker, started from the previous frame's twist (device_rigid.rigid_run_3d,
-`rigid_iterations` iterations; 0 keeps the previous twist), against a reference volume chosen by `tracking_reference`:
+first tracked, started from the previous frame's twist, as `tracking_reference` chooses: by the 6-DoF rigid tracker
+(device_rigid.rigid_run_3d, `rigid_iterations` iterations; 0 keeps the previous twist) against a reference volume, or
+by ICP against the model's prediction:
     "model"    the model's tsdf itself (the default)
     "raycast"  the live volume, under the previous twist, of the model ray-cast at the previous twist with the holes
                filled from the previous frame's depth -- KillingFusion-style tracking against the model's prediction.
                Voxels behind the fused band keep the model's initial +1, where a frame has -1; tracking against the
                model itself meets that residual at every band's back edge, and the prediction does not have it.
+    "icp"      projective point-to-plane ICP (rigid_opt.ProjectiveIcp3d, device_icp.icp_run) of the frame against the
+               model ray-cast with normals at the previous twist, without a fallback image; `icp_iterations`,
+               `icp_strides` and `icp_max_distance` set the pyramid, and `rigid_iterations` is not used.
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
 With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
 generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
 
-Host synchronisations per frame: the rigid run's one copy back (frames >= 1 with rigid_iterations > 0; in "raycast"
-mode it also brings the prediction's hit count), the non-rigid optimize()'s own (when one is given), and one read of
+Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
+or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
+count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals.
 
 Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
 field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
-fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, frame-to-model tracking with
-the prediction's normals (point-to-plane ICP), an adaptive ray-casting step, a colour or confidence image in the
+fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, a normal-angle gate in ICP,
+bilateral filtering or downsampled image pyramids, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
+an adaptive ray-casting step, a colour or confidence image in the
 prediction, marching squares for 2-D models, vertex attributes beyond normals, welding vertices by position,
 decimation, and a mesh extracted without the host read of its totals."""
 import math
@@ -44,16 +50,19 @@ import math
 import numpy as np
 import torch
 
-from .. import device_fusion, device_mesh, device_raycast, device_rigid
+from .. import device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
 from ..device_fusion import RECORD_FIELDS, unpack_record
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS", "TRACKING_REFERENCES"]
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS", "TRACKING_REFERENCES",
+           "TRACKING_MODES"]
 
+# the trackers with a reference volume (rigid_run_3d), and every tracking mode SequenceFusion3d accepts
 TRACKING_REFERENCES = ("model", "raycast")
+TRACKING_MODES = TRACKING_REFERENCES + ("icp",)
 
 
 def _model_shape(shape):
@@ -134,15 +143,18 @@ class CanonicalVolume:
 
 
 class SequenceFusion3d:
-    """track each depth frame against the model (tracking_reference "model") or its ray-cast prediction ("raycast")
-    and fuse it (module docstring).  Keeps `canonical` (the CanonicalVolume), `twists` (one float64 (6,) per frame),
+    """track each depth frame against the model (tracking_reference "model"), the live volume of its ray-cast
+    prediction ("raycast") or, by point-to-plane ICP, the prediction's depth and normals ("icp"), and fuse it (module
+    docstring).  Keeps `canonical` (the CanonicalVolume), `twists` (one float64 (6,) per frame),
     `frame_records` (one dict per frame: frame, twist, rigid_records, nonrigid, fusion, prediction_hits -- the pixels
-    of the prediction that hit the model, None without a prediction) and, in "raycast" mode, `prediction` (the last
-    predicted depth image, a float32 device tensor in metres)."""
+    of the prediction that hit the model, None without a prediction) and, in "raycast" and "icp" mode, `prediction`
+    (the last predicted depth image, a float32 device tensor in metres).  In "icp" mode rigid_records holds the ICP
+    records (device_icp.unpack_record)."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
-                 initial_twist=None, tracking_reference="model"):
+                 initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
+                 icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE):
         self.camera = camera
         self.field_shape = device_rigid.volume_shape(field_shape)
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
@@ -152,8 +164,12 @@ class SequenceFusion3d:
             raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
         if int(rigid_iterations) < 0:
             raise ValueError("rigid_iterations must be >= 0")
-        if tracking_reference not in TRACKING_REFERENCES:
-            raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_REFERENCES, tracking_reference))
+        if tracking_reference not in TRACKING_MODES:
+            raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_MODES, tracking_reference))
+        self.icp_iterations, self.icp_strides = device_icp.levels(icp_iterations, icp_strides)
+        if not float(icp_max_distance) > 0:
+            raise ValueError("icp_max_distance must be positive")
+        self.icp_max_distance = float(icp_max_distance)
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -165,7 +181,7 @@ class SequenceFusion3d:
         self.canonical = CanonicalVolume(self.field_shape, max_weight)
         self.twists = []
         self.frame_records = []
-        self.prediction = None  # "raycast": the last prediction, a float32 device depth image in metres
+        self.prediction = None  # "raycast", "icp": the last prediction, a float32 device depth image in metres
         self._previous = None  # "raycast": the previous frame's (device depth, LSF_DEPTH_* code)
         P = camera.intrinsics.intrinsic_matrix
         # the prediction is in metres: its live volume is generated with ratio 1
@@ -183,6 +199,17 @@ class SequenceFusion3d:
                                            self.array_offset, twist, self.voxel_size, self.narrow_band_width_voxels)
         return live, hits
 
+    def _track_icp(self, depth, code, twist):
+        """ICP of the frame against the model ray-cast with normals at twist (no fallback), started from twist: the
+        new twist, the unpacked ICP records and the prediction's device hit count"""
+        model = self.canonical
+        self.prediction, normals, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
+                                                                self.array_offset, self.voxel_size, tuple(depth.shape),
+                                                                normals=True)
+        twist, records, _ = device_icp.icp_run(depth, code, self.prediction, normals, self.camera, twist, twist,
+                                               self.icp_iterations, self.icp_strides, self.icp_max_distance)
+        return twist, [device_icp.unpack_record(r) for r in records], hits
+
     def integrate(self, depth_image):
         """track and fuse one frame; returns its record (also appended to frame_records)"""
         k = len(self.twists)
@@ -194,7 +221,10 @@ class SequenceFusion3d:
             twist = self.initial_twist.copy()
         else:
             twist = self.twists[-1].copy()
-            if self.rigid_iterations > 0:
+            if self.tracking_reference == "icp":
+                if sum(self.icp_iterations) > 0:
+                    twist, rigid_records, hits = self._track_icp(depth, code, twist)
+            elif self.rigid_iterations > 0:
                 reference = model.tsdf
                 if self.tracking_reference == "raycast":
                     reference, hits = self._prediction_volume(twist)

@@ -1,3 +1,5 @@
 """SDF-2-SDF rigid tracking (reference rigid_opt/): Sdf2SdfOptimizer2d, its datasets and calculate_gradient_wrt_twist,
-and their 6-DoF 3-D generalisation Sdf2SdfOptimizer3d and calculate_gradient_wrt_twist_3d.  The optimizers' whole loops
-run on the GPU (csrc/lsf_rigid.hip, csrc/lsf_rigid3d.hip)."""
+and their 6-DoF 3-D generalisation Sdf2SdfOptimizer3d and calculate_gradient_wrt_twist_3d; ProjectiveIcp3d tracks a depth
+frame against a ray-cast prediction by point-to-plane ICP.  The optimizers' whole loops run on the GPU
+(csrc/lsf_rigid.hip, csrc/lsf_rigid3d.hip, csrc/lsf_icp.hip)."""
+from .projective_icp3d import ProjectiveIcp3d  # noqa: F401

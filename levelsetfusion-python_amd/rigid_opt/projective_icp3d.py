@@ -1,0 +1,56 @@
+"""ProjectiveIcp3d: frame-to-model tracking by projective point-to-plane ICP (the KinectFusion tracker), which the
+reference does not have.  INTEGRATION.md section 3 ("Projective ICP") defines the arithmetic and
+tests/icp_restatement.py restates it.
+
+The model's prediction -- depth and camera-space normals ray-cast at prediction_twist (CanonicalVolume.raycast with
+normals=True) -- is the target.  Each live pixel with depth > 0 is taken to the world under the current twist,
+projected into the prediction's camera and paired with the prediction pixel it lands on (rint on both axes) when that
+pixel has a depth and a normal and the two points are at most max_distance apart.  Every iteration solves the 6 x 6
+point-to-plane normal equations and composes the step into the twist; levels run coarse first, a level of stride s
+using the live pixels (s i, s j) only.  The whole pyramid is one enqueue (device_icp.icp_run: sum(iterations) + 1
+launches of csrc/lsf_icp.hip) and one copy back; the per-iteration records stay on the tracker as `last_records` (a
+list of dicts: delta, twist, energy, matrix_a, vector_b, skipped, count, level)."""
+import numpy as np
+import torch
+
+from .. import device_icp
+from ..device_core import require_gpu
+from ..device_rigid import twist6
+from ..tsdf.generation import device_depth
+
+__all__ = ["ProjectiveIcp3d"]
+
+
+def _prediction(x, trailing):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    t = t.to("cuda").to(torch.float32).contiguous()
+    if t.dim() != 2 + len(trailing) or tuple(t.shape[2:]) != trailing:
+        raise ValueError("the prediction must be depth (H, W) and normals (H, W, 3), got shape %s" % (tuple(t.shape),))
+    return t
+
+
+class ProjectiveIcp3d:
+    def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
+                 max_distance=device_icp.MAX_DISTANCE):
+        self.camera = camera
+        self.iterations, self.strides = device_icp.levels(iterations, strides)
+        if not float(max_distance) > 0:
+            raise ValueError("max_distance must be positive")
+        self.max_distance = float(max_distance)
+        self.last_records = []
+        self.last_residuals = None
+
+    def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
+                 residuals=False):
+        """the float64 (6,) twist of the live depth frame (uint16 / float32 / float64, scaled by the camera's
+        depth_unit_ratio), started from twist (prediction_twist by default).  residuals=True also keeps the last
+        iteration's residual image (float32 device tensor, NaN without a correspondence) as `last_residuals`."""
+        require_gpu()
+        depth, code = device_depth(live_depth)
+        twist_p = twist6(prediction_twist)
+        out, records, res = device_icp.icp_run(
+            depth, code, _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,)), self.camera,
+            twist_p, twist_p if twist is None else twist, self.iterations, self.strides, self.max_distance, residuals)
+        self.last_records = [device_icp.unpack_record(r) for r in records]
+        self.last_residuals = res
+        return out
