@@ -1083,7 +1083,8 @@ typedef struct lsf_icp_params {
 /* one record per iteration, LSF_ICP_RECORD_DOUBLES doubles, written by the launch after it:
  *   [0, 6) delta = A^-1 b (0 when skipped)   [6, 12) twist after the update   [12] energy (sum r^2)   [13, 49) A
  *   row-major   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)
- *   [56] correspondence count   [57] level   [58, 64) reserved */
+ *   [56] correspondence count   [57] level   [58] pairs the normal-angle gate rejected (lsf_icp_run_pyramid; 0 from
+ *   lsf_icp_run)   [59, 64) reserved */
 #define LSF_ICP_RECORD_DOUBLES 64
 /* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
  * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
@@ -1101,6 +1102,62 @@ typedef struct lsf_icp_params {
  * another output. */
 int lsf_icp_run(const void *live_depth, const float *pred_depth, const float *pred_normals, double *twist_inout,
                 double *records, void *scratch, float *residuals_out, const lsf_icp_params *params, void *stream);
+
+/* ---- the live depth pyramid: bilateral filter, depth-gated 2 x 2 means, per-level normals ---------------------------
+ * The measurement stage KinectFusion puts in front of ICP; the reference has none.  The arithmetic is INTEGRATION.md
+ * section 3 ("Depth pyramid"), every step one float64 operation.  Level 0 is the live depth scaled by depth_unit_ratio
+ * (lsf_icp_run's scaling) and bilaterally filtered over the window |du|, |dv| <= radius (radius 0: unfiltered); level
+ * l + 1 is the depth-gated mean of level l's 2 x 2 blocks; every level gets normals n = B x A of its forward
+ * differences, 0 at the last row and column, at invalid depths and across a depth step > depth_gate.  Level l has
+ * extents (height >> l, width >> l) and the intrinsics fx_l = fx_{l-1} / 2, fy_l = fy_{l-1} / 2,
+ * cx_l = (cx_{l-1} - 0.5) / 2, cy_l = (cy_{l-1} - 0.5) / 2.  Levels are stored back to back, level 0 first. */
+#define LSF_PYRAMID_MAX_RADIUS 8
+typedef struct lsf_depth_pyramid_params {
+    double fx, fy, cx, cy;     /* level-0 intrinsics, pixels; finite, fx and fy non-zero */
+    double depth_unit_ratio;   /* metres per unit of the depth image, finite */
+    double sigma_space;        /* pixels, finite and > 0 when radius > 0 */
+    double sigma_range;        /* metres, finite and > 0 when radius > 0 */
+    double depth_gate;         /* metres, > 0 (inf allowed) */
+    int32_t height, width;     /* level-0 extents, >= 1 each, at most 2^31 - 1 pixels */
+    int32_t depth_dtype;       /* LSF_DEPTH_* of the depth image */
+    int32_t levels;            /* 1 .. LSF_ICP_MAX_LEVELS; height >> (levels - 1) and width >> (levels - 1) >= 1 */
+    int32_t radius;            /* 0 .. LSF_PYRAMID_MAX_RADIUS */
+} lsf_depth_pyramid_params;
+
+/* depth_image: DEVICE [height][width] of depth_dtype.  pyramid_depth: DEVICE float32, sum over levels of
+ * (height >> l) (width >> l) values, metres, 0 where invalid; pyramid_normals: DEVICE float32, three times that,
+ * [y][x][3] per level, camera coordinates.  levels + 1 launches on stream with no host wait: the filter, one per
+ * coarser level, one for the normals of every level.  No buffer may alias another. */
+int lsf_depth_pyramid(const void *depth_image, float *pyramid_depth, float *pyramid_normals,
+                      const lsf_depth_pyramid_params *params, void *stream);
+
+/* ---- projective point-to-plane ICP over a depth pyramid, with a normal-angle gate ----------------------------------
+ * lsf_icp_run's arithmetic, schedule and records, with the live pixels taken from a lsf_depth_pyramid output: the level
+ * of iterations entry k (coarse first) is levels - 1 - k; every pixel of it is back-projected with that level's
+ * intrinsics and associated into the full-resolution prediction with the level-0 ones.  With angle_gate != 0 a pair is
+ * kept only when the live normal n is non-zero and (R^T n) . N_w >= cos_max_angle, tested after the distance; record
+ * slot 58 counts the pairs the gate rejects.  The partial sums hold a 30th entry (that count), hence the scratch
+ * size. */
+typedef struct lsf_icp_pyramid_params {
+    double fx, fy, cx, cy;             /* level-0 intrinsics, pixels; finite, fx and fy non-zero */
+    double max_distance;               /* metres, > 0 (inf allowed) */
+    double cos_max_angle;              /* the gate: -1 .. 1 */
+    double twist_p[6];                 /* the prediction's twist, float64 (rounded to float32 as the ray-cast does) */
+    int32_t height, width;             /* level-0 extents of the live pyramid and the prediction */
+    int32_t pyramid_levels;            /* levels the live pyramid holds, 1 .. LSF_ICP_MAX_LEVELS */
+    int32_t levels;                    /* levels tracked, 1 .. pyramid_levels */
+    int32_t angle_gate;                /* 0: no gate, else gate at cos_max_angle */
+    int32_t iterations[LSF_ICP_MAX_LEVELS]; /* per tracked level, coarse first, >= 0 */
+} lsf_icp_pyramid_params;
+#define LSF_ICP_PYRAMID_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 30 * 8)
+
+/* live_depth, live_normals: lsf_depth_pyramid's outputs for (height, width, pyramid_levels); pred_depth,
+ * pred_normals, twist_inout, records: as lsf_icp_run; scratch: DEVICE, LSF_ICP_PYRAMID_SCRATCH_BYTES; residuals_out:
+ * NULL, or DEVICE float32 of the last iteration's level extents, r there, NaN where a pixel has no correspondence.
+ * sum(iterations) + 1 launches, none when sum(iterations) == 0.  No output may alias an input or another output. */
+int lsf_icp_run_pyramid(const float *live_depth, const float *live_normals, const float *pred_depth,
+                        const float *pred_normals, double *twist_inout, double *records, void *scratch,
+                        float *residuals_out, const lsf_icp_pyramid_params *params, void *stream);
 
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):

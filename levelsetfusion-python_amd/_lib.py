@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "328469b091d8b5a3"
+HEADER_ABI_HASH = "845b6f86b0b9638d"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -239,6 +239,25 @@ class IcpParams(ctypes.Structure):
                [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS), ("strides", ctypes.c_int32 * ICP_MAX_LEVELS)]
 
 
+PYRAMID_MAX_RADIUS = 8
+ICP_PYRAMID_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 30 * 8
+
+
+class DepthPyramidParams(ctypes.Structure):
+    """lsf_depth_pyramid_params: the live depth pyramid (lsf_depth_pyramid)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_unit_ratio", "sigma_space",
+                                               "sigma_range", "depth_gate")] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "depth_dtype", "levels", "radius")]
+
+
+class IcpPyramidParams(ctypes.Structure):
+    """lsf_icp_pyramid_params: point-to-plane ICP over a live depth pyramid (lsf_icp_run_pyramid)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "max_distance", "cos_max_angle")] + \
+               [("twist_p", ctypes.c_double * 6)] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "pyramid_levels", "levels", "angle_gate")] + \
+               [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -355,6 +374,8 @@ PROTOTYPES = {
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
+    "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
+    "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),
 }
 
 

@@ -1,14 +1,16 @@
 """Torch-facing wrapper of projective point-to-plane ICP (include/lsf_hip.h: lsf_icp_run).  Every argument is checked on
 the host before the launches; a call enqueues sum(iterations) + 1 launches with no host wait and copies the twist and
 the records back once.  The public interfaces are rigid_opt.ProjectiveIcp3d and
-fusion.SequenceFusion3d(tracking_reference="icp")."""
+fusion.SequenceFusion3d(tracking_reference="icp").  icp_run_pyramid (lsf_icp_run_pyramid) is the same schedule over a
+live depth pyramid (device_depth_pyramid), with an optional normal-angle gate."""
 import ctypes
+import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, check, lib
+from ._lib import IcpParams, IcpPyramidParams, check, lib
 from .device_core import require_gpu, stream_ptr
 from .device_raycast import image_extents
 from .device_rigid import twist6
@@ -95,8 +97,99 @@ def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, t
     return host[:6].copy(), host[head:].reshape(total, RECORD).copy(), res
 
 
+def pyramid_iterations(iterations, pyramid_levels):
+    """the iterations of a pyramid run as a tuple of ints >= 0, coarse first: one entry per tracked level, at most
+    pyramid_levels of them; entry k runs on pyramid level len(iterations) - 1 - k"""
+    it = tuple(int(v) for v in np.atleast_1d(iterations))
+    if not 1 <= len(it) <= int(pyramid_levels) or min(it) < 0:
+        raise ValueError("iterations need 1 to %d entries >= 0 (one per pyramid level), got %s"
+                         % (int(pyramid_levels), it))
+    return it
+
+
+def cos_max_angle(max_normal_angle):
+    """the gate's cosine of an angle in radians, 0 .. pi"""
+    a = float(max_normal_angle)
+    if not 0.0 <= a <= math.pi:
+        raise ValueError("max_normal_angle must be in [0, pi] radians, got %r" % (max_normal_angle,))
+    return max(-1.0, min(1.0, math.cos(a)))
+
+
+def pyramid_params(camera, image_shape, pyramid_levels, twist_p, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
+                   max_normal_angle=None):
+    """the lsf_icp_pyramid_params of a call, after the host checks; max_normal_angle None: no gate"""
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    p = IcpPyramidParams()
+    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
+    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
+        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    p.max_distance = float(max_distance)
+    if not p.max_distance > 0:
+        raise ValueError("max_distance must be positive")
+    p.angle_gate = 0 if max_normal_angle is None else 1
+    p.cos_max_angle = -1.0 if max_normal_angle is None else cos_max_angle(max_normal_angle)
+    tp = twist6(twist_p)
+    if not np.all(np.isfinite(tp)):
+        raise ValueError("twist_p must be finite")
+    p.twist_p[:] = list(tp)
+    p.height, p.width = image_extents(image_shape)
+    p.pyramid_levels = int(pyramid_levels)
+    if not 1 <= p.pyramid_levels <= _lib.ICP_MAX_LEVELS or (p.height >> (p.pyramid_levels - 1)) < 1 or \
+            (p.width >> (p.pyramid_levels - 1)) < 1:
+        raise ValueError("a %d x %d image has no %d-level pyramid" % (p.height, p.width, p.pyramid_levels))
+    it = pyramid_iterations(iterations, p.pyramid_levels)
+    p.levels = len(it)
+    p.iterations[:len(it)] = list(it)
+    return p
+
+
+def last_level(iterations):
+    """the pyramid level of a run's last iteration (0 when there is none)"""
+    it = tuple(iterations)
+    ks = [k for k, n in enumerate(it) if n > 0]
+    return len(it) - 1 - ks[-1] if ks else 0
+
+
+def icp_run_pyramid(pyramid_depth, pyramid_normals, pyramid_levels, pred_depth, pred_normals, camera, twist_p,
+                    twist=None, iterations=ITERATIONS, max_distance=MAX_DISTANCE, max_normal_angle=None,
+                    residuals=False):
+    """ICP over a live pyramid (device_depth_pyramid.depth_pyramid's two buffers of pyramid_levels levels, at the
+    prediction's extents), enqueued: sum(iterations) + 1 launches and one copy back.  iterations: one entry per tracked
+    level, coarse first.  max_normal_angle (radians): the normal-angle gate, None for none.  Returns icp_run's triple;
+    the residual image has the extents of the last iteration's level."""
+    require_gpu()
+    if not (isinstance(pred_depth, torch.Tensor) and pred_depth.dim() == 2):
+        raise ValueError("pred_depth must be an (H, W) device tensor (device_raycast.raycast)")
+    h, w = (int(v) for v in pred_depth.shape)
+    p = pyramid_params(camera, (h, w), pyramid_levels, twist_p, iterations, max_distance, max_normal_angle)
+    _prediction(pred_depth, "pred_depth", (h, w))
+    _prediction(pred_normals, "pred_normals", (h, w, 3))
+    pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
+    _prediction(pyramid_depth, "pyramid_depth", (pixels,))
+    _prediction(pyramid_normals, "pyramid_normals", (pixels, 3))
+    it = tuple(p.iterations[:p.levels])
+    total = sum(it)
+    head = 8
+    out = torch.zeros(head + total * RECORD, dtype=torch.float64, device=pred_depth.device)
+    out[:6] = torch.from_numpy(twist6(twist_p if twist is None else twist).copy())
+    scratch = torch.empty(_lib.ICP_PYRAMID_SCRATCH_BYTES // 8, dtype=torch.float64, device=pred_depth.device)
+    last = last_level(it)
+    res = torch.empty((h >> last, w >> last), dtype=torch.float32, device=pred_depth.device) if residuals else None
+    base = out.data_ptr()
+    check(lib.lsf_icp_run_pyramid(ctypes.c_void_p(pyramid_depth.data_ptr()), ctypes.c_void_p(pyramid_normals.data_ptr()),
+                                  ctypes.c_void_p(pred_depth.data_ptr()), ctypes.c_void_p(pred_normals.data_ptr()),
+                                  ctypes.c_void_p(base), ctypes.c_void_p(base + head * 8),
+                                  ctypes.c_void_p(scratch.data_ptr()),
+                                  None if res is None else ctypes.c_void_p(res.data_ptr()), ctypes.byref(p),
+                                  stream_ptr()),
+          "lsf_icp_run_pyramid")
+    host = out.cpu().numpy()
+    return host[:6].copy(), host[head:].reshape(total, RECORD).copy(), res
+
+
 def unpack_record(r):
-    """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES)"""
+    """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES); angle_rejected is 0 on
+    every lsf_icp_run record"""
     return {"delta": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
             "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
-            "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57])}
+            "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57]), "angle_rejected": int(r[58])}

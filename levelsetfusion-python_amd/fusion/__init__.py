@@ -27,7 +27,10 @@ by ICP against the model's prediction:
                model itself meets that residual at every band's back edge, and the prediction does not have it.
     "icp"      projective point-to-plane ICP (rigid_opt.ProjectiveIcp3d, device_icp.icp_run) of the frame against the
                model ray-cast with normals at the previous twist, without a fallback image; `icp_iterations`,
-               `icp_strides` and `icp_max_distance` set the pyramid, and `rigid_iterations` is not used.
+               `icp_strides` and `icp_max_distance` set the pyramid, and `rigid_iterations` is not used.  With
+               `icp_pyramid` (a rigid_opt.DepthPyramid) the frame's filtered depth pyramid is built on the device and
+               `icp_iterations` runs over its levels (device_icp.icp_run_pyramid), `icp_strides` not used;
+               `icp_max_normal_angle` (radians) adds the normal-angle gate.  Fusion still integrates the raw depth.
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
 With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
 generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
@@ -40,8 +43,8 @@ vertex and face totals.
 
 Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
 field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
-fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, a normal-angle gate in ICP,
-bilateral filtering or downsampled image pyramids, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
+fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, fusing the filtered depth, a
+downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
 an adaptive ray-casting step, a colour or confidence image in the
 prediction, marching squares for 2-D models, vertex attributes beyond normals, welding vertices by position,
 decimation, and a mesh extracted without the host read of its totals."""
@@ -53,6 +56,7 @@ import torch
 from .. import device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
 from ..device_fusion import RECORD_FIELDS, unpack_record
+from ..rigid_opt.projective_icp3d import checked_pyramid
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
@@ -154,7 +158,8 @@ class SequenceFusion3d:
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
-                 icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE):
+                 icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
+                 icp_max_normal_angle=None):
         self.camera = camera
         self.field_shape = device_rigid.volume_shape(field_shape)
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
@@ -166,7 +171,12 @@ class SequenceFusion3d:
             raise ValueError("rigid_iterations must be >= 0")
         if tracking_reference not in TRACKING_MODES:
             raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_MODES, tracking_reference))
-        self.icp_iterations, self.icp_strides = device_icp.levels(icp_iterations, icp_strides)
+        self.icp_pyramid, self.icp_max_normal_angle = checked_pyramid(icp_pyramid, icp_max_normal_angle)
+        if icp_pyramid is None:
+            self.icp_iterations, self.icp_strides = device_icp.levels(icp_iterations, icp_strides)
+        else:
+            self.icp_iterations, self.icp_strides = device_icp.pyramid_iterations(icp_iterations,
+                                                                                  icp_pyramid.levels), None
         if not float(icp_max_distance) > 0:
             raise ValueError("icp_max_distance must be positive")
         self.icp_max_distance = float(icp_max_distance)
@@ -206,8 +216,14 @@ class SequenceFusion3d:
         self.prediction, normals, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
                                                                 self.array_offset, self.voxel_size, tuple(depth.shape),
                                                                 normals=True)
-        twist, records, _ = device_icp.icp_run(depth, code, self.prediction, normals, self.camera, twist, twist,
-                                               self.icp_iterations, self.icp_strides, self.icp_max_distance)
+        if self.icp_pyramid is None:
+            twist, records, _ = device_icp.icp_run(depth, code, self.prediction, normals, self.camera, twist, twist,
+                                                   self.icp_iterations, self.icp_strides, self.icp_max_distance)
+        else:
+            pyramid = self.icp_pyramid.build(depth, self.camera)
+            twist, records, _ = device_icp.icp_run_pyramid(*pyramid.buffers, self.icp_pyramid.levels, self.prediction,
+                                                           normals, self.camera, twist, twist, self.icp_iterations,
+                                                           self.icp_max_distance, self.icp_max_normal_angle)
         return twist, [device_icp.unpack_record(r) for r in records], hits
 
     def integrate(self, depth_image):

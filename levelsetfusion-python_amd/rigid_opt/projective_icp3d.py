@@ -9,13 +9,18 @@ pixel has a depth and a normal and the two points are at most max_distance apart
 point-to-plane normal equations and composes the step into the twist; levels run coarse first, a level of stride s
 using the live pixels (s i, s j) only.  The whole pyramid is one enqueue (device_icp.icp_run: sum(iterations) + 1
 launches of csrc/lsf_icp.hip) and one copy back; the per-iteration records stay on the tracker as `last_records` (a
-list of dicts: delta, twist, energy, matrix_a, vector_b, skipped, count, level)."""
+list of dicts: delta, twist, energy, matrix_a, vector_b, skipped, count, level, angle_rejected).
+
+With a DepthPyramid (pyramid=...) the live frame is first turned into a filtered pyramid on the device, and level k of
+the iterations (coarse first) uses every pixel of pyramid level len(iterations) - 1 - k instead of a stride;
+max_normal_angle (radians) adds the normal-angle gate.  The pyramid of the last call stays as `last_pyramid`."""
 import numpy as np
 import torch
 
 from .. import device_icp
 from ..device_core import require_gpu
 from ..device_rigid import twist6
+from .depth_pyramid import DepthPyramid
 from ..tsdf.generation import device_depth
 
 __all__ = ["ProjectiveIcp3d"]
@@ -31,26 +36,55 @@ def _prediction(x, trailing):
 
 class ProjectiveIcp3d:
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
-                 max_distance=device_icp.MAX_DISTANCE):
+                 max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None):
+        """pyramid: None (the strided live image) or a DepthPyramid, with which strides is not used and iterations has
+        one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only)"""
         self.camera = camera
-        self.iterations, self.strides = device_icp.levels(iterations, strides)
+        self.pyramid, self.max_normal_angle = checked_pyramid(pyramid, max_normal_angle)
+        if pyramid is None:
+            self.iterations, self.strides = device_icp.levels(iterations, strides)
+        else:
+            self.iterations = device_icp.pyramid_iterations(iterations, pyramid.levels)
+            self.strides = None
         if not float(max_distance) > 0:
             raise ValueError("max_distance must be positive")
         self.max_distance = float(max_distance)
         self.last_records = []
         self.last_residuals = None
+        self.last_pyramid = None
 
     def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
                  residuals=False):
         """the float64 (6,) twist of the live depth frame (uint16 / float32 / float64, scaled by the camera's
         depth_unit_ratio), started from twist (prediction_twist by default).  residuals=True also keeps the last
-        iteration's residual image (float32 device tensor, NaN without a correspondence) as `last_residuals`."""
+        iteration's residual image (float32 device tensor, NaN without a correspondence) as `last_residuals`; with a
+        pyramid it has the extents of the last iteration's level."""
         require_gpu()
         depth, code = device_depth(live_depth)
         twist_p = twist6(prediction_twist)
-        out, records, res = device_icp.icp_run(
-            depth, code, _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,)), self.camera,
-            twist_p, twist_p if twist is None else twist, self.iterations, self.strides, self.max_distance, residuals)
+        start = twist_p if twist is None else twist
+        pd, pn = _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,))
+        if self.pyramid is None:
+            out, records, res = device_icp.icp_run(depth, code, pd, pn, self.camera, twist_p, start, self.iterations,
+                                                   self.strides, self.max_distance, residuals)
+        else:
+            self.last_pyramid = self.pyramid.build(depth, self.camera)
+            out, records, res = device_icp.icp_run_pyramid(
+                *self.last_pyramid.buffers, self.pyramid.levels, pd, pn, self.camera, twist_p, start, self.iterations,
+                self.max_distance, self.max_normal_angle, residuals)
         self.last_records = [device_icp.unpack_record(r) for r in records]
         self.last_residuals = res
         return out
+
+
+def checked_pyramid(pyramid, max_normal_angle):
+    """(pyramid, max_normal_angle) after the host checks: a DepthPyramid or None; an angle in [0, pi] radians, only
+    with a pyramid"""
+    if pyramid is not None and not isinstance(pyramid, DepthPyramid):
+        raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
+    if max_normal_angle is None:
+        return pyramid, None
+    if pyramid is None:
+        raise ValueError("max_normal_angle needs a pyramid: the strided path has no live normals")
+    device_icp.cos_max_angle(max_normal_angle)
+    return pyramid, float(max_normal_angle)
