@@ -1,19 +1,24 @@
-// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run): the KinectFusion
-// tracker, which the reference does not have.  The arithmetic is INTEGRATION.md section 3 ("Projective ICP");
-// tests/icp_restatement.py restates it.  Every per-pixel step is one float64 operation in the order written there;
-// -ffp-contract=off keeps products and sums separately rounded, so the residual image and the correspondence count
-// equal the restatement bit for bit.  One kernel, two modes, with the 3-D rigid tracker's schedule (RigidMode,
-// lsf_rigid_solve.h):
-//   ITERATE  iteration k: prologue = combine iteration k-1's per-block partial sums in a fixed order, solve the 6 x 6
+// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run and
+// lsf_icp_run_pyramid): the KinectFusion tracker, which the reference does not have.  The arithmetic is INTEGRATION.md
+// section 3 ("Projective ICP"); tests/icp_restatement.py restates it.  Every per-pixel step is one float64 operation in
+// the order written there; -ffp-contract=off keeps products and sums separately rounded, so the residual image and
+// the correspondence count equal the restatement bit for bit.  One iteration kernel over a live source, and the 3-D
+// rigid tracker's schedule (lsf_rigid_solve.h):
+//   iterate  iteration k: prologue = combine iteration k-1's per-block partial sums in a fixed order, solve the 6 x 6
 //            system, compose the step into the twist (every block computes the same twist bit for bit, block 0 writes
-//            record k-1); body = one lane per strided live pixel, a wave per 8 x 8 block of them, a grid-stride loop
-//            over 16 x 16 tiles, the 29 float64 sums kept in registers; one block reduction at the end into this
-//            block's partial (ping-pong buffer k & 1)
-//   FINISH   the prologue alone for the last iteration, one block; writes the final twist
+//            record k-1); body = one lane per pixel of the source's level, a wave per 8 x 8 block of them, a
+//            grid-stride loop over 16 x 16 tiles, the float64 sums kept in registers; one block reduction at the end
+//            into this block's partial (ping-pong buffer k & 1)
+//   finish   the prologue alone for the last iteration, one block; writes the final twist
 // The partials cross launch boundaries only: no float atomics, no in-launch hand-off, so a rerun is bit-identical.
-// lsf_icp_run_pyramid is the same schedule over a live depth pyramid (lsf_depth_pyramid's output): a lane per pixel
-// of the level, back-projected with the level's intrinsics, an optional normal-angle gate after the distance test, and
-// a 30th sum, the pairs the gate rejected (record slot 58).
+// A source is the level of a launch: its pixel grid, a pixel's camera-space vertex, and how the residual is stored.
+//   StridedSource  lsf_icp_run: the pixels (stride i, stride j) of the live depth image, 29 sums
+//   PyramidSource  lsf_icp_run_pyramid: every pixel of one level of lsf_depth_pyramid's output, back-projected with
+//                  the level's intrinsics; an optional normal-angle gate after the distance test, and a 30th sum, the
+//                  pairs the gate rejected (record slot 58)
+#include <initializer_list>
+#include <type_traits>
+
 #include "lsf_device.h"
 #include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
@@ -42,18 +47,74 @@ struct IcpDev {
     int height, width;
 };
 
-// the strided pixel grid of one launch's level
-struct Level {
-    int stride, ni, nj;  // pixels (stride i, stride j), i < ni, j < nj
-    int tiles_x, tiles;  // 16 x 16 tiles of the strided grid
+// the pixels (i, j), i < ni, j < nj, of one launch's level and their 16 x 16 tiles
+struct Grid {
+    int ni, nj, tiles_x, tiles;
 };
 
-// one level of the live pyramid: every pixel (i, j), i < ni, j < nj, at offset + j ni, back-projected with fx ... cy
-struct PyrLevel {
-    double fx, fy, cx, cy;
-    long long offset;
-    int ni, nj;
-    int tiles_x, tiles;
+Grid grid_of(int ni, int nj) {
+    const int tiles_x = (ni + kTile - 1) / kTile;
+    return {ni, nj, tiles_x, tiles_x * ((nj + kTile - 1) / kTile)};
+}
+
+// lsf_icp_run: pixel (i, j) is the live image's (stride i, stride j), its depth scaled by the ratio
+template <typename DT>
+struct StridedSource {
+    static constexpr int K = kSums;
+    static constexpr bool kGate = false;
+    using Live = DT;
+    Grid grid;
+    int stride;
+    static constexpr long long offset = 0;  // of the level in the live buffers
+
+    struct Pixel {
+        int u, v;  // < width, height: ni = ceil(width / stride)
+    };
+    __device__ Pixel pixel(int i, int j) const { return {i * stride, j * stride}; }
+    // the depth of a pixel in metres (it has one when it is > 0), and its vertex in camera coordinates
+    __device__ double depth(const DT* __restrict__ live, const IcpDev& p, Pixel px) const {
+        return (double)scaled_depth(live, (long long)px.v * p.width + px.u, p.ratio);
+    }
+    __device__ void vertex(const IcpDev& p, Pixel px, double d, double (&vx)[3]) const {
+        vx[0] = d * (((double)px.u - p.cx) / p.fx);
+        vx[1] = d * (((double)px.v - p.cy) / p.fy);
+        vx[2] = d * 1.0;
+    }
+    // r at the pixel, NaN at the rest of its stride x stride cell
+    __device__ void store(float* __restrict__ residuals, const IcpDev& p, Pixel px, float res) const {
+        for (int y = px.v; y < min(px.v + stride, p.height); ++y)
+            for (int x = px.u; x < min(px.u + stride, p.width); ++x)
+                residuals[(long long)y * p.width + x] = (x == px.u && y == px.v) ? res : NAN;
+    }
+};
+
+// lsf_icp_run_pyramid: every pixel of one pyramid level, float32 metres at live[j ni + i], normals beside them
+template <bool GATE>
+struct PyramidSource {
+    static constexpr int K = kPyrSums;
+    static constexpr bool kGate = GATE;
+    using Live = float;
+    double fx, fy, cx, cy, cos_max;
+    long long offset;  // of the level in the live buffers: the launch passes their pointers advanced by it
+    Grid grid;
+
+    struct Pixel {
+        int i, j;
+        long long at;  // in the level's arrays
+    };
+    __device__ Pixel pixel(int i, int j) const { return {i, j, (long long)j * grid.ni + i}; }
+    __device__ double depth(const float* __restrict__ live, const IcpDev&, Pixel px) const {
+        return (double)live[px.at];
+    }
+    __device__ void vertex(const IcpDev&, Pixel px, double d, double (&vx)[3]) const {
+        vx[0] = d * (((double)px.i - cx) / fx);
+        vx[1] = d * (((double)px.j - cy) / fy);
+        vx[2] = d * 1.0;
+    }
+    __device__ const float* normal(const float* __restrict__ normals, Pixel px) const { return normals + px.at * 3; }
+    __device__ void store(float* __restrict__ residuals, const IcpDev&, Pixel px, float res) const {
+        residuals[px.at] = res;
+    }
 };
 
 // the twist after the step delta = (tau, omega): R' = R Rodrigues(omega)^T, t' = t - R' tau, out = (t', log R')
@@ -137,14 +198,15 @@ __device__ __forceinline__ void load_poses(const double* tw, const IcpDev& p, do
     for (int q = 0; q < 12; ++q) { e[q] = pose[q]; ep[q] = pose_p[q]; }
 }
 
-// the live vertex vx (camera coordinates) against the prediction at the estimate e: its residual r, the pair's terms
-// added to acc, when the pair is valid and (GATE) the live normal nl passes the angle gate; NaN otherwise.  A pair
-// that passes the distance test and fails the gate counts in acc[kSums].
-template <bool GATE, int K>
-__device__ __forceinline__ float accumulate_pair(const double (&vx)[3], const double (&e)[12], const double (&ep)[12],
-                                                 const IcpDev& p, const float* __restrict__ pred_depth,
-                                                 const float* __restrict__ pred_normals, const float* __restrict__ nl,
-                                                 double cos_max, double (&acc)[K]) {
+// the live vertex vx (camera coordinates) of the source's pixel px against the prediction at the estimate e: its
+// residual r, the pair's terms added to acc, when the pair is valid and (SRC::kGate) the live normal passes the angle
+// gate; NaN otherwise.  A pair that passes the distance test and fails the gate counts in acc[kSums].
+template <typename SRC>
+__device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __restrict__ live_normals,
+                                                 typename SRC::Pixel px, const double (&vx)[3],
+                                                 const double (&e)[12], const double (&ep)[12], const IcpDev& p,
+                                                 const float* __restrict__ pred_depth,
+                                                 const float* __restrict__ pred_normals, double (&acc)[SRC::K]) {
     double dv[3], g[3], q[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) dv[c] = vx[c] - e[c * 4 + 3];
@@ -174,14 +236,15 @@ __device__ __forceinline__ float accumulate_pair(const double (&vx)[3], const do
     for (int c = 0; c < 3; ++c) diff[c] = g[c] - Vw[c];
     const double dist = sqrt((diff[0] * diff[0] + diff[1] * diff[1]) + diff[2] * diff[2]);
     if (!(dist <= p.max_distance)) return NAN;
-    if constexpr (GATE) {  // the live normal in world directions, m = R^T n, against N_w
+    if constexpr (SRC::kGate) {  // the live normal in world directions, m = R^T n, against N_w
+        const float* nl = src.normal(live_normals, px);
         const double ln[3] = {(double)nl[0], (double)nl[1], (double)nl[2]};
         bool keep = ln[0] != 0.0 || ln[1] != 0.0 || ln[2] != 0.0;
         if (keep) {
             double m[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) m[c] = (e[c] * ln[0] + e[4 + c] * ln[1]) + e[8 + c] * ln[2];
-            keep = (m[0] * Nw[0] + m[1] * Nw[1]) + m[2] * Nw[2] >= cos_max;
+            keep = (m[0] * Nw[0] + m[1] * Nw[1]) + m[2] * Nw[2] >= src.cos_max;
         }
         if (!keep) {
             acc[kSums] += 1.0;
@@ -203,131 +266,149 @@ __device__ __forceinline__ float accumulate_pair(const double (&vx)[3], const do
     return (float)r;
 }
 
-template <int MODE, typename DT>
-__global__ __launch_bounds__(kBlock) void icp_kernel(const DT* __restrict__ live, const float* __restrict__ pred_depth,
-                                                     const float* __restrict__ pred_normals,
-                                                     double* __restrict__ twist_io, double* __restrict__ records,
-                                                     double* __restrict__ scratch, float* __restrict__ residuals,
-                                                     IcpDev p, Level lv, int k, int prev_blocks, int prev_level) {
-    __shared__ double red[kBlock / kWave][kSums];
-    __shared__ double tw[6], pose[12], pose_p[12];
-
-    icp_prologue<kSums>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw,
-                        MODE == FINISH ? twist_io : nullptr);
-    if (MODE == FINISH) return;
-    double e[12], ep[12];
-    load_poses(tw, p, pose, pose_p, e, ep);
-
-    double acc[kSums];
-#pragma unroll
-    for (int c = 0; c < kSums; ++c) acc[c] = 0.0;
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    const int ox = (wave % (kTile / kSub)) * kSub + lane % kSub, oy = (wave / (kTile / kSub)) * kSub + lane / kSub;
-    for (int tile = blockIdx.x; tile < lv.tiles; tile += gridDim.x) {
-        const int i = (tile % lv.tiles_x) * kTile + ox, j = (tile / lv.tiles_x) * kTile + oy;
-        if (i >= lv.ni || j >= lv.nj) continue;
-        const int u = i * lv.stride, v = j * lv.stride;  // < width, height: ni = ceil(width / stride)
-        const double d = (double)scaled_depth(live, (long long)v * p.width + u, p.ratio);
-        float res = NAN;
-        if (d > 0.0) {  // NaN is not > 0
-            const double vx[3] = {d * (((double)u - p.cx) / p.fx), d * (((double)v - p.cy) / p.fy), d * 1.0};
-            res = accumulate_pair<false>(vx, e, ep, p, pred_depth, pred_normals, nullptr, 0.0, acc);
-        }
-        if (residuals) {  // the last iteration: r at the pixel, NaN at the rest of its stride x stride cell
-            for (int y = v; y < min(v + lv.stride, p.height); ++y)
-                for (int x = u; x < min(u + lv.stride, p.width); ++x)
-                    residuals[(long long)y * p.width + x] = (x == u && y == v) ? res : NAN;
-        }
-    }
-    store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * kSums);
-}
-
-// lsf_icp_run_pyramid: every pixel of the pyramid level lv, float32 metres, its vertex from the level's intrinsics
-template <int MODE, bool GATE>
-__global__ __launch_bounds__(kBlock) void icp_pyramid_kernel(const float* __restrict__ live,
+template <typename SRC>
+__global__ __launch_bounds__(kBlock) void icp_iterate_kernel(SRC src, const typename SRC::Live* __restrict__ live,
                                                              const float* __restrict__ live_normals,
                                                              const float* __restrict__ pred_depth,
                                                              const float* __restrict__ pred_normals,
                                                              double* __restrict__ twist_io, double* __restrict__ records,
                                                              double* __restrict__ scratch, float* __restrict__ residuals,
-                                                             IcpDev p, PyrLevel lv, double cos_max, int k,
-                                                             int prev_blocks, int prev_level) {
-    __shared__ double red[kBlock / kWave][kPyrSums];
+                                                             IcpDev p, int k, int prev_blocks, int prev_level) {
+    constexpr int K = SRC::K;
+    __shared__ double red[kBlock / kWave][K];
     __shared__ double tw[6], pose[12], pose_p[12];
 
-    icp_prologue<kPyrSums>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw,
-                           MODE == FINISH ? twist_io : nullptr);
-    if (MODE == FINISH) return;
+    icp_prologue<K>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, nullptr);
     double e[12], ep[12];
     load_poses(tw, p, pose, pose_p, e, ep);
 
-    double acc[kPyrSums];
+    double acc[K];
 #pragma unroll
-    for (int c = 0; c < kPyrSums; ++c) acc[c] = 0.0;
+    for (int c = 0; c < K; ++c) acc[c] = 0.0;
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     const int ox = (wave % (kTile / kSub)) * kSub + lane % kSub, oy = (wave / (kTile / kSub)) * kSub + lane / kSub;
-    for (int tile = blockIdx.x; tile < lv.tiles; tile += gridDim.x) {
-        const int i = (tile % lv.tiles_x) * kTile + ox, j = (tile / lv.tiles_x) * kTile + oy;
-        if (i >= lv.ni || j >= lv.nj) continue;
-        const long long at = (long long)j * lv.ni + i;
-        const double d = (double)live[lv.offset + at];
+    for (int tile = blockIdx.x; tile < src.grid.tiles; tile += gridDim.x) {
+        const int i = (tile % src.grid.tiles_x) * kTile + ox, j = (tile / src.grid.tiles_x) * kTile + oy;
+        if (i >= src.grid.ni || j >= src.grid.nj) continue;
+        const auto px = src.pixel(i, j);
+        const double d = src.depth(live, p, px);
         float res = NAN;
-        if (d > 0.0) {
-            const double vx[3] = {d * (((double)i - lv.cx) / lv.fx), d * (((double)j - lv.cy) / lv.fy), d * 1.0};
-            res = accumulate_pair<GATE>(vx, e, ep, p, pred_depth, pred_normals, live_normals + (lv.offset + at) * 3,
-                                        cos_max, acc);
+        if (d > 0.0) {  // NaN is not > 0
+            double vx[3];
+            src.vertex(p, px, d, vx);
+            res = accumulate_pair(src, live_normals, px, vx, e, ep, p, pred_depth, pred_normals, acc);
         }
-        if (residuals) residuals[at] = res;
+        if (residuals) src.store(residuals, p, px, res);  // the last iteration
     }
-    store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * kPyrSums);
+    store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * K);
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
+// the prologue alone, one block: the last iteration's record and the final twist.  K: the sums of the run's source
+template <int K>
+__global__ __launch_bounds__(kBlock) void icp_finish_kernel(double* __restrict__ twist_io, double* __restrict__ records,
+                                                            const double* __restrict__ scratch, int k, int prev_blocks,
+                                                            int prev_level) {
+    __shared__ double red[kBlock / kWave][K];
+    __shared__ double tw[6];
+    icp_prologue<K>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, twist_io);
 }
 
-Level level_of(const lsf_icp_params* q, int stride) {
-    Level lv;
-    lv.stride = stride;
-    lv.ni = (q->width + stride - 1) / stride;
-    lv.nj = (q->height + stride - 1) / stride;
-    lv.tiles_x = (lv.ni + kTile - 1) / kTile;
-    lv.tiles = lv.tiles_x * ((lv.nj + kTile - 1) / kTile);
-    return lv;
-}
+// what every launch of a run shares
+struct Run {
+    const void* live;           // the source's Live type
+    const float* live_normals;  // NULL on the strided path
+    const float* pred_depth;
+    const float* pred_normals;
+    double* twist;
+    double* records;
+    double* scratch;
+    float* residuals;
+    IcpDev p;
+    int total;  // iterations, > 0
+    hipStream_t stream;
+};
 
-template <int MODE, typename DT>
-int launch(unsigned blocks, const void* live, const float* pred_depth, const float* pred_normals, double* twist,
-           double* records, double* scratch, float* residuals, const IcpDev& p, const Level& lv, int k,
-           int prev_blocks, int prev_level, hipStream_t s) {
-    hipLaunchKernelGGL((icp_kernel<MODE, DT>), dim3(blocks), dim3(kBlock), 0, s, reinterpret_cast<const DT*>(live),
-                       pred_depth, pred_normals, twist, records, scratch, residuals, p, lv, k, prev_blocks,
-                       prev_level);
-    return launch_status();
-}
-
-template <typename DT>
-int launch_run(const lsf_icp_params* q, const IcpDev& p, const void* live, const float* pred_depth,
-               const float* pred_normals, double* twist, double* records, double* scratch, float* residuals,
-               int total, hipStream_t s) {
+// the schedule: levels coarse first, iterations[l] launches over source_of(l), the residuals from launch total - 1,
+// then the finishing launch
+template <typename SourceOf>
+int launch_run(const Run& r, int levels, const int32_t* iterations, SourceOf source_of) {
+    using SRC = decltype(source_of(0));
     int k = 0, prev_blocks = 0, prev_level = 0;
-    Level lv = level_of(q, 1);
-    for (int l = 0; l < q->levels; ++l) {
-        lv = level_of(q, q->strides[l]);
-        const int blocks = lv.tiles < kMaxBlocks ? lv.tiles : kMaxBlocks;
-        for (int it = 0; it < q->iterations[l]; ++it, ++k) {
-            if (int e = launch<ITERATE, DT>(blocks, live, pred_depth, pred_normals, twist, records, scratch,
-                                            k == total - 1 ? residuals : nullptr, p, lv, k, prev_blocks, prev_level,
-                                            s))
-                return e;
+    for (int l = 0; l < levels; ++l) {
+        const SRC src = source_of(l);
+        const int blocks = src.grid.tiles < kMaxBlocks ? src.grid.tiles : kMaxBlocks;
+        for (int it = 0; it < iterations[l]; ++it, ++k) {
+            hipLaunchKernelGGL(icp_iterate_kernel<SRC>, dim3(blocks), dim3(kBlock), 0, r.stream, src,
+                               reinterpret_cast<const typename SRC::Live*>(r.live) + src.offset,
+                               r.live_normals + src.offset * 3, r.pred_depth,
+                               r.pred_normals, r.twist, r.records, r.scratch,
+                               k == r.total - 1 ? r.residuals : nullptr, r.p, k, prev_blocks, prev_level);
+            if (int e = launch_status()) return e;
             prev_blocks = blocks;
             prev_level = l;
         }
     }
-    return launch<FINISH, DT>(1, live, pred_depth, pred_normals, twist, records, scratch, nullptr, p, lv, total,
-                              prev_blocks, prev_level, s);
+    hipLaunchKernelGGL(icp_finish_kernel<SRC::K>, dim3(1), dim3(kBlock), 0, r.stream, r.twist, r.records, r.scratch,
+                       r.total, prev_blocks, prev_level);
+    return launch_status();
+}
+
+// the checks the two parameter structs share: the extents, finite intrinsics and twist_p, max_distance
+template <typename Q>
+bool camera_ok(const Q* q) {
+    if (q->height < 1 || q->width < 1 || (long long)q->height * q->width > 0x7fffffffll) return false;
+    const double all[] = {q->fx, q->fy, q->cx, q->cy, q->twist_p[0], q->twist_p[1], q->twist_p[2], q->twist_p[3],
+                          q->twist_p[4], q->twist_p[5]};
+    for (double x : all)
+        if (!std::isfinite(x)) return false;
+    return q->fx != 0.0 && q->fy != 0.0 && q->max_distance > 0.0;
+}
+
+// sum(iterations), or -1 when an entry is negative, the records would not fit an int index, or there are none to
+// write them to
+long long iteration_total(const int32_t* iterations, int levels, const double* records) {
+    long long total = 0;
+    for (int l = 0; l < levels; ++l) {
+        if (iterations[l] < 0) return -1;
+        total += iterations[l];
+    }
+    return total > 0x7fffffffll / kRecord || (total > 0 && !records) ? -1 : total;
+}
+
+struct Buffer {
+    const void* at;  // may be NULL: aliases nothing
+    size_t bytes;
+};
+
+// an output overlaps an input or another output
+bool aliased(std::initializer_list<Buffer> outs, std::initializer_list<Buffer> ins) {
+    auto overlaps = [](const Buffer& a, const Buffer& b) {
+        const uintptr_t x = (uintptr_t)a.at, y = (uintptr_t)b.at;
+        return a.at && b.at && x < y + b.bytes && y < x + a.bytes;
+    };
+    for (const Buffer* o = outs.begin(); o != outs.end(); ++o) {
+        for (const Buffer& in : ins)
+            if (overlaps(*o, in)) return true;
+        for (const Buffer* other = o + 1; other != outs.end(); ++other)
+            if (overlaps(*o, *other)) return true;
+    }
+    return false;
+}
+
+template <typename Q>
+Run run_of(const Q* q, double ratio, const void* live, const float* live_normals, const float* pred_depth,
+           const float* pred_normals, double* twist,
+           double* records, void* scratch, float* residuals, long long total, void* stream) {
+    Run r = {live, live_normals, pred_depth, pred_normals, twist, records, reinterpret_cast<double*>(scratch),
+             residuals, {}, (int)total,
+             as_stream(stream)};
+    r.p.fx = q->fx; r.p.fy = q->fy; r.p.cx = q->cx; r.p.cy = q->cy;
+    r.p.ratio = ratio;
+    r.p.max_distance = q->max_distance;
+    for (int i = 0; i < 6; ++i) r.p.twist_p[i] = q->twist_p[i];
+    r.p.height = q->height;
+    r.p.width = q->width;
+    return r;
 }
 
 }  // namespace
@@ -338,103 +419,32 @@ extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, cons
     (void)hipGetLastError();
     if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params) return LSF_ERR_BAD_ARGUMENT;
     const lsf_icp_params* q = params;
-    if (q->height < 1 || q->width < 1 || (long long)q->height * q->width > 0x7fffffffll) return LSF_ERR_BAD_ARGUMENT;
-    const double all[] = {q->fx, q->fy, q->cx, q->cy, q->depth_unit_ratio, q->twist_p[0], q->twist_p[1],
-                          q->twist_p[2], q->twist_p[3], q->twist_p[4], q->twist_p[5]};
-    for (double x : all)
-        if (!std::isfinite(x)) return LSF_ERR_BAD_ARGUMENT;
-    if (q->fx == 0.0 || q->fy == 0.0 || !(q->max_distance > 0.0)) return LSF_ERR_BAD_ARGUMENT;
-    if (!depth_dtype_ok(q->depth_dtype)) return LSF_ERR_BAD_ARGUMENT;
+    if (!camera_ok(q) || !std::isfinite(q->depth_unit_ratio) || !depth_dtype_ok(q->depth_dtype))
+        return LSF_ERR_BAD_ARGUMENT;
     if (q->levels < 1 || q->levels > LSF_ICP_MAX_LEVELS) return LSF_ERR_BAD_ARGUMENT;
-    long long total = 0;
-    for (int l = 0; l < q->levels; ++l) {
-        if (q->strides[l] < 1 || q->iterations[l] < 0) return LSF_ERR_BAD_ARGUMENT;
-        total += q->iterations[l];
-    }
-    if (total > 0x7fffffffll / kRecord || (total > 0 && !records)) return LSF_ERR_BAD_ARGUMENT;
-    // no output may alias an input or another output
+    for (int l = 0; l < q->levels; ++l)
+        if (q->strides[l] < 1) return LSF_ERR_BAD_ARGUMENT;
+    const long long total = iteration_total(q->iterations, q->levels, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
     static const size_t kDepthBytes[3] = {2, 4, 8};
     const size_t pixels = (size_t)q->height * q->width;
-    const void* outs[4] = {twist_inout, records, scratch, residuals_out};
-    const size_t out_bytes[4] = {6 * 8, (size_t)total * kRecord * 8, LSF_ICP_SCRATCH_BYTES, pixels * 4};
-    const void* ins[3] = {live_depth, pred_depth, pred_normals};
-    const size_t in_bytes[3] = {pixels * kDepthBytes[q->depth_dtype], pixels * 4, pixels * 12};
-    for (int i = 0; i < 4; ++i) {
-        for (int j = 0; j < 3; ++j)
-            if (overlaps(outs[i], out_bytes[i], ins[j], in_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-        for (int j = i + 1; j < 4; ++j)
-            if (overlaps(outs[i], out_bytes[i], outs[j], out_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-    }
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_ICP_SCRATCH_BYTES},
+                 {residuals_out, pixels * 4}},
+                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {pred_depth, pixels * 4},
+                 {pred_normals, pixels * 12}}))
+        return LSF_ERR_BAD_ARGUMENT;
     if (total == 0) return 0;
-    IcpDev p;
-    p.fx = q->fx; p.fy = q->fy; p.cx = q->cx; p.cy = q->cy;
-    p.ratio = q->depth_unit_ratio;
-    p.max_distance = q->max_distance;
-    for (int i = 0; i < 6; ++i) p.twist_p[i] = q->twist_p[i];
-    p.height = q->height;
-    p.width = q->width;
-    double* sc = reinterpret_cast<double*>(scratch);
-    hipStream_t s = as_stream(stream);
+    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
+                         scratch, residuals_out, total, stream);
     return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        return launch_run<decltype(dt)>(q, p, live_depth, pred_depth, pred_normals, twist_inout, records, sc,
-                                        residuals_out, (int)total, s);
+        using DT = decltype(dt);
+        return launch_run(r, q->levels, q->iterations, [&](int l) {
+            const int stride = q->strides[l];
+            return StridedSource<DT>{grid_of((q->width + stride - 1) / stride, (q->height + stride - 1) / stride),
+                                     stride};
+        });
     });
 }
-
-namespace {
-
-PyrLevel pyr_level_of(const lsf_icp_pyramid_params* q, int level) {
-    PyrLevel lv;
-    lv.fx = q->fx; lv.fy = q->fy; lv.cx = q->cx; lv.cy = q->cy;
-    lv.offset = 0;
-    for (int l = 0; l < level; ++l) {  // lsf_depth_pyramid's level intrinsics and layout
-        lv.offset += (long long)(q->height >> l) * (q->width >> l);
-        lv.fx = lv.fx / 2.0;
-        lv.fy = lv.fy / 2.0;
-        lv.cx = (lv.cx - 0.5) / 2.0;
-        lv.cy = (lv.cy - 0.5) / 2.0;
-    }
-    lv.ni = q->width >> level;
-    lv.nj = q->height >> level;
-    lv.tiles_x = (lv.ni + kTile - 1) / kTile;
-    lv.tiles = lv.tiles_x * ((lv.nj + kTile - 1) / kTile);
-    return lv;
-}
-
-template <int MODE, bool GATE>
-int launch_pyramid(unsigned blocks, const float* live, const float* live_normals, const float* pred_depth,
-                   const float* pred_normals, double* twist, double* records, double* scratch, float* residuals,
-                   const IcpDev& p, const PyrLevel& lv, double cos_max, int k, int prev_blocks, int prev_level,
-                   hipStream_t s) {
-    hipLaunchKernelGGL((icp_pyramid_kernel<MODE, GATE>), dim3(blocks), dim3(kBlock), 0, s, live, live_normals,
-                       pred_depth, pred_normals, twist, records, scratch, residuals, p, lv, cos_max, k, prev_blocks,
-                       prev_level);
-    return launch_status();
-}
-
-template <bool GATE>
-int launch_run_pyramid(const lsf_icp_pyramid_params* q, const IcpDev& p, const float* live, const float* live_normals,
-                       const float* pred_depth, const float* pred_normals, double* twist, double* records,
-                       double* scratch, float* residuals, int total, hipStream_t s) {
-    int k = 0, prev_blocks = 0, prev_level = 0;
-    PyrLevel lv = pyr_level_of(q, 0);
-    for (int l = 0; l < q->levels; ++l) {
-        lv = pyr_level_of(q, q->levels - 1 - l);
-        const int blocks = lv.tiles < kMaxBlocks ? lv.tiles : kMaxBlocks;
-        for (int it = 0; it < q->iterations[l]; ++it, ++k) {
-            if (int e = launch_pyramid<ITERATE, GATE>(blocks, live, live_normals, pred_depth, pred_normals, twist,
-                                                      records, scratch, k == total - 1 ? residuals : nullptr, p, lv,
-                                                      q->cos_max_angle, k, prev_blocks, prev_level, s))
-                return e;
-            prev_blocks = blocks;
-            prev_level = l;
-        }
-    }
-    return launch_pyramid<FINISH, GATE>(1, live, live_normals, pred_depth, pred_normals, twist, records, scratch,
-                                        nullptr, p, lv, q->cos_max_angle, total, prev_blocks, prev_level, s);
-}
-
-}  // namespace
 
 extern "C" int lsf_icp_run_pyramid(const float* live_depth, const float* live_normals, const float* pred_depth,
                                    const float* pred_normals, double* twist_inout, double* records, void* scratch,
@@ -443,53 +453,45 @@ extern "C" int lsf_icp_run_pyramid(const float* live_depth, const float* live_no
     if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params)
         return LSF_ERR_BAD_ARGUMENT;
     const lsf_icp_pyramid_params* q = params;
-    if (q->height < 1 || q->width < 1 || (long long)q->height * q->width > 0x7fffffffll) return LSF_ERR_BAD_ARGUMENT;
-    const double all[] = {q->fx, q->fy, q->cx, q->cy, q->twist_p[0], q->twist_p[1], q->twist_p[2], q->twist_p[3],
-                          q->twist_p[4], q->twist_p[5]};
-    for (double x : all)
-        if (!std::isfinite(x)) return LSF_ERR_BAD_ARGUMENT;
-    if (q->fx == 0.0 || q->fy == 0.0 || !(q->max_distance > 0.0)) return LSF_ERR_BAD_ARGUMENT;
-    if (!(q->cos_max_angle >= -1.0 && q->cos_max_angle <= 1.0)) return LSF_ERR_BAD_ARGUMENT;
+    if (!camera_ok(q) || !(q->cos_max_angle >= -1.0 && q->cos_max_angle <= 1.0)) return LSF_ERR_BAD_ARGUMENT;
     if (q->pyramid_levels < 1 || q->pyramid_levels > LSF_ICP_MAX_LEVELS || q->levels < 1 ||
         q->levels > q->pyramid_levels || (q->height >> (q->pyramid_levels - 1)) < 1 ||
         (q->width >> (q->pyramid_levels - 1)) < 1)
         return LSF_ERR_BAD_ARGUMENT;
-    long long total = 0;
+    const long long total = iteration_total(q->iterations, q->levels, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
     int last = 0;  // the pyramid level of the last iteration
-    for (int l = 0; l < q->levels; ++l) {
-        if (q->iterations[l] < 0) return LSF_ERR_BAD_ARGUMENT;
-        total += q->iterations[l];
+    for (int l = 0; l < q->levels; ++l)
         if (q->iterations[l] > 0) last = q->levels - 1 - l;
-    }
-    if (total > 0x7fffffffll / kRecord || (total > 0 && !records)) return LSF_ERR_BAD_ARGUMENT;
-    // no output may alias an input or another output
     size_t pyramid_pixels = 0;
     for (int l = 0; l < q->pyramid_levels; ++l) pyramid_pixels += (size_t)(q->height >> l) * (q->width >> l);
     const size_t pixels = (size_t)q->height * q->width;
-    const void* outs[4] = {twist_inout, records, scratch, residuals_out};
-    const size_t out_bytes[4] = {6 * 8, (size_t)total * kRecord * 8, LSF_ICP_PYRAMID_SCRATCH_BYTES,
-                                 (size_t)(q->height >> last) * (q->width >> last) * 4};
-    const void* ins[4] = {live_depth, live_normals, pred_depth, pred_normals};
-    const size_t in_bytes[4] = {pyramid_pixels * 4, pyramid_pixels * 12, pixels * 4, pixels * 12};
-    for (int i = 0; i < 4; ++i) {
-        for (int j = 0; j < 4; ++j)
-            if (overlaps(outs[i], out_bytes[i], ins[j], in_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-        for (int j = i + 1; j < 4; ++j)
-            if (overlaps(outs[i], out_bytes[i], outs[j], out_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-    }
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
+                 {scratch, LSF_ICP_PYRAMID_SCRATCH_BYTES},
+                 {residuals_out, (size_t)(q->height >> last) * (q->width >> last) * 4}},
+                {{live_depth, pyramid_pixels * 4}, {live_normals, pyramid_pixels * 12}, {pred_depth, pixels * 4},
+                 {pred_normals, pixels * 12}}))
+        return LSF_ERR_BAD_ARGUMENT;
     if (total == 0) return 0;
-    IcpDev p;
-    p.fx = q->fx; p.fy = q->fy; p.cx = q->cx; p.cy = q->cy;
-    p.ratio = 1.0;
-    p.max_distance = q->max_distance;
-    for (int i = 0; i < 6; ++i) p.twist_p[i] = q->twist_p[i];
-    p.height = q->height;
-    p.width = q->width;
-    double* sc = reinterpret_cast<double*>(scratch);
-    hipStream_t s = as_stream(stream);
-    return q->angle_gate
-               ? launch_run_pyramid<true>(q, p, live_depth, live_normals, pred_depth, pred_normals, twist_inout,
-                                          records, sc, residuals_out, (int)total, s)
-               : launch_run_pyramid<false>(q, p, live_depth, live_normals, pred_depth, pred_normals, twist_inout,
-                                           records, sc, residuals_out, (int)total, s);
+    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
+                         residuals_out, total, stream);
+    auto run = [&](auto gate) {
+        return launch_run(r, q->levels, q->iterations, [&](int l) {
+            // lsf_depth_pyramid's layout and level intrinsics
+            PyramidSource<decltype(gate)::value> src = {q->fx, q->fy, q->cx, q->cy,
+                                                        q->cos_max_angle, 0, {}};
+            const int level = q->levels - 1 - l;
+            for (int c = 0; c < level; ++c) {
+                const long long n = (long long)(q->height >> c) * (q->width >> c);
+                src.offset += n;
+                src.fx = src.fx / 2.0;
+                src.fy = src.fy / 2.0;
+                src.cx = (src.cx - 0.5) / 2.0;
+                src.cy = (src.cy - 0.5) / 2.0;
+            }
+            src.grid = grid_of(q->width >> level, q->height >> level);
+            return src;
+        });
+    };
+    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
 }

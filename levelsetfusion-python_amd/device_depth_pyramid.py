@@ -5,13 +5,12 @@ rigid_opt.DepthPyramid; device_icp.icp_run_pyramid tracks against its output."""
 import ctypes
 import math
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import DepthPyramidParams, check, lib
 from .device_core import require_gpu, stream_ptr
-from .device_raycast import image_extents
+from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
 
 LEVELS, RADIUS, SIGMA_SPACE, SIGMA_RANGE, DEPTH_GATE = 3, 3, 3.0, 0.03, 0.03
 
@@ -41,10 +40,7 @@ def level_shapes(image_shape, levels):
 
 def level_intrinsics(camera, levels):
     """(fx, fy, cx, cy) of every level, float64: fx / 2, fy / 2, (cx - 0.5) / 2, (cy - 0.5) / 2 per level"""
-    P = np.asarray(camera.intrinsics.intrinsic_matrix)
-    fx, fy, cx, cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
-    if not (np.all(np.isfinite([fx, fy, cx, cy])) and fx != 0 and fy != 0):
-        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    fx, fy, cx, cy = checked_intrinsics(camera)
     out = [(fx, fy, cx, cy)]
     for _ in range(1, levels):
         fx, fy, cx, cy = fx / 2.0, fy / 2.0, (cx - 0.5) / 2.0, (cy - 0.5) / 2.0
@@ -59,9 +55,7 @@ def params(camera, image_shape, depth_code, levels=LEVELS, radius=RADIUS, sigma_
                                                                     depth_gate)
     p = DepthPyramidParams()
     p.fx, p.fy, p.cx, p.cy = level_intrinsics(camera, 1)[0]
-    p.depth_unit_ratio = float(camera.depth_unit_ratio)
-    if not math.isfinite(p.depth_unit_ratio):
-        raise ValueError("the camera's depth_unit_ratio must be finite")
+    p.depth_unit_ratio = checked_depth_unit_ratio(camera)
     p.sigma_space, p.sigma_range, p.depth_gate = sigma_space, sigma_range, depth_gate
     p.height, p.width = image_extents(image_shape)
     level_shapes((p.height, p.width), levels)

@@ -3,17 +3,16 @@ the host before the launches; a call enqueues sum(iterations) + 1 launches with 
 the records back once.  The public interfaces are rigid_opt.ProjectiveIcp3d and
 fusion.SequenceFusion3d(tracking_reference="icp").  icp_run_pyramid (lsf_icp_run_pyramid) is the same schedule over a
 live depth pyramid (device_depth_pyramid), with an optional normal-angle gate."""
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, IcpPyramidParams, check, lib
-from .device_core import require_gpu, stream_ptr
-from .device_raycast import image_extents
-from .device_rigid import twist6
+from ._lib import IcpParams, IcpPyramidParams, lib
+from .device_core import require_gpu
+from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
+from .device_rigid import enqueue_run, twist6
 
 RECORD = _lib.ICP_RECORD_DOUBLES
 ITERATIONS, STRIDES, MAX_DISTANCE = (4, 4, 6), (4, 2, 1), 0.02
@@ -32,17 +31,9 @@ def levels(iterations, strides):
     return it, st
 
 
-def params(camera, image_shape, twist_p, depth_code, iterations=ITERATIONS, strides=STRIDES,
-           max_distance=MAX_DISTANCE):
-    """the lsf_icp_params of a call, after the host checks"""
-    P = np.asarray(camera.intrinsics.intrinsic_matrix)
-    p = IcpParams()
-    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
-    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
-        raise ValueError("the intrinsics must be finite with fx, fy != 0")
-    p.depth_unit_ratio = float(camera.depth_unit_ratio)
-    if not np.isfinite(p.depth_unit_ratio):
-        raise ValueError("the camera's depth_unit_ratio must be finite")
+def _common(p, camera, image_shape, twist_p, max_distance, iterations):
+    """the fields lsf_icp_params and lsf_icp_pyramid_params share, checked, into p"""
+    p.fx, p.fy, p.cx, p.cy = checked_intrinsics(camera)
     p.max_distance = float(max_distance)
     if not p.max_distance > 0:
         raise ValueError("max_distance must be positive")
@@ -51,10 +42,18 @@ def params(camera, image_shape, twist_p, depth_code, iterations=ITERATIONS, stri
         raise ValueError("twist_p must be finite")
     p.twist_p[:] = list(tp)
     p.height, p.width = image_extents(image_shape)
-    p.depth_dtype = int(depth_code)
+    p.levels = len(iterations)
+    p.iterations[:len(iterations)] = list(iterations)
+    return p
+
+
+def params(camera, image_shape, twist_p, depth_code, iterations=ITERATIONS, strides=STRIDES,
+           max_distance=MAX_DISTANCE):
+    """the lsf_icp_params of a call, after the host checks"""
     it, st = levels(iterations, strides)
-    p.levels = len(it)
-    p.iterations[:len(it)] = list(it)
+    p = _common(IcpParams(), camera, image_shape, twist_p, max_distance, it)
+    p.depth_unit_ratio = checked_depth_unit_ratio(camera)
+    p.depth_dtype = int(depth_code)
     p.strides[:len(st)] = list(st)
     return p
 
@@ -65,6 +64,18 @@ def _prediction(x, name, shape):
     if tuple(x.shape) != shape:
         raise ValueError("%s has shape %s, expected %s" % (name, tuple(x.shape), shape))
     return x
+
+
+def _run(entry, name, live, pred_depth, pred_normals, p, twist, scratch_bytes, residual_shape):
+    """the run of p enqueued (device_rigid.enqueue_run) after the checks of the prediction: icp_run's triple"""
+    h, w = p.height, p.width
+    inputs = live + (_prediction(pred_depth, "pred_depth", (h, w)), _prediction(pred_normals, "pred_normals", (h, w, 3)))
+    res = None
+    if residual_shape is not None:
+        res = torch.empty(residual_shape, dtype=torch.float32, device=pred_depth.device)
+    out, records = enqueue_run(entry, name, inputs, p, twist, 6, 8, RECORD, scratch_bytes,
+                               sum(p.iterations[:p.levels]), (res,))
+    return out, records, res
 
 
 def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, twist=None, iterations=ITERATIONS,
@@ -79,22 +90,8 @@ def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, t
         raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
     h, w = (int(v) for v in live_depth.shape)
     p = params(camera, (h, w), twist_p, depth_code, iterations, strides, max_distance)
-    _prediction(pred_depth, "pred_depth", (h, w))
-    _prediction(pred_normals, "pred_normals", (h, w, 3))
-    total = sum(p.iterations[:p.levels])
-    head = 8
-    out = torch.zeros(head + total * RECORD, dtype=torch.float64, device=live_depth.device)
-    out[:6] = torch.from_numpy(twist6(twist_p if twist is None else twist).copy())
-    scratch = torch.empty(_lib.ICP_SCRATCH_BYTES // 8, dtype=torch.float64, device=live_depth.device)
-    res = torch.empty((h, w), dtype=torch.float32, device=live_depth.device) if residuals else None
-    base = out.data_ptr()
-    check(lib.lsf_icp_run(ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(pred_depth.data_ptr()),
-                          ctypes.c_void_p(pred_normals.data_ptr()), ctypes.c_void_p(base),
-                          ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr()),
-                          None if res is None else ctypes.c_void_p(res.data_ptr()), ctypes.byref(p), stream_ptr()),
-          "lsf_icp_run")
-    host = out.cpu().numpy()
-    return host[:6].copy(), host[head:].reshape(total, RECORD).copy(), res
+    return _run(lib.lsf_icp_run, "lsf_icp_run", (live_depth,), pred_depth, pred_normals, p,
+                twist_p if twist is None else twist, _lib.ICP_SCRATCH_BYTES, (h, w) if residuals else None)
 
 
 def pyramid_iterations(iterations, pyramid_levels):
@@ -118,28 +115,15 @@ def cos_max_angle(max_normal_angle):
 def pyramid_params(camera, image_shape, pyramid_levels, twist_p, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
                    max_normal_angle=None):
     """the lsf_icp_pyramid_params of a call, after the host checks; max_normal_angle None: no gate"""
-    P = np.asarray(camera.intrinsics.intrinsic_matrix)
     p = IcpPyramidParams()
-    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
-    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
-        raise ValueError("the intrinsics must be finite with fx, fy != 0")
-    p.max_distance = float(max_distance)
-    if not p.max_distance > 0:
-        raise ValueError("max_distance must be positive")
-    p.angle_gate = 0 if max_normal_angle is None else 1
-    p.cos_max_angle = -1.0 if max_normal_angle is None else cos_max_angle(max_normal_angle)
-    tp = twist6(twist_p)
-    if not np.all(np.isfinite(tp)):
-        raise ValueError("twist_p must be finite")
-    p.twist_p[:] = list(tp)
     p.height, p.width = image_extents(image_shape)
     p.pyramid_levels = int(pyramid_levels)
     if not 1 <= p.pyramid_levels <= _lib.ICP_MAX_LEVELS or (p.height >> (p.pyramid_levels - 1)) < 1 or \
             (p.width >> (p.pyramid_levels - 1)) < 1:
         raise ValueError("a %d x %d image has no %d-level pyramid" % (p.height, p.width, p.pyramid_levels))
-    it = pyramid_iterations(iterations, p.pyramid_levels)
-    p.levels = len(it)
-    p.iterations[:len(it)] = list(it)
+    _common(p, camera, image_shape, twist_p, max_distance, pyramid_iterations(iterations, p.pyramid_levels))
+    p.angle_gate = 0 if max_normal_angle is None else 1
+    p.cos_max_angle = -1.0 if max_normal_angle is None else cos_max_angle(max_normal_angle)
     return p
 
 
@@ -162,29 +146,13 @@ def icp_run_pyramid(pyramid_depth, pyramid_normals, pyramid_levels, pred_depth, 
         raise ValueError("pred_depth must be an (H, W) device tensor (device_raycast.raycast)")
     h, w = (int(v) for v in pred_depth.shape)
     p = pyramid_params(camera, (h, w), pyramid_levels, twist_p, iterations, max_distance, max_normal_angle)
-    _prediction(pred_depth, "pred_depth", (h, w))
-    _prediction(pred_normals, "pred_normals", (h, w, 3))
     pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
-    _prediction(pyramid_depth, "pyramid_depth", (pixels,))
-    _prediction(pyramid_normals, "pyramid_normals", (pixels, 3))
-    it = tuple(p.iterations[:p.levels])
-    total = sum(it)
-    head = 8
-    out = torch.zeros(head + total * RECORD, dtype=torch.float64, device=pred_depth.device)
-    out[:6] = torch.from_numpy(twist6(twist_p if twist is None else twist).copy())
-    scratch = torch.empty(_lib.ICP_PYRAMID_SCRATCH_BYTES // 8, dtype=torch.float64, device=pred_depth.device)
-    last = last_level(it)
-    res = torch.empty((h >> last, w >> last), dtype=torch.float32, device=pred_depth.device) if residuals else None
-    base = out.data_ptr()
-    check(lib.lsf_icp_run_pyramid(ctypes.c_void_p(pyramid_depth.data_ptr()), ctypes.c_void_p(pyramid_normals.data_ptr()),
-                                  ctypes.c_void_p(pred_depth.data_ptr()), ctypes.c_void_p(pred_normals.data_ptr()),
-                                  ctypes.c_void_p(base), ctypes.c_void_p(base + head * 8),
-                                  ctypes.c_void_p(scratch.data_ptr()),
-                                  None if res is None else ctypes.c_void_p(res.data_ptr()), ctypes.byref(p),
-                                  stream_ptr()),
-          "lsf_icp_run_pyramid")
-    host = out.cpu().numpy()
-    return host[:6].copy(), host[head:].reshape(total, RECORD).copy(), res
+    live = (_prediction(pyramid_depth, "pyramid_depth", (pixels,)),
+            _prediction(pyramid_normals, "pyramid_normals", (pixels, 3)))
+    last = last_level(p.iterations[:p.levels])
+    return _run(lib.lsf_icp_run_pyramid, "lsf_icp_run_pyramid", live, pred_depth, pred_normals, p,
+                twist_p if twist is None else twist, _lib.ICP_PYRAMID_SCRATCH_BYTES,
+                (h >> last, w >> last) if residuals else None)
 
 
 def unpack_record(r):

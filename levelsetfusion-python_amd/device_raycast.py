@@ -20,15 +20,29 @@ def image_extents(image_shape):
     return s
 
 
+def checked_intrinsics(camera):
+    """(fx, fy, cx, cy) of the camera's intrinsic matrix as floats: finite, fx and fy non-zero"""
+    P = np.asarray(camera.intrinsics.intrinsic_matrix)
+    k = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
+    if not (np.all(np.isfinite(k)) and k[0] != 0 and k[1] != 0):
+        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    return k
+
+
+def checked_depth_unit_ratio(camera):
+    """the camera's depth_unit_ratio as a float: finite"""
+    ratio = float(camera.depth_unit_ratio)
+    if not np.isfinite(ratio):
+        raise ValueError("the camera's depth_unit_ratio must be finite")
+    return ratio
+
+
 def params(shape, camera, twist, array_offset, voxel_size, image_shape, fallback_code=None):
     """the lsf_raycast_params of a call, after the host checks"""
     if len(shape) != 3 or min(shape) < 2:
         raise ValueError("ray-casting needs a 3-D (Z, Y, X) volume of extents >= 2, got shape %s" % (tuple(shape),))
-    P = np.asarray(camera.intrinsics.intrinsic_matrix)
     p = RaycastParams()
-    p.fx, p.fy, p.cx, p.cy = float(P[0, 0]), float(P[1, 1]), float(P[0, 2]), float(P[1, 2])
-    if not (np.all(np.isfinite([p.fx, p.fy, p.cx, p.cy])) and p.fx != 0 and p.fy != 0):
-        raise ValueError("the intrinsics must be finite with fx, fy != 0")
+    p.fx, p.fy, p.cx, p.cy = checked_intrinsics(camera)
     p.depth_unit_ratio = float(camera.depth_unit_ratio)
     p.voxel_size = float(voxel_size)
     if not (np.isfinite(p.voxel_size) and p.voxel_size > 0):
@@ -40,8 +54,7 @@ def params(shape, camera, twist, array_offset, voxel_size, image_shape, fallback
     p.depth, p.height, p.width = (int(v) for v in shape)
     p.image_height, p.image_width = image_extents(image_shape)
     if fallback_code is not None:
-        if not np.isfinite(p.depth_unit_ratio):
-            raise ValueError("the camera's depth_unit_ratio must be finite")
+        checked_depth_unit_ratio(camera)
         p.fallback_dtype = int(fallback_code)
     return p
 

@@ -48,19 +48,21 @@ def twist6(twist):
     return twist_n(twist, 6)
 
 
-def _enqueue_run(entry, name, canonical, live_depth, p, twist, n, head, record, scratch_bytes):
-    """the whole optimize() enqueued by `entry` (lsf_rigid_run / lsf_rigid3d_run): p.iterations + 1 launches into one
-    buffer [twist (n)][pad to head][records (iterations x record)], and one copy back.  Returns (final twist float64
-    (n,), records float64 (iterations, record))."""
-    iterations = p.iterations
-    out = torch.zeros(head + iterations * record, dtype=torch.float64, device="cuda")
+def enqueue_run(entry, name, inputs, p, twist, n, head, record, scratch_bytes, iterations, outputs=()):
+    """a whole tracker run enqueued by `entry` (lsf_rigid_run / lsf_rigid3d_run / lsf_icp_run / lsf_icp_run_pyramid):
+    iterations + 1 launches into one buffer [twist (n)][pad to head][records (iterations x record)], and one copy back.
+    inputs: the device tensors the entry point reads, in its order; outputs: what it takes after the scratch buffer
+    (device tensors, or None for a NULL).  Returns (final twist float64 (n,), records float64 (iterations, record))."""
+    device = inputs[0].device
+    out = torch.zeros(head + iterations * record, dtype=torch.float64, device=device)
     if twist is not None:
-        out[:n] = torch.from_numpy(twist_n(twist, n))
-    scratch = torch.empty(scratch_bytes // 8, dtype=torch.float64, device="cuda")
+        out[:n] = torch.from_numpy(twist_n(twist, n).copy())
+    scratch = torch.empty(scratch_bytes // 8, dtype=torch.float64, device=device)
     base = out.data_ptr()
-    check(entry(ctypes.c_void_p(canonical.data_ptr()), ctypes.c_void_p(live_depth.data_ptr()), ctypes.c_void_p(base),
-                ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()),
-          name)
+    ptr = [ctypes.c_void_p(t.data_ptr()) for t in inputs]
+    ptr += [ctypes.c_void_p(base), ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr())]
+    ptr += [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in outputs]
+    check(entry(*ptr, ctypes.byref(p), stream_ptr()), name)
     host = out.cpu().numpy()
     return host[:n].copy(), host[head:].reshape(iterations, record).copy()
 
@@ -103,8 +105,8 @@ def rigid_run(canonical, live_depth, depth_code, camera, image_y_coordinate, arr
     p.depth_dtype = int(depth_code)
     p.height, p.width = int(canonical.shape[0]), int(canonical.shape[1])
     p.iterations = iterations
-    return _enqueue_run(lib.lsf_rigid_run, "lsf_rigid_run", canonical, live_depth, p, twist, 3, 3, RECORD,
-                        _lib.RIGID_SCRATCH_BYTES)
+    return enqueue_run(lib.lsf_rigid_run, "lsf_rigid_run", (canonical, live_depth), p, twist, 3, 3, RECORD,
+                       _lib.RIGID_SCRATCH_BYTES, iterations)
 
 
 # ---- the 6-DoF 3-D tracker (lsf_rigid3d_gradient, lsf_rigid3d_run) ----------------------------------------------------
@@ -194,5 +196,5 @@ def rigid_run_3d(canonical, live_depth, depth_code, camera, array_offset, iterat
     p.eta = float(np.float32(eta))
     p.depth_dtype = int(depth_code)
     p.iterations = iterations
-    return _enqueue_run(lib.lsf_rigid3d_run, "lsf_rigid3d_run", canonical, live_depth, p, twist, 6, 8, RECORD3D,
-                        _lib.RIGID3D_SCRATCH_BYTES)
+    return enqueue_run(lib.lsf_rigid3d_run, "lsf_rigid3d_run", (canonical, live_depth), p, twist, 6, 8, RECORD3D,
+                       _lib.RIGID3D_SCRATCH_BYTES, iterations)

@@ -56,7 +56,7 @@ import torch
 from .. import device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
 from ..device_fusion import RECORD_FIELDS, unpack_record
-from ..rigid_opt.projective_icp3d import checked_pyramid
+from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
@@ -171,15 +171,11 @@ class SequenceFusion3d:
             raise ValueError("rigid_iterations must be >= 0")
         if tracking_reference not in TRACKING_MODES:
             raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_MODES, tracking_reference))
-        self.icp_pyramid, self.icp_max_normal_angle = checked_pyramid(icp_pyramid, icp_max_normal_angle)
-        if icp_pyramid is None:
-            self.icp_iterations, self.icp_strides = device_icp.levels(icp_iterations, icp_strides)
-        else:
-            self.icp_iterations, self.icp_strides = device_icp.pyramid_iterations(icp_iterations,
-                                                                                  icp_pyramid.levels), None
-        if not float(icp_max_distance) > 0:
-            raise ValueError("icp_max_distance must be positive")
-        self.icp_max_distance = float(icp_max_distance)
+        # the "icp" tracker; its arguments are checked in every mode
+        t = self.icp = ProjectiveIcp3d(camera, icp_iterations, icp_strides, icp_max_distance, icp_pyramid,
+                                       icp_max_normal_angle)
+        self.icp_iterations, self.icp_strides, self.icp_max_distance = t.iterations, t.strides, t.max_distance
+        self.icp_pyramid, self.icp_max_normal_angle = t.pyramid, t.max_normal_angle
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -216,15 +212,8 @@ class SequenceFusion3d:
         self.prediction, normals, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
                                                                 self.array_offset, self.voxel_size, tuple(depth.shape),
                                                                 normals=True)
-        if self.icp_pyramid is None:
-            twist, records, _ = device_icp.icp_run(depth, code, self.prediction, normals, self.camera, twist, twist,
-                                                   self.icp_iterations, self.icp_strides, self.icp_max_distance)
-        else:
-            pyramid = self.icp_pyramid.build(depth, self.camera)
-            twist, records, _ = device_icp.icp_run_pyramid(*pyramid.buffers, self.icp_pyramid.levels, self.prediction,
-                                                           normals, self.camera, twist, twist, self.icp_iterations,
-                                                           self.icp_max_distance, self.icp_max_normal_angle)
-        return twist, [device_icp.unpack_record(r) for r in records], hits
+        twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist)
+        return twist, records, hits
 
     def integrate(self, depth_image):
         """track and fuse one frame; returns its record (also appended to frame_records)"""

@@ -34,7 +34,10 @@ class DepthPyramid:
         """the pyramid of a depth image (uint16 / float32 / float64, numpy or device, scaled by the camera's
         depth_unit_ratio), enqueued without waiting: a PyramidLevels"""
         require_gpu()
-        depth, code = device_depth(live_depth)
+        return self.build_device(*device_depth(live_depth), camera)
+
+    def build_device(self, depth, code, camera):
+        """build() of a device depth image and its LSF_DEPTH_* code (tsdf.generation.device_depth)"""
         d, n = P.depth_pyramid(depth, code, camera, **self.settings())
         shapes = P.level_shapes(tuple(depth.shape), self.levels)
         return PyramidLevels(P.split_levels(d, shapes), P.split_levels(n, shapes),

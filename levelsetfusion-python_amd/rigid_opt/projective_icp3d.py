@@ -40,7 +40,14 @@ class ProjectiveIcp3d:
         """pyramid: None (the strided live image) or a DepthPyramid, with which strides is not used and iterations has
         one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only)"""
         self.camera = camera
-        self.pyramid, self.max_normal_angle = checked_pyramid(pyramid, max_normal_angle)
+        if pyramid is not None and not isinstance(pyramid, DepthPyramid):
+            raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
+        self.pyramid, self.max_normal_angle = pyramid, None
+        if max_normal_angle is not None:
+            if pyramid is None:
+                raise ValueError("max_normal_angle needs a pyramid: the strided path has no live normals")
+            device_icp.cos_max_angle(max_normal_angle)
+            self.max_normal_angle = float(max_normal_angle)
         if pyramid is None:
             self.iterations, self.strides = device_icp.levels(iterations, strides)
         else:
@@ -53,6 +60,20 @@ class ProjectiveIcp3d:
         self.last_residuals = None
         self.last_pyramid = None
 
+    def track(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals=False):
+        """optimize() on device inputs (tsdf.generation.device_depth's depth and LSF_DEPTH_* code, the prediction's
+        float32 device depth and normals at twist_p): (final twist, the unpacked records, the residual image or None)"""
+        if self.pyramid is None:
+            out, records, res = device_icp.icp_run(depth, code, prediction_depth, prediction_normals, self.camera,
+                                                   twist_p, twist, self.iterations, self.strides, self.max_distance,
+                                                   residuals)
+        else:
+            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
+            out, records, res = device_icp.icp_run_pyramid(
+                *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
+                twist_p, twist, self.iterations, self.max_distance, self.max_normal_angle, residuals)
+        return out, [device_icp.unpack_record(r) for r in records], res
+
     def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
                  residuals=False):
         """the float64 (6,) twist of the live depth frame (uint16 / float32 / float64, scaled by the camera's
@@ -62,29 +83,7 @@ class ProjectiveIcp3d:
         require_gpu()
         depth, code = device_depth(live_depth)
         twist_p = twist6(prediction_twist)
-        start = twist_p if twist is None else twist
-        pd, pn = _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,))
-        if self.pyramid is None:
-            out, records, res = device_icp.icp_run(depth, code, pd, pn, self.camera, twist_p, start, self.iterations,
-                                                   self.strides, self.max_distance, residuals)
-        else:
-            self.last_pyramid = self.pyramid.build(depth, self.camera)
-            out, records, res = device_icp.icp_run_pyramid(
-                *self.last_pyramid.buffers, self.pyramid.levels, pd, pn, self.camera, twist_p, start, self.iterations,
-                self.max_distance, self.max_normal_angle, residuals)
-        self.last_records = [device_icp.unpack_record(r) for r in records]
-        self.last_residuals = res
+        out, self.last_records, self.last_residuals = self.track(
+            depth, code, _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,)), twist_p,
+            twist_p if twist is None else twist, residuals)
         return out
-
-
-def checked_pyramid(pyramid, max_normal_angle):
-    """(pyramid, max_normal_angle) after the host checks: a DepthPyramid or None; an angle in [0, pi] radians, only
-    with a pyramid"""
-    if pyramid is not None and not isinstance(pyramid, DepthPyramid):
-        raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
-    if max_normal_angle is None:
-        return pyramid, None
-    if pyramid is None:
-        raise ValueError("max_normal_angle needs a pyramid: the strided path has no live normals")
-    device_icp.cos_max_angle(max_normal_angle)
-    return pyramid, float(max_normal_angle)

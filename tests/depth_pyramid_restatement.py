@@ -11,7 +11,6 @@ import numpy as np
 import fusion_restatement as F
 import icp_restatement as I
 import raycast_restatement as RC
-from rigid_restatement import rodrigues
 
 __all__ = ["LEVELS", "RADIUS", "SIGMA_SPACE", "SIGMA_RANGE", "DEPTH_GATE", "level_intrinsics", "bilateral",
            "downsample", "normals", "pyramid", "pyramid_from_level0", "iteration", "icp", "sequence"]
@@ -121,84 +120,13 @@ def pyramid(depth, ratio, K, levels=LEVELS, radius=RADIUS, sigma_space=SIGMA_SPA
     return pyramid_from_level0(bilateral(depth, ratio, radius, sigma_space, sigma_range), K, levels, depth_gate)
 
 
-def _associate(d, n_live, intr, pred_depth, pred_normals, K, twist, twist_p, max_distance, cos_max):
-    """icp_restatement.associate over every pixel of one pyramid level (vertices from the level's intrinsics), then the
-    gate (cos_max None: none): (valid, rejected, g, V_w, N_w)"""
-    K = np.asarray(K)
-    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
-    lfx, lfy, lcx, lcy = intr
-    dd = np.asarray(d, np.float32).astype(np.float64)
-    hl, wl = dd.shape
-    pd = np.asarray(pred_depth, np.float32)
-    pn = np.asarray(pred_normals, np.float32)
-    h, w = pd.shape
-    tw = np.asarray(twist, np.float64).reshape(6)
-    R, t = rodrigues(tw[3:]), tw[:3]
-    Ep = RC.extrinsic(twist_p)
-    Rp, tp = Ep[:, :3], Ep[:, 3]
-    v, u = np.meshgrid(np.arange(hl, dtype=np.float64), np.arange(wl, dtype=np.float64), indexing="ij")
-    live = dd > 0.0
-    vx = [dd * ((u - lcx) / lfx), dd * ((v - lcy) / lfy), dd * 1.0]
-    g = I._rt(R, vx, t)
-    q = [((Rp[i, 0] * g[0] + Rp[i, 1] * g[1]) + Rp[i, 2] * g[2]) + tp[i] for i in range(3)]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ph = np.rint((fx * q[0]) / q[2] + cx)
-        pv = np.rint((fy * q[1]) / q[2] + cy)
-        valid = live & (q[2] > 0.0) & (ph >= 0.0) & (ph <= float(w - 1)) & (pv >= 0.0) & (pv <= float(h - 1))
-    iu = np.where(valid, ph, 0.0).astype(np.int64)
-    iv = np.where(valid, pv, 0.0).astype(np.int64)
-    D = pd[iv, iu].astype(np.float64)
-    Nc = [pn[iv, iu, i].astype(np.float64) for i in range(3)]
-    valid &= (D > 0.0) & ((Nc[0] != 0.0) | (Nc[1] != 0.0) | (Nc[2] != 0.0))
-    V = [D * ((iu.astype(np.float64) - cx) / fx), D * ((iv.astype(np.float64) - cy) / fy), D * 1.0]
-    Vw = I._rt(Rp, V, tp)
-    Nw = I._rt(Rp, Nc)
-    diff = [g[i] - Vw[i] for i in range(3)]
-    with np.errstate(invalid="ignore"):
-        dist = np.sqrt((diff[0] * diff[0] + diff[1] * diff[1]) + diff[2] * diff[2])
-        valid &= dist <= float(max_distance)
-    rejected = np.zeros_like(valid)
-    if cos_max is not None:
-        ln = [np.asarray(n_live, np.float32)[..., i].astype(np.float64) for i in range(3)]
-        m = I._rt(R, ln)
-        with np.errstate(invalid="ignore"):
-            keep = ((ln[0] != 0.0) | (ln[1] != 0.0) | (ln[2] != 0.0)) & \
-                (((m[0] * Nw[0] + m[1] * Nw[1]) + m[2] * Nw[2]) >= cos_max)
-        rejected = valid & ~keep
-        valid &= keep
-    return valid, rejected, g, Vw, Nw
-
-
 def iteration(d, n_live, intr, pred_depth, pred_normals, K, twist, twist_p, max_distance=I.MAX_DISTANCE,
               cos_max=None):
-    """one iteration on one pyramid level at twist: (record dict with angle_rejected, residual image of the level's
-    extents (NaN without a correspondence), next twist)"""
-    valid, rejected, g, Vw, Nw = _associate(d, n_live, intr, pred_depth, pred_normals, K, twist, twist_p,
-                                            max_distance, cos_max)
-    diff = [g[i] - Vw[i] for i in range(3)]
-    with np.errstate(invalid="ignore"):
-        r = (Nw[0] * diff[0] + Nw[1] * diff[1]) + Nw[2] * diff[2]
-        J = [Nw[0], Nw[1], Nw[2], g[1] * Nw[2] - g[2] * Nw[1], g[2] * Nw[0] - g[0] * Nw[2],
-             g[0] * Nw[1] - g[1] * Nw[0]]
-    a, a_abs = np.zeros((6, 6)), np.zeros((6, 6))
-    b, b_abs = np.zeros(6), np.zeros(6)
-    for i in range(6):
-        for j in range(i, 6):
-            a[i, j] = a[j, i] = np.sum((J[i] * J[j])[valid])
-            a_abs[i, j] = a_abs[j, i] = np.sum(np.abs(J[i] * J[j])[valid])
-        b[i] = -np.sum((J[i] * r)[valid])
-        b_abs[i] = np.sum(np.abs(J[i] * r)[valid])
-    residuals = np.full(valid.shape, np.nan, np.float32)
-    residuals[valid] = r[valid].astype(np.float32)
-    twist = np.asarray(twist, np.float64).reshape(6)
-    skipped = 1 if not np.all(np.isfinite(a)) else I._singular(a)
-    delta = np.zeros(6)
-    if skipped == 0:
-        delta = np.dot(np.linalg.inv(a), b)
-        twist = I.compose(twist, delta)
-    rec = dict(A=a, b=b, energy=float(np.sum((r * r)[valid])), count=int(valid.sum()), delta=delta, twist=twist.copy(),
-               skipped=skipped, A_abs=a_abs, b_abs=b_abs, angle_rejected=int(rejected.sum()))
-    return rec, residuals, twist
+    """one iteration on one pyramid level at twist: icp_restatement.iteration over every pixel of the level (float32
+    metres), its vertices from the level's intrinsics, with the gate (cos_max None: none).  Returns (record dict with
+    angle_rejected, residual image of the level's extents (NaN without a correspondence), next twist)"""
+    return I.iteration(np.asarray(d, np.float32), pred_depth, pred_normals, K, 1.0, twist, twist_p, 1, max_distance,
+                       intr, n_live, cos_max)
 
 
 def icp(levels, pred_depth, pred_normals, K, twist_p, twist=None, iterations=I.ITERATIONS,

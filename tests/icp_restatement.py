@@ -67,32 +67,38 @@ def _rt(R, x, t=None):
     return [(R[0, j] * x[0] + R[1, j] * x[1]) + R[2, j] * x[2] for j in range(3)]
 
 
-def associate(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, stride=1, max_distance=MAX_DISTANCE):
-    """the correspondences of the live pixels (stride * i, stride * j) at twist: (rows, cols, valid, g, V_w, N_w) with
-    g, V_w, N_w lists of three float64 arrays over the strided pixels"""
+def associate(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, stride=1, max_distance=MAX_DISTANCE,
+              intrinsics=None, live_normals=None, cos_max=None):
+    """the correspondences of the live pixels (stride * i, stride * j) at twist: (rows, cols, valid, rejected, g, V_w,
+    N_w) with g, V_w, N_w lists of three float64 arrays over the strided pixels.  intrinsics: the (fx, fy, cx, cy) the
+    live vertices are made with, K's by default; another set makes live_depth one level of a pyramid, which need not
+    have the prediction's extents.  cos_max (None: no gate): a pair within max_distance whose live normal
+    (live_normals, (h, w, 3)) is zero or has (R^T n) . N_w < cos_max is `rejected`, not valid"""
     K = np.asarray(K)
     fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    lfx, lfy, lcx, lcy = (fx, fy, cx, cy) if intrinsics is None else intrinsics
     d = scaled_depth(live_depth, ratio)
-    h, w = d.shape
     pd = np.asarray(pred_depth, np.float32)
     pn = np.asarray(pred_normals, np.float32)
-    if pd.shape != (h, w) or pn.shape != (h, w, 3):
-        raise ValueError("the prediction must be (%d, %d) depth and (%d, %d, 3) normals" % (h, w, h, w))
+    h, w = pd.shape
+    if (intrinsics is None and d.shape != (h, w)) or pn.shape != (h, w, 3):
+        raise ValueError("the prediction must be depth of the live extents %s and normals (h, w, 3), got %s and %s"
+                         % (d.shape, pd.shape, pn.shape))
     tw = np.asarray(twist, np.float64).reshape(6)
     R, t = rodrigues(tw[3:]), tw[:3]
     Ep = RC.extrinsic(twist_p)
     Rp, tp = Ep[:, :3], Ep[:, 3]
-    rows, cols = np.meshgrid(np.arange(0, h, stride), np.arange(0, w, stride), indexing="ij")
+    rows, cols = np.meshgrid(np.arange(0, d.shape[0], stride), np.arange(0, d.shape[1], stride), indexing="ij")
     u, v = cols.astype(np.float64), rows.astype(np.float64)
     dd = d[rows, cols]
     live = dd > 0.0
-    vx = [dd * ((u - cx) / fx), dd * ((v - cy) / fy), dd * 1.0]
+    vx = [dd * ((u - lcx) / lfx), dd * ((v - lcy) / lfy), dd * 1.0]
     g = _rt(R, vx, t)
     q = [((Rp[i, 0] * g[0] + Rp[i, 1] * g[1]) + Rp[i, 2] * g[2]) + tp[i] for i in range(3)]
     with np.errstate(divide="ignore", invalid="ignore"):
         ph = np.rint((fx * q[0]) / q[2] + cx)
         pv = np.rint((fy * q[1]) / q[2] + cy)
-    valid = live & (q[2] > 0.0) & (ph >= 0.0) & (ph <= float(w - 1)) & (pv >= 0.0) & (pv <= float(h - 1))
+        valid = live & (q[2] > 0.0) & (ph >= 0.0) & (ph <= float(w - 1)) & (pv >= 0.0) & (pv <= float(h - 1))
     iu = np.where(valid, ph, 0.0).astype(np.int64)
     iv = np.where(valid, pv, 0.0).astype(np.int64)
     D = pd[iv, iu].astype(np.float64)
@@ -105,17 +111,29 @@ def associate(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, st
     with np.errstate(invalid="ignore"):
         dist = np.sqrt((diff[0] * diff[0] + diff[1] * diff[1]) + diff[2] * diff[2])
         valid &= dist <= float(max_distance)
-    return rows, cols, valid, g, Vw, Nw
+    rejected = np.zeros_like(valid)
+    if cos_max is not None:
+        ln = [np.asarray(live_normals, np.float32)[rows, cols, i].astype(np.float64) for i in range(3)]
+        m = _rt(R, ln)
+        with np.errstate(invalid="ignore"):
+            keep = ((ln[0] != 0.0) | (ln[1] != 0.0) | (ln[2] != 0.0)) & \
+                (((m[0] * Nw[0] + m[1] * Nw[1]) + m[2] * Nw[2]) >= cos_max)
+        rejected = valid & ~keep
+        valid &= keep
+    return rows, cols, valid, rejected, g, Vw, Nw
 
 
-def iteration(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, stride=1, max_distance=MAX_DISTANCE):
-    """one iteration at twist: (record dict, residual image (H, W) float32, NaN where a pixel has no correspondence,
-    next twist)"""
-    rows, cols, valid, g, Vw, Nw = associate(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, stride,
-                                             max_distance)
+def iteration(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, stride=1, max_distance=MAX_DISTANCE,
+              intrinsics=None, live_normals=None, cos_max=None):
+    """one iteration at twist over associate()'s pairs: (record dict, residual image of live_depth's extents, float32,
+    NaN where a pixel has no correspondence, next twist)"""
+    rows, cols, valid, rejected, g, Vw, Nw = associate(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p,
+                                                       stride, max_distance, intrinsics, live_normals, cos_max)
     diff = [g[i] - Vw[i] for i in range(3)]
-    r = (Nw[0] * diff[0] + Nw[1] * diff[1]) + Nw[2] * diff[2]
-    J = [Nw[0], Nw[1], Nw[2], g[1] * Nw[2] - g[2] * Nw[1], g[2] * Nw[0] - g[0] * Nw[2], g[0] * Nw[1] - g[1] * Nw[0]]
+    with np.errstate(invalid="ignore"):
+        r = (Nw[0] * diff[0] + Nw[1] * diff[1]) + Nw[2] * diff[2]
+        J = [Nw[0], Nw[1], Nw[2], g[1] * Nw[2] - g[2] * Nw[1], g[2] * Nw[0] - g[0] * Nw[2],
+             g[0] * Nw[1] - g[1] * Nw[0]]
     a, a_abs = np.zeros((6, 6)), np.zeros((6, 6))
     b, b_abs = np.zeros(6), np.zeros(6)
     for i in range(6):
@@ -125,9 +143,7 @@ def iteration(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, st
         b[i] = -np.sum((J[i] * r)[valid])
         b_abs[i] = np.sum(np.abs(J[i] * r)[valid])
     energy = float(np.sum((r * r)[valid]))
-    count = int(valid.sum())
-    h, w = np.shape(live_depth)
-    residuals = np.full((h, w), np.nan, np.float32)
+    residuals = np.full(np.shape(live_depth), np.nan, np.float32)
     residuals[rows[valid], cols[valid]] = r[valid].astype(np.float32)
     twist = np.asarray(twist, np.float64).reshape(6)
     skipped = 1 if not np.all(np.isfinite(a)) else _singular(a)
@@ -136,8 +152,8 @@ def iteration(live_depth, pred_depth, pred_normals, K, ratio, twist, twist_p, st
         delta = np.dot(np.linalg.inv(a), b)
         twist = compose(twist, delta)
     # A_abs, b_abs: the sums of the terms' magnitudes, the scale of a sum's rounding in another order
-    rec = dict(A=a, b=b, energy=energy, count=count, delta=delta, twist=twist.copy(), skipped=skipped, A_abs=a_abs,
-               b_abs=b_abs)
+    rec = dict(A=a, b=b, energy=energy, count=int(valid.sum()), delta=delta, twist=twist.copy(), skipped=skipped,
+               A_abs=a_abs, b_abs=b_abs, angle_rejected=int(rejected.sum()))
     return rec, residuals, twist
 
 

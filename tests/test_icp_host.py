@@ -9,11 +9,13 @@ import os
 import numpy as np
 import pytest
 
+import depth_pyramid_restatement as P
 import fusion_restatement as F
 import fusion_scene as S
 import icp_restatement as I
+import noisy_scene as N
 import raycast_restatement as RC
-from conftest import ROOT
+from conftest import ROOT, load_golden
 from rigid_restatement import rodrigues
 from test_raycast_host import SEQUENCE_ATOL_R as RAYCAST_ATOL_R, SEQUENCE_ATOL_T as RAYCAST_ATOL_T
 
@@ -93,6 +95,51 @@ def test_empty_prediction_skips_every_iteration():
     assert np.array_equal(twist, start) and len(records) == 3
     for r in records:
         assert r["skipped"] == 1 and r["count"] == 0 and not r["A"].any() and not r["delta"].any()
+
+
+PINNED_FIELDS = ("A", "b", "A_abs", "b_abs", "energy", "count", "delta", "twist", "skipped", "level")
+
+
+def pinned_runs():
+    """the arrays of tests/golden/ref_icp_restatement.npz: frame 1 of the noisy scene tracked from the zero twist
+    against frame 0's 48^3 model, iterations (2, 2), by the strided restatement at strides (2, 1) and by the pyramid
+    restatement over two levels without the gate and with a 20 degree gate.  Per run: the records' fields stacked over
+    the iterations, the final twist and the last iteration's residual image"""
+    n = 48
+    frames = N.frames(2)
+    tsdf, weight, _ = F.fuse_depth(*F.empty_model((n,) * 3), frames[0], S.K, N.RATIO, S.offset(n), np.zeros(6))
+    pd, pn, _ = RC.raycast(tsdf, weight, S.K, np.zeros(6), S.offset(n), normals=True)
+    live, zero = frames[1], np.zeros(6)
+    out = {"hits": np.array(np.count_nonzero(pd))}
+
+    def keep(name, records, twist, residuals, fields):
+        for f in fields:
+            out[name + "_" + f] = np.array([r[f] for r in records])
+        out[name + "_final_twist"], out[name + "_residuals"] = twist, residuals
+
+    records, twist = I.icp(live, pd, pn, S.K, N.RATIO, zero, zero, (2, 2), (2, 1))
+    last, residuals, _ = I.iteration(live, pd, pn, S.K, N.RATIO, records[-2]["twist"], zero, 1)
+    assert np.array_equal(last["twist"], twist)
+    keep("strided", records, twist, residuals, PINNED_FIELDS)
+    levels = P.pyramid(live, N.RATIO, S.K, levels=2)
+    for name, cos_max in (("pyramid", None), ("gated", P.cos_of(math.radians(20)))):
+        records, twist, residuals = P.icp(levels, pd, pn, S.K, zero, zero, (2, 2), cos_max=cos_max)
+        keep(name, records, twist, residuals, PINNED_FIELDS + ("angle_rejected",))
+    return out
+
+
+def test_the_restatements_equal_their_pinned_results():
+    """the oracle of every ICP GPU test, pinned: the strided and the pyramid restatement recompute the stored runs
+    (tests/golden/make_golden_icp.py) bit for bit, NaNs in the same places"""
+    want, got = load_golden("ref_icp_restatement.npz"), pinned_runs()
+    assert sorted(want.files) == sorted(got)
+    for name in want.files:
+        assert np.array_equal(want[name], got[name], equal_nan=want[name].dtype.kind == "f"), name
+    assert got["hits"] == 44447
+    assert got["strided_count"].tolist() == [8753, 9004, 35942, 35920]
+    assert got["pyramid_count"].tolist() == [8767, 8938, 35924, 35935]
+    assert got["gated_count"].tolist() == [6584, 8395, 33074, 33120]
+    assert got["gated_angle_rejected"].tolist() == [2183, 581, 2849, 2830]
 
 
 @pytest.mark.parametrize("angle", [0.0, 1e-9, 1e-4, 0.3, 1.0, 2.0, 2.5, 3.0])
