@@ -204,3 +204,6 @@ def decode_records(records_host):
     index = (~packed.astype(np.uint32)).astype(np.int64)
     return dict(executed=executed, max_value=max_value, argmax=index, data_energy=energies[:, 0],
                 smoothing_energy=energies[:, 1], level_set_energy=energies[:, 2])
+
+
+checked_pointer = _ptr  # the public spelling, for callers outside the device_*.py wrappers

@@ -8,7 +8,9 @@ the tiny iteration records to learn whether the device-side convergence gate has
 This module is the import point; the code lives in
     engine_common.py     input conversion, pyramid level rule, graph-capture lock
     engine_options.py    the knobs that are not part of the reference's signatures, and the last call's report
-    engine_hier.py       HierarchicalEngine (whole volumes and z-slabs, HIP graphs, persistent 2-D levels)
+    engine_hier.py       HierarchicalEngine: a level and its filter plan, the eager / HIP-graph / blocked 2-D / z-slab
+                         drivers, the level outcome they all return and the results and reports made of it
+    engine_hier_pyramid.py  ... its canonical / live pyramids (whole volumes and z-slabs)
     engine_slavcheva.py  SlavchevaEngine: construction, the general call path, hooks, gradient_field
     engine_run.py        ... its library-enqueued calls on whole volumes (fixed-count, threshold-terminated)
     engine_slab.py       ... on z- / y-slabs: launch plan, exchange groups, compact faces, the wider re-run

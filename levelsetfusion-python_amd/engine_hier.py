@@ -2,14 +2,14 @@
 z-slabs (nonrigid_opt/hierarchical/hierarchical_optimizer2d.py:123-246).  The drop-in classes
 HierarchicalOptimizer2d / 3d are thin shells around it."""
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _lib, device as dev, engine_options
-from .engine_common import (_CAPTURE_LOCK, _RETIRED_GRAPHS, _combine_statistics, _conv_axis_order, _retire_graphs,
-                            pyramid_level_count)
-from .slab import SlabComm, SlabLayout
+from .engine_common import _CAPTURE_LOCK, _RETIRED_GRAPHS, _combine_statistics, _conv_axis_order, _retire_graphs
+from .engine_hier_pyramid import build_pyramids
 
 
 class LevelResult:
@@ -70,86 +70,10 @@ class HierarchicalEngine:
         self.check_interval = max(1, int(check_interval))
         self.level_results = []
         self.last_gradient = None  # planar gradient of the finest level after the last iteration
-
-    # ------------------------------------------------------------------------------------------------
-    def _slab(self):
-        return self.comm is not None and self.comm.active
-
-    def _slab_comm_of(self, layout):
-        for c in getattr(self, "_level_comms", []) or [self.comm]:
-            if c is not None and c.layout is layout:
-                return c
-        return self.comm
-
-    def build_pyramids(self, canonical, live):
-        """canonical / live pyramids, coarsest first; live is packed with its full-resolution np.gradient
-        BEFORE restriction (gradients are averaged, not recomputed: hierarchical_optimizer2d.py:126-131).
-        Returns (canonical levels, packed levels, per-level SlabComm or None)."""
-        if not self._slab():
-            n_levels = pyramid_level_count(live.shape, self.maximum_chunk_size)
-            canon_levels = [canonical]
-            packed_levels = [dev.pack_live_gradient(live)]
-            restrict = dev.downsample2x_linear if self.linear_resampling else dev.restrict_mean
-            for _ in range(1, n_levels):
-                canon_levels.append(restrict(canon_levels[-1], 1))
-                packed_levels.append(restrict(packed_levels[-1], 4))
-            canon_levels.reverse()
-            packed_levels.reverse()
-            return canon_levels, packed_levels, [None] * n_levels
-        # z-slab: every level keeps `halo` neighbour slices; a level's owned slices are the restriction of the finer
-        # level's owned slices (slab boundaries are multiples of 2^levels), its halos come from one exchange per level
-        L0 = self.comm.layout
-        if live.dim() != 3 or live.shape[0] != L0.nz_local:
-            raise ValueError("slab runs need 3-D local fields with %d slices, got %r" % (L0.nz_local, tuple(live.shape)))
-        global_shape = (L0.nz_global,) + tuple(live.shape[1:])
-        n_levels = pyramid_level_count(global_shape, self.maximum_chunk_size)
-        per = L0.z1 - L0.z0
-        if per % (1 << (n_levels - 1)) != 0 or (per >> (n_levels - 1)) < max(L0.halo, 1):
-            raise ValueError("a slab of %d slices cannot carry %d pyramid levels with a %d-slice halo"
-                             % (per, n_levels, L0.halo))
-        comms = [self.comm]
-        packed = dev.pack_live_gradient(live)
-        # the outermost halo slice got a one-sided z difference: refresh the halos from their owners
-        comms[0].exchange_halos([packed.view(packed.shape[0], packed.shape[1], -1)])
-        canon_levels, packed_levels = [canonical], [packed]
-        for k in range(1, n_levels):
-            fine_comm = comms[-1]
-            Lf = fine_comm.layout
-            Lc = SlabLayout(Lf.nz_global // 2, Lf.rank, Lf.world, Lf.halo)
-            cc = SlabComm(Lc, fine_comm.group)
-            own_f = Lf.owned_local()
-            if self.linear_resampling:
-                c_own = self._restrict_linear_owned(canon_levels[-1], Lf, 1)
-                p_own = self._restrict_linear_owned(packed_levels[-1], Lf, 4)
-            else:
-                c_own = dev.restrict_mean(canon_levels[-1][own_f].contiguous(), 1)
-                p_own = dev.restrict_mean(packed_levels[-1][own_f].contiguous(), 4)
-            c_loc = torch.zeros((Lc.nz_local,) + tuple(c_own.shape[1:]), dtype=torch.float32, device=live.device)
-            p_loc = torch.zeros((Lc.nz_local,) + tuple(p_own.shape[1:]), dtype=torch.float32, device=live.device)
-            c_loc[Lc.owned_local()] = c_own
-            p_loc[Lc.owned_local()] = p_own
-            cc.exchange_halos([c_loc])
-            cc.exchange_halos([p_loc.view(p_loc.shape[0], p_loc.shape[1], -1)])
-            canon_levels.append(c_loc)
-            packed_levels.append(p_loc)
-            comms.append(cc)
-        canon_levels.reverse()
-        packed_levels.reverse()
-        comms.reverse()
-        self._level_comms = comms
-        return canon_levels, packed_levels, comms
-
-    @staticmethod
-    def _restrict_linear_owned(fine, layout, channels):
-        """LINEAR restriction (4x4x4 windows, math_utils/resampling.py:90-109) of a slab's owned slices: the window of a
-        coarse slice reaches one fine slice past the owned range -- the neighbour's slice from the halo, or the edge
-        slice again where the volume ends (the kernel's clamp).  Two slices are put on either side so that the window
-        origin stays even; the outer one and the two extra coarse slices it produces are never looked at."""
-        own = layout.owned_local()
-        below = fine[own.start - 1:own.start] if layout.halo_lo >= 1 else fine[own.start:own.start + 1]
-        above = fine[own.stop:own.stop + 1] if layout.halo_hi >= 1 else fine[own.stop - 1:own.stop]
-        padded = torch.cat([below, below, fine[own], above, above], 0).contiguous()
-        return dev.downsample2x_linear(padded, channels)[1:-1].contiguous()
+        # z-slab runs: levels whose gather operand had to be replicated on every rank because the cumulative warp outgrew
+        # the halo (_optimize_level_slab); once a level needed it the finer ones start that way -- warps are not rescaled
+        # between levels (hierarchical_optimizer2d.py:155-156), so they only grow
+        self.replicated_levels = 0
 
     def optimize(self, canonical, live):
         """canonical, live: float32 device tensors [z,]y,x (z-slab runs: the local slab incl. halos).
@@ -158,19 +82,15 @@ class HierarchicalEngine:
             raise ValueError("canonical and live fields must have the same shape")
         dims = live.dim()
         self.last_call = engine_options.new_call_report()
-        canon_levels, packed_levels, comms = self.build_pyramids(canonical, live)
-        self.level_results = []
-        self._pending_levels = []
-        self.iteration_data = []
-        # z-slab runs: levels whose gather operand had to be replicated on every rank because the cumulative warp
-        # outgrew the halo (optimize_level); once a level needed it the finer ones start that way -- warps are not
-        # rescaled between levels (hierarchical_optimizer2d.py:155-156), so they only grow
-        self.replicated_levels = 0
-        warp = None
+        canon_levels, packed_levels, comms = build_pyramids(canonical, live, self.maximum_chunk_size,
+                                                            self.linear_resampling, self.comm)
+        self.level_results, self.iteration_data, self.replicated_levels = [], [], 0
+        waiting = []  # outcomes of levels whose results are made later (level_results stays in level order)
+        warp = torch.zeros((dims,) + tuple(canon_levels[0].shape), dtype=torch.float32, device=live.device)
         for level, (canon_l, packed_l, comm_l) in enumerate(zip(canon_levels, packed_levels, comms)):
-            if level == 0:
-                warp = torch.zeros((dims,) + tuple(canon_l.shape), dtype=torch.float32, device=live.device)
-            self.optimize_level(canon_l, packed_l, warp, comm_l)
+            waiting.append(self.optimize_level(canon_l, packed_l, warp, comm_l))
+            if not waiting[-1].deferred:
+                self._finish_levels(waiting)
             if level != len(canon_levels) - 1:
                 if self.linear_resampling:
                     if comm_l is not None:
@@ -184,7 +104,7 @@ class HierarchicalEngine:
                     lo = comm_l.layout.halo_lo
                     fine = fine[:, lo:lo + comms[level + 1].layout.nz_local].contiguous()
                 warp = fine
-        self._finish_pending_levels()
+        self._finish_levels(waiting)
         return warp
 
     # ------------------------------------------------------------------------------------------------
@@ -193,55 +113,76 @@ class HierarchicalEngine:
     # intermediate filter passes ping-pong between two scratch buffers and the LAST pass writes F[(i + 1) % 2].  The
     # buffer roles therefore repeat with period 2, which is what lets a batch of iterations be captured ONCE as a HIP
     # graph and replayed (launch-bound levels: 2-D fields, coarse 3-D levels).
-    class _Level:
-        pass
+    def _filter_plan(self, grid, full_grid, warp, S, comm):
+        """the launches behind lsf_hier_iteration that filter the raw gradient in S[0] into this iteration's F, decided
+        once per level: steps (run, src, dst) -- run(src, dst, gate) enqueues one, dst None = F -- and whether the last
+        one also moves the warp by the gradient it writes"""
+        taps, rate, fused, steps = self.gradient_kernel, self.rate, self.fused_filter, []
+        if comm is not None:  # z-slab: the z pass reads taps / 2 slices of the (x,y)-filtered field on either side
+            steps.append((lambda src, dst, gate: comm.exchange_halos([src], width=len(taps) // 2), S[0], S[0]))
+        if fused and dev.n_voxels(grid) >= self.fused_filter_min_voxels and dev.convolve_xyz_ok(grid, taps):
+            # x, y, z in one launch, which also moves the warp by its filtered gradient, component by component
+            steps.append((lambda src, dst, gate: dev.convolve_xyz(src, dst, grid, taps, gate, warp, rate), S[0], None))
+            return steps, True
+        axes, src = _conv_axis_order(grid.dims), S[0]
+        if len(axes) == 3 and fused and dev.convolve_xy_ok(full_grid, taps):
+            # smaller 3-D levels: the x and the y pass in one launch (these levels are launch-bound)
+            steps.append((lambda src, dst, gate: dev.convolve_xy(src, dst, full_grid, taps, gate), S[0], S[1]))
+            axes, src = axes[2:], S[1]
+        # the last pass moves the warp by the gradient it writes, instead of lsf_hier_update reading the gradient again
+        moves_warp = dev.convolve_axis_update_ok(grid, taps)
+        for axis in axes:
+            last = axis == axes[-1]
+            dst = None if last else (S[0] if src is S[1] else S[1])
+            g = grid if axis == 2 else full_grid
+            if last and moves_warp:
+                run = lambda src, dst, gate, g=g, a=axis: dev.convolve_axis_update(src, dst, warp, rate, g, a, taps, gate)
+            else:
+                run = lambda src, dst, gate, g=g, a=axis: dev.convolve_axis(src, dst, None, g, a, taps, gate)
+            steps.append((run, src, dst))
+            src = dst
+        return steps, moves_warp
 
-    def _make_level(self, canonical, packed, warp, grid, full_grid, n_records, packed_global=None):
+    def _make_level(self, canonical, packed, warp, grid, full_grid, n_records, packed_global=None, comm=None):
         """packed_global: the packed live field of the WHOLE level (every rank's owned slices, SlabComm.all_gather_owned)
-        for the gather instead of the local slab + halo"""
-        lv = HierarchicalEngine._Level()
-        dims = canonical.dim()
-        tik, ker = self.tikhonov_term_enabled, self.gradient_kernel_enabled
-        lv.canonical, lv.packed, lv.warp, lv.grid, lv.full_grid, lv.dims = canonical, packed, warp, grid, full_grid, dims
-        lv.params = _lib.HierParams(float(self.data_term_amplifier), float(self.tikhonov_strength), float(self.rate),
-                                    int(tik), int(not ker), int(self.compute_energy))
-        lv.packed_global = packed_global
+        for the gather instead of the local slab + halo; comm: the level's SlabComm (z-slab runs)"""
+        dims, tik, ker = canonical.dim(), self.tikhonov_term_enabled, self.gradient_kernel_enabled
+        params = _lib.HierParams(float(self.data_term_amplifier), float(self.tikhonov_strength), float(self.rate),
+                                 int(tik), int(not ker), int(self.compute_energy))
         if packed_global is not None:
-            lv.params.packed_nz, lv.params.packed_z_global_offset = int(packed_global.shape[0]), 0
-        lv.F = [torch.zeros_like(warp) for _ in range(2)] if (tik or ker) else []
-        lv.S = [torch.zeros_like(warp) for _ in range(2)] if ker else []
-        lv.report_g = torch.zeros_like(warp) if (self.collect_reports and not lv.F) else None
-        lv.records = dev.new_records(n_records, canonical.device)
-        f = dev.IterationLauncher(grid, lv.records, _lib.GATE_HIERARCHICAL, float(self.maximum_warp_update_threshold))
+            params.packed_nz, params.packed_z_global_offset = int(packed_global.shape[0]), 0
+        F = [torch.zeros_like(warp) for _ in range(2)] if (tik or ker) else []
+        S = [torch.zeros_like(warp) for _ in range(2)] if ker else []
+        report_g = torch.zeros_like(warp) if (self.collect_reports and not F) else None
+        records = dev.new_records(n_records, canonical.device)
+        f = dev.IterationLauncher(grid, records, _lib.GATE_HIERARCHICAL, float(self.maximum_warp_update_threshold))
         n = dev.n_voxels(grid)
-        lv.p_packed = f.pointer(packed, 4 * n, "packed live") if packed_global is None else \
-            f.pointer(packed_global, packed_global.numel(), "packed live (whole level)")
-        lv.p_canon = f.pointer(canonical, n, "canonical")
-        lv.p_warp = f.pointer(warp, n * dims, "warp")
-        lv.p_F = [f.pointer(t, n * dims, "gradient buffer") for t in lv.F]
-        lv.p_S = [f.pointer(t, n * dims, "scratch buffer") for t in lv.S]
-        lv.p_report = f.pointer(lv.report_g, n * dims, "gradient", allow_none=True)
-        lv.params_ref = ctypes.byref(lv.params)
-        lv.launcher = f
-        # Deferred maximum (3-D levels whose filter runs in lsf_convolve_xyz, Tikhonov on): when the stop test cannot
-        # fire (threshold <= 0) the maximum update length is only a log value, and the NEXT iteration's kernel reads the
+        steps, moves_warp = self._filter_plan(grid, full_grid, warp, S, comm) if ker else ([], False)
+        # Deferred maximum (3-D levels whose filter moves the warp itself, Tikhonov on): when the stop test cannot fire
+        # (threshold <= 0) the maximum update length is only a log value, and the NEXT iteration's kernel reads the
         # gradient it belongs to anyway (as g_prev, for the Laplacian): that kernel writes it into the previous record
         # (lsf_hier_params::previous_max, an LSF_GATE_OPEN gate naming the record), and only the last iteration of a
-        # batch keeps the separate maximum pass (44 us of 520 per 256^3 iteration).
-        # (smaller levels, whose filter runs pass by pass: the last pass moves the warp, lsf_convolve_axis_update)
-        lv.defer_max = (dims == 3 and tik and ker and float(self.maximum_warp_update_threshold) <= 0.0
-                        and ((self.fused_filter and n >= self.fused_filter_min_voxels
-                              and dev.convolve_xyz_ok(grid, self.gradient_kernel))
-                             or dev.convolve_axis_update_ok(grid, self.gradient_kernel))
-                        and self.defer_maximum)
-        if lv.defer_max:
-            lv.params_prevmax = _lib.HierParams.from_buffer_copy(lv.params)
-            lv.params_prevmax.previous_max = 1
-            lv.params_prevmax_ref = ctypes.byref(lv.params_prevmax)
-            base = lv.records.data_ptr()
-            lv.open_gates = [_lib.Gate(base + i * _lib.RECORD_BYTES, _lib.GATE_OPEN, 0.0, 0.0) for i in range(n_records)]
-            lv.open_gate_refs = [ctypes.byref(g) for g in lv.open_gates]
-        return lv
+        # batch keeps the separate maximum pass (44 us of 520 per 256^3 iteration).  Slab levels reduce every iteration's
+        # maximum over the ranks, the hook and the telemetry look at every iteration: they keep the pass.
+        defer_max = bool(dims == 3 and tik and moves_warp and float(self.maximum_warp_update_threshold) <= 0.0
+                         and self.defer_maximum and comm is None and self.iteration_hook is None
+                         and not self.collect_iteration_data)
+        prevmax, open_gates = _lib.HierParams.from_buffer_copy(params), []
+        if defer_max:
+            prevmax.previous_max = 1
+            open_gates = [_lib.Gate(records.data_ptr() + i * _lib.RECORD_BYTES, _lib.GATE_OPEN, 0.0, 0.0)
+                          for i in range(n_records)]
+        return _Level(
+            canonical=canonical, packed=packed, packed_global=packed_global, warp=warp, grid=grid, comm=comm, params=params,
+            params_ref=ctypes.byref(params), F=F, S=S, report_g=report_g, records=records, launcher=f, steps=steps,
+            moves_warp=moves_warp,
+            p_packed=f.pointer(packed, 4 * n, "packed live") if packed_global is None else
+            f.pointer(packed_global, packed_global.numel(), "packed live (whole level)"),
+            p_canon=f.pointer(canonical, n, "canonical"), p_warp=f.pointer(warp, n * dims, "warp"),
+            p_F=[f.pointer(t, n * dims, "gradient buffer") for t in F],
+            p_S=[f.pointer(t, n * dims, "scratch buffer") for t in S],
+            p_report=f.pointer(report_g, n * dims, "gradient", allow_none=True), defer_max=defer_max, prevmax=prevmax,
+            prevmax_ref=ctypes.byref(prevmax), open_gates=open_gates, open_gate_refs=[ctypes.byref(g) for g in open_gates])
 
     def _graph_key(self, canonical):
         K = min(self.check_interval, self.maximum_iteration_count)
@@ -257,216 +198,217 @@ class HierarchicalEngine:
         except Exception:  # noqa: BLE001 -- interpreter shutdown: nothing left to protect
             pass
 
-    def _enqueue(self, lv, rec_idx, prev_idx, parity, comm=None, defer_max=False, prev_deferred=False):
+    def _enqueue(self, lv, rec_idx, prev_idx, parity, defer_max=False, prev_deferred=False):
         """one iteration: record slot rec_idx, gated on record prev_idx (None: always runs), buffer parity 0/1.
         defer_max: leave this iteration's maximum to the next one (see _make_level); prev_deferred: the previous did"""
         f = lv.launcher
-        tik, ker = self.tikhonov_term_enabled, self.gradient_kernel_enabled
-        gate_ref = f.gate_ref(prev_idx)
-        gate = None if prev_idx is None or prev_idx < 0 else f.gates[prev_idx]
-        lib_hier = _lib.lib.lsf_hier_iteration
-        if ker:
-            prev, out = (lv.p_F[parity] if tik else None), lv.F[1 - parity]
-            if prev_deferred and prev_idx is not None and prev_idx >= 0:
-                _lib.check(lib_hier(lv.p_packed, lv.p_canon, lv.p_warp, prev, lv.p_S[0], f.grid_ref,
-                                    lv.params_prevmax_ref, lv.open_gate_refs[prev_idx], f.record_ptrs[rec_idx],
-                                    dev.stream_ptr()), "lsf_hier_iteration")
-            else:
-                _lib.check(lib_hier(lv.p_packed, lv.p_canon, lv.p_warp, prev, lv.p_S[0], f.grid_ref, lv.params_ref,
-                                    gate_ref, f.record_ptrs[rec_idx], dev.stream_ptr()), "lsf_hier_iteration")
-            slab = comm is not None and comm.active
-            if slab:  # the z pass reads taps/2 slices of the (x,y)-filtered field on either side
-                comm.exchange_halos([lv.S[0]], width=len(self.gradient_kernel) // 2)
-            axes = _conv_axis_order(lv.dims)
-            src = lv.S[0]
-            moved = False
-            if (self.fused_filter and dev.n_voxels(lv.grid) >= self.fused_filter_min_voxels
-                    and dev.convolve_xyz_ok(lv.grid, self.gradient_kernel)):
-                # x, y, z in one launch, which also moves the warp by its filtered gradient, component by component
-                dev.convolve_xyz(src, out, lv.grid, self.gradient_kernel, gate, lv.warp, self.rate)
-                axes, moved = (), True
-            if len(axes) == 3 and self.fused_filter and dev.convolve_xy_ok(lv.full_grid, self.gradient_kernel):
-                # smaller 3-D levels: the x and the y pass in one launch (these levels are launch-bound)
-                dev.convolve_xy(src, lv.S[1], lv.full_grid, self.gradient_kernel, gate)
-                src, axes = lv.S[1], [None, None, 2]
-            for k, axis in enumerate(axes):
-                if axis is None:
-                    continue
-                dst = out if k == len(axes) - 1 else lv.S[(k + 1) % 2]
-                if k == len(axes) - 1 and dev.convolve_axis_update_ok(lv.grid, self.gradient_kernel):
-                    # the last pass moves the warp by the gradient it writes (one launch reads and writes the warp
-                    # instead of lsf_hier_update reading the gradient again)
-                    dev.convolve_axis_update(src, dst, lv.warp, self.rate, lv.grid if axis == 2 else lv.full_grid, axis,
-                                             self.gradient_kernel, gate)
-                    moved = True
-                else:
-                    dev.convolve_axis(src, dst, None, lv.grid if axis == 2 else lv.full_grid, axis,
-                                      self.gradient_kernel, gate)
-                src = dst
-            if not (moved and defer_max):
-                dev.hier_update(out, None if moved else lv.warp, lv.grid, self.rate, gate, lv.records, rec_idx)
-        elif tik:
-            _lib.check(lib_hier(lv.p_packed, lv.p_canon, lv.p_warp, lv.p_F[parity], lv.p_F[1 - parity], f.grid_ref,
-                                lv.params_ref, gate_ref, f.record_ptrs[rec_idx], dev.stream_ptr()),
-                       "lsf_hier_iteration")
-        else:
-            _lib.check(lib_hier(lv.p_packed, lv.p_canon, lv.p_warp, None, lv.p_report, f.grid_ref, lv.params_ref,
-                                gate_ref, f.record_ptrs[rec_idx], dev.stream_ptr()), "lsf_hier_iteration")
+        gated = prev_idx is not None and prev_idx >= 0
+        # the gradient kernel: after the previous gradient (Tikhonov term) it writes the raw gradient for the filter,
+        # this iteration's gradient (it then moves the warp itself) or, with neither term, the reports' gradient
+        prev = lv.p_F[parity] if self.tikhonov_term_enabled else None
+        first = lv.p_S[0] if lv.steps else (lv.p_F[1 - parity] if lv.F else lv.p_report)
+        params_ref, gate_ref = lv.params_ref, f.gate_ref(prev_idx)
+        if prev_deferred and gated:
+            params_ref, gate_ref = lv.prevmax_ref, lv.open_gate_refs[prev_idx]
+        _lib.check(_lib.lib.lsf_hier_iteration(lv.p_packed, lv.p_canon, lv.p_warp, prev, first, f.grid_ref, params_ref,
+                                               gate_ref, f.record_ptrs[rec_idx], dev.stream_ptr()), "lsf_hier_iteration")
+        if not lv.steps:
+            return
+        gate, out = (f.gates[prev_idx] if gated else None), lv.F[1 - parity]
+        for run, src, dst in lv.steps:
+            run(src, out if dst is None else dst, gate)
+        if not (lv.moves_warp and defer_max):
+            dev.hier_update(out, None if lv.moves_warp else lv.warp, lv.grid, self.rate, gate, lv.records, rec_idx)
 
-    def _final_gradient(self, lv, n_exec):
-        if lv.F and n_exec:
-            return lv.F[n_exec % 2]  # iteration n_exec - 1 wrote F[((n_exec - 1) + 1) % 2]
-        return lv.report_g
+    def _read_batch(self, records, log):
+        """the one host synchronisation of a batch of iterations: their records, decoded, the executed ones added to `log`;
+        returns (executed iterations, whether the level ends here: a gate closed or the last maximum is below the threshold)"""
+        dec = dev.decode_records(dev.records_to_host(records))
+        k_exec = int(dec["executed"].sum())
+        log.append({k: v[:k_exec].copy() for k, v in dec.items()})
+        return k_exec, bool(k_exec < records.shape[0]
+                            or dec["max_value"][k_exec - 1] < np.float32(self.maximum_warp_update_threshold))
 
-    def _finish_level(self, lv, n_exec, dec, slab_layout=None):
+    @staticmethod
+    def _merged(log):
+        if not log:  # maximum_iteration_count == 0: the reference's loop body never runs
+            return dev.decode_records(np.zeros((1, dev.RECORD_WORDS), np.int64))
+        return {k: np.concatenate([part[k] for part in log]) for k in log[0]}
+
+    def _finish_levels(self, outcomes):
+        """results (and reports) of levels in level order; the records that are still on the card -- the fixed-count
+        levels of _optimize_level_blocked -- are read in ONE transfer with ONE synchronisation"""
+        unread = [o for o in outcomes if o.decoded is None]
+        if unread:
+            used = torch.cat([dev.slot_view(o.records)[:, :, :dev.USED_SLOT_WORDS].reshape(-1) for o in unread])
+            host = dev.pinned_scratch("level records", used.numel(), torch.int64)[:used.numel()]
+            host.copy_(used, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            flat, at = host.numpy(), 0
+            for o in unread:
+                n = o.records.shape[0]
+                words = n * _lib.RECORD_SLOTS * dev.USED_SLOT_WORDS
+                o.decoded = dev.decode_records(flat[at:at + words].reshape(n, _lib.RECORD_SLOTS, -1).copy())
+                o.n_exec = int(o.decoded["executed"].sum())
+                at += words
+        for o in outcomes:
+            self._finish_level(o)
+        del outcomes[:]
+
+    def _finish_level(self, o):
         thr = float(self.maximum_warp_update_threshold)
-        n_vox = dev.n_voxels(lv.grid) if slab_layout is None else slab_layout.nz_global * lv.grid.ny * lv.grid.nx
-        res = LevelResult(n_exec, [float(v) for v in dec["max_value"][:n_exec]],
-                          [int(v) for v in dec["argmax"][:n_exec]],
-                          [float(v) for v in dec["data_energy"][:n_exec]], n_vox,
-                          [float(v) for v in dec["smoothing_energy"][:n_exec]])
+        L = o.comm.layout if o.comm is not None else None
+        n_exec, dec = o.n_exec, o.decoded
+        n_vox = dev.n_voxels(o.grid) if L is None else L.nz_global * o.grid.ny * o.grid.nx
+        log = lambda key, kind=float: [kind(v) for v in dec[key][:n_exec]]
+        res = LevelResult(n_exec, log("max_value"), log("argmax", int), log("data_energy"), n_vox, log("smoothing_energy"))
         res.iteration_limit_reached = n_exec >= self.maximum_iteration_count
         self.level_results.append(res)
-        self.last_gradient = self._final_gradient(lv, n_exec)
-        if self.collect_reports and slab_layout is None:
-            # per-level ConvergenceReport (cpp get_per_level_convergence_reports, run_hierarchical_optimizer3d.py:104):
-            # statistics of the last iteration's update field and of |canonical - resampled live| at this level
-            from .convergence_report import (ConvergenceReport, build_tsdf_difference_statistics,
-                                             build_warp_delta_statistics)
-            resampled = dev.warp_field(lv.packed[..., 0].contiguous(), lv.warp, 1.0)
-            g_final = self.last_gradient if self.last_gradient is not None else torch.zeros_like(lv.warp)
-            res.report = ConvergenceReport(n_exec, res.iteration_limit_reached,
-                                           build_warp_delta_statistics(g_final, lv.canonical, resampled, thr,
-                                                                       float("inf")),
-                                           build_tsdf_difference_statistics(lv.canonical, resampled))
-        elif self.collect_reports:
+        self.last_gradient = o.gradient
+        if not self.collect_reports:
+            return
+        # per-level ConvergenceReport (cpp get_per_level_convergence_reports, run_hierarchical_optimizer3d.py:104):
+        # statistics of the last iteration's update field and of |canonical - resampled live| at this level
+        from .convergence_report import (ConvergenceReport, tsdf_difference_statistics_from_raw,
+                                         warp_delta_statistics_from_raw)
+        g_final = o.gradient if o.gradient is not None else torch.zeros_like(o.warp)
+        if L is None:
+            shape = tuple(o.canonical.shape)
+            resampled = dev.warp_field(o.packed[..., 0].contiguous(), o.warp, 1.0)
+            raw_warp = dev.warp_statistics(g_final, o.canonical, resampled, thr).cpu().numpy()
+            raw_tsdf = dev.tsdf_difference_statistics(o.canonical, resampled).cpu().numpy()
+        else:
             # z-slab: the same statistics over the OWNED slices (global voxel indices through z_global_offset), then
             # combined over the ranks -- counts and sums add, minima / maxima compare, the arg-max of the larger
             # maximum wins (smallest index on a tie, as np.argmax over the whole volume)
-            from .convergence_report import (ConvergenceReport, tsdf_difference_statistics_from_raw,
-                                             warp_delta_statistics_from_raw)
-            L = slab_layout
-            whole = dev.make_grid(lv.canonical.shape, 0, L.nz_local, L.z_global_offset)
-            if lv.packed_global is None:
-                resampled = dev.warp_field(lv.packed[..., 0].contiguous(), lv.warp, 1.0, whole)
-            else:
-                # the warp reaches past the halo: resample the replicated live field under the whole level's warp (every
-                # rank the same work; reports are an opt-in) and keep the owned slices
-                c_l = self._slab_comm_of(L)
-                warp_g = torch.stack([c_l.all_gather_owned(lv.warp[c]) for c in range(lv.warp.shape[0])])
-                whole_level = dev.warp_field(lv.packed_global[..., 0].contiguous(), warp_g, 1.0)
-                resampled = torch.zeros_like(lv.canonical)
-                resampled[L.owned_local()] = whole_level[L.z0:L.z1]
-            g_final = self.last_gradient if self.last_gradient is not None else torch.zeros_like(lv.warp)
-            raw = torch.stack([dev.warp_statistics(g_final, lv.canonical, resampled, thr, lv.grid),
-                               dev.tsdf_difference_statistics(lv.canonical, resampled, lv.grid)])
-            rows = self._slab_comm_of(L).gather_rows(raw)
-            shape = (L.nz_global,) + tuple(lv.canonical.shape[1:])
-            res.report = ConvergenceReport(
-                n_exec, res.iteration_limit_reached,
-                warp_delta_statistics_from_raw(_combine_statistics([r[0] for r in rows], has_min=False), shape, thr,
-                                               float("inf")),
-                tsdf_difference_statistics_from_raw(_combine_statistics([r[1] for r in rows], has_min=True), shape))
+            shape = (L.nz_global,) + tuple(o.canonical.shape[1:])
+            resampled = self._slab_resampled(o, L)
+            raw = torch.stack([dev.warp_statistics(g_final, o.canonical, resampled, thr, o.grid),
+                               dev.tsdf_difference_statistics(o.canonical, resampled, o.grid)])
+            rows = o.comm.gather_rows(raw)
+            raw_warp = _combine_statistics([r[0] for r in rows], has_min=False)
+            raw_tsdf = _combine_statistics([r[1] for r in rows], has_min=True)
+        res.report = ConvergenceReport(n_exec, res.iteration_limit_reached,
+                                       warp_delta_statistics_from_raw(raw_warp, shape, thr, float("inf")),
+                                       tsdf_difference_statistics_from_raw(raw_tsdf, shape))
+
+    @staticmethod
+    def _slab_resampled(o, L):
+        """the live field of a slab level under its warp, on every local slice"""
+        if o.packed_global is None:
+            whole = dev.make_grid(o.canonical.shape, 0, L.nz_local, L.z_global_offset)
+            return dev.warp_field(o.packed[..., 0].contiguous(), o.warp, 1.0, whole)
+        # the warp reaches past the halo: resample the replicated live field under the whole level's warp (every
+        # rank the same work; reports are an opt-in) and keep the owned slices
+        warp_g = torch.stack([o.comm.all_gather_owned(o.warp[c]) for c in range(o.warp.shape[0])])
+        whole_level = dev.warp_field(o.packed_global[..., 0].contiguous(), warp_g, 1.0)
+        resampled = torch.zeros_like(o.canonical)
+        resampled[L.owned_local()] = whole_level[L.z0:L.z1]
+        return resampled
 
     OPEN_RECORD = 0x7F800000FFFFFFFF  # packed max = +inf: "previous iteration has not converged" for the gate
 
     def optimize_level(self, canonical, packed, warp, comm=None):
-        slab = comm is not None and comm.active
+        """one level by the driver that fits it; the level's warp is advanced in place, returns the _LevelOutcome"""
+        comm = comm if comm is not None and comm.active else None
         max_it = self.maximum_iteration_count
-        n_vox = canonical.numel()
-        hooked = self.iteration_hook is not None
-        if (self.blocked_levels and canonical.dim() == 2 and not slab and not hooked and not self.collect_iteration_data
+        watched = self.iteration_hook is not None or self.collect_iteration_data  # every iteration is looked at
+        if (self.blocked_levels and canonical.dim() == 2 and comm is None and not watched
                 and not self.compute_energy and max_it >= 1
                 and (not self.gradient_kernel_enabled or len(self.gradient_kernel) in dev.XYZ_TAP_COUNTS)):
             return self._optimize_level_blocked(canonical, packed, warp)
-        if (self.use_graphs and not slab and not self.collect_iteration_data and not hooked and max_it >= 4
-                and self.check_interval >= 2 and n_vox <= self.graph_max_voxels
+        if (self.use_graphs and comm is None and not watched and max_it >= 4
+                and self.check_interval >= 2 and canonical.numel() <= self.graph_max_voxels
                 and (self.allow_graph_capture or self._graph_key(canonical) in self._graphs)):
             return self._optimize_level_graph(canonical, packed, warp)
-        if slab:
-            L = comm.layout
-            grid = dev.make_grid(canonical.shape, L.z_begin, L.z_end, L.z_global_offset)
-            full_grid = dev.make_grid(canonical.shape, 0, L.nz_local, L.z_global_offset)
-            reach = len(self.gradient_kernel) // 2 if self.gradient_kernel_enabled else 0
-            if L.halo < max(reach, 2):
-                raise ValueError("slab halo of %d slices is too narrow: this configuration needs >= %d"
-                                 % (L.halo, max(reach, 2)))
-        else:
-            L = None
-            grid = full_grid = dev.make_grid(canonical.shape)
-        thr = float(self.maximum_warp_update_threshold)
-        tik = self.tikhonov_term_enabled
-        packed_global = warp_at_start = None
-        if slab and getattr(self, "replicated_levels", 0) > 0:
-            packed_global = comm.all_gather_owned(packed)
-            self.replicated_levels += 1
-        elif slab:
-            warp_at_start = warp.clone()  # what a restart of this level on the replicated field begins from
-        lv = self._make_level(canonical, packed, warp, grid, full_grid, max(max_it, 1), packed_global)
-        records = lv.records
-        snapshots = []
-        it = 0
-        n_exec = 0
-        dec = None
+        if comm is not None:
+            return self._optimize_level_slab(canonical, packed, warp, comm)
+        grid = dev.make_grid(canonical.shape)
+        return self._optimize_level_eager(self._make_level(canonical, packed, warp, grid, grid, max(max_it, 1)))
+
+    def _optimize_level_slab(self, canonical, packed, warp, comm):
+        """a z-slab's level.  The gather follows the cumulative warp: it must stay inside the halo of the static packed
+        field.  When it does not, the reference does not stop either (hierarchical_optimizer2d.py:169-171 tests the update
+        threshold only): every rank sees the same reduced maximum, so all of them together discard this level's
+        iterations, replicate the level's packed field (5 x 512 MiB at 512^3 against 288 GB) and run the
+        level again from the warp it started with -- the gather then never leaves the device"""
+        L = comm.layout
+        grid = dev.make_grid(canonical.shape, L.z_begin, L.z_end, L.z_global_offset)
+        full_grid = dev.make_grid(canonical.shape, 0, L.nz_local, L.z_global_offset)
+        reach = len(self.gradient_kernel) // 2 if self.gradient_kernel_enabled else 0
+        if L.halo < max(reach, 2):
+            raise ValueError("slab halo of %d slices is too narrow: this configuration needs >= %d"
+                             % (L.halo, max(reach, 2)))
+        def run(packed_global):
+            return self._optimize_level_eager(self._make_level(canonical, packed, warp, grid, full_grid,
+                                                               max(self.maximum_iteration_count, 1), packed_global, comm))
+        if self.replicated_levels == 0:
+            warp_at_start = warp.clone()
+            outcome = run(None)
+            if outcome is not None:
+                return outcome
+            warp.copy_(warp_at_start)
+            self.replicated_levels = 1
+        self.replicated_levels += 1
+        return run(comm.all_gather_owned(packed))
+
+    def _optimize_level_eager(self, lv):
+        """one foreign call per launch, check_interval iterations (one, under a hook) per host synchronisation.  Returns
+        the outcome -- or None: the warp of a slab level left the halo of its local packed field"""
+        max_it, hook, comm = self.maximum_iteration_count, self.iteration_hook, lv.comm
+        log, snapshots, it, n_exec = [], [], 0, 0
         while it < max_it:
-            batch = 1 if hooked else min(self.check_interval, max_it - it)
+            batch = 1 if hook is not None else min(self.check_interval, max_it - it)
             for i in range(it, it + batch):
                 if self.collect_iteration_data:
-                    # telemetry (cpp LoggingParameters.collect_per_level_iteration_data): the two gradient terms
-                    # the reference hands to its visualiser (hierarchical_optimizer2d.py:196,202,242-245) are
-                    # produced by two extra launches of the same kernel on the pre-update warp
-                    gate = lv.launcher.gates[i - 1] if i > 0 else None
-                    d_snap = torch.zeros_like(warp)
-                    gathered = packed if packed_global is None else packed_global
-                    wide = (0, 0, 0, 0) if packed_global is None else (0, 0, int(packed_global.shape[0]), 0)
-                    dev.hier_iteration(gathered, canonical, warp, None, d_snap, grid,
-                                       _lib.HierParams(1.0, 0.0, 0.0, 0, 0, 0, *wide), gate, records, i)
-                    t_snap = None
-                    if tik:
-                        t_snap = torch.zeros_like(warp)  # = laplace(previous gradient): 0*gd - (-1)*lap
-                        dev.hier_iteration(gathered, canonical, warp, lv.F[i % 2], t_snap, grid,
-                                           _lib.HierParams(0.0, -1.0, 0.0, 1, 0, 0, *wide), gate, records, i)
-                    snapshots.append([None, d_snap, t_snap])
-                defer = lv.defer_max and not slab and not hooked and not self.collect_iteration_data
-                self._enqueue(lv, i, i - 1 if i > 0 else None, i % 2, comm, defer_max=defer and i + 1 < it + batch,
-                              prev_deferred=defer and i > it)
+                    snapshots.append(self._term_snapshots(lv, i))
+                self._enqueue(lv, i, i - 1 if i > 0 else None, i % 2, defer_max=lv.defer_max and i + 1 < it + batch,
+                              prev_deferred=lv.defer_max and i > it)
                 if self.collect_iteration_data:
-                    snapshots[-1][0] = warp.clone()
-                if slab:
-                    if tik:  # the next iteration's Laplacian reads one slice of this gradient on either side
+                    snapshots[-1][0] = lv.warp.clone()
+                if comm is not None:
+                    if self.tikhonov_term_enabled:  # the next Laplacian reads one slice of this gradient on either side
                         comm.exchange_halos([lv.F[(i + 1) % 2]], width=1)
                     if i + 1 < max_it:
-                        comm.reduce_max(records, i)  # the next iteration's gate tests the GLOBAL max
-            if slab:
-                comm.reduce_records(records, it, it + batch)
-            it += batch
-            dec = dev.decode_records(dev.records_to_host(records[:it]))  # the only host sync of the batch
-            n_exec = int(dec["executed"].sum())
-            if slab and packed_global is None:
-                # the gather follows the cumulative warp: it must stay inside the halo of the static packed field.  When it
-                # does not, the reference does not stop either (hierarchical_optimizer2d.py:169-171 tests the update
-                # threshold only): every rank sees the same reduced maximum, so all of them together discard this level's
-                # iterations, replicate the level's packed field (SURVEY 8e: 5 x 512 MiB at 512^3 against 288 GB) and run
-                # the level again from the warp it started with -- the gather then never leaves the device
-                wz = warp[2][L.owned_local()].abs().max().reshape(1)
+                        comm.reduce_max(lv.records, i)  # the next iteration's gate tests the GLOBAL max
+            if comm is not None:
+                comm.reduce_records(lv.records, it, it + batch)
+            k_exec, ended = self._read_batch(lv.records[it:it + batch], log)
+            it, n_exec = it + batch, n_exec + k_exec
+            if comm is not None and lv.packed_global is None:
+                wz = lv.warp[2][comm.layout.owned_local()].abs().max().reshape(1)
                 comm.reduce_scalar_max(wz)
-                if not (float(wz.item()) < L.halo - 1):
-                    warp.copy_(warp_at_start)
-                    self.replicated_levels = 1
-                    return self.optimize_level(canonical, packed, warp, comm)
-            if hooked and n_exec == it:  # iteration it - 1 ran: its gradient is in the buffer the next one reads
+                if not (float(wz.item()) < comm.layout.halo - 1):
+                    return None
+            if hook is not None and k_exec == batch:  # iteration it - 1 ran: its gradient is in the buffer the next reads
                 g_now = lv.F[it % 2] if lv.F else lv.report_g
-                own = (slice(None), L.owned_local()) if slab else (slice(None),)
-                self.iteration_hook(len(self.level_results), it - 1, dev.interleave(warp[own].contiguous()),
-                                    dev.interleave(g_now[own].contiguous()), float(dec["max_value"][it - 1]))
-            if n_exec < it or dec["max_value"][n_exec - 1] < np.float32(thr):
+                own = (slice(None), comm.layout.owned_local()) if comm is not None else (slice(None),)
+                # (a watched level is never deferred: level_results holds every coarser level)
+                hook(len(self.level_results), it - 1, dev.interleave(lv.warp[own].contiguous()),
+                     dev.interleave(g_now[own].contiguous()), float(log[-1]["max_value"][-1]))
+            if ended:
                 break
-        if dec is None:  # maximum_iteration_count == 0: the reference's loop body never runs
-            dec = dev.decode_records(dev.records_to_host(records[:1]))
         if self.collect_iteration_data:
             self.iteration_data.append(snapshots[:n_exec])  # snapshots of gated (not executed) launches are dropped
-        self._finish_level(lv, n_exec, dec, L)
-        return warp
+        # iteration n_exec - 1 wrote F[((n_exec - 1) + 1) % 2]
+        return _LevelOutcome(lv.canonical, lv.packed, lv.warp, lv.grid, lv.F[n_exec % 2] if lv.F and n_exec else lv.report_g,
+                             self._merged(log), n_exec, packed_global=lv.packed_global, comm=comm)
+
+    def _term_snapshots(self, lv, i):
+        """telemetry (cpp LoggingParameters.collect_per_level_iteration_data): the two gradient terms the reference hands
+        to its visualiser (hierarchical_optimizer2d.py:196,202,242-245) are produced by two extra launches of the same
+        kernel on the pre-update warp: [the warp after the iteration (the caller's to fill in), data term, Tikhonov term]"""
+        gate = lv.launcher.gates[i - 1] if i > 0 else None
+        gathered = lv.packed if lv.packed_global is None else lv.packed_global
+        wide = (0, 0, 0, 0) if lv.packed_global is None else (0, 0, int(lv.packed_global.shape[0]), 0)
+        terms = [(None, _lib.HierParams(1.0, 0.0, 0.0, 0, 0, 0, *wide))]
+        if self.tikhonov_term_enabled:  # laplace(previous gradient) = 0*gd - (-1)*lap
+            terms.append((lv.F[i % 2], _lib.HierParams(0.0, -1.0, 0.0, 1, 0, 0, *wide)))
+        snapshots = [None, None, None]
+        for k, (g_prev, params) in enumerate(terms, 1):
+            snapshots[k] = torch.zeros_like(lv.warp)
+            dev.hier_iteration(gathered, lv.canonical, lv.warp, g_prev, snapshots[k], lv.grid, params, gate, lv.records, i)
+        return snapshots
 
     # ------------------------------------------------------------------------------------------------
     BLOCKED_ITERATIONS_PER_LAUNCH = 8
@@ -504,9 +446,9 @@ class HierarchicalEngine:
         records = dev.new_records(max_it, canonical.device)
         params = _lib.HierParams(float(self.data_term_amplifier), float(self.tikhonov_strength), float(self.rate),
                                  int(bool(self.tikhonov_term_enabled)), int(n_taps == 0), 0)
-        p_packed, p_canonical = dev._ptr(packed, 4 * n, "packed live"), dev._ptr(canonical, n, "canonical")
-        p_warp = [dev._ptr(w, 2 * n, "warp") for w in warps]
-        p_g = [dev._ptr(g, 2 * n, "gradient") for g in F]
+        ptr = dev.checked_pointer
+        p_packed, p_canonical = ptr(packed, 4 * n, "packed live"), ptr(canonical, n, "canonical")
+        p_warp, p_g = [ptr(w, 2 * n, "warp") for w in warps], [ptr(g, 2 * n, "gradient") for g in F]
 
         def run(first, record_ptr, iterations, threshold):  # launches reading pair `first` first
             _lib.check(_lib.lib.lsf_hier_level_run_2d(
@@ -516,7 +458,7 @@ class HierarchicalEngine:
 
         run(0, ctypes.c_void_p(records.data_ptr()), max_it, float(thr) if gated else 0.0)
         launches = (max_it + K - 1) // K
-        dec = None
+        dec = n_exec = None
         if gated:
             dec = dev.decode_records(dev.records_to_host(records[:max_it]))
             ran = int(dec["executed"].sum())  # whole launches: a multiple of K, or every iteration
@@ -529,49 +471,13 @@ class HierarchicalEngine:
             launches = last + 1
         if launches % 2:
             warp.copy_(warps[1])
-        lv = HierarchicalEngine._Level()
-        lv.canonical, lv.packed, lv.warp, lv.grid, lv.full_grid, lv.dims = canonical, packed, warp, grid, grid, 2
-        final = F[launches % 2]
-        lv.F = [final, final]  # _final_gradient reads F[n_exec % 2]
-        lv.report_g = None
         self.last_call.blocked_levels += 1
-        if gated:
-            # (the level's results are made of `dec` at the end of optimize(): the card has nothing queued right now)
-            self._pending_levels.append((lv, dec, n_exec))
-            self.level_results.append(None)
-            return warp
-        # nothing on the host depends on this level's records (a fixed count): they are read with the other levels' at the
-        # end of optimize() -- ONE synchronisation per call instead of one per level, with the next level's launches
-        # already queued behind this one's
-        self._pending_levels.append((lv, records, max_it))
-        self.level_results.append(None)
-        return warp
-
-    def _finish_pending_levels(self):
-        """the records of the levels _optimize_level_blocked left unread: one transfer, then every level's results"""
-        pending, self._pending_levels = self._pending_levels, []
-        if not pending:
-            return
-        if isinstance(pending[0][1], dict):  # levels with a stop test: their records were read level by level
-            first = self.level_results.index(None)
-            self.level_results = self.level_results[:first]
-            for lv, dec, n_exec in pending:
-                self._finish_level(lv, n_exec, dec)
-            return
-        used = torch.cat([dev.slot_view(records)[:n, :, :dev.USED_SLOT_WORDS].reshape(-1) for _, records, n in pending])
-        host = dev.pinned_scratch("level records", used.numel(), torch.int64)[:used.numel()]
-        host.copy_(used, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        flat, at = host.numpy(), 0
-        slots = dev.slot_view(pending[0][1]).shape[1]
-        first = self.level_results.index(None)
-        results, self.level_results = self.level_results, self.level_results[:first]
-        for lv, records, n in pending:
-            words = n * slots * dev.USED_SLOT_WORDS
-            dec = dev.decode_records(flat[at:at + words].reshape(n, slots, dev.USED_SLOT_WORDS).copy())
-            at += words
-            self._finish_level(lv, int(dec["executed"].sum()), dec)
-        assert len(self.level_results) == len(results)
+        # (what the per-iteration drivers leave: with neither term there are no F buffers, and a gradient only for reports)
+        keep = self.tikhonov_term_enabled or self.gradient_kernel_enabled or self.collect_reports
+        # deferred: results and reports are made at the end of optimize().  Nothing on the host depends on the records of a
+        # fixed count: they are read with the other levels' -- ONE synchronisation per call, not one per level
+        return _LevelOutcome(canonical, packed, warp, grid, F[launches % 2] if keep else None, dec, n_exec,
+                             records=records, deferred=True)
 
     def _optimize_level_graph(self, canonical, packed, warp):
         """launch-bound levels: K iterations (K even) are captured once per level shape as a HIP graph over persistent
@@ -579,7 +485,6 @@ class HierarchicalEngine:
         graph itself re-zeroes, slot K keeps the previous batch's last record for the first gate of the next batch, so
         iteration counts and results are exactly those of the eager path (tests demand equality)."""
         max_it = self.maximum_iteration_count
-        thr = np.float32(self.maximum_warp_update_threshold)
         key = self._graph_key(canonical)
         K = key[2]
         entry = self._graphs.get(key)
@@ -617,34 +522,55 @@ class HierarchicalEngine:
             t.zero_()
         lv.records.zero_()
         dev.set_record_max(lv.records, K - 1, HierarchicalEngine.OPEN_RECORD)
-        done, n_exec, converged = 0, 0, False
-        parts = []
-        while done + K <= max_it and not converged:
+        log, done, n_exec, ended = [], 0, 0, False
+        while done + K <= max_it and not ended:
             graph.replay()
-            dec = dev.decode_records(dev.records_to_host(lv.records[:K]))  # host sync once per K iterations
-            k_exec = int(dec["executed"].sum())
-            parts.append({k: v[:k_exec].copy() for k, v in dec.items()})
-            n_exec += k_exec
-            done += K
-            converged = k_exec < K or dec["max_value"][k_exec - 1] < thr
+            k_exec, ended = self._read_batch(lv.records[:K], log)  # host sync once per K iterations
+            done, n_exec = done + K, n_exec + k_exec
         rest = max_it - done
-        if not converged and rest > 0:  # the remainder of a limit that is not a multiple of K: eager, same buffers
-            rem = self._make_level(lv.canonical, lv.packed, lv.warp, lv.grid, lv.full_grid, rest + 1)
-            rem.F, rem.S, rem.report_g = lv.F, lv.S, lv.report_g
-            rem.p_F, rem.p_S, rem.p_report = lv.p_F, lv.p_S, lv.p_report
-            rem.records[0].copy_(lv.records[K - 1])
+        if not ended and rest > 0:
+            # the remainder of a limit that is not a multiple of K (rest < K): eagerly on the captured level, its record
+            # ring started afresh -- slot 0 the last record, iteration t in slot t + 1
+            lv.records[0].copy_(lv.records[K - 1])
+            lv.records[1:rest + 1].zero_()
             for t in range(rest):
-                self._enqueue(rem, t + 1, t, (done + t) % 2)
-            dec = dev.decode_records(dev.records_to_host(rem.records[1:rest + 1]))
-            k_exec = int(dec["executed"].sum())
-            parts.append({k: v[:k_exec].copy() for k, v in dec.items()})
-            n_exec += k_exec
-        merged = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]} if parts else \
-            dev.decode_records(np.zeros((1, dev.RECORD_WORDS), np.int64))
+                self._enqueue(lv, t + 1, t, (done + t) % 2)
+            n_exec += self._read_batch(lv.records[1:rest + 1], log)[0]
         warp.copy_(lv.warp)
-        final_level = lv
-        self._finish_level(final_level, n_exec, merged)
-        # _finish_level looked at the persistent buffers; hand out copies so that the next optimize() cannot alias them
-        if self.last_gradient is not None:
-            self.last_gradient = self.last_gradient.clone()
-        return warp
+        # (the level's buffers are persistent: the caller's fields and a copy of the gradient, which the next call cannot alias)
+        final = lv.F[n_exec % 2] if lv.F and n_exec else lv.report_g
+        return _LevelOutcome(canonical, packed, warp, lv.grid, None if final is None else final.clone(),
+                             self._merged(log), n_exec)
+
+
+class _Level:
+    """What the per-iteration drivers (eager, graph) enqueue a level's iterations from; _make_level makes it.  The fields
+    (packed_global: the whole level's packed live field when a slab level runs on a replicated one), the launch grid and
+    the level's SlabComm or None; the parameter block; the gradient buffers F ([] with neither Tikhonov term nor gradient
+    kernel), the filter's scratch buffers S ([] without a kernel), report_g for the gradient when there is no F and
+    reports are collected; the records and their launcher (dev.IterationLauncher); the filter plan (_filter_plan); the
+    checked device pointers; the deferred maximum (_make_level): whether, and its kernel's parameters and open gates."""
+    __slots__ = ("canonical", "packed", "packed_global", "warp", "grid", "comm", "params", "params_ref", "F", "S",
+                 "report_g", "records", "launcher", "steps", "moves_warp", "p_packed", "p_canon", "p_warp", "p_F", "p_S",
+                 "p_report", "defer_max", "prevmax", "prevmax_ref", "open_gates", "open_gate_refs")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:  # every field, every time
+            setattr(self, name, fields.pop(name))
+        assert not fields, fields
+
+
+@dataclass(eq=False)
+class _LevelOutcome:
+    """what a driver leaves of a level, and all that _finish_level looks at"""
+    canonical: torch.Tensor
+    packed: torch.Tensor
+    warp: torch.Tensor
+    grid: object
+    gradient: object       # the last executed iteration's (filtered) gradient, or None
+    decoded: object        # dev.decode_records of the level's records; None: still on the card, in `records`
+    n_exec: object         # executed iterations; None until the records are read
+    records: object = None
+    packed_global: object = None
+    comm: object = None    # the level's SlabComm (z-slab runs)
+    deferred: bool = False  # results are made at the end of optimize() (blocked levels), not when the level ends

@@ -36,7 +36,8 @@ def _same(a, b):
         assert np.array_equal(np.float32(ma), np.float32(mb))
     for ra, rb in zip(oa.engine.level_results, ob.engine.level_results):
         assert list(ra.argmax) == list(rb.argmax)
-    assert torch.equal(oa.engine.last_gradient, ob.engine.last_gradient), "the last iteration's gradient"
+    ga, gb = oa.engine.last_gradient, ob.engine.last_gradient  # (None with neither Tikhonov term nor gradient kernel)
+    assert (ga is None) == (gb is None) and (ga is None or torch.equal(ga, gb)), "the last iteration's gradient"
 
 
 # iteration counts: a multiple of 8, a remainder, fewer than one launch's worth, one
@@ -139,6 +140,24 @@ def test_blocked_levels_without_the_tikhonov_term(lsf, n_taps, threshold):
     assert opt.get_per_level_iteration_counts() == o.per_level_iteration_counts
     for mine, theirs in zip(opt.get_per_level_maximum_updates(), o.per_level_max_updates):
         assert np.array_equal(np.float32(mine), np.float32(theirs))
+
+
+@pytest.mark.parametrize("reports", [False, True])
+@pytest.mark.parametrize("threshold", [0.0, 0.03])
+def test_the_data_term_alone_leaves_the_same_engine_state(lsf, reports, threshold):
+    """neither Tikhonov term nor gradient kernel: the per-iteration path keeps no gradient buffers and leaves
+    engine.last_gradient None -- or, when convergence reports are collected, the last iteration's gradient; the blocked
+    levels leave the same, with the same level_results (counts, maxima, arg-max), reports and warp"""
+    canonical, live = O.sphere_pair(128, d=2)
+    kw = dict(tikhonov_term_enabled=False, gradient_kernel_enabled=False, maximum_chunk_size=8, rate=0.2,
+              maximum_iteration_count=19, maximum_warp_update_threshold=threshold,
+              logging_parameters=lsf.HierarchicalOptimizer2d.LoggingParameters(collect_per_level_convergence_reports=reports))
+    a, b = _run(lsf, canonical, live, True, **kw), _run(lsf, canonical, live, False, **kw)
+    _same(a, b)
+    assert (a[0].engine.last_gradient is None) == (not reports)
+    assert float(np.abs(a[1]).max()) > 1e-3
+    ra, rb = a[0].get_per_level_convergence_reports(), b[0].get_per_level_convergence_reports()
+    assert len(ra) == len(rb) == (4 if reports else 0) and all(x == y for x, y in zip(ra, rb)), (ra, rb)
 
 
 def test_energy_printouts_keep_the_per_iteration_path(lsf):
