@@ -1018,6 +1018,52 @@ int lsf_fusion_integrate_volume(float *tsdf, float *weight, const float *live, d
 int lsf_fusion_integrate_depth(float *tsdf, float *weight, const void *depth_image, double *record, void *scratch,
                                const lsf_fusion_params *params, void *stream);
 
+/* ---- weighted depth-mode fusion with free-space carving ------------------------------------------------------------
+ * The rule is INTEGRATION.md section 3, "Weighted fusion and carving".  Voxel, pixel (ix, iy), scaled depth and live
+ * value l are lsf_fusion_integrate_depth's.  A voxel has a valid pixel when it lies in front of the camera, projects into
+ * the image and the scaled depth there is > 0 or NaN; tsdf.default_value is not used.  With a valid pixel the voxel is in
+ * band when -1 < l < 1 and, with carve != 0, carved when l == 1 exactly (the seen free space in front of the band), which
+ * fuses l = 1.  Its weight is w_eff = weight * pixel_weight[iy][ix], one float32 multiply (weight itself without an
+ * image); when w_eff is not finite and > 0 the voxel is left alone and counted.  Otherwise W1 = W + w_eff,
+ * tsdf = (W t + w_eff l) / W1, weight = min(W1, max_weight) as above.  Every other voxel keeps its tsdf and weight bit
+ * for bit.  The record: [0] fused (in-band updates), [1] first_seen (updates of either kind whose weight was 0), [2] sum
+ * and [3] max of |t1 - t| over updates of either kind, [4] carved, [5] weight_rejected, [6..7] 0; summed as above, reruns
+ * bit-identical.  With carve == 0 and no image, tsdf, weight and record [0..3] equal lsf_fusion_integrate_depth's bit for
+ * bit whenever default_value is not strictly inside (-1, 1). */
+typedef struct lsf_fusion_weighted_params {
+    lsf_fusion_params fusion;  /* as lsf_fusion_integrate_depth reads it */
+    int32_t carve;             /* 0: in-band voxels only; else also fuse +1 where l == 1 with a valid pixel */
+    int32_t has_pixel_weight;  /* 0: pixel_weight is NULL; else it is given */
+} lsf_fusion_weighted_params;
+/* per-workgroup partials: fused, first_seen, sum, max, carved, weight_rejected */
+#define LSF_FUSION_WEIGHTED_SCRATCH_BYTES (LSF_FUSION_MAX_BLOCKS * 6 * 8)
+
+/* tsdf, weight, depth_image, record: as lsf_fusion_integrate_depth.  pixel_weight: NULL, or DEVICE float32
+ * [image_height][image_width], overlapping neither tsdf nor weight; scratch: DEVICE,
+ * LSF_FUSION_WEIGHTED_SCRATCH_BYTES.  Two launches, no host synchronisation. */
+int lsf_fusion_integrate_depth_weighted(float *tsdf, float *weight, const void *depth_image, const float *pixel_weight,
+                                        double *record, void *scratch, const lsf_fusion_weighted_params *params,
+                                        void *stream);
+
+/* ---- a per-pixel confidence image for weighted fusion ----------------------------------------------------------------
+ * c(u, v) = |n . r| min(1, (reference_depth / z)^2): the cosine between the pixel's unit ray r and its normal n, times
+ * the inverse of the sensor's axial noise growth beyond reference_depth.  Every step is one float64 operation, in this
+ * order, rounded once to float32 at the end ("Depth confidence"):
+ *   x = (u - cx) / fx,  y = (v - cy) / fy,  len = sqrt((x x + y y) + 1),  dot = (n_x x + n_y y) + n_z,
+ *   a = |dot| / len,  q = reference_depth / z,  s = q q,  m = s < 1 ? s : 1,  c = a m
+ * c is 0 where z is not > 0 (NaN included) or where n is lsf_depth_pyramid's "no normal" value, all three components 0. */
+typedef struct lsf_depth_confidence_params {
+    double fx, fy, cx, cy;     /* intrinsics, pixels; finite, fx and fy non-zero */
+    double reference_depth;    /* metres, finite and > 0 */
+    int32_t height, width;     /* image extents, >= 1 each, at most 2^31 - 1 pixels */
+} lsf_depth_confidence_params;
+
+/* depth: DEVICE float32 [height][width], metres; normals: DEVICE float32 [height][width][3], camera coordinates (level 0
+ * of lsf_depth_pyramid's outputs); confidence_out: DEVICE float32 [height][width], overlapping neither input.  One lane
+ * per pixel, one launch, no host synchronisation. */
+int lsf_depth_confidence(const float *depth, const float *normals, float *confidence_out,
+                         const lsf_depth_confidence_params *params, void *stream);
+
 /* ---- ray-casting the canonical TSDF into a depth (and normal) image -------------------------------------------------
  * The reference has no ray-caster; the arithmetic is this project's ("Ray-casting"), every
  * step one float64 operation.  The camera is the generator's: E = twist_vector_to_matrix3d of the float32-rounded

@@ -31,10 +31,10 @@ from .rigid_opt.sdf_2_sdf_optimizer2d import Sdf2SdfOptimizer2d
 from .rigid_opt.sdf_2_sdf_optimizer3d import Sdf2SdfOptimizer3d
 from .rigid_opt.projective_icp3d import ProjectiveIcp3d
 from . import fusion, mesh_io
-from .fusion import CanonicalVolume, SequenceFusion3d
+from .fusion import CanonicalVolume, DepthConfidence, SequenceFusion3d
 
 __all__ = ["HierarchicalOptimizer2d", "HierarchicalOptimizer3d", "SlavchevaOptimizer2d", "SlavchevaOptimizer3d",
            "ComputeMethod", "AdaptiveLearningRateMethod", "DataTermMethod", "SmoothingTermMethod",
            "generate_1d_sobolev_kernel", "data_term", "smoothing_term", "level_set_term", "rigid_opt",
            "transformation", "Sdf2SdfOptimizer2d", "Sdf2SdfOptimizer3d", "ProjectiveIcp3d", "fusion", "CanonicalVolume",
-           "SequenceFusion3d", "mesh_io"]
+           "SequenceFusion3d", "DepthConfidence", "mesh_io"]

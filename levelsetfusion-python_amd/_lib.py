@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "845b6f86b0b9638d"
+HEADER_ABI_HASH = "0ec1059400c2db73"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -202,6 +202,20 @@ class FusionParams(ctypes.Structure):
                 ("weight", ctypes.c_float), ("max_weight", ctypes.c_float), ("depth_dtype", ctypes.c_int32)]
 
 
+FUSION_WEIGHTED_SCRATCH_BYTES = FUSION_MAX_BLOCKS * 6 * 8
+
+
+class FusionWeightedParams(ctypes.Structure):
+    """lsf_fusion_weighted_params: weighted depth-mode fusion with carving (lsf_fusion_integrate_depth_weighted)"""
+    _fields_ = [("fusion", FusionParams), ("carve", ctypes.c_int32), ("has_pixel_weight", ctypes.c_int32)]
+
+
+class DepthConfidenceParams(ctypes.Structure):
+    """lsf_depth_confidence_params: the per-pixel confidence image (lsf_depth_confidence)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "reference_depth")] + \
+               [(n, ctypes.c_int32) for n in ("height", "width")]
+
+
 RAYCAST_STEPS_PER_VOXEL = 2
 RAYCAST_TILE = 16
 
@@ -370,6 +384,9 @@ PROTOTYPES = {
     "lsf_rigid3d_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(Rigid3dParams), _vp]),
     "lsf_fusion_integrate_volume": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
     "lsf_fusion_integrate_depth": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
+    "lsf_fusion_integrate_depth_weighted": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(FusionWeightedParams),
+                                                           _vp]),
+    "lsf_depth_confidence": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthConfidenceParams), _vp]),
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),

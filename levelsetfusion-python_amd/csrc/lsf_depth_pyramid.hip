@@ -130,11 +130,6 @@ __global__ __launch_bounds__(kBlock) void normals_kernel(const float* __restrict
     for (int c = 0; c < 3; ++c) normals[at * 3 + c] = (float)n[c];
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 unsigned blocks_of(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace

@@ -653,6 +653,14 @@ __host__ inline lsf_gate gate_or_open(const lsf_gate* gate) {
     return gate ? *gate : lsf_gate{nullptr, 0, 0.0f, 0.0f};
 }
 
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte: the aliasing check of the entry points.  A NULL
+// (optional) buffer or an empty range overlaps nothing.
+inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int launch_status() { return (int)hipGetLastError(); }

@@ -10,6 +10,10 @@
 // scratch; a finishing one-workgroup launch combines them in a fixed order (the sums by the trackers' butterfly,
 // wave_sum_xor in lsf_rigid_solve.h): no atomics, reruns are bit-identical.
 // -ffp-contract=off keeps W t + w l two roundings and an add, as numpy computes it.
+// lsf_fusion_integrate_depth_weighted is the DEPTH kernel with the weighted rule ("Weighted
+// fusion and carving"; tests/fusion_weighted_restatement.py): the same four voxels per lane, 16-byte accesses, grid and
+// finishing launch, with the pixel a voxel projects to (typed_tsdf_sample) selecting its weight from a float32 image,
+// +1 fused in the seen free space in front of the band, and six partials per workgroup instead of four.
 #include "lsf_device.h"
 #include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
@@ -18,10 +22,14 @@ using namespace lsf;
 
 namespace {
 
-constexpr int kParts = 4;  // fused, first_seen, sum |t1 - t|, max |t1 - t|
+constexpr int kParts = 4;   // fused, first_seen, sum |t1 - t|, max |t1 - t|
+constexpr int kWParts = 6;  // the weighted rule: those, carved, weight_rejected
+constexpr int kMaxPart = 3; // the one partial that is a maximum; every other is a sum
 constexpr int kMaxBlocks = LSF_FUSION_MAX_BLOCKS;
 constexpr int kRec = LSF_FUSION_RECORD_DOUBLES;
-static_assert(kRec >= kParts, "the record holds the four results");
+static_assert(kRec >= kWParts, "the record holds the results of either rule");
+static_assert(LSF_FUSION_SCRATCH_BYTES == kMaxBlocks * kParts * 8, "a workgroup's partials");
+static_assert(LSF_FUSION_WEIGHTED_SCRATCH_BYTES == kMaxBlocks * kWParts * 8, "a workgroup's partials");
 
 enum Source { VOLUME = 0, DEPTH = 1 };
 
@@ -42,6 +50,11 @@ struct Acc {
     float max;
 };
 
+struct WeightedAcc {
+    Acc a;
+    int carved, rejected;
+};
+
 // the rule at one voxel; true when the voxel was observed (and its tsdf and weight may have changed)
 __device__ inline bool fuse_voxel(float l, float& t, float& W, const FusionDev& p, Acc& a) {
     if (!(l > -1.0f && l < 1.0f)) return false;  // +-1 and NaN are not fused
@@ -52,6 +65,33 @@ __device__ inline bool fuse_voxel(float l, float& t, float& W, const FusionDev& 
     a.first += W == 0.0f ? 1 : 0;
     a.sum += (double)d;
     a.max = d > a.max ? d : a.max;
+    t = t1;
+    W = W1 > p.max_weight ? p.max_weight : W1;
+    return true;
+}
+
+// the weighted rule at one voxel.  s: what the voxel sees (typed_tsdf_sample); in band it is fused as fuse_voxel does,
+// at exactly +1 with a valid pixel it is carved (fused with l = 1) when carve is set; the weight is w times the pixel's
+// (one float32 multiply), and a weight that is not finite and > 0 leaves the voxel alone and is counted
+__device__ inline bool fuse_voxel_weighted(const TsdfSample& s, const float* __restrict__ pixel_weight, bool carve,
+                                           float& t, float& W, const FusionDev& p, WeightedAcc& acc) {
+    if (!s.valid) return false;
+    const float l = s.value;
+    const bool band = l > -1.0f && l < 1.0f;
+    if (!band && !(carve && l == 1.0f)) return false;
+    const float w = pixel_weight ? p.w * pixel_weight[s.pixel] : p.w;
+    if (!(w > 0.0f) || isinf(w)) {
+        acc.rejected += 1;
+        return false;
+    }
+    const float W1 = W + w;
+    const float t1 = (W * t + w * l) / W1;
+    const float d = fabsf(t1 - t);
+    acc.a.fused += band ? 1 : 0;
+    acc.carved += band ? 0 : 1;
+    acc.a.first += W == 0.0f ? 1 : 0;
+    acc.a.sum += (double)d;
+    acc.a.max = d > acc.a.max ? d : acc.a.max;
     t = t1;
     W = W1 > p.max_weight ? p.max_weight : W1;
     return true;
@@ -76,14 +116,21 @@ __device__ inline void store4(float* __restrict__ f, long long i, const float (&
     }
 }
 
-// the live value of voxel i (flat [z][y][x] index) under extrinsic e: lsf_rigid3d_gradient's generation
+// what voxel i (flat [z][y][x] index) sees under extrinsic e: lsf_rigid3d_gradient's generation
 template <typename DT, typename PT>
-__device__ inline float depth_voxel(const DT* __restrict__ depth, const FusionDev& p, const double* e, long long i) {
+__device__ inline TsdfSample depth_sample(const DT* __restrict__ depth, const FusionDev& p, const double* e,
+                                          long long i) {
     const long long row = i / p.nx;
     const int x = (int)(i - row * p.nx);
     const int z = (int)(row / p.ny);
     const int y = (int)(row - (long long)z * p.ny);
-    return typed_tsdf_voxel<3, double, PT, DT>(depth, p.t, e, x, y, z);
+    return typed_tsdf_sample<3, double, PT, DT>(depth, p.t, e, x, y, z);
+}
+
+// its live value alone
+template <typename DT, typename PT>
+__device__ inline float depth_voxel(const DT* __restrict__ depth, const FusionDev& p, const double* e, long long i) {
+    return depth_sample<DT, PT>(depth, p, e, i).value;
 }
 
 __device__ inline float wave_max(float v) {
@@ -96,20 +143,21 @@ __device__ inline float wave_max(float v) {
 }
 
 // the block's totals of v[] (counts and sum added, max taken) in a fixed order; they land in thread 0's v[]
-__device__ inline void block_combine(double (&v)[kParts], double (*red)[kParts]) {
+template <int N>
+__device__ inline void block_combine(double (&v)[N], double (*red)[N]) {
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = wave_sum_xor(v[c]);
-    v[3] = (double)wave_max((float)v[3]);
+    for (int c = 0; c < N; ++c) v[c] = c == kMaxPart ? (double)wave_max((float)v[c]) : wave_sum_xor(v[c]);
     if (lane == 0)
 #pragma unroll
-        for (int c = 0; c < kParts; ++c) red[wave][c] = v[c];
+        for (int c = 0; c < N; ++c) red[wave][c] = v[c];
     __syncthreads();
     if (threadIdx.x == 0)
         for (int q = 1; q < kBlock / kWave; ++q) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] += red[q][c];
-            v[3] = red[q][3] > v[3] ? red[q][3] : v[3];
+            for (int c = 0; c < N; ++c)
+                if (c == kMaxPart) v[c] = red[q][c] > v[c] ? red[q][c] : v[c];
+                else v[c] += red[q][c];
         }
 }
 
@@ -162,22 +210,71 @@ __global__ __launch_bounds__(kBlock) void fusion_kernel(float* __restrict__ tsdf
         for (int c = 0; c < kParts; ++c) scratch[(size_t)blockIdx.x * kParts + c] = v[c];
 }
 
+// the weighted rule on a depth image: fusion_kernel<DEPTH>'s walk, stores and partials with fuse_voxel_weighted
+template <typename DT, typename PT>
+__global__ __launch_bounds__(kBlock) void fusion_weighted_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
+                                                                 const DT* __restrict__ depth,
+                                                                 const float* __restrict__ pixel_weight,
+                                                                 double* __restrict__ scratch, FusionDev p, int carve) {
+    __shared__ double e[12];
+    __shared__ double red[kBlock / kWave][kWParts];
+    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
+    __syncthreads();
+    const bool aligned = p.aligned != 0, carving = carve != 0;
+    WeightedAcc a = {{0, 0, 0.0, 0.0f}, 0, 0};
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
+        const long long i = g * 4;
+        TsdfSample s[4];
+        float t[4], W[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = depth_sample<DT, PT>(depth, p, e, i + k);
+        load4(tsdf, i, t, aligned);
+        load4(weight, i, W, aligned);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) any = fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a) || any;
+        if (any) {  // a step without an updated voxel stores nothing
+            store4(tsdf, i, t, aligned);
+            store4(weight, i, W, aligned);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
+        for (long long i = p.groups * 4; i < p.n; ++i) {
+            float t = tsdf[i], W = weight[i];
+            if (fuse_voxel_weighted(depth_sample<DT, PT>(depth, p, e, i), pixel_weight, carving, t, W, p, a)) {
+                tsdf[i] = t;
+                weight[i] = W;
+            }
+        }
+    double v[kWParts] = {(double)a.a.fused, (double)a.a.first, a.a.sum, (double)a.a.max, (double)a.carved,
+                         (double)a.rejected};
+    block_combine(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < kWParts; ++c) scratch[(size_t)blockIdx.x * kWParts + c] = v[c];
+}
+
 // one workgroup: lane q combines partials q, q + kBlock, ... in order, then the block in a fixed order
+template <int N>
 __global__ __launch_bounds__(kBlock) void fusion_finish_kernel(const double* __restrict__ scratch,
                                                                double* __restrict__ record, int nblocks) {
-    __shared__ double red[kBlock / kWave][kParts];
-    double v[kParts] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = threadIdx.x; q < nblocks; q += kBlock) {
-        const double* s = scratch + (size_t)q * kParts;
+    __shared__ double red[kBlock / kWave][N];
+    double v[N];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] += s[c];
-        v[3] = s[3] > v[3] ? s[3] : v[3];
+    for (int c = 0; c < N; ++c) v[c] = 0.0;
+    for (int q = threadIdx.x; q < nblocks; q += kBlock) {
+        const double* s = scratch + (size_t)q * N;
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            if (c == kMaxPart) v[c] = s[c] > v[c] ? s[c] : v[c];
+            else v[c] += s[c];
     }
     block_combine(v, red);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int c = 0; c < kParts; ++c) record[c] = v[c];
-        for (int c = kParts; c < kRec; ++c) record[c] = 0.0;
+        for (int c = 0; c < N; ++c) record[c] = v[c];
+        for (int c = N; c < kRec; ++c) record[c] = 0.0;
     }
 }
 
@@ -207,7 +304,19 @@ int launch(float* tsdf, float* weight, const float* live, const void* depth, dou
     hipLaunchKernelGGL((fusion_kernel<SOURCE, DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, live,
                        reinterpret_cast<const DT*>(depth), scratch, p);
     if (int e = launch_status()) return e;
-    hipLaunchKernelGGL(fusion_finish_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record, p.nblocks);
+    hipLaunchKernelGGL(fusion_finish_kernel<kParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
+                       p.nblocks);
+    return launch_status();
+}
+
+template <typename DT, typename PT>
+int launch_weighted(float* tsdf, float* weight, const void* depth, const float* pixel_weight, double* record,
+                    double* scratch, const FusionDev& p, int carve, hipStream_t s) {
+    hipLaunchKernelGGL((fusion_weighted_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight,
+                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(fusion_finish_kernel<kWParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
+                       p.nblocks);
     return launch_status();
 }
 
@@ -245,5 +354,31 @@ extern "C" int lsf_fusion_integrate_depth(float* tsdf, float* weight, const void
     double* sc = reinterpret_cast<double*>(scratch);
     return dispatch_typed(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
         return launch<DEPTH, decltype(dt), decltype(pt)>(tsdf, weight, nullptr, depth_image, record, sc, p, s);
+    });
+}
+
+extern "C" int lsf_fusion_integrate_depth_weighted(float* tsdf, float* weight, const void* depth_image,
+                                                   const float* pixel_weight, double* record, void* scratch,
+                                                   const lsf_fusion_weighted_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!params) return LSF_ERR_BAD_ARGUMENT;
+    const lsf_fusion_params* f = &params->fusion;
+    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
+    FusionDev p;
+    if (int e = convert(f, p)) return e;
+    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
+    if ((params->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    if (pixel_weight) {
+        const size_t image = (size_t)f->tsdf.image_width * f->tsdf.image_height * 4, model = (size_t)p.n * 4;
+        if (overlaps(pixel_weight, image, tsdf, model) || overlaps(pixel_weight, image, weight, model))
+            return LSF_ERR_BAD_ARGUMENT;
+    }
+    p.aligned = aligned16(tsdf) && aligned16(weight);
+    hipStream_t s = as_stream(stream);
+    double* sc = reinterpret_cast<double*>(scratch);
+    const int carve = params->carve != 0;
+    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch_weighted<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p,
+                                                           carve, s);
     });
 }

@@ -312,12 +312,6 @@ int convert(const lsf_mesh_params* q, MeshDev& p) {
     return 0;
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 // no output overlaps an input or another output
 template <int NI, int NO>
 bool any_alias(const void* const (&ins)[NI], const size_t (&in_bytes)[NI], const void* const (&outs)[NO],

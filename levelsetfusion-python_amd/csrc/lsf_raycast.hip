@@ -199,12 +199,6 @@ int convert(const lsf_raycast_params* q, bool with_fallback, RayDev& p) {
     return 0;
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 template <typename DT>
 int launch(const Volume& vol, const void* fallback, float* depth_out, float* normals_out, uint64_t* hits,
            const RayDev& p, hipStream_t s) {

@@ -1,8 +1,9 @@
 // Nearest-pixel TSDF value of one voxel on the typed inputs of lsf_tsdf_generate_nearest_typed (reference
 // tsdf/generation.py:130-207, :356-437; tsdf/common.py:34-47): uint16 / float32 / float64 depth, fractional array
 // offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip, the live-field stages of lsf_rigid.hip
-// and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip), as is the host-side setup at the end of this file
-// (lsf_tsdf_params -> TypedTsdf, the depth-dtype and image checks, the (depth dtype, intrinsics dtype) dispatch).
+// and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip; the weighted rule also reads the pixel a voxel projects
+// to, typed_tsdf_sample), as is the host-side setup at the end of this file (lsf_tsdf_params -> TypedTsdf, the
+// depth-dtype and image checks, the (depth dtype, intrinsics dtype) dispatch).
 // The dtypes are those numpy >= 2 gives the reference's expressions (oracle: tests/rigid_restatement.py):
 //   voxel point     ((index + offset) * voxel_size) in float64, rounded to float32 (np.array(..., dtype=float32))
 //   camera point    extrinsic.dot(point): float32 or float64 as the extrinsic, ((e0 x + e1 y) + e2 z) + e3
@@ -41,27 +42,45 @@ __device__ inline long long typed_project(Q f, Q pc, Q z, Q c) {
     return (long long)v;
 }
 
+// what a voxel sees of the depth image: its live value, and the pixel it projects to.  valid: the voxel lies in front of
+// the camera, projects into the image and its pixel's scaled depth is > 0 or NaN (value is then not default_value, and
+// pixel = iy * width + ix); otherwise value is default_value and pixel is -1.
+struct TsdfSample {
+    float value;
+    long long pixel;
+    bool valid;
+};
+
 // D = 2: field[y][x], x from the x index, the depth axis from the y index, y_voxel = 0, depth row p.image_y.
 // D = 3: field[z][y][x].  E = float or double: the extrinsic's dtype (e: first three rows, row-major); P = the
 // intrinsic matrix's dtype; DT = the depth image's element type.
 template <int D, typename E, typename P, typename DT>
-__device__ inline float typed_tsdf_voxel(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x, int y,
-                                         int z) {
+__device__ inline TsdfSample typed_tsdf_sample(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x,
+                                               int y, int z) {
     using Q = decltype(E() + P());
+    const TsdfSample none = {p.default_value, -1, false};
     const float xv = (float)(((double)x + p.off[0]) * p.voxel_size);
     const float yv = D == 3 ? (float)(((double)y + p.off[1]) * p.voxel_size) : 0.0f;
     const float zv = (float)(((double)(D == 3 ? z : y) + p.off[2]) * p.voxel_size);
     const E pcx = ((e[0] * (E)xv + e[1] * (E)yv) + e[2] * (E)zv) + e[3] * (E)1;
     const E pcy = ((e[4] * (E)xv + e[5] * (E)yv) + e[6] * (E)zv) + e[7] * (E)1;
     const E pcz = ((e[8] * (E)xv + e[9] * (E)yv) + e[10] * (E)zv) + e[11] * (E)1;
-    if (!(pcz > (E)0)) return p.default_value;
+    if (!(pcz > (E)0)) return none;
     const long long ix = typed_project<Q>((Q)(P)p.fx, (Q)pcx, (Q)pcz, (Q)(P)p.cx);
     const long long iy = D == 3 ? typed_project<Q>((Q)(P)p.fy, (Q)pcy, (Q)pcz, (Q)(P)p.cy) : (long long)p.image_y;
-    if (ix < 0 || ix >= p.width || iy < 0 || iy >= p.height) return p.default_value;
-    const auto d = scaled_depth(depth, iy * p.width + ix, p.depth_unit_ratio);
-    if (d <= 0) return p.default_value;  // NaN goes on, as in the reference
+    if (ix < 0 || ix >= p.width || iy < 0 || iy >= p.height) return none;
+    const long long pixel = iy * p.width + ix;
+    const auto d = scaled_depth(depth, pixel, p.depth_unit_ratio);
+    if (d <= 0) return none;  // NaN goes on, as in the reference
     using S = decltype(d + pcz);
-    return typed_tsdf_value<S>((S)d - (S)pcz, p.half_width);
+    return {typed_tsdf_value<S>((S)d - (S)pcz, p.half_width), pixel, true};
+}
+
+// the live value alone: what the generator, the trackers and unweighted fusion read
+template <int D, typename E, typename P, typename DT>
+__device__ inline float typed_tsdf_voxel(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x, int y,
+                                         int z) {
+    return typed_tsdf_sample<D, E, P, DT>(depth, p, e, x, y, z).value;
 }
 
 // cv2.Rodrigues of a float64 rotation vector (math_utils/transformation.py::rodrigues), row-major

@@ -1,7 +1,7 @@
 """Torch-facing wrapper of the fusion entry points (include/lsf_hip.h: lsf_fusion_integrate_volume,
-lsf_fusion_integrate_depth).  Every argument is checked on the host before a launch; a call enqueues two launches and
-returns the record as a device tensor without waiting for it -- the caller decides when to copy it back.  The public
-interface is fusion.CanonicalVolume / fusion.SequenceFusion3d."""
+lsf_fusion_integrate_depth, lsf_fusion_integrate_depth_weighted).  Every argument is checked on the host before a
+launch; a call enqueues two launches and returns the record as a device tensor without waiting for it -- the caller
+decides when to copy it back.  The public interface is fusion.CanonicalVolume / fusion.SequenceFusion3d."""
 import ctypes
 import math
 
@@ -9,13 +9,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FusionParams, check, lib
+from ._lib import FusionParams, FusionWeightedParams, check, lib
 from .device_core import require_gpu, stream_ptr
 from .device_rigid import _tsdf3d, twist6
 from .tsdf.generation import offsets_of
 
 RECORD = _lib.FUSION_RECORD_DOUBLES
 RECORD_FIELDS = ("fused", "first_seen", "sum_abs_change", "max_abs_change")
+WEIGHTED_RECORD_FIELDS = RECORD_FIELDS + ("carved", "weight_rejected")
 
 
 def fusion_weights(weight, max_weight):
@@ -77,9 +78,13 @@ def _params(shape, weight, max_weight):
     return p
 
 
-def _launch(fn, name, tsdf, weight, source, p, record):
+def _record_and_scratch(tsdf, record, scratch_bytes):
     record = torch.empty(RECORD, dtype=torch.float64, device=tsdf.device) if record is None else record
-    scratch = torch.empty(_lib.FUSION_SCRATCH_BYTES // 8, dtype=torch.float64, device=tsdf.device)
+    return record, torch.empty(scratch_bytes // 8, dtype=torch.float64, device=tsdf.device)
+
+
+def _launch(fn, name, tsdf, weight, source, p, record):
+    record, scratch = _record_and_scratch(tsdf, record, _lib.FUSION_SCRATCH_BYTES)
     check(fn(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(source.data_ptr()),
              ctypes.c_void_p(record.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()),
           name)
@@ -95,12 +100,9 @@ def integrate_volume(tsdf, weight, live, w=1.0, max_weight=math.inf, record=None
     return _launch(lib.lsf_fusion_integrate_volume, "lsf_fusion_integrate_volume", tsdf, weight, live, p, record)
 
 
-def integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
-                    narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, default_value=1, record=None):
-    """generate the live volume of the device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*) under
-    twist exactly as device_rigid.live_and_gradient_3d does, and fuse it into the (Z, Y, X) model in the same pass;
-    returns the record as integrate_volume does"""
-    require_gpu()
+def _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                  narrow_band_width_voxels, w, max_weight, default_value):
+    """the checks of a depth-mode call and its lsf_fusion_params"""
     check_model(tsdf, weight)
     if tsdf.dim() != 3:
         raise ValueError("depth mode fuses a 3-D (Z, Y, X) volume, got shape %s" % (tuple(tsdf.shape),))
@@ -116,7 +118,59 @@ def integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist
     p.twist[:] = list(twist6(twist))
     p.array_offset[:] = list(offsets_of(array_offset))
     p.depth_dtype = int(depth_code)
+    return p
+
+
+def integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                    narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, default_value=1, record=None):
+    """generate the live volume of the device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*) under
+    twist exactly as device_rigid.live_and_gradient_3d does, and fuse it into the (Z, Y, X) model in the same pass;
+    returns the record as integrate_volume does"""
+    require_gpu()
+    p = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                      narrow_band_width_voxels, w, max_weight, default_value)
     return _launch(lib.lsf_fusion_integrate_depth, "lsf_fusion_integrate_depth", tsdf, weight, depth, p, record)
+
+
+def check_pixel_weight(pixel_weight, depth, tsdf, weight):
+    """a weight image: a float32 contiguous tensor on the model's device, of the depth image's shape, aliasing neither
+    the model nor the depth image"""
+    if not isinstance(pixel_weight, torch.Tensor):
+        raise TypeError("pixel_weight must be a torch tensor, got %s" % type(pixel_weight).__name__)
+    if pixel_weight.dtype != torch.float32:
+        raise ValueError("pixel_weight must be float32, got %s" % pixel_weight.dtype)
+    if pixel_weight.device != tsdf.device:
+        raise ValueError("pixel_weight is on %s, tsdf on %s: all buffers must be on one device"
+                         % (pixel_weight.device, tsdf.device))
+    if not pixel_weight.is_contiguous():
+        raise ValueError("pixel_weight must be contiguous")
+    if tuple(pixel_weight.shape) != tuple(depth.shape):
+        raise ValueError("pixel_weight has shape %s, the depth image %s: they must have one shape"
+                         % (tuple(pixel_weight.shape), tuple(depth.shape)))
+    if _overlap(pixel_weight, tsdf) or _overlap(pixel_weight, weight) or _overlap(pixel_weight, depth):
+        raise ValueError("pixel_weight must not alias tsdf, weight or the depth image")
+
+
+def integrate_depth_weighted(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                             narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None, carve=False,
+                             record=None):
+    """integrate_depth with the weighted rule ("Weighted fusion and carving"): a voxel's
+    weight is w times pixel_weight at the pixel it projects to (a float32 device image of depth's shape; None: w
+    itself), and with carve the seen free space in front of the band (live value exactly 1 at a valid pixel) is fused
+    with +1.  Two launches, no host wait; returns the record (unpack_weighted_record once it is on the host)"""
+    require_gpu()
+    p = FusionWeightedParams()
+    p.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                             narrow_band_width_voxels, w, max_weight, 1)
+    if pixel_weight is not None:
+        check_pixel_weight(pixel_weight, depth, tsdf, weight)
+    p.carve, p.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
+    record, scratch = _record_and_scratch(tsdf, record, _lib.FUSION_WEIGHTED_SCRATCH_BYTES)
+    check(lib.lsf_fusion_integrate_depth_weighted(
+        ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(depth.data_ptr()),
+        ctypes.c_void_p(None if pixel_weight is None else pixel_weight.data_ptr()), ctypes.c_void_p(record.data_ptr()),
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_weighted")
+    return record
 
 
 def unpack_record(r):
@@ -124,3 +178,11 @@ def unpack_record(r):
     r = np.asarray(r, dtype=np.float64).reshape(-1)
     return {"fused": int(r[0]), "first_seen": int(r[1]), "sum_abs_change": float(r[2]),
             "max_abs_change": float(r[3])}
+
+
+def unpack_weighted_record(r):
+    """unpack_record of a weighted call, with its two further exact counts: carved and weight_rejected"""
+    out = unpack_record(r)
+    r = np.asarray(r, dtype=np.float64).reshape(-1)
+    out["carved"], out["weight_rejected"] = int(r[4]), int(r[5])
+    return out

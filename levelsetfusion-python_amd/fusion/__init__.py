@@ -8,6 +8,19 @@ CanonicalVolume holds the model, two float32 device arrays of one shape: `tsdf` 
 in float32, the average taken with the uncapped W1; every other voxel keeps its tsdf and weight bit for bit.  Each
 integrate_* call is two launches of csrc/lsf_fusion.hip and returns the call's record as a float64 device tensor
 (unpack_record turns a host copy into {fused, first_seen, sum_abs_change, max_abs_change}); nothing waits for the GPU.
+
+Depth mode also has a weighted rule with free-space carving (INTEGRATION.md section 3, "Weighted fusion and carving";
+tests/fusion_weighted_restatement.py restates it): CanonicalVolume.integrate_depth(..., pixel_weight=, carve=).  A
+voxel has a valid pixel when it lies in front of the camera, projects into the image and the depth there is > 0.  With
+one it is in band when -1 < l < 1 and, with carve, carved when l == 1 exactly: the camera has looked through it, and
++1 is fused.  Its weight is w_eff = w * pixel_weight[iy][ix], one float32 multiply (w itself without an image); a
+w_eff that is not finite and > 0 leaves the voxel alone and is counted.  The average then runs with w_eff in place
+of w.  A surface that later frames look through is thereby averaged towards +1: a fused value t0 > -1 gives
+(t0 + 1) / 2 > 0 after one carving frame of equal weight.  The record gains carved and weight_rejected
+(unpack_weighted_record).  With both arguments at their defaults the call is the unweighted one, unchanged.
+DepthConfidence builds the weight image c = |n . r| min(1, (reference_depth / z)^2) on the device from the level-0
+depth and normals of a DepthPyramid (csrc/lsf_depth_confidence.hip; INTEGRATION.md section 3, "Depth confidence"):
+grazing and far pixels, whose axial noise grows with z^2, count less.
 CanonicalVolume.raycast renders the model into a depth (and normal) image seen from a camera at a twist: one launch of
 csrc/lsf_raycast.hip ("Ray-casting"; tests/raycast_restatement.py restates it).
 CanonicalVolume.extract_mesh takes the model's surface out as a triangle mesh: marching cubes over the cells whose 8
@@ -32,6 +45,10 @@ by ICP against the model's prediction:
                `icp_iterations` runs over its levels (device_icp.icp_run_pyramid), `icp_strides` not used;
                `icp_max_normal_angle` (radians) adds the normal-angle gate.  Fusion still integrates the raw depth.
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
+With `carve` or `confidence` (a DepthConfidence) every frame, frame 0 included, is fused by the weighted rule; the
+confidence image comes from the frame's own pyramid -- the tracker's, built once, when "icp" mode has an `icp_pyramid`
+with the filter settings of `confidence.pyramid`, else a one-level pyramid of those settings.  Neither combines with a
+non-rigid optimizer: volume-mode carving would need an observation mask warped with the live field.
 With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
 generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
 
@@ -41,7 +58,7 @@ count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals.
 
-Not covered: free-space carving (fusing +1 in front of the surface), per-voxel confidence weights, keeping the warp
+Not covered: carving or weights in volume mode and with the non-rigid step, a carve-distance limit, keeping the warp
 field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
 fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, fusing the filtered depth, a
 downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
@@ -53,16 +70,17 @@ import math
 import numpy as np
 import torch
 
-from .. import device_fusion, device_icp, device_mesh, device_raycast, device_rigid
+from .. import device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
-from ..device_fusion import RECORD_FIELDS, unpack_record
+from ..device_fusion import RECORD_FIELDS, WEIGHTED_RECORD_FIELDS, unpack_record, unpack_weighted_record
+from ..rigid_opt.depth_pyramid import DepthPyramid
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "unpack_record", "RECORD_FIELDS", "TRACKING_REFERENCES",
-           "TRACKING_MODES"]
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "unpack_record", "unpack_weighted_record",
+           "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS", "TRACKING_REFERENCES", "TRACKING_MODES"]
 
 # the trackers with a reference volume (rigid_run_3d), and every tracking mode SequenceFusion3d accepts
 TRACKING_REFERENCES = ("model", "raycast")
@@ -83,6 +101,52 @@ def _live(live):
     if a.dtype.kind not in "fiub":
         raise ValueError("live must be numeric, got %s" % a.dtype)
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda")
+
+
+def _filter_settings(pyramid):
+    """what decides a pyramid's level 0: the filter and the normals' gate"""
+    return pyramid.radius, pyramid.sigma_space, pyramid.sigma_range, pyramid.depth_gate
+
+
+class DepthConfidence:
+    """the settings of the per-pixel confidence image c = |n . r| min(1, (reference_depth / z)^2)
+    (device_depth_confidence.depth_confidence).  reference_depth: metres, finite and > 0, the depth up to which a
+    frontal pixel counts fully; pyramid: a rigid_opt.DepthPyramid whose filter settings give the level-0 depth and
+    normals (its levels are not used), DepthPyramid()'s own by default."""
+
+    def __init__(self, reference_depth=device_depth_confidence.REFERENCE_DEPTH, pyramid=None):
+        self.reference_depth = device_depth_confidence.checked_reference_depth(reference_depth)
+        if pyramid is not None and not isinstance(pyramid, DepthPyramid):
+            raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
+        self.pyramid = DepthPyramid() if pyramid is None else pyramid
+
+    def shares(self, pyramid):
+        """whether level 0 of `pyramid` (a DepthPyramid or None) is the one this confidence is computed from"""
+        return pyramid is not None and _filter_settings(pyramid) == _filter_settings(self.pyramid)
+
+    def from_levels(self, levels, camera):
+        """the float32 (H, W) device weight image of a built pyramid's level 0 (a PyramidLevels), enqueued"""
+        return device_depth_confidence.depth_confidence(levels.depth[0], levels.normals[0], camera,
+                                                        self.reference_depth)
+
+    def build_device(self, depth, code, camera):
+        """the weight image of a device depth image and its LSF_DEPTH_* code: a one-level pyramid, then from_levels"""
+        settings = dict(self.pyramid.settings(), levels=1)
+        return self.from_levels(DepthPyramid(**settings).build_device(depth, code, camera), camera)
+
+    def build(self, depth_image, camera):
+        """build_device of a depth image (uint16 / float32 / float64, numpy or device)"""
+        require_gpu()
+        return self.build_device(*device_depth(depth_image), camera)
+
+
+def _pixel_weight(pixel_weight):
+    if pixel_weight is None or isinstance(pixel_weight, torch.Tensor):
+        return pixel_weight
+    a = np.asarray(pixel_weight)
+    if a.dtype != np.float32:
+        raise ValueError("pixel_weight must be float32, got %s" % a.dtype)
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
 class CanonicalVolume:
@@ -107,12 +171,18 @@ class CanonicalVolume:
         return device_fusion.integrate_volume(self.tsdf, self.weight, _live(live), weight, self.max_weight)
 
     def integrate_depth(self, depth_image, camera, twist, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
-                        weight=1.0):
+                        weight=1.0, pixel_weight=None, carve=False):
         """generate the live volume of depth_image (uint16 / float32 / float64, numpy or device) under twist, as the
-        rigid tracker does, and fuse it in the same pass; returns the device record"""
+        rigid tracker does, and fuse it in the same pass; returns the device record.  pixel_weight (a float32 image of
+        depth_image's shape, numpy or device) and carve choose the weighted rule (module docstring), whose record
+        unpack_weighted_record reads; with neither the call is the unweighted one."""
         depth, code = device_depth(depth_image)
-        return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
-                                             voxel_size, narrow_band_width_voxels, weight, self.max_weight)
+        if pixel_weight is None and not carve:
+            return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
+                                                 voxel_size, narrow_band_width_voxels, weight, self.max_weight)
+        return device_fusion.integrate_depth_weighted(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
+                                                      voxel_size, narrow_band_width_voxels, weight, self.max_weight,
+                                                      _pixel_weight(pixel_weight), carve)
 
     def raycast(self, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
                 fallback_depth=None, as_tensor=False):
@@ -159,7 +229,13 @@ class SequenceFusion3d:
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
-                 icp_max_normal_angle=None):
+                 icp_max_normal_angle=None, carve=False, confidence=None):
+        if confidence is not None and not isinstance(confidence, DepthConfidence):
+            raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
+        self.carve, self.confidence = bool(carve), confidence
+        if nonrigid_optimizer is not None and (self.carve or confidence is not None):
+            raise ValueError("carve and confidence need depth-mode fusion and do not combine with a nonrigid_optimizer: "
+                             "volume-mode carving needs an observation mask warped with the live field")
         self.camera = camera
         self.field_shape = device_rigid.volume_shape(field_shape)
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
@@ -215,12 +291,22 @@ class SequenceFusion3d:
         twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist)
         return twist, records, hits
 
+    def _frame_weight(self, depth, code, tracked):
+        """the frame's confidence image (None without `confidence`): from the tracker's pyramid of this frame when it
+        built one (tracked) with the confidence's filter settings, else from a one-level pyramid of its own"""
+        c = self.confidence
+        if c is None:
+            return None
+        if tracked and self.tracking_reference == "icp" and c.shares(self.icp_pyramid):
+            return c.from_levels(self.icp.last_pyramid, self.camera)
+        return c.build_device(depth, code, self.camera)
+
     def integrate(self, depth_image):
         """track and fuse one frame; returns its record (also appended to frame_records)"""
         k = len(self.twists)
         depth, code = device_depth(depth_image)
         model = self.canonical
-        rigid_records, nonrigid, hits = [], None, None
+        rigid_records, nonrigid, hits, tracked = [], None, None, False
         gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
         if k == 0:
             twist = self.initial_twist.copy()
@@ -229,6 +315,7 @@ class SequenceFusion3d:
             if self.tracking_reference == "icp":
                 if sum(self.icp_iterations) > 0:
                     twist, rigid_records, hits = self._track_icp(depth, code, twist)
+                    tracked = True
             elif self.rigid_iterations > 0:
                 reference = model.tsdf
                 if self.tracking_reference == "raycast":
@@ -238,7 +325,14 @@ class SequenceFusion3d:
                     self.eta, self.voxel_size, self.voxel_size, self.narrow_band_width_voxels, twist=twist)
                 rigid_records = [unpack_rigid_record(r) for r in records]
                 del reference
-        if k == 0 or self.nonrigid_optimizer is None:
+        unpack = unpack_record
+        if self.carve or self.confidence is not None:
+            record = device_fusion.integrate_depth_weighted(
+                model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, w=1.0,
+                max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
+                **gen)
+            unpack = unpack_weighted_record
+        elif k == 0 or self.nonrigid_optimizer is None:
             record = device_fusion.integrate_depth(model.tsdf, model.weight, depth, code, self.camera,
                                                    self.array_offset, twist, w=1.0, max_weight=model.max_weight, **gen)
         else:
@@ -249,7 +343,7 @@ class SequenceFusion3d:
             record = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0, model.max_weight)
         frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
-                 "fusion": unpack_record(record.cpu().numpy()),
+                 "fusion": unpack(record.cpu().numpy()),
                  "prediction_hits": None if hits is None else int(hits.item())}
         if self.tracking_reference == "raycast":
             self._previous = (depth, code)
