@@ -133,8 +133,10 @@ def whole(lsf, term, **kw):
     gradients = [device_terms._device(g) for g in kw.pop("gradients", ())]
     shape = tuple(live.shape) if live is not None else tuple(warp.shape[:-1])
     dev = (live if live is not None else warp).device
-    g = torch.empty(shape + (len(shape),), dtype=torch.float32, device=dev)
-    e = torch.empty(shape, dtype=torch.float64, device=dev)
+    # NaN, not torch.empty: a recycled block may hold a same-shaped earlier call's right answer, and a location the
+    # kernel never wrote would then pass
+    g = torch.full(shape + (len(shape),), float("nan"), dtype=torch.float32, device=dev)
+    e = torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
     total = torch.zeros(1, dtype=torch.float64, device=dev)
     band = kw.pop("band", False)
     device_terms.term_gradient(term, device_core.make_grid(shape), live, canonical, gradients, warp, g, e, total,
@@ -196,25 +198,44 @@ def test_reference_outputs_12x12(lsf, ref_leaf):
 
 
 # ------------------------------------------------------------------------------- 3. the oracle, bit for bit
-def rand_field(rng, shape, noise=0.05):
+def rand_field(rng, shape, noise=0.05, slope=0.06):
     grids = np.meshgrid(*[np.arange(s) for s in shape], indexing="ij")
-    f = 0.06 * (grids[-2] - shape[-2] / 2) + 0.3 * np.sin(grids[-1] * 0.35) + noise * rng.standard_normal(shape)
+    f = slope * (grids[-2] - shape[-2] / 2) + 0.3 * np.sin(grids[-1] * 0.35) + noise * rng.standard_normal(shape)
     if len(shape) == 3:
         f = f + 0.2 * np.cos(grids[0] * 0.4)
     return np.clip(f, -1.0, 1.0).astype(np.float32)
 
 
+TERM_CAP = 2048 * 256  # kTermMaxBlocks * kTermBlock, csrc/lsf_terms.hip: a lane of term_kernel loops past this count
+
+
+def term_fields(shape, slope=0.06):
+    """(live, canonical, warp) of the oracle comparisons; slope: of the fields along their second-to-last axis"""
+    rng = np.random.default_rng(7)
+    live = rand_field(rng, shape, slope=slope)
+    canonical = rand_field(rng, shape, noise=0.08, slope=slope)
+    warp = (0.4 * rng.standard_normal(shape + (len(shape),))).astype(np.float32)
+    return live, canonical, warp
+
+
 @pytest.mark.parametrize("shape", [(33, 70), (9, 20, 67)])
 def test_terms_match_the_oracle(lsf, shape):
+    assert_terms_match_the_oracle(lsf, shape)
+
+
+def assert_terms_match_the_oracle(lsf, shape, slope=0.06):
+    """every term over the whole field and over its band against the oracle, bit for bit; the oracle's terms are
+    whole-array numpy (no per-location loop), so every location is compared at every shape.  Past TERM_CAP voxels the
+    band and its complement must both reach into the second trip of the kernel's loop."""
     L = lsf._lib
-    rng = np.random.default_rng(7)
     d = len(shape)
-    live = rand_field(rng, shape)
-    canonical = rand_field(rng, shape, noise=0.08)
-    warp = (0.4 * rng.standard_normal(shape + (d,))).astype(np.float32)
+    live, canonical, warp = term_fields(shape, slope)
     grads = O.gradient(live)
     band = band_mask(live, canonical)
     assert 0 < band.sum() < band.size
+    if band.size > TERM_CAP:
+        past = band.reshape(-1)[TERM_CAP:]
+        assert past.any() and not past.all()
 
     for method, term in ((O.BASIC, L.TERM_DATA_BASIC), (O.THRESHOLDED_FDM, L.TERM_DATA_THRESHOLDED_FDM)):
         expected, diff = O.data_term_gradient(live, canonical, method)
