@@ -1045,6 +1045,33 @@ int lsf_fusion_integrate_depth_weighted(float *tsdf, float *weight, const void *
                                         double *record, void *scratch, const lsf_fusion_weighted_params *params,
                                         void *stream);
 
+/* ---- weighted depth-mode fusion that also fuses colour ---------------------------------------------------------------
+ * The rule is INTEGRATION.md section 3, "Colour fusion".  Geometry is lsf_fusion_integrate_depth_weighted's with the same
+ * weight, pixel_weight and carve: tsdf, weight and record [0..5] equal its results bit for bit.  The colour volume holds
+ * one 16-byte record per voxel, float32 (R, G, B, Wc): the colour in units of the 8-bit image and the colour weight.  A
+ * voxel is coloured when it has a valid pixel, its live value satisfies -colour_band < l < colour_band strictly and its
+ * w_eff (the geometry rule's) is finite and > 0; with c_j = (float)colour_image[pixel][j], in float32 with separately
+ * rounded operations,
+ *   Wc1 = Wc + w_eff,  C_j = (Wc C_j + w_eff c_j) / Wc1,  Wc = min(Wc1, max_weight)
+ * Carved voxels (l == 1) are never coloured, and every voxel that is not coloured keeps its 16 bytes bit for bit: colour
+ * memory is read and written for coloured voxels only.  A rejected weight counts once, in record [5].  The record: [0..5]
+ * as lsf_fusion_integrate_depth_weighted, [6] coloured, [7] first_coloured (coloured voxels whose Wc was 0), exact
+ * counts; reruns bit-identical. */
+typedef struct lsf_fusion_colour_params {
+    lsf_fusion_weighted_params weighted; /* as lsf_fusion_integrate_depth_weighted reads it */
+    float colour_band;                   /* finite, in (0, 1]: the coloured part of the band, in live-value units */
+} lsf_fusion_colour_params;
+/* per-workgroup partials: fused, first_seen, sum, max, carved, weight_rejected, coloured, first_coloured */
+#define LSF_FUSION_COLOUR_SCRATCH_BYTES (LSF_FUSION_MAX_BLOCKS * 8 * 8)
+
+/* tsdf, weight, depth_image, pixel_weight, record: as lsf_fusion_integrate_depth_weighted.  colour: DEVICE float32
+ * [depth][height][width][4], in/out, 16-byte aligned.  colour_image: DEVICE uint8 [image_height][image_width][3] (R, G,
+ * B), registered to the depth image.  scratch: DEVICE, LSF_FUSION_COLOUR_SCRATCH_BYTES.  tsdf, weight, colour,
+ * colour_image, pixel_weight and depth_image must not overlap one another.  Two launches, no host synchronisation. */
+int lsf_fusion_integrate_depth_colour(float *tsdf, float *weight, float *colour, const void *depth_image,
+                                      const float *pixel_weight, const uint8_t *colour_image, double *record,
+                                      void *scratch, const lsf_fusion_colour_params *params, void *stream);
+
 /* ---- a per-pixel confidence image for weighted fusion ----------------------------------------------------------------
  * c(u, v) = |n . r| min(1, (reference_depth / z)^2): the cosine between the pixel's unit ray r and its normal n, times
  * the inverse of the sensor's axial noise growth beyond reference_depth.  Every step is one float64 operation, in this
@@ -1242,6 +1269,18 @@ int lsf_mesh_count(const float *tsdf, const float *weight, uint8_t *cell_code, u
 int lsf_mesh_emit(const float *tsdf, const float *weight, const uint8_t *cell_code, const uint8_t *edge_mask,
                   const int32_t *block_offsets, int32_t *vertex_base, float *vertices, float *normals, int32_t *faces,
                   int64_t vertex_count, int64_t face_count, const lsf_mesh_params *params, void *stream);
+
+/* After lsf_mesh_emit on the same inputs and workspaces: the colour of every vertex from a colour volume (DEVICE float32
+ * [depth][height][width][4], (R, G, B, Wc) per voxel, 16-byte aligned; lsf_fusion_integrate_depth_colour's).  For the
+ * vertex on the grid edge from voxel v to w with lsf_mesh_emit's float64 t = (iso - tsdf[v]) / (tsdf[w] - tsdf[v]): with
+ * both colour weights > 0 each channel is C_v (1 - t) + C_w t in float64, in that order; with one, that voxel's colour;
+ * with neither, the default colour (each channel 0..255).  The stored byte is floor(min(max(x, 0), 255) + 0.5), and 0 for
+ * a NaN.  colours: DEVICE uint8 [vertex_count][3], row i the colour of vertex i, overlapping no input.  One launch, none
+ * when vertex_count is 0; each voxel with a non-zero edge_mask writes the rows of its own one to three vertices, from
+ * vertex_base: no scan, no dependence between workgroups. */
+int lsf_mesh_vertex_colours(const float *tsdf, const float *colour, const uint8_t *edge_mask,
+                            const int32_t *vertex_base, uint8_t *colours, int64_t vertex_count, int32_t default_red,
+                            int32_t default_green, int32_t default_blue, const lsf_mesh_params *params, void *stream);
 
 #ifdef __cplusplus
 }

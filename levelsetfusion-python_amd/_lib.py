@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "0ec1059400c2db73"
+HEADER_ABI_HASH = "4fec077c2ef775e5"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -210,6 +210,14 @@ class FusionWeightedParams(ctypes.Structure):
     _fields_ = [("fusion", FusionParams), ("carve", ctypes.c_int32), ("has_pixel_weight", ctypes.c_int32)]
 
 
+FUSION_COLOUR_SCRATCH_BYTES = FUSION_MAX_BLOCKS * 8 * 8
+
+
+class FusionColourParams(ctypes.Structure):
+    """lsf_fusion_colour_params: weighted depth-mode fusion that also fuses colour (lsf_fusion_integrate_depth_colour)"""
+    _fields_ = [("weighted", FusionWeightedParams), ("colour_band", ctypes.c_float)]
+
+
 class DepthConfidenceParams(ctypes.Structure):
     """lsf_depth_confidence_params: the per-pixel confidence image (lsf_depth_confidence)"""
     _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "reference_depth")] + \
@@ -386,10 +394,14 @@ PROTOTYPES = {
     "lsf_fusion_integrate_depth": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _P(FusionParams), _vp]),
     "lsf_fusion_integrate_depth_weighted": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(FusionWeightedParams),
                                                            _vp]),
+    "lsf_fusion_integrate_depth_colour": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                         _P(FusionColourParams), _vp]),
     "lsf_depth_confidence": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthConfidenceParams), _vp]),
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
+    "lsf_mesh_vertex_colours": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, _P(MeshParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),

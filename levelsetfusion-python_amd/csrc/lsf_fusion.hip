@@ -14,6 +14,10 @@
 // fusion and carving"; tests/fusion_weighted_restatement.py): the same four voxels per lane, 16-byte accesses, grid and
 // finishing launch, with the pixel a voxel projects to (typed_tsdf_sample) selecting its weight from a float32 image,
 // +1 fused in the seen free space in front of the band, and six partials per workgroup instead of four.
+// lsf_fusion_integrate_depth_colour is that kernel again with a colour volume beside the model (INTEGRATION.md section 3,
+// "Colour fusion"; tests/colour_restatement.py): one float32 (R, G, B, Wc) record per voxel, loaded and stored in one
+// 16-byte access each and only where the voxel lies inside the colour band, three byte reads of the colour image at the
+// voxel's pixel, and eight partials per workgroup.  The geometry code is fuse_voxel_weighted itself.
 #include "lsf_device.h"
 #include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
@@ -24,12 +28,14 @@ namespace {
 
 constexpr int kParts = 4;   // fused, first_seen, sum |t1 - t|, max |t1 - t|
 constexpr int kWParts = 6;  // the weighted rule: those, carved, weight_rejected
+constexpr int kCParts = 8;  // with colour: those, coloured, first_coloured
 constexpr int kMaxPart = 3; // the one partial that is a maximum; every other is a sum
 constexpr int kMaxBlocks = LSF_FUSION_MAX_BLOCKS;
 constexpr int kRec = LSF_FUSION_RECORD_DOUBLES;
-static_assert(kRec >= kWParts, "the record holds the results of either rule");
+static_assert(kRec >= kWParts && kRec >= kCParts, "the record holds the results of every rule");
 static_assert(LSF_FUSION_SCRATCH_BYTES == kMaxBlocks * kParts * 8, "a workgroup's partials");
 static_assert(LSF_FUSION_WEIGHTED_SCRATCH_BYTES == kMaxBlocks * kWParts * 8, "a workgroup's partials");
+static_assert(LSF_FUSION_COLOUR_SCRATCH_BYTES == kMaxBlocks * kCParts * 8, "a workgroup's partials");
 
 enum Source { VOLUME = 0, DEPTH = 1 };
 
@@ -53,6 +59,18 @@ struct Acc {
 struct WeightedAcc {
     Acc a;
     int carved, rejected;
+};
+
+struct ColourAcc {
+    WeightedAcc w;
+    int coloured, first;
+};
+
+// the colour side of a call: the volume of (R, G, B, Wc) records, the uint8 (R, G, B) image, the band
+struct ColourDev {
+    float4* __restrict__ volume;
+    const unsigned char* __restrict__ image;
+    float band;
 };
 
 // the rule at one voxel; true when the voxel was observed (and its tsdf and weight may have changed)
@@ -95,6 +113,27 @@ __device__ inline bool fuse_voxel_weighted(const TsdfSample& s, const float* __r
     t = t1;
     W = W1 > p.max_weight ? p.max_weight : W1;
     return true;
+}
+
+// the colour rule at voxel i, after fuse_voxel_weighted has updated it (so its pixel is valid and its weight usable):
+// inside the colour band -- which lies in (-1, 1), so a carved voxel never is -- its record is averaged with the pixel's
+// colour under the same weight, one 16-byte load and one 16-byte store; outside, colour memory is not touched
+__device__ inline void colour_voxel(const TsdfSample& s, const float* __restrict__ pixel_weight, const ColourDev& c,
+                                    long long i, const FusionDev& p, ColourAcc& acc) {
+    const float l = s.value;
+    if (!(l > -c.band && l < c.band)) return;
+    const float w = pixel_weight ? p.w * pixel_weight[s.pixel] : p.w;
+    const unsigned char* px = c.image + s.pixel * 3;
+    const float r = (float)px[0], g = (float)px[1], b = (float)px[2];
+    float4 q = c.volume[i];
+    const float Wc = q.w, Wc1 = Wc + w;
+    q.x = (Wc * q.x + w * r) / Wc1;
+    q.y = (Wc * q.y + w * g) / Wc1;
+    q.z = (Wc * q.z + w * b) / Wc1;
+    q.w = Wc1 > p.max_weight ? p.max_weight : Wc1;
+    c.volume[i] = q;
+    acc.coloured += 1;
+    acc.first += Wc == 0.0f ? 1 : 0;
 }
 
 __device__ inline void load4(const float* __restrict__ f, long long i, float (&v)[4], bool aligned) {
@@ -255,6 +294,58 @@ __global__ __launch_bounds__(kBlock) void fusion_weighted_kernel(float* __restri
         for (int c = 0; c < kWParts; ++c) scratch[(size_t)blockIdx.x * kWParts + c] = v[c];
 }
 
+// the weighted rule with colour: fusion_weighted_kernel's walk, stores and partials, and colour_voxel at every updated voxel
+template <typename DT, typename PT>
+__global__ __launch_bounds__(kBlock) void fusion_colour_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
+                                                               const DT* __restrict__ depth,
+                                                               const float* __restrict__ pixel_weight,
+                                                               double* __restrict__ scratch, FusionDev p, int carve,
+                                                               ColourDev c) {
+    __shared__ double e[12];
+    __shared__ double red[kBlock / kWave][kCParts];
+    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
+    __syncthreads();
+    const bool aligned = p.aligned != 0, carving = carve != 0;
+    ColourAcc a = {{{0, 0, 0.0, 0.0f}, 0, 0}, 0, 0};
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
+        const long long i = g * 4;
+        TsdfSample s[4];
+        float t[4], W[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = depth_sample<DT, PT>(depth, p, e, i + k);
+        load4(tsdf, i, t, aligned);
+        load4(weight, i, W, aligned);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a.w)) {
+                any = true;
+                colour_voxel(s[k], pixel_weight, c, i + k, p, a);
+            }
+        if (any) {  // a step without an updated voxel stores nothing
+            store4(tsdf, i, t, aligned);
+            store4(weight, i, W, aligned);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
+        for (long long i = p.groups * 4; i < p.n; ++i) {
+            float t = tsdf[i], W = weight[i];
+            const TsdfSample s = depth_sample<DT, PT>(depth, p, e, i);
+            if (fuse_voxel_weighted(s, pixel_weight, carving, t, W, p, a.w)) {
+                tsdf[i] = t;
+                weight[i] = W;
+                colour_voxel(s, pixel_weight, c, i, p, a);
+            }
+        }
+    double v[kCParts] = {(double)a.w.a.fused, (double)a.w.a.first,  a.w.a.sum,          (double)a.w.a.max,
+                         (double)a.w.carved,  (double)a.w.rejected, (double)a.coloured, (double)a.first};
+    block_combine(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c8 = 0; c8 < kCParts; ++c8) scratch[(size_t)blockIdx.x * kCParts + c8] = v[c8];
+}
+
 // one workgroup: lane q combines partials q, q + kBlock, ... in order, then the block in a fixed order
 template <int N>
 __global__ __launch_bounds__(kBlock) void fusion_finish_kernel(const double* __restrict__ scratch,
@@ -320,6 +411,17 @@ int launch_weighted(float* tsdf, float* weight, const void* depth, const float* 
     return launch_status();
 }
 
+template <typename DT, typename PT>
+int launch_colour(float* tsdf, float* weight, const void* depth, const float* pixel_weight, double* record,
+                  double* scratch, const FusionDev& p, int carve, const ColourDev& c, hipStream_t s) {
+    hipLaunchKernelGGL((fusion_colour_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight,
+                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve, c);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(fusion_finish_kernel<kCParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
+                       p.nblocks);
+    return launch_status();
+}
+
 int check_buffers(const float* tsdf, const float* weight, const void* source, const double* record,
                   const void* scratch) {
     if (!tsdf || !weight || !source || !record || !scratch) return LSF_ERR_BAD_ARGUMENT;
@@ -380,5 +482,39 @@ extern "C" int lsf_fusion_integrate_depth_weighted(float* tsdf, float* weight, c
     return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
         return launch_weighted<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p,
                                                            carve, s);
+    });
+}
+
+extern "C" int lsf_fusion_integrate_depth_colour(float* tsdf, float* weight, float* colour, const void* depth_image,
+                                                 const float* pixel_weight, const uint8_t* colour_image,
+                                                 double* record, void* scratch, const lsf_fusion_colour_params* params,
+                                                 void* stream) {
+    (void)hipGetLastError();
+    if (!params || !colour || !colour_image) return LSF_ERR_BAD_ARGUMENT;
+    const lsf_fusion_weighted_params* wp = &params->weighted;
+    const lsf_fusion_params* f = &wp->fusion;
+    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
+    FusionDev p;
+    if (int e = convert(f, p)) return e;
+    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
+    if ((wp->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    const float band = params->colour_band;
+    if (!(band > 0.0f && band <= 1.0f)) return LSF_ERR_BAD_ARGUMENT;  // NaN fails
+    if (((uintptr_t)colour & 15) != 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t pixels = (size_t)f->tsdf.image_width * f->tsdf.image_height, model = (size_t)p.n * 4;
+    const size_t depth_bytes = pixels * (f->depth_dtype == LSF_DEPTH_U16 ? 2 : (f->depth_dtype == LSF_DEPTH_F32 ? 4 : 8));
+    const void* const buffers[6] = {tsdf, weight, colour, colour_image, pixel_weight, depth_image};
+    const size_t bytes[6] = {model, model, model * 4, pixels * 3, pixels * 4, depth_bytes};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j)
+            if (overlaps(buffers[i], bytes[i], buffers[j], bytes[j])) return LSF_ERR_BAD_ARGUMENT;
+    p.aligned = aligned16(tsdf) && aligned16(weight);
+    hipStream_t s = as_stream(stream);
+    double* sc = reinterpret_cast<double*>(scratch);
+    const int carve = wp->carve != 0;
+    const ColourDev c{reinterpret_cast<float4*>(colour), colour_image, band};
+    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch_colour<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p, carve,
+                                                         c, s);
     });
 }

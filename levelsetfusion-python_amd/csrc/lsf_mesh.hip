@@ -14,6 +14,9 @@
 //          faces      a ballot scan gives each cell its first face; each edge's vertex is
 //                     vertex_base[owner] + popcount(edge_mask[owner] & ((1 << axis) - 1))
 // The order of the outputs is the order of the voxels, whatever the schedule: no atomics between workgroups, no flags.
+// lsf_mesh_vertex_colours is a sixth, optional launch after emit ("Colour fusion";
+// tests/colour_restatement.py): every voxel that owns vertices interpolates their colours from a volume of float32
+// (R, G, B, Wc) records with the vertices' own t and writes its rows from vertex_base; it needs no scan.
 #include "lsf_device.h"
 #include "lsf_mesh_tables.h"
 
@@ -290,6 +293,59 @@ __global__ __launch_bounds__(kBlock) void faces_kernel(const unsigned char* __re
     }
 }
 
+// one channel as a byte: floor(min(max(x, 0), 255) + 0.5), 0 for a NaN
+__device__ inline unsigned char colour_byte(double x) {
+    if (isnan(x)) return 0;
+    const double lo = x > 0.0 ? x : 0.0;
+    const double hi = lo < 255.0 ? lo : 255.0;
+    return (unsigned char)floor(hi + 0.5);
+}
+
+struct DefaultColour {
+    unsigned char c[3];
+};
+
+__global__ __launch_bounds__(kBlock) void vertex_colours_kernel(const float* __restrict__ tsdf,
+                                                                const float4* __restrict__ colour,
+                                                                const unsigned char* __restrict__ edge_mask,
+                                                                const int* __restrict__ vertex_base,
+                                                                unsigned char* __restrict__ colours,
+                                                                long long vertex_count, DefaultColour fallback,
+                                                                MeshDev p) {
+    const long long stride[3] = {1, p.nx, (long long)p.nx * p.ny};
+    const int n[3] = {p.nx, p.ny, p.nz};
+    const long long tile = (long long)blockIdx.x * kTile;
+    for (int r = 0; r < kSteps; ++r) {
+        const long long v = tile + r * kBlock + threadIdx.x;
+        if (v >= p.voxels) break;
+        const unsigned m = edge_mask[v];
+        if (!m) continue;
+        long long id = vertex_base[v];
+        int g[3];  // (x, y, z)
+        coords(v, p, g[0], g[1], g[2]);
+        const float4 ca = colour[v];
+        for (int axis = 0; axis < 3; ++axis) {
+            if (!((m >> axis) & 1u)) continue;
+            if (id < 0 || id >= vertex_count || g[axis] + 1 >= n[axis]) break;  // not lsf_mesh_emit's workspaces
+            const long long w = v + stride[axis];
+            const double a = (double)tsdf[v], b = (double)tsdf[w];
+            const double t = (p.iso - a) / (b - a);
+            const float4 cb = colour[w];
+            const bool has_a = ca.w > 0.0f, has_b = cb.w > 0.0f;  // NaN weights fail
+            const float va[3] = {ca.x, ca.y, ca.z}, vb[3] = {cb.x, cb.y, cb.z};
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                unsigned char out = fallback.c[j];
+                if (has_a && has_b) out = colour_byte((double)va[j] * (1.0 - t) + (double)vb[j] * t);
+                else if (has_a) out = colour_byte((double)va[j]);
+                else if (has_b) out = colour_byte((double)vb[j]);
+                colours[id * 3 + j] = out;
+            }
+            ++id;
+        }
+    }
+}
+
 bool finite(double x) { return std::isfinite(x); }
 
 int convert(const lsf_mesh_params* q, MeshDev& p) {
@@ -380,5 +436,34 @@ extern "C" int lsf_mesh_emit(const float* tsdf, const float* weight, const uint8
     if (face_count == 0) return 0;
     hipLaunchKernelGGL(faces_kernel, dim3(p.blocks), dim3(kBlock), 0, s, cell_code, edge_mask, block_offsets + p.blocks,
                        vertex_base, faces, (long long)face_count, p);
+    return launch_status();
+}
+
+extern "C" int lsf_mesh_vertex_colours(const float* tsdf, const float* colour, const uint8_t* edge_mask,
+                                       const int32_t* vertex_base, uint8_t* colours, int64_t vertex_count,
+                                       int32_t default_red, int32_t default_green, int32_t default_blue,
+                                       const lsf_mesh_params* params, void* stream) {
+    (void)hipGetLastError();
+    MeshDev p;
+    if (int e = convert(params, p)) return e;
+    if (vertex_count < 0 || vertex_count > 3 * p.voxels) return LSF_ERR_BAD_ARGUMENT;
+    const int32_t rgb[3] = {default_red, default_green, default_blue};
+    DefaultColour fallback;
+    for (int j = 0; j < 3; ++j) {
+        if (rgb[j] < 0 || rgb[j] > 255) return LSF_ERR_BAD_ARGUMENT;
+        fallback.c[j] = (unsigned char)rgb[j];
+    }
+    if (vertex_count == 0) return 0;
+    if (!tsdf || !colour || !edge_mask || !vertex_base || !colours) return LSF_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)colour & 15) != 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t n = (size_t)p.voxels;
+    const void* const ins[4] = {tsdf, colour, edge_mask, vertex_base};
+    const size_t in_bytes[4] = {n * 4, n * 16, n, n * 4};
+    const void* const outs[1] = {colours};
+    const size_t out_bytes[1] = {(size_t)vertex_count * 3};
+    if (any_alias(ins, in_bytes, outs, out_bytes)) return LSF_ERR_BAD_ARGUMENT;
+    hipLaunchKernelGGL(vertex_colours_kernel, dim3(p.blocks), dim3(kBlock), 0, as_stream(stream), tsdf,
+                       reinterpret_cast<const float4*>(colour), edge_mask, vertex_base, colours, (long long)vertex_count,
+                       fallback, p);
     return launch_status();
 }

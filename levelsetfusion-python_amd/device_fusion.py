@@ -1,7 +1,8 @@
 """Torch-facing wrapper of the fusion entry points (include/lsf_hip.h: lsf_fusion_integrate_volume,
-lsf_fusion_integrate_depth, lsf_fusion_integrate_depth_weighted).  Every argument is checked on the host before a
-launch; a call enqueues two launches and returns the record as a device tensor without waiting for it -- the caller
-decides when to copy it back.  The public interface is fusion.CanonicalVolume / fusion.SequenceFusion3d."""
+lsf_fusion_integrate_depth, lsf_fusion_integrate_depth_weighted, lsf_fusion_integrate_depth_colour).  Every argument is
+checked on the host before a launch; a call enqueues two launches and returns the record as a device tensor without
+waiting for it -- the caller decides when to copy it back.  The public interface is fusion.CanonicalVolume /
+fusion.SequenceFusion3d."""
 import ctypes
 import math
 
@@ -9,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FusionParams, FusionWeightedParams, check, lib
+from ._lib import FusionColourParams, FusionParams, FusionWeightedParams, check, lib
 from .device_core import require_gpu, stream_ptr
 from .device_rigid import _tsdf3d, twist6
 from .tsdf.generation import offsets_of
@@ -17,6 +18,7 @@ from .tsdf.generation import offsets_of
 RECORD = _lib.FUSION_RECORD_DOUBLES
 RECORD_FIELDS = ("fused", "first_seen", "sum_abs_change", "max_abs_change")
 WEIGHTED_RECORD_FIELDS = RECORD_FIELDS + ("carved", "weight_rejected")
+COLOUR_RECORD_FIELDS = WEIGHTED_RECORD_FIELDS + ("coloured", "first_coloured")
 
 
 def fusion_weights(weight, max_weight):
@@ -173,6 +175,84 @@ def integrate_depth_weighted(tsdf, weight, depth, depth_code, camera, array_offs
     return record
 
 
+def colour_band_of(colour_band):
+    """colour_band as a float32 value after the rule's check: finite and in (0, 1]"""
+    band = np.float32(colour_band)
+    if not (band > 0 and band <= 1):  # NaN fails
+        raise ValueError("colour_band must be finite and in (0, 1], got %r" % (colour_band,))
+    return float(band)
+
+
+def check_colour_volume(colour, tsdf, weight):
+    """a colour volume: a float32 contiguous tensor of shape tsdf.shape + (4,) on the model's device, 16-byte aligned,
+    aliasing neither tsdf nor weight"""
+    if not isinstance(colour, torch.Tensor):
+        raise TypeError("colour must be a torch tensor, got %s" % type(colour).__name__)
+    if colour.dtype != torch.float32:
+        raise ValueError("colour must be float32, got %s" % colour.dtype)
+    if colour.device != tsdf.device:
+        raise ValueError("colour is on %s, tsdf on %s: all buffers must be on one device" % (colour.device, tsdf.device))
+    if not colour.is_contiguous():
+        raise ValueError("colour must be contiguous")
+    if tuple(colour.shape) != tuple(tsdf.shape) + (4,):
+        raise ValueError("colour has shape %s, the model %s: it must be the model's shape + (4,)"
+                         % (tuple(colour.shape), tuple(tsdf.shape)))
+    if colour.data_ptr() % 16:
+        raise ValueError("colour must be 16-byte aligned: a voxel's record is one 16-byte access")
+    if _overlap(colour, tsdf) or _overlap(colour, weight):
+        raise ValueError("colour must not alias tsdf or weight")
+
+
+def check_colour_image(colour_image, depth, others):
+    """a colour image: a uint8 contiguous (H, W, 3) tensor on the depth image's device, H and W the depth image's,
+    aliasing none of `others` ((name, tensor) pairs; None tensors are skipped)"""
+    if not isinstance(colour_image, torch.Tensor):
+        raise TypeError("colour_image must be a torch tensor, got %s" % type(colour_image).__name__)
+    if colour_image.dtype != torch.uint8:
+        raise ValueError("colour_image must be uint8, got %s" % colour_image.dtype)
+    if colour_image.device != depth.device:
+        raise ValueError("colour_image is on %s, the depth image on %s: all buffers must be on one device"
+                         % (colour_image.device, depth.device))
+    if not colour_image.is_contiguous():
+        raise ValueError("colour_image must be contiguous")
+    if tuple(colour_image.shape) != tuple(depth.shape) + (3,):
+        raise ValueError("colour_image has shape %s, the depth image %s: it must be (H, W, 3) with the depth image's H, W"
+                         % (tuple(colour_image.shape), tuple(depth.shape)))
+    for name, t in others:
+        if t is not None and _overlap(colour_image, t):
+            raise ValueError("colour_image must not alias %s" % name)
+
+
+def integrate_depth_colour(tsdf, weight, colour, depth, depth_code, camera, array_offset, twist, colour_image,
+                           voxel_size=0.004, narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None,
+                           carve=False, colour_band=1.0, record=None):
+    """integrate_depth_weighted that also fuses colour_image (uint8 (H, W, 3) device tensor registered to the depth
+    image) into the colour volume (float32, tsdf.shape + (4,): R, G, B in 0..255 and the colour weight) of the voxels
+    whose live value lies strictly inside (-colour_band, colour_band) ("Colour fusion").
+    tsdf, weight and record slots 0..5 are integrate_depth_weighted's bit for bit.  Two launches, no host wait; returns
+    the record (unpack_colour_record once it is on the host)"""
+    require_gpu()
+    p = FusionColourParams()
+    p.weighted.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                                      narrow_band_width_voxels, w, max_weight, 1)
+    if pixel_weight is not None:
+        check_pixel_weight(pixel_weight, depth, tsdf, weight)
+    check_colour_volume(colour, tsdf, weight)
+    check_colour_image(colour_image, depth, [("tsdf", tsdf), ("weight", weight), ("colour", colour), ("depth", depth),
+                                             ("pixel_weight", pixel_weight)])
+    if _overlap(colour, depth) or (pixel_weight is not None and _overlap(colour, pixel_weight)):
+        raise ValueError("colour must not alias the depth image or pixel_weight")
+    p.weighted.carve, p.weighted.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
+    p.colour_band = colour_band_of(colour_band)
+    record, scratch = _record_and_scratch(tsdf, record, _lib.FUSION_COLOUR_SCRATCH_BYTES)
+    check(lib.lsf_fusion_integrate_depth_colour(
+        ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(colour.data_ptr()),
+        ctypes.c_void_p(depth.data_ptr()), ctypes.c_void_p(None if pixel_weight is None else pixel_weight.data_ptr()),
+        ctypes.c_void_p(colour_image.data_ptr()), ctypes.c_void_p(record.data_ptr()),
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_colour")
+    return record
+
+
 def unpack_record(r):
     """the host record (RECORD float64) as a dict: exact counts as ints, the float64 sum and the max"""
     r = np.asarray(r, dtype=np.float64).reshape(-1)
@@ -185,4 +265,12 @@ def unpack_weighted_record(r):
     out = unpack_record(r)
     r = np.asarray(r, dtype=np.float64).reshape(-1)
     out["carved"], out["weight_rejected"] = int(r[4]), int(r[5])
+    return out
+
+
+def unpack_colour_record(r):
+    """unpack_weighted_record of a colour call, with its two further exact counts: coloured and first_coloured"""
+    out = unpack_weighted_record(r)
+    r = np.asarray(r, dtype=np.float64).reshape(-1)
+    out["coloured"], out["first_coloured"] = int(r[6]), int(r[7])
     return out

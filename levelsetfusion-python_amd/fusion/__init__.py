@@ -21,6 +21,18 @@ of w.  A surface that later frames look through is thereby averaged towards +1: 
 DepthConfidence builds the weight image c = |n . r| min(1, (reference_depth / z)^2) on the device from the level-0
 depth and normals of a DepthPyramid (csrc/lsf_depth_confidence.hip; INTEGRATION.md section 3, "Depth confidence"):
 grazing and far pixels, whose axial noise grows with z^2, count less.
+Colour ("Colour fusion"; tests/colour_restatement.py restates it): CanonicalVolume(shape,
+max_weight, colour=True) also holds `colour`, a float32 (Z, Y, X, 4) device tensor of one 16-byte record per voxel --
+R, G, B in units of the 8-bit image and the colour weight Wc, all starting at 0.  integrate_depth(..., colour_image=,
+colour_band=1.0) takes a uint8 (H, W, 3) image registered to the depth camera, fuses the geometry exactly as the
+weighted rule does with the same arguments, and colours every voxel with a valid pixel whose live value lies strictly
+inside (-colour_band, colour_band) and whose w_eff is finite and > 0:
+    Wc1 = Wc + w_eff,  C_j = (Wc C_j + w_eff c_j) / Wc1,  Wc = min(Wc1, max_weight)
+in float32, c_j the pixel's channel.  Carved voxels are never coloured; every other voxel keeps its record bit for bit.
+A small colour_band keeps the colour of a voxel to the frames that see the surface near it, not through it.  The record
+gains coloured and first_coloured (unpack_colour_record).  extract_mesh(..., colours=True) adds the uint8 (V, 3) vertex
+colours: a vertex on the edge from voxel v to w takes C_v (1 - t) + C_w t with the vertex's own t when both have
+Wc > 0, the colour of the one that has, else default_colour; mesh_io.write_ply(..., colours=) writes them.
 CanonicalVolume.raycast renders the model into a depth (and normal) image seen from a camera at a twist: one launch of
 csrc/lsf_raycast.hip ("Ray-casting"; tests/raycast_restatement.py restates it).
 CanonicalVolume.extract_mesh takes the model's surface out as a triangle mesh: marching cubes over the cells whose 8
@@ -49,6 +61,10 @@ With `carve` or `confidence` (a DepthConfidence) every frame, frame 0 included, 
 confidence image comes from the frame's own pyramid -- the tracker's, built once, when "icp" mode has an `icp_pyramid`
 with the filter settings of `confidence.pyramid`, else a one-level pyramid of those settings.  Neither combines with a
 non-rigid optimizer: volume-mode carving would need an observation mask warped with the live field.
+With `colour` the model holds a colour volume, integrate(depth_image, colour_image) needs a colour image on every frame
+and fuses it through the colour entry point, with `carve` and `confidence` as set, in every tracking mode; tracking
+does not read the colour.  It does not combine with a non-rigid optimizer either: the colour would have to be warped
+with the live field.
 With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
 generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
 
@@ -63,8 +79,9 @@ field between frames as a warm start, a whole frame enqueued without host synchr
 fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, fusing the filtered depth, a
 downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
 an adaptive ray-casting step, a colour or confidence image in the
-prediction, marching squares for 2-D models, vertex attributes beyond normals, welding vertices by position,
-decimation, and a mesh extracted without the host read of its totals."""
+prediction, photometric (colour) tracking, colour in volume mode and with the non-rigid step, a colour image of another
+resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
+colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
 import math
 
 import numpy as np
@@ -72,7 +89,8 @@ import torch
 
 from .. import device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
-from ..device_fusion import RECORD_FIELDS, WEIGHTED_RECORD_FIELDS, unpack_record, unpack_weighted_record
+from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WEIGHTED_RECORD_FIELDS, unpack_colour_record,
+                             unpack_record, unpack_weighted_record)
 from ..rigid_opt.depth_pyramid import DepthPyramid
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
@@ -80,7 +98,8 @@ from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "unpack_record", "unpack_weighted_record",
-           "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS", "TRACKING_REFERENCES", "TRACKING_MODES"]
+           "unpack_colour_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS", "COLOUR_RECORD_FIELDS",
+           "TRACKING_REFERENCES", "TRACKING_MODES"]
 
 # the trackers with a reference volume (rigid_run_3d), and every tracking mode SequenceFusion3d accepts
 TRACKING_REFERENCES = ("model", "raycast")
@@ -149,34 +168,59 @@ def _pixel_weight(pixel_weight):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
+def _colour_image(colour_image):
+    if isinstance(colour_image, torch.Tensor):
+        return colour_image if colour_image.is_cuda else colour_image.to("cuda")
+    a = np.asarray(colour_image)
+    if a.dtype != np.uint8:
+        raise ValueError("colour_image must be uint8, got %s" % a.dtype)
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
 class CanonicalVolume:
     """the weighted canonical TSDF: `tsdf` and `weight`, float32 device tensors of `shape` ((Z, Y, X), (H, W) or an
-    int for a cube).  Depth mode needs a 3-D volume."""
+    int for a cube).  Depth mode needs a 3-D volume.  With colour=True (3-D only) also `colour`, a float32 device
+    tensor of shape (Z, Y, X, 4): R, G, B in 0..255 and the colour weight, all 0 at the start; None otherwise."""
 
-    def __init__(self, shape, max_weight=math.inf):
+    def __init__(self, shape, max_weight=math.inf, colour=False):
+        if colour and np.ndim(shape) != 0 and np.size(shape) != 3:
+            raise ValueError("a colour volume needs a 3-D model, got shape %s" % (tuple(shape),))
         require_gpu()
         self.shape = _model_shape(shape)
         device_fusion.fusion_weights(1.0, max_weight)
         self.max_weight = max_weight
         self.tsdf = torch.ones(self.shape, dtype=torch.float32, device="cuda")
         self.weight = torch.zeros(self.shape, dtype=torch.float32, device="cuda")
+        self.colour = torch.zeros(self.shape + (4,), dtype=torch.float32, device="cuda") if colour else None
 
     def reset(self):
-        """back to the empty model: tsdf 1, weight 0 everywhere"""
+        """back to the empty model: tsdf 1, weight 0 everywhere (and a colour volume 0)"""
         self.tsdf.fill_(1.0)
         self.weight.zero_()
+        if self.colour is not None:
+            self.colour.zero_()
 
     def integrate_volume(self, live, weight=1.0):
         """fuse a live field of the model's shape (numpy or a float32 device tensor); returns the device record"""
         return device_fusion.integrate_volume(self.tsdf, self.weight, _live(live), weight, self.max_weight)
 
     def integrate_depth(self, depth_image, camera, twist, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
-                        weight=1.0, pixel_weight=None, carve=False):
+                        weight=1.0, pixel_weight=None, carve=False, colour_image=None, colour_band=1.0):
         """generate the live volume of depth_image (uint16 / float32 / float64, numpy or device) under twist, as the
         rigid tracker does, and fuse it in the same pass; returns the device record.  pixel_weight (a float32 image of
         depth_image's shape, numpy or device) and carve choose the weighted rule (module docstring), whose record
-        unpack_weighted_record reads; with neither the call is the unweighted one."""
+        unpack_weighted_record reads; with neither the call is the unweighted one.  colour_image (uint8 (H, W, 3),
+        numpy or device, registered to depth_image; the volume must have been made with colour=True) also fuses colour
+        inside (-colour_band, colour_band), the geometry as the weighted rule does; unpack_colour_record reads its
+        record."""
         depth, code = device_depth(depth_image)
+        if colour_image is not None:
+            if self.colour is None:
+                raise ValueError("colour_image needs a volume made with colour=True")
+            return device_fusion.integrate_depth_colour(self.tsdf, self.weight, self.colour, depth, code, camera,
+                                                        array_offset, twist, _colour_image(colour_image), voxel_size,
+                                                        narrow_band_width_voxels, weight, self.max_weight,
+                                                        _pixel_weight(pixel_weight), carve, colour_band)
         if pixel_weight is None and not carve:
             return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
                                                  voxel_size, narrow_band_width_voxels, weight, self.max_weight)
@@ -199,18 +243,27 @@ class CanonicalVolume:
             out = tuple(t.cpu().numpy() for t in out)
         return out if normals else out[0]
 
-    def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False):
+    def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False,
+                     colours=False, default_colour=device_mesh.DEFAULT_COLOUR):
         """the level set iso of the model as a triangle mesh, with raycast's conventions (voxel (i, j, k) at
         ((k, j, i) + array_offset) * voxel_size): float32 vertices (V, 3) in world metres, (x, y, z); int32 faces
         (F, 3), their right-hand normal towards larger tsdf; with normals=True also the float32 unit normals (V, 3).
         Only cells whose 8 corners have weight > min_weight draw.  Returns (vertices, faces) or (vertices, faces,
-        normals): device tensors with as_tensor=True, numpy copies otherwise.  One host synchronisation: the read of
-        the two totals."""
+        normals): device tensors with as_tensor=True, numpy copies otherwise.  With colours=True (a volume made with
+        colour=True) the uint8 vertex colours (V, 3) are appended, row i the colour of vertex i, default_colour where
+        neither end of the vertex's grid edge has a colour.  One host synchronisation: the read of the two totals."""
         if len(self.shape) != 3:
             raise ValueError("mesh extraction needs a 3-D model, this one has shape %s" % (self.shape,))
-        verts, faces, out_normals = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso,
-                                                             min_weight, normals)
-        out = (verts, faces, out_normals) if normals else (verts, faces)
+        if not colours:
+            verts, faces, out_normals = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso,
+                                                                 min_weight, normals)
+            out = (verts, faces, out_normals) if normals else (verts, faces)
+        else:
+            if self.colour is None:
+                raise ValueError("colours=True needs a volume made with colour=True")
+            verts, faces, out_normals, out_colours = device_mesh.extract_mesh(
+                self.tsdf, self.weight, array_offset, voxel_size, iso, min_weight, normals, self.colour, default_colour)
+            out = (verts, faces, out_normals, out_colours) if normals else (verts, faces, out_colours)
         if not as_tensor:
             out = tuple(t.cpu().numpy() for t in out)
         return out
@@ -229,13 +282,18 @@ class SequenceFusion3d:
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
-                 icp_max_normal_angle=None, carve=False, confidence=None):
+                 icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0):
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
         if nonrigid_optimizer is not None and (self.carve or confidence is not None):
             raise ValueError("carve and confidence need depth-mode fusion and do not combine with a nonrigid_optimizer: "
                              "volume-mode carving needs an observation mask warped with the live field")
+        self.colour = bool(colour)
+        if nonrigid_optimizer is not None and self.colour:
+            raise ValueError("colour needs depth-mode fusion and does not combine with a nonrigid_optimizer: "
+                             "the colour would have to be warped with the live field")
+        self.colour_band = device_fusion.colour_band_of(colour_band)
         self.camera = camera
         self.field_shape = device_rigid.volume_shape(field_shape)
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
@@ -260,7 +318,7 @@ class SequenceFusion3d:
         self.nonrigid_optimizer = nonrigid_optimizer
         self.initial_twist = np.zeros(6) if initial_twist is None else device_rigid.twist6(initial_twist).copy()
         self.tracking_reference = tracking_reference
-        self.canonical = CanonicalVolume(self.field_shape, max_weight)
+        self.canonical = CanonicalVolume(self.field_shape, max_weight, colour=self.colour)
         self.twists = []
         self.frame_records = []
         self.prediction = None  # "raycast", "icp": the last prediction, a float32 device depth image in metres
@@ -301,8 +359,13 @@ class SequenceFusion3d:
             return c.from_levels(self.icp.last_pyramid, self.camera)
         return c.build_device(depth, code, self.camera)
 
-    def integrate(self, depth_image):
-        """track and fuse one frame; returns its record (also appended to frame_records)"""
+    def integrate(self, depth_image, colour_image=None):
+        """track and fuse one frame; returns its record (also appended to frame_records).  A sequence made with
+        colour=True needs the frame's colour_image (uint8 (H, W, 3), numpy or device), any other takes none"""
+        if self.colour and colour_image is None:
+            raise ValueError("a sequence made with colour=True needs a colour_image on every frame")
+        if not self.colour and colour_image is not None:
+            raise ValueError("colour_image needs a sequence made with colour=True")
         k = len(self.twists)
         depth, code = device_depth(depth_image)
         model = self.canonical
@@ -326,7 +389,14 @@ class SequenceFusion3d:
                 rigid_records = [unpack_rigid_record(r) for r in records]
                 del reference
         unpack = unpack_record
-        if self.carve or self.confidence is not None:
+        if self.colour:
+            record = device_fusion.integrate_depth_colour(
+                model.tsdf, model.weight, model.colour, depth, code, self.camera, self.array_offset, twist,
+                _colour_image(colour_image), w=1.0, max_weight=model.max_weight,
+                pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve, colour_band=self.colour_band,
+                **gen)
+            unpack = unpack_colour_record
+        elif self.carve or self.confidence is not None:
             record = device_fusion.integrate_depth_weighted(
                 model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, w=1.0,
                 max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
@@ -351,6 +421,8 @@ class SequenceFusion3d:
         self.frame_records.append(frame)
         return frame
 
-    def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False):
+    def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False, colours=False,
+                     default_colour=device_mesh.DEFAULT_COLOUR):
         """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size"""
-        return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor)
+        return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
+                                           colours, default_colour)
