@@ -1072,6 +1072,40 @@ int lsf_fusion_integrate_depth_colour(float *tsdf, float *weight, float *colour,
                                       const float *pixel_weight, const uint8_t *colour_image, double *record,
                                       void *scratch, const lsf_fusion_colour_params *params, void *stream);
 
+/* ---- weighted depth-mode fusion through a non-rigid warp field -------------------------------------------------------
+ * The rule is INTEGRATION.md section 3, "Warped depth fusion".  warp holds one displacement psi per voxel, float32
+ * [depth][height][width][3] interleaved, channel 0 the x displacement, 1 y, 2 z, in voxels: the cumulative warp
+ * HierarchicalOptimizer3d.optimize(canonical, live) returns, live(v + psi(v)) ~ canonical(v).  Voxel (x, y, z) observes
+ * the frame at its warped point
+ *   ((float)((((double)x + (double)psi_x) + array_offset[0]) * voxel_size), likewise y and z)
+ * -- lsf_fusion_integrate_depth's voxel point with one float64 add in front, so psi = +-0 reproduces it exactly.  That
+ * point is transformed, projected and compared with the depth at its pixel exactly as the voxel's centre is, and from
+ * there on the rule is lsf_fusion_integrate_depth_weighted's (valid pixel, in band, carved at exactly +1 with carve,
+ * w_eff = weight * pixel_weight[pixel], weight rejection) and, with a colour volume, lsf_fusion_integrate_depth_colour's
+ * (colour band, the pixel's colour under w_eff).  A voxel whose psi has a component that is not finite is left alone,
+ * its colour record too, and is counted in warp_rejected and in nothing else.  With psi = 0 everywhere tsdf, weight,
+ * colour and record [0..7] equal those entry points' bit for bit.  The record has LSF_FUSION_WARPED_RECORD_DOUBLES
+ * doubles: [0..7] as lsf_fusion_integrate_depth_colour ([6], [7] are 0 without colour), [8] warp_rejected; summed as
+ * above, reruns bit-identical. */
+typedef struct lsf_fusion_warped_params {
+    lsf_fusion_colour_params colour; /* as lsf_fusion_integrate_depth_colour reads it; colour_band is checked with
+                                        has_colour only */
+    int32_t has_colour;              /* 0: colour and colour_image are NULL; else both are given */
+} lsf_fusion_warped_params;
+#define LSF_FUSION_WARPED_RECORD_DOUBLES 9
+/* per-workgroup partials: the colour call's eight, warp_rejected */
+#define LSF_FUSION_WARPED_SCRATCH_BYTES (LSF_FUSION_MAX_BLOCKS * 9 * 8)
+
+/* tsdf, weight, depth_image, pixel_weight (NULL allowed): as lsf_fusion_integrate_depth_weighted.  colour, colour_image:
+ * as lsf_fusion_integrate_depth_colour, both given or both NULL.  warp: DEVICE float32, 3 * depth * height * width, read
+ * with 16-byte accesses when its base is 16-byte aligned.  record: DEVICE LSF_FUSION_WARPED_RECORD_DOUBLES doubles;
+ * scratch: DEVICE, LSF_FUSION_WARPED_SCRATCH_BYTES.  tsdf, weight, colour, warp, depth_image, pixel_weight and
+ * colour_image must not overlap one another.  Two launches, no host synchronisation. */
+int lsf_fusion_integrate_depth_warped(float *tsdf, float *weight, float *colour, const float *warp,
+                                      const void *depth_image, const float *pixel_weight, const uint8_t *colour_image,
+                                      double *record, void *scratch, const lsf_fusion_warped_params *params,
+                                      void *stream);
+
 /* ---- a per-pixel confidence image for weighted fusion ----------------------------------------------------------------
  * c(u, v) = |n . r| min(1, (reference_depth / z)^2): the cosine between the pixel's unit ray r and its normal n, times
  * the inverse of the sensor's axial noise growth beyond reference_depth.  Every step is one float64 operation, in this

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "4fec077c2ef775e5"
+HEADER_ABI_HASH = "5802ce7ed08edc24"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -218,6 +218,15 @@ class FusionColourParams(ctypes.Structure):
     _fields_ = [("weighted", FusionWeightedParams), ("colour_band", ctypes.c_float)]
 
 
+FUSION_WARPED_RECORD_DOUBLES = 9
+FUSION_WARPED_SCRATCH_BYTES = FUSION_MAX_BLOCKS * 9 * 8
+
+
+class FusionWarpedParams(ctypes.Structure):
+    """lsf_fusion_warped_params: weighted depth-mode fusion through a warp field (lsf_fusion_integrate_depth_warped)"""
+    _fields_ = [("colour", FusionColourParams), ("has_colour", ctypes.c_int32)]
+
+
 class DepthConfidenceParams(ctypes.Structure):
     """lsf_depth_confidence_params: the per-pixel confidence image (lsf_depth_confidence)"""
     _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "reference_depth")] + \
@@ -396,6 +405,8 @@ PROTOTYPES = {
                                                            _vp]),
     "lsf_fusion_integrate_depth_colour": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                          _P(FusionColourParams), _vp]),
+    "lsf_fusion_integrate_depth_warped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                         _P(FusionWarpedParams), _vp]),
     "lsf_depth_confidence": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthConfidenceParams), _vp]),
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),

@@ -18,6 +18,10 @@
 // "Colour fusion"; tests/colour_restatement.py): one float32 (R, G, B, Wc) record per voxel, loaded and stored in one
 // 16-byte access each and only where the voxel lies inside the colour band, three byte reads of the colour image at the
 // voxel's pixel, and eight partials per workgroup.  The geometry code is fuse_voxel_weighted itself.
+// lsf_fusion_integrate_depth_warped is the non-rigid step's fusion ("Warped depth fusion";
+// tests/warped_fusion_restatement.py): a voxel observes the frame at its point displaced by a warp field, float32
+// (Z, Y, X, 3) interleaved -- 12 floats per four-voxel step, three 16-byte loads -- and fuse_voxel_weighted and
+// colour_voxel run unchanged on what that point sees (typed_tsdf_sample_at); nine partials per workgroup.
 #include "lsf_device.h"
 #include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
@@ -29,6 +33,7 @@ namespace {
 constexpr int kParts = 4;   // fused, first_seen, sum |t1 - t|, max |t1 - t|
 constexpr int kWParts = 6;  // the weighted rule: those, carved, weight_rejected
 constexpr int kCParts = 8;  // with colour: those, coloured, first_coloured
+constexpr int kXParts = 9;  // through a warp field: those, warp_rejected
 constexpr int kMaxPart = 3; // the one partial that is a maximum; every other is a sum
 constexpr int kMaxBlocks = LSF_FUSION_MAX_BLOCKS;
 constexpr int kRec = LSF_FUSION_RECORD_DOUBLES;
@@ -36,6 +41,8 @@ static_assert(kRec >= kWParts && kRec >= kCParts, "the record holds the results 
 static_assert(LSF_FUSION_SCRATCH_BYTES == kMaxBlocks * kParts * 8, "a workgroup's partials");
 static_assert(LSF_FUSION_WEIGHTED_SCRATCH_BYTES == kMaxBlocks * kWParts * 8, "a workgroup's partials");
 static_assert(LSF_FUSION_COLOUR_SCRATCH_BYTES == kMaxBlocks * kCParts * 8, "a workgroup's partials");
+static_assert(LSF_FUSION_WARPED_SCRATCH_BYTES == kMaxBlocks * kXParts * 8, "a workgroup's partials");
+static_assert(LSF_FUSION_WARPED_RECORD_DOUBLES == kXParts, "the warped record is its partials");
 
 enum Source { VOLUME = 0, DEPTH = 1 };
 
@@ -346,6 +353,101 @@ __global__ __launch_bounds__(kBlock) void fusion_colour_kernel(float* __restrict
         for (int c8 = 0; c8 < kCParts; ++c8) scratch[(size_t)blockIdx.x * kCParts + c8] = v[c8];
 }
 
+// the twelve warp floats of the four voxels from i on: three 16-byte loads, or scalar ones off alignment
+__device__ inline void load_warp4(const float* __restrict__ warp, long long i, float (&v)[12], bool aligned) {
+    const float* f = warp + i * 3;
+    if (aligned) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float4 q = reinterpret_cast<const float4*>(f)[k];
+            v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = f[k];
+    }
+}
+
+// what voxel i sees at its point displaced by psi = (px, py, pz) voxels: depth_sample with one float64 add in front of
+// the voxel point's expression, so psi = +-0 gives depth_sample's bits.  A psi that is not finite sees nothing and is
+// counted
+template <typename DT, typename PT>
+__device__ inline TsdfSample warped_sample(const DT* __restrict__ depth, const FusionDev& p, const double* e,
+                                           long long i, float px, float py, float pz, int& rejected) {
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) {
+        rejected += 1;
+        return {p.t.default_value, -1, false};
+    }
+    const long long row = i / p.nx;
+    const int x = (int)(i - row * p.nx);
+    const int z = (int)(row / p.ny);
+    const int y = (int)(row - (long long)z * p.ny);
+    const float xv = (float)((((double)x + (double)px) + p.t.off[0]) * p.t.voxel_size);
+    const float yv = (float)((((double)y + (double)py) + p.t.off[1]) * p.t.voxel_size);
+    const float zv = (float)((((double)z + (double)pz) + p.t.off[2]) * p.t.voxel_size);
+    return typed_tsdf_sample_at<3, double, PT, DT>(depth, p.t, e, xv, yv, zv);
+}
+
+// the weighted rule (and colour, when c.volume is given) at the warped point of every voxel: fusion_colour_kernel's
+// walk, stores and partials
+template <typename DT, typename PT>
+__global__ __launch_bounds__(kBlock) void fusion_warped_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
+                                                               const float* __restrict__ warp,
+                                                               const DT* __restrict__ depth,
+                                                               const float* __restrict__ pixel_weight,
+                                                               double* __restrict__ scratch, FusionDev p, int carve,
+                                                               ColourDev c, int warp_aligned) {
+    __shared__ double e[12];
+    __shared__ double red[kBlock / kWave][kXParts];
+    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
+    __syncthreads();
+    const bool aligned = p.aligned != 0, carving = carve != 0, psi_aligned = warp_aligned != 0;
+    const bool colouring = c.volume != nullptr;
+    ColourAcc a = {{{0, 0, 0.0, 0.0f}, 0, 0}, 0, 0};
+    int rejected = 0;
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
+        const long long i = g * 4;
+        TsdfSample s[4];
+        float psi[12], t[4], W[4];
+        load_warp4(warp, i, psi, psi_aligned);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            s[k] = warped_sample<DT, PT>(depth, p, e, i + k, psi[3 * k], psi[3 * k + 1], psi[3 * k + 2], rejected);
+        load4(tsdf, i, t, aligned);
+        load4(weight, i, W, aligned);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a.w)) {
+                any = true;
+                if (colouring) colour_voxel(s[k], pixel_weight, c, i + k, p, a);
+            }
+        if (any) {  // a step without an updated voxel stores nothing
+            store4(tsdf, i, t, aligned);
+            store4(weight, i, W, aligned);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
+        for (long long i = p.groups * 4; i < p.n; ++i) {
+            float t = tsdf[i], W = weight[i];
+            const float* f = warp + i * 3;
+            const TsdfSample s = warped_sample<DT, PT>(depth, p, e, i, f[0], f[1], f[2], rejected);
+            if (fuse_voxel_weighted(s, pixel_weight, carving, t, W, p, a.w)) {
+                tsdf[i] = t;
+                weight[i] = W;
+                if (colouring) colour_voxel(s, pixel_weight, c, i, p, a);
+            }
+        }
+    double v[kXParts] = {(double)a.w.a.fused, (double)a.w.a.first,  a.w.a.sum,          (double)a.w.a.max,
+                         (double)a.w.carved,  (double)a.w.rejected, (double)a.coloured, (double)a.first,
+                         (double)rejected};
+    block_combine(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c9 = 0; c9 < kXParts; ++c9) scratch[(size_t)blockIdx.x * kXParts + c9] = v[c9];
+}
+
 // one workgroup: lane q combines partials q, q + kBlock, ... in order, then the block in a fixed order
 template <int N>
 __global__ __launch_bounds__(kBlock) void fusion_finish_kernel(const double* __restrict__ scratch,
@@ -418,6 +520,18 @@ int launch_colour(float* tsdf, float* weight, const void* depth, const float* pi
                        reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve, c);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(fusion_finish_kernel<kCParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
+                       p.nblocks);
+    return launch_status();
+}
+
+template <typename DT, typename PT>
+int launch_warped(float* tsdf, float* weight, const float* warp, const void* depth, const float* pixel_weight,
+                  double* record, double* scratch, const FusionDev& p, int carve, const ColourDev& c, int warp_aligned,
+                  hipStream_t s) {
+    hipLaunchKernelGGL((fusion_warped_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, warp,
+                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve, c, warp_aligned);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(fusion_finish_kernel<kXParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
                        p.nblocks);
     return launch_status();
 }
@@ -516,5 +630,43 @@ extern "C" int lsf_fusion_integrate_depth_colour(float* tsdf, float* weight, flo
     return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
         return launch_colour<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p, carve,
                                                          c, s);
+    });
+}
+
+extern "C" int lsf_fusion_integrate_depth_warped(float* tsdf, float* weight, float* colour, const float* warp,
+                                                 const void* depth_image, const float* pixel_weight,
+                                                 const uint8_t* colour_image, double* record, void* scratch,
+                                                 const lsf_fusion_warped_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!params || !warp) return LSF_ERR_BAD_ARGUMENT;
+    const lsf_fusion_weighted_params* wp = &params->colour.weighted;
+    const lsf_fusion_params* f = &wp->fusion;
+    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
+    FusionDev p;
+    if (int e = convert(f, p)) return e;
+    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
+    if ((wp->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    const bool has_colour = params->has_colour != 0;
+    if (has_colour != (colour != nullptr) || has_colour != (colour_image != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    const float band = params->colour.colour_band;
+    if (has_colour) {
+        if (!(band > 0.0f && band <= 1.0f)) return LSF_ERR_BAD_ARGUMENT;  // NaN fails
+        if (((uintptr_t)colour & 15) != 0) return LSF_ERR_BAD_ARGUMENT;
+    }
+    const size_t pixels = (size_t)f->tsdf.image_width * f->tsdf.image_height, model = (size_t)p.n * 4;
+    const size_t depth_bytes = pixels * (f->depth_dtype == LSF_DEPTH_U16 ? 2 : (f->depth_dtype == LSF_DEPTH_F32 ? 4 : 8));
+    const void* const buffers[7] = {tsdf, weight, colour, warp, depth_image, pixel_weight, colour_image};
+    const size_t bytes[7] = {model, model, model * 4, model * 3, depth_bytes, pixels * 4, pixels * 3};
+    for (int i = 0; i < 7; ++i)
+        for (int j = i + 1; j < 7; ++j)
+            if (overlaps(buffers[i], bytes[i], buffers[j], bytes[j])) return LSF_ERR_BAD_ARGUMENT;
+    p.aligned = aligned16(tsdf) && aligned16(weight);
+    hipStream_t s = as_stream(stream);
+    double* sc = reinterpret_cast<double*>(scratch);
+    const int carve = wp->carve != 0, warp_aligned = aligned16(warp);
+    const ColourDev c{reinterpret_cast<float4*>(colour), colour_image, has_colour ? band : 1.0f};
+    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch_warped<decltype(dt), decltype(pt)>(tsdf, weight, warp, depth_image, pixel_weight, record, sc, p,
+                                                         carve, c, warp_aligned, s);
     });
 }

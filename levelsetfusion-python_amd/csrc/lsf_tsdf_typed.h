@@ -2,8 +2,9 @@
 // tsdf/generation.py:130-207, :356-437; tsdf/common.py:34-47): uint16 / float32 / float64 depth, fractional array
 // offsets, and an extrinsic evaluated in its own dtype.  Shared by lsf_tsdf.hip, the live-field stages of lsf_rigid.hip
 // and lsf_rigid3d.hip, and depth-mode fusion (lsf_fusion.hip; the weighted rule also reads the pixel a voxel projects
-// to, typed_tsdf_sample), as is the host-side setup at the end of this file (lsf_tsdf_params -> TypedTsdf, the
-// depth-dtype and image checks, the (depth dtype, intrinsics dtype) dispatch).
+// to, typed_tsdf_sample, and warped fusion samples at a displaced point, typed_tsdf_sample_at), as is the host-side
+// setup at the end of this file (lsf_tsdf_params -> TypedTsdf, the depth-dtype and image checks, the (depth dtype,
+// intrinsics dtype) dispatch).
 // The dtypes are those numpy >= 2 gives the reference's expressions (oracle: tests/rigid_restatement.py):
 //   voxel point     ((index + offset) * voxel_size) in float64, rounded to float32 (np.array(..., dtype=float32))
 //   camera point    extrinsic.dot(point): float32 or float64 as the extrinsic, ((e0 x + e1 y) + e2 z) + e3
@@ -51,17 +52,13 @@ struct TsdfSample {
     bool valid;
 };
 
-// D = 2: field[y][x], x from the x index, the depth axis from the y index, y_voxel = 0, depth row p.image_y.
-// D = 3: field[z][y][x].  E = float or double: the extrinsic's dtype (e: first three rows, row-major); P = the
-// intrinsic matrix's dtype; DT = the depth image's element type.
+// what the float32 point (xv, yv, zv), in the generator's metres, sees: everything of typed_tsdf_sample after the voxel
+// point.  Warped depth fusion (lsf_fusion.hip) calls it with a voxel's point displaced by a warp field.
 template <int D, typename E, typename P, typename DT>
-__device__ inline TsdfSample typed_tsdf_sample(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x,
-                                               int y, int z) {
+__device__ inline TsdfSample typed_tsdf_sample_at(const DT* __restrict__ depth, const TypedTsdf& p, const E* e,
+                                                  float xv, float yv, float zv) {
     using Q = decltype(E() + P());
     const TsdfSample none = {p.default_value, -1, false};
-    const float xv = (float)(((double)x + p.off[0]) * p.voxel_size);
-    const float yv = D == 3 ? (float)(((double)y + p.off[1]) * p.voxel_size) : 0.0f;
-    const float zv = (float)(((double)(D == 3 ? z : y) + p.off[2]) * p.voxel_size);
     const E pcx = ((e[0] * (E)xv + e[1] * (E)yv) + e[2] * (E)zv) + e[3] * (E)1;
     const E pcy = ((e[4] * (E)xv + e[5] * (E)yv) + e[6] * (E)zv) + e[7] * (E)1;
     const E pcz = ((e[8] * (E)xv + e[9] * (E)yv) + e[10] * (E)zv) + e[11] * (E)1;
@@ -74,6 +71,18 @@ __device__ inline TsdfSample typed_tsdf_sample(const DT* __restrict__ depth, con
     if (d <= 0) return none;  // NaN goes on, as in the reference
     using S = decltype(d + pcz);
     return {typed_tsdf_value<S>((S)d - (S)pcz, p.half_width), pixel, true};
+}
+
+// D = 2: field[y][x], x from the x index, the depth axis from the y index, y_voxel = 0, depth row p.image_y.
+// D = 3: field[z][y][x].  E = float or double: the extrinsic's dtype (e: first three rows, row-major); P = the
+// intrinsic matrix's dtype; DT = the depth image's element type.
+template <int D, typename E, typename P, typename DT>
+__device__ inline TsdfSample typed_tsdf_sample(const DT* __restrict__ depth, const TypedTsdf& p, const E* e, int x,
+                                               int y, int z) {
+    const float xv = (float)(((double)x + p.off[0]) * p.voxel_size);
+    const float yv = D == 3 ? (float)(((double)y + p.off[1]) * p.voxel_size) : 0.0f;
+    const float zv = (float)(((double)(D == 3 ? z : y) + p.off[2]) * p.voxel_size);
+    return typed_tsdf_sample_at<D, E, P, DT>(depth, p, e, xv, yv, zv);
 }
 
 // the live value alone: what the generator, the trackers and unweighted fusion read

@@ -1,8 +1,8 @@
 """Torch-facing wrapper of the fusion entry points (include/lsf_hip.h: lsf_fusion_integrate_volume,
-lsf_fusion_integrate_depth, lsf_fusion_integrate_depth_weighted, lsf_fusion_integrate_depth_colour).  Every argument is
-checked on the host before a launch; a call enqueues two launches and returns the record as a device tensor without
-waiting for it -- the caller decides when to copy it back.  The public interface is fusion.CanonicalVolume /
-fusion.SequenceFusion3d."""
+lsf_fusion_integrate_depth, lsf_fusion_integrate_depth_weighted, lsf_fusion_integrate_depth_colour,
+lsf_fusion_integrate_depth_warped).  Every argument is checked on the host before a launch; a call enqueues two launches
+and returns the record as a device tensor without waiting for it -- the caller decides when to copy it back.  The public
+interface is fusion.CanonicalVolume / fusion.SequenceFusion3d."""
 import ctypes
 import math
 
@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FusionColourParams, FusionParams, FusionWeightedParams, check, lib
+from ._lib import FusionColourParams, FusionParams, FusionWarpedParams, FusionWeightedParams, check, lib
 from .device_core import require_gpu, stream_ptr
 from .device_rigid import _tsdf3d, twist6
 from .tsdf.generation import offsets_of
@@ -19,6 +19,8 @@ RECORD = _lib.FUSION_RECORD_DOUBLES
 RECORD_FIELDS = ("fused", "first_seen", "sum_abs_change", "max_abs_change")
 WEIGHTED_RECORD_FIELDS = RECORD_FIELDS + ("carved", "weight_rejected")
 COLOUR_RECORD_FIELDS = WEIGHTED_RECORD_FIELDS + ("coloured", "first_coloured")
+WARPED_RECORD = _lib.FUSION_WARPED_RECORD_DOUBLES
+WARPED_RECORD_FIELDS = COLOUR_RECORD_FIELDS + ("warp_rejected",)
 
 
 def fusion_weights(weight, max_weight):
@@ -253,6 +255,67 @@ def integrate_depth_colour(tsdf, weight, colour, depth, depth_code, camera, arra
     return record
 
 
+def check_warp(warp, tsdf, others):
+    """a warp field: a float32 contiguous tensor of shape tsdf.shape + (3,) on the model's device (what
+    HierarchicalOptimizer3d.optimize returns for device inputs), aliasing none of `others` ((name, tensor) pairs; None
+    tensors are skipped)"""
+    if not isinstance(warp, torch.Tensor):
+        raise TypeError("warp must be a torch tensor, got %s" % type(warp).__name__)
+    if warp.dtype != torch.float32:
+        raise ValueError("warp must be float32, got %s" % warp.dtype)
+    if warp.device != tsdf.device:
+        raise ValueError("warp is on %s, tsdf on %s: all buffers must be on one device" % (warp.device, tsdf.device))
+    if not warp.is_contiguous():
+        raise ValueError("warp must be contiguous")
+    if tuple(warp.shape) != tuple(tsdf.shape) + (3,):
+        raise ValueError("warp has shape %s, the model %s: it must be the model's shape + (3,)"
+                         % (tuple(warp.shape), tuple(tsdf.shape)))
+    for name, t in others:
+        if t is not None and _overlap(warp, t):
+            raise ValueError("warp must not alias %s" % name)
+
+
+def integrate_depth_warped(tsdf, weight, depth, depth_code, camera, array_offset, twist, warp, voxel_size=0.004,
+                           narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None, carve=False,
+                           colour=None, colour_image=None, colour_band=1.0, record=None):
+    """integrate_depth_weighted -- and integrate_depth_colour, when colour and colour_image are given (both or neither)
+    -- through a non-rigid warp field ("Warped depth fusion"): warp is a float32 device tensor
+    of shape tsdf.shape + (3,), channel 0 the x displacement, 1 y, 2 z, in voxels; voxel v observes the frame at
+    v + warp[v] in place of its centre, and a voxel whose displacement is not finite is left alone and counted.  With a
+    zero warp the result equals those calls bit for bit.  Two launches, no host wait; returns the record, WARPED_RECORD
+    doubles (unpack_warped_record once it is on the host)"""
+    require_gpu()
+    if (colour is None) != (colour_image is None):
+        raise ValueError("colour and colour_image are given together or not at all")
+    p = FusionWarpedParams()
+    p.colour.weighted.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                                             narrow_band_width_voxels, w, max_weight, 1)
+    if pixel_weight is not None:
+        check_pixel_weight(pixel_weight, depth, tsdf, weight)
+    if colour is not None:
+        check_colour_volume(colour, tsdf, weight)
+        check_colour_image(colour_image, depth, [("tsdf", tsdf), ("weight", weight), ("colour", colour),
+                                                 ("depth", depth), ("pixel_weight", pixel_weight)])
+        if _overlap(colour, depth) or (pixel_weight is not None and _overlap(colour, pixel_weight)):
+            raise ValueError("colour must not alias the depth image or pixel_weight")
+    check_warp(warp, tsdf, [("tsdf", tsdf), ("weight", weight), ("colour", colour), ("depth", depth),
+                            ("pixel_weight", pixel_weight), ("colour_image", colour_image)])
+    p.colour.weighted.carve, p.colour.weighted.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
+    p.colour.colour_band = colour_band_of(colour_band)
+    p.has_colour = int(colour is not None)
+    if record is None:
+        record = torch.empty(WARPED_RECORD, dtype=torch.float64, device=tsdf.device)
+    scratch = torch.empty(_lib.FUSION_WARPED_SCRATCH_BYTES // 8, dtype=torch.float64, device=tsdf.device)
+
+    def ptr(t):
+        return ctypes.c_void_p(None if t is None else t.data_ptr())
+
+    check(lib.lsf_fusion_integrate_depth_warped(
+        ptr(tsdf), ptr(weight), ptr(colour), ptr(warp), ptr(depth), ptr(pixel_weight), ptr(colour_image), ptr(record),
+        ptr(scratch), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_warped")
+    return record
+
+
 def unpack_record(r):
     """the host record (RECORD float64) as a dict: exact counts as ints, the float64 sum and the max"""
     r = np.asarray(r, dtype=np.float64).reshape(-1)
@@ -273,4 +336,12 @@ def unpack_colour_record(r):
     out = unpack_weighted_record(r)
     r = np.asarray(r, dtype=np.float64).reshape(-1)
     out["coloured"], out["first_coloured"] = int(r[6]), int(r[7])
+    return out
+
+
+def unpack_warped_record(r):
+    """unpack_colour_record of a warped call (coloured and first_coloured are 0 without colour), with the exact count of
+    voxels whose displacement was not finite: warp_rejected"""
+    out = unpack_colour_record(r)
+    out["warp_rejected"] = int(np.asarray(r, dtype=np.float64).reshape(-1)[8])
     return out

@@ -59,14 +59,29 @@ by ICP against the model's prediction:
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
 With `carve` or `confidence` (a DepthConfidence) every frame, frame 0 included, is fused by the weighted rule; the
 confidence image comes from the frame's own pyramid -- the tracker's, built once, when "icp" mode has an `icp_pyramid`
-with the filter settings of `confidence.pyramid`, else a one-level pyramid of those settings.  Neither combines with a
-non-rigid optimizer: volume-mode carving would need an observation mask warped with the live field.
+with the filter settings of `confidence.pyramid`, else a one-level pyramid of those settings.
 With `colour` the model holds a colour volume, integrate(depth_image, colour_image) needs a colour image on every frame
 and fuses it through the colour entry point, with `carve` and `confidence` as set, in every tracking mode; tracking
-does not read the colour.  It does not combine with a non-rigid optimizer either: the colour would have to be warped
-with the live field.
-With one (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration) the live volume under the twist is
-generated, warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode.
+does not read the colour.
+With a `nonrigid_optimizer` that is a HierarchicalOptimizer3d, every frame k >= 1 is fused through its warp field
+("Warped depth fusion"; tests/warped_fusion_restatement.py restates it).  After tracking, the
+live volume under the twist is generated (device_rigid.live_volume_3d), `psi = optimizer.optimize(model.tsdf, live)` is
+the cumulative displacement in voxels with live(v + psi(v)) ~ model(v), a float32 (Z, Y, X, 3) device tensor (x, y, z
+channels), and the frame is fused in depth mode with "the voxel's centre" replaced by "the voxel's warped point":
+    point(v) = float32((float64(v) + float64(psi(v)) + array_offset) * voxel_size),   per axis
+is transformed by the twist, projected, and the depth, the pixel weight and the colour are read at its pixel; the
+weighted, carving and colour rules then apply unchanged (csrc/lsf_fusion.hip, lsf_fusion_integrate_depth_warped).  Nothing
+is warped as a volume, so `carve`, `confidence` and `colour` combine with this optimizer, and with this one only.  A voxel
+whose psi is not finite is left alone and counted in the record's warp_rejected (unpack_warped_record); psi = 0 gives
+the unwarped calls bit for bit.  Frame 0 is fused as without an optimizer; `warp` keeps the last psi.
+CanonicalVolume.integrate_depth(..., warp=) is the same call for a given field.  In 3-D the optimizer's default
+tikhonov_strength = 0.2 diverges: its recursion g <- data - s * laplace(g) has gain 12 s at the highest frequency of the
+7-point Laplacian, so s must lie below 1 / 12; 0.05 is stable.
+With any other non-rigid optimizer (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration: its final
+warp_field is the last iteration's update only, not a cumulative warp) the live volume under the twist is generated,
+warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode: unweighted,
+uncarved, uncoloured -- `carve`, `confidence` and `colour` raise with it, since the observation mask, the weights and
+the colour would have to be warped with the live field.
 
 Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
@@ -74,12 +89,12 @@ count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals.
 
-Not covered: carving or weights in volume mode and with the non-rigid step, a carve-distance limit, keeping the warp
-field between frames as a warm start, a whole frame enqueued without host synchronisations, z-slab / multi-GPU
-fusion, a 2-D depth-mode row generator, HierarchicalOptimizer3d as the non-rigid step, fusing the filtered depth, a
-downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
+Not covered: carving, weights or colour in volume mode, a cumulative warp out of SlavchevaOptimizer3d, a carve-distance
+limit, keeping the warp field between frames as a warm start, ray-casting or meshing in the live frame, a whole frame
+enqueued without host synchronisations, z-slab / multi-GPU fusion, a 2-D depth-mode row generator, fusing the filtered
+depth, a downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
 an adaptive ray-casting step, a colour or confidence image in the
-prediction, photometric (colour) tracking, colour in volume mode and with the non-rigid step, a colour image of another
+prediction, photometric (colour) tracking, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
 import math
@@ -89,8 +104,9 @@ import torch
 
 from .. import device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid
 from ..device_core import require_gpu
-from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WEIGHTED_RECORD_FIELDS, unpack_colour_record,
-                             unpack_record, unpack_weighted_record)
+from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
+                             unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
+from ..nonrigid_opt.hierarchical.hierarchical_optimizer3d import HierarchicalOptimizer3d
 from ..rigid_opt.depth_pyramid import DepthPyramid
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
@@ -98,7 +114,8 @@ from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "unpack_record", "unpack_weighted_record",
-           "unpack_colour_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS", "COLOUR_RECORD_FIELDS",
+           "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
+           "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
            "TRACKING_REFERENCES", "TRACKING_MODES"]
 
 # the trackers with a reference volume (rigid_run_3d), and every tracking mode SequenceFusion3d accepts
@@ -177,6 +194,15 @@ def _colour_image(colour_image):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
+def _warp(warp):
+    if isinstance(warp, torch.Tensor):
+        return warp if warp.is_cuda else warp.to("cuda")
+    a = np.asarray(warp)
+    if a.dtype != np.float32:
+        raise ValueError("warp must be float32, got %s" % a.dtype)
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
 class CanonicalVolume:
     """the weighted canonical TSDF: `tsdf` and `weight`, float32 device tensors of `shape` ((Z, Y, X), (H, W) or an
     int for a cube).  Depth mode needs a 3-D volume.  With colour=True (3-D only) also `colour`, a float32 device
@@ -205,18 +231,27 @@ class CanonicalVolume:
         return device_fusion.integrate_volume(self.tsdf, self.weight, _live(live), weight, self.max_weight)
 
     def integrate_depth(self, depth_image, camera, twist, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
-                        weight=1.0, pixel_weight=None, carve=False, colour_image=None, colour_band=1.0):
+                        weight=1.0, pixel_weight=None, carve=False, colour_image=None, colour_band=1.0, warp=None):
         """generate the live volume of depth_image (uint16 / float32 / float64, numpy or device) under twist, as the
         rigid tracker does, and fuse it in the same pass; returns the device record.  pixel_weight (a float32 image of
         depth_image's shape, numpy or device) and carve choose the weighted rule (module docstring), whose record
         unpack_weighted_record reads; with neither the call is the unweighted one.  colour_image (uint8 (H, W, 3),
         numpy or device, registered to depth_image; the volume must have been made with colour=True) also fuses colour
         inside (-colour_band, colour_band), the geometry as the weighted rule does; unpack_colour_record reads its
-        record."""
+        record.  warp (float32, the model's shape + (3,), numpy or device: x, y, z displacement in voxels, what
+        HierarchicalOptimizer3d.optimize(model, live) returns) makes every voxel observe the frame at its displaced
+        point, by the weighted rule and with colour_image the colour rule (module docstring); unpack_warped_record
+        reads its record of nine doubles.  Without a warp nothing changes."""
         depth, code = device_depth(depth_image)
+        if colour_image is not None and self.colour is None:
+            raise ValueError("colour_image needs a volume made with colour=True")
+        if warp is not None:
+            coloured = colour_image is not None
+            return device_fusion.integrate_depth_warped(
+                self.tsdf, self.weight, depth, code, camera, array_offset, twist, _warp(warp), voxel_size,
+                narrow_band_width_voxels, weight, self.max_weight, _pixel_weight(pixel_weight), carve,
+                self.colour if coloured else None, _colour_image(colour_image) if coloured else None, colour_band)
         if colour_image is not None:
-            if self.colour is None:
-                raise ValueError("colour_image needs a volume made with colour=True")
             return device_fusion.integrate_depth_colour(self.tsdf, self.weight, self.colour, depth, code, camera,
                                                         array_offset, twist, _colour_image(colour_image), voxel_size,
                                                         narrow_band_width_voxels, weight, self.max_weight,
@@ -274,8 +309,10 @@ class SequenceFusion3d:
     prediction ("raycast") or, by point-to-plane ICP, the prediction's depth and normals ("icp"), and fuse it (module
     docstring).  Keeps `canonical` (the CanonicalVolume), `twists` (one float64 (6,) per frame),
     `frame_records` (one dict per frame: frame, twist, rigid_records, nonrigid, fusion, prediction_hits -- the pixels
-    of the prediction that hit the model, None without a prediction) and, in "raycast" and "icp" mode, `prediction`
-    (the last predicted depth image, a float32 device tensor in metres).  In "icp" mode rigid_records holds the ICP
+    of the prediction that hit the model, None without a prediction), in "raycast" and "icp" mode `prediction`
+    (the last predicted depth image, a float32 device tensor in metres) and, with a HierarchicalOptimizer3d as the
+    non-rigid step, `warp` (the last frame's displacement field, a float32 (Z, Y, X, 3) device tensor; None before
+    frame 1).  In "icp" mode rigid_records holds the ICP
     records (device_icp.unpack_record)."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
@@ -286,11 +323,14 @@ class SequenceFusion3d:
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
-        if nonrigid_optimizer is not None and (self.carve or confidence is not None):
+        # the one optimizer that returns a cumulative warp: its frames are fused through it, in depth mode
+        self.warped = isinstance(nonrigid_optimizer, HierarchicalOptimizer3d)
+        volume_mode = nonrigid_optimizer is not None and not self.warped
+        if volume_mode and (self.carve or confidence is not None):
             raise ValueError("carve and confidence need depth-mode fusion and do not combine with a nonrigid_optimizer: "
                              "volume-mode carving needs an observation mask warped with the live field")
         self.colour = bool(colour)
-        if nonrigid_optimizer is not None and self.colour:
+        if volume_mode and self.colour:
             raise ValueError("colour needs depth-mode fusion and does not combine with a nonrigid_optimizer: "
                              "the colour would have to be warped with the live field")
         self.colour_band = device_fusion.colour_band_of(colour_band)
@@ -322,6 +362,7 @@ class SequenceFusion3d:
         self.twists = []
         self.frame_records = []
         self.prediction = None  # "raycast", "icp": the last prediction, a float32 device depth image in metres
+        self.warp = None  # a HierarchicalOptimizer3d step: the last frame's psi, a float32 (Z, Y, X, 3) device tensor
         self._previous = None  # "raycast": the previous frame's (device depth, LSF_DEPTH_* code)
         P = camera.intrinsics.intrinsic_matrix
         # the prediction is in metres: its live volume is generated with ratio 1
@@ -389,7 +430,19 @@ class SequenceFusion3d:
                 rigid_records = [unpack_rigid_record(r) for r in records]
                 del reference
         unpack = unpack_record
-        if self.colour:
+        if self.warped and k > 0:
+            live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
+                                               **gen)
+            self.warp = self.nonrigid_optimizer.optimize(model.tsdf, live)
+            nonrigid = self.nonrigid_optimizer.engine.last_call
+            del live
+            record = device_fusion.integrate_depth_warped(
+                model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, self.warp, w=1.0,
+                max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
+                colour=model.colour, colour_image=_colour_image(colour_image) if self.colour else None,
+                colour_band=self.colour_band, **gen)
+            unpack = unpack_warped_record
+        elif self.colour:
             record = device_fusion.integrate_depth_colour(
                 model.tsdf, model.weight, model.colour, depth, code, self.camera, self.array_offset, twist,
                 _colour_image(colour_image), w=1.0, max_weight=model.max_weight,
