@@ -1158,6 +1158,19 @@ typedef struct lsf_raycast_params {
 int lsf_raycast(const float *tsdf, const float *weight, const void *fallback_depth, float *depth_out, float *normals_out,
                 uint64_t *hit_count, const lsf_raycast_params *params, void *stream);
 
+/* lsf_raycast with the model's colour ("Ray-cast colour"): the same march, and depth_out,
+ * normals_out, the fallback and hit_count equal lsf_raycast's bit for bit.  colour: DEVICE float32
+ * [depth][height][width][4], the model's records (R, G, B in units of the 8-bit image, the colour weight), read only.
+ * colour_out: DEVICE float32 [image_height][image_width][4].  A hit pixel takes the float64 voxel coordinates of its hit
+ * point (the refined depth along the ray, before it is rounded) and samples R, G and B there trilinearly, each in float64
+ * in the order of the tsdf sample; the sample is valid when the 8 corners lie inside the volume and all 8 colour weights
+ * are > 0 (they are read first).  It stores (R, G, B, Y), Y = ((0.299 R + 0.587 G) + 0.114 B) / 255 in float64, each
+ * rounded to float32.  A pixel without a hit (one the fallback filled included) or without a valid sample gets four
+ * NaNs.  colour and colour_out must not be NULL; no output may alias an input or another output. */
+int lsf_raycast_colour(const float *tsdf, const float *weight, const float *colour, const void *fallback_depth,
+                       float *depth_out, float *normals_out, float *colour_out, uint64_t *hit_count,
+                       const lsf_raycast_params *params, void *stream);
+
 /* ---- projective point-to-plane ICP against the ray-cast prediction -------------------------------------------------
  * The KinectFusion tracker; the reference has none, the arithmetic is this project's (INTEGRATION.md section 3,
  * "Projective ICP"), every step one float64 operation.  The prediction is lsf_raycast's depth and normals at twist_p
@@ -1191,7 +1204,8 @@ typedef struct lsf_icp_params {
  *   [0, 6) delta = A^-1 b (0 when skipped)   [6, 12) twist after the update   [12] energy (sum r^2)   [13, 49) A
  *   row-major   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)
  *   [56] correspondence count   [57] level   [58] pairs the normal-angle gate rejected (lsf_icp_run_pyramid; 0 from
- *   lsf_icp_run)   [59, 64) reserved */
+ *   lsf_icp_run)   [59] photometric pair count   [60] photometric energy, sum r_I^2 (lsf_icp_run_photometric; 0 from
+ *   the other two)   [61, 64) reserved */
 #define LSF_ICP_RECORD_DOUBLES 64
 /* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
  * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
@@ -1265,6 +1279,45 @@ typedef struct lsf_icp_pyramid_params {
 int lsf_icp_run_pyramid(const float *live_depth, const float *live_normals, const float *pred_depth,
                         const float *pred_normals, double *twist_inout, double *records, void *scratch,
                         float *residuals_out, const lsf_icp_pyramid_params *params, void *stream);
+
+/* ---- joint geometric and photometric ICP on the strided path -------------------------------------------------------
+ * lsf_icp_run's pairs, schedule and records, and for every live pixel with a geometric pair an intensity term against
+ * the ray-cast colour image (lsf_raycast_colour at twist_p; INTEGRATION.md section 3, "Photometric ICP"), every step
+ * one float64 operation.  With q the pixel's point in the prediction's camera: pu = (fx q_x) / q_z + cx,
+ * pv = (fy q_y) / q_z + cy (the values before rint), x0 = floor(pu), y0 = floor(pv); the term needs 0 <= x0,
+ * x0 + 1 <= width - 1, 0 <= y0, y0 + 1 <= height - 1 and the four Y = pred_colour[..][3] at (x0, y0), (x0 + 1, y0),
+ * (x0, y0 + 1), (x0 + 1, y0 + 1) finite.  I_p is their bilinear interpolant at (pu, pv), (I_u, I_v) its exact
+ * derivatives, I_l = ((0.299 R + 0.587 G) + 0.114 B) / 255 of the live pixel's bytes, r_I = I_p - I_l, kept when
+ * |r_I| <= max_intensity_difference.  c = (I_u fx / q_z, I_v fy / q_z, -((I_u fx) q_x + (I_v fy) q_y) / (q_z q_z)),
+ * a = R_p^T c, J_I = (a, g x a).  lambda J_I and lambda r_I go into the same A and b as the geometric term.  Record
+ * slot 59 is the photometric pair count, slot 60 sum r_I^2 (unscaled); slot 12 stays the geometric energy, slot 56 the
+ * geometric count, slot 58 is 0. */
+typedef struct lsf_icp_photometric_params {
+    double fx, fy, cx, cy;             /* as lsf_icp_params */
+    double depth_unit_ratio;
+    double max_distance;
+    double photometric_weight;         /* lambda: finite and > 0 */
+    double max_intensity_difference;   /* the gate on |r_I|, units of Y (0 .. 1): > 0 (inf allowed) */
+    double twist_p[6];
+    int32_t height, width;
+    int32_t depth_dtype;
+    int32_t levels;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    int32_t strides[LSF_ICP_MAX_LEVELS];
+} lsf_icp_photometric_params;
+/* 31 partial sums per workgroup: lsf_icp_run's 29, the photometric pair count, sum r_I^2 */
+#define LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 31 * 8)
+
+/* live_depth, pred_depth, pred_normals, twist_inout, records, residuals_out: as lsf_icp_run.  live_colour: DEVICE uint8
+ * [height][width][3], registered to the depth; pred_colour: DEVICE float32 [height][width][4], lsf_raycast_colour's
+ * output at twist_p; scratch: DEVICE, LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES; intensity_residuals_out: NULL, or DEVICE
+ * float32 [height][width] that receives the last iteration's r_I, NaN where a pixel has no photometric term (or is not
+ * on the last level's stride).  sum(iterations) + 1 launches, none when sum(iterations) == 0; no float atomics, no host
+ * wait, a rerun is bit-identical.  No output may alias an input or another output. */
+int lsf_icp_run_photometric(const void *live_depth, const uint8_t *live_colour, const float *pred_depth,
+                            const float *pred_normals, const float *pred_colour, double *twist_inout, double *records,
+                            void *scratch, float *residuals_out, float *intensity_residuals_out,
+                            const lsf_icp_photometric_params *params, void *stream);
 
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "5802ce7ed08edc24"
+HEADER_ABI_HASH = "92edb0e3afe3c3d5"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -289,6 +289,18 @@ class IcpPyramidParams(ctypes.Structure):
                [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS)]
 
 
+ICP_PHOTOMETRIC_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 31 * 8
+
+
+class IcpPhotometricParams(ctypes.Structure):
+    """lsf_icp_photometric_params: joint geometric and photometric ICP on the strided path (lsf_icp_run_photometric)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_unit_ratio", "max_distance",
+                                               "photometric_weight", "max_intensity_difference")] + \
+               [("twist_p", ctypes.c_double * 6)] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "depth_dtype", "levels")] + \
+               [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS), ("strides", ctypes.c_int32 * ICP_MAX_LEVELS)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -409,6 +421,7 @@ PROTOTYPES = {
                                                          _P(FusionWarpedParams), _vp]),
     "lsf_depth_confidence": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthConfidenceParams), _vp]),
     "lsf_raycast": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
+    "lsf_raycast_colour": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(RaycastParams), _vp]),
     "lsf_mesh_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(MeshParams), _vp]),
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
     "lsf_mesh_vertex_colours": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
@@ -416,6 +429,8 @@ PROTOTYPES = {
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),
+    "lsf_icp_run_photometric": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _P(IcpPhotometricParams), _vp]),
 }
 
 

@@ -1,5 +1,5 @@
-// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run and
-// lsf_icp_run_pyramid): the KinectFusion tracker, which the reference does not have.  The arithmetic is INTEGRATION.md
+// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run, lsf_icp_run_pyramid
+// and lsf_icp_run_photometric): the KinectFusion tracker, which the reference does not have.  The arithmetic is INTEGRATION.md
 // section 3 ("Projective ICP"); tests/icp_restatement.py restates it.  Every per-pixel step is one float64 operation in
 // the order written there; -ffp-contract=off keeps products and sums separately rounded, so the residual image and
 // the correspondence count equal the restatement bit for bit.  One iteration kernel over a live source, and the 3-D
@@ -16,6 +16,10 @@
 //   PyramidSource  lsf_icp_run_pyramid: every pixel of one level of lsf_depth_pyramid's output, back-projected with
 //                  the level's intrinsics; an optional normal-angle gate after the distance test, and a 30th sum, the
 //                  pairs the gate rejected (record slot 58)
+//   PhotometricSource  lsf_icp_run_photometric: StridedSource's pixels; a pixel with a geometric pair also gets the
+//                  intensity term of INTEGRATION.md section 3 ("Photometric ICP") against the ray-cast colour image,
+//                  scaled by lambda into the same 27 sums, and two more: the photometric pairs and sum r_I^2 (record
+//                  slots 59 and 60)
 #include <initializer_list>
 #include <type_traits>
 
@@ -31,15 +35,17 @@ constexpr int kTile = 16;  // a workgroup covers 16 x 16 strided pixels
 constexpr int kSub = 8;    // a wave's block is kSub x kSub of them
 constexpr int kSums = 29;  // A's upper triangle (21, row by row), b (6), energy, count
 constexpr int kPyrSums = 30;  // lsf_icp_run_pyramid: and the pairs the angle gate rejected
+constexpr int kPhotoSums = 31;  // lsf_icp_run_photometric: kSums, then the photometric pairs and sum r_I^2
 constexpr int kMaxBlocks = LSF_ICP_MAX_BLOCKS;
 constexpr int kRecord = LSF_ICP_RECORD_DOUBLES;
 constexpr int kDelta = 0, kTwist = 6, kEnergy = 12, kA = 13, kB = 49, kSkipped = 55, kCount = 56, kLevel = 57,
-              kRejected = 58;
+              kRejected = 58, kPhotoCount = 59, kPhotoEnergy = 60;
 static_assert(kSub * kSub == kWave && (kTile / kSub) * (kTile / kSub) * kWave == kBlock, "4 waves of 8 x 8 pixels");
 static_assert(LSF_ICP_SCRATCH_BYTES == 2 * kMaxBlocks * kSums * 8, "two ping-pong buffers of kMaxBlocks partials");
 static_assert(LSF_ICP_PYRAMID_SCRATCH_BYTES == 2 * kMaxBlocks * kPyrSums * 8, "the same with the 30th sum");
+static_assert(LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES == 2 * kMaxBlocks * kPhotoSums * 8, "the same with 31 sums");
 static_assert(kMaxBlocks <= kBlock, "the prologue gives every partial one thread");
-static_assert(kRejected < kRecord && kB == kA + 36 && kSkipped == kB + 6, "the record holds every field");
+static_assert(kPhotoEnergy < kRecord && kRejected < kRecord && kB == kA + 36 && kSkipped == kB + 6, "the record holds every field");
 
 struct IcpDev {
     double fx, fy, cx, cy, ratio, max_distance;
@@ -61,7 +67,7 @@ Grid grid_of(int ni, int nj) {
 template <typename DT>
 struct StridedSource {
     static constexpr int K = kSums;
-    static constexpr bool kGate = false;
+    static constexpr bool kGate = false, kPhoto = false;
     using Live = DT;
     Grid grid;
     int stride;
@@ -92,7 +98,7 @@ struct StridedSource {
 template <bool GATE>
 struct PyramidSource {
     static constexpr int K = kPyrSums;
-    static constexpr bool kGate = GATE;
+    static constexpr bool kGate = GATE, kPhoto = false;
     using Live = float;
     double fx, fy, cx, cy, cos_max;
     long long offset;  // of the level in the live buffers: the launch passes their pointers advanced by it
@@ -115,6 +121,17 @@ struct PyramidSource {
     __device__ void store(float* __restrict__ residuals, const IcpDev&, Pixel px, float res) const {
         residuals[px.at] = res;
     }
+};
+
+// lsf_icp_run_photometric: the strided pixels, and what the intensity term reads
+template <typename DT>
+struct PhotometricSource : StridedSource<DT> {
+    static constexpr int K = kPhotoSums;
+    static constexpr bool kPhoto = true;
+    const uint8_t* live_colour;  // [height][width][3]
+    const float* pred_colour;    // [height][width][4], Y last
+    float* intensity;            // r_I of the launch, or NULL: launch_run keeps it for the last iteration
+    double lambda, max_difference;
 };
 
 // the twist after the step delta = (tau, omega): R' = R Rodrigues(omega)^T, t' = t - R' tau, out = (t', log R')
@@ -141,7 +158,8 @@ __device__ inline void compose(const double* tw, const double* delta, double* ou
 // the twist of launch k into tw (LDS): twist_io (k = 0), or iteration k-1's partials (prev_blocks of them) combined,
 // solved and composed onto the twist before it (record k-2's, or twist_io); block 0 writes record k-1 and, with
 // twist_final, the final twist.  The finishing launch has one block, which reads twist_io before it writes it.
-// K = kPyrSums also writes the gate's rejections to record slot kRejected.
+// K = kPyrSums also writes the gate's rejections to record slot kRejected, K = kPhotoSums the photometric pairs and
+// energy to kPhotoCount and kPhotoEnergy.
 template <int K>
 __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_level, double* __restrict__ twist_io,
                                              double* __restrict__ records, const double* __restrict__ scratch,
@@ -172,6 +190,12 @@ __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_le
             r[kLevel] = (double)prev_level;
             int i = kLevel + 1;
             if constexpr (K == kPyrSums) r[i++] = v[kSums];
+            if constexpr (K == kPhotoSums) {
+                r[kRejected] = 0.0;
+                r[kPhotoCount] = v[kSums];
+                r[kPhotoEnergy] = v[kSums + 1];
+                i = kPhotoEnergy + 1;
+            }
             for (; i < kRecord; ++i) r[i] = 0.0;
             if (twist_final)
                 for (int i = 0; i < 6; ++i) twist_final[i] = next[i];
@@ -198,15 +222,63 @@ __device__ __forceinline__ void load_poses(const double* tw, const IcpDev& p, do
     for (int q = 0; q < 12; ++q) { e[q] = pose[q]; ep[q] = pose_p[q]; }
 }
 
+// the intensity term of a pixel that has a geometric pair (q: its point in the prediction's camera, before the
+// projection is rounded; g: its world point): r_I, its scaled terms added to acc; NaN and nothing added when the 2 x 2
+// neighbourhood leaves the image, one of its four Y is not finite, or |r_I| exceeds the gate
+template <typename SRC>
+__device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::Pixel px, double pu, double pv,
+                                                  const double (&q)[3], const double (&g)[3], const double (&ep)[12],
+                                                  const IcpDev& p, double (&acc)[SRC::K]) {
+    const double x0 = floor(pu), y0 = floor(pv);
+    // compared as doubles first: NaN and far-off values never reach the integer conversion
+    if (!(0.0 <= x0 && x0 + 1.0 <= (double)(p.width - 1) && 0.0 <= y0 && y0 + 1.0 <= (double)(p.height - 1)))
+        return NAN;
+    const long long at = (long long)(int)y0 * p.width + (int)x0;
+    const double I00 = (double)src.pred_colour[at * 4 + 3], I10 = (double)src.pred_colour[(at + 1) * 4 + 3];
+    const double I01 = (double)src.pred_colour[(at + p.width) * 4 + 3];
+    const double I11 = (double)src.pred_colour[(at + p.width + 1) * 4 + 3];
+    if (!(isfinite(I00) && isfinite(I10) && isfinite(I01) && isfinite(I11))) return NAN;
+    const double al = pu - x0, be = pv - y0;
+    const double ha = 1.0 - al, hb = 1.0 - be;
+    const double Ip = hb * (ha * I00 + al * I10) + be * (ha * I01 + al * I11);
+    const double Iu = hb * (I10 - I00) + be * (I11 - I01);
+    const double Iv = ha * (I01 - I00) + al * (I11 - I10);
+    const uint8_t* lc = src.live_colour + ((long long)px.v * p.width + px.u) * 3;
+    const double Il = ((0.299 * (double)lc[0] + 0.587 * (double)lc[1]) + 0.114 * (double)lc[2]) / 255.0;
+    const double rI = Ip - Il;
+    if (!(fabs(rI) <= src.max_difference)) return NAN;
+    const double su = Iu * p.fx, sv = Iv * p.fy;
+    const double c[3] = {su / q[2], sv / q[2], -((su * q[0] + sv * q[1]) / (q[2] * q[2]))};
+    double a[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = (ep[j] * c[0] + ep[4 + j] * c[1]) + ep[8 + j] * c[2];
+    const double J[6] = {src.lambda * a[0], src.lambda * a[1], src.lambda * a[2],
+                         src.lambda * (g[1] * a[2] - g[2] * a[1]), src.lambda * (g[2] * a[0] - g[0] * a[2]),
+                         src.lambda * (g[0] * a[1] - g[1] * a[0])};
+    const double r = src.lambda * rI;
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] -= J[i] * r;
+    acc[kSums] += 1.0;
+    acc[kSums + 1] += rI * rI;
+    return (float)rI;
+}
+
 // the live vertex vx (camera coordinates) of the source's pixel px against the prediction at the estimate e: its
 // residual r, the pair's terms added to acc, when the pair is valid and (SRC::kGate) the live normal passes the angle
-// gate; NaN otherwise.  A pair that passes the distance test and fails the gate counts in acc[kSums].
+// gate; NaN otherwise.  A pair that passes the distance test and fails the gate counts in acc[kSums].  SRC::kPhoto:
+// a pixel with a pair also gets photometric_term, its r_I into photo.
 template <typename SRC>
 __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __restrict__ live_normals,
                                                  typename SRC::Pixel px, const double (&vx)[3],
                                                  const double (&e)[12], const double (&ep)[12], const IcpDev& p,
                                                  const float* __restrict__ pred_depth,
-                                                 const float* __restrict__ pred_normals, double (&acc)[SRC::K]) {
+                                                 const float* __restrict__ pred_normals, double (&acc)[SRC::K],
+                                                 float& photo) {
     double dv[3], g[3], q[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) dv[c] = vx[c] - e[c * 4 + 3];
@@ -215,7 +287,8 @@ __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __
 #pragma unroll
     for (int c = 0; c < 3; ++c) q[c] = ((ep[c * 4] * g[0] + ep[c * 4 + 1] * g[1]) + ep[c * 4 + 2] * g[2]) + ep[c * 4 + 3];
     if (!(q[2] > 0.0)) return NAN;
-    const double fu = rint((p.fx * q[0]) / q[2] + p.cx), fv = rint((p.fy * q[1]) / q[2] + p.cy);
+    const double pu = (p.fx * q[0]) / q[2] + p.cx, pv = (p.fy * q[1]) / q[2] + p.cy;
+    const double fu = rint(pu), fv = rint(pv);
     // compared as doubles first: NaN and far-off values never reach the integer conversion
     if (!(fu >= 0.0 && fu <= (double)(p.width - 1) && fv >= 0.0 && fv <= (double)(p.height - 1))) return NAN;
     const long long at = (long long)(int)fv * p.width + (int)fu;
@@ -263,6 +336,7 @@ __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __
     for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
     acc[27] += r * r;
     acc[28] += 1.0;
+    if constexpr (SRC::kPhoto) photo = photometric_term(src, px, pu, pv, q, g, ep, p, acc);
     return (float)r;
 }
 
@@ -292,13 +366,15 @@ __global__ __launch_bounds__(kBlock) void icp_iterate_kernel(SRC src, const type
         if (i >= src.grid.ni || j >= src.grid.nj) continue;
         const auto px = src.pixel(i, j);
         const double d = src.depth(live, p, px);
-        float res = NAN;
+        float res = NAN, photo = NAN;
         if (d > 0.0) {  // NaN is not > 0
             double vx[3];
             src.vertex(p, px, d, vx);
-            res = accumulate_pair(src, live_normals, px, vx, e, ep, p, pred_depth, pred_normals, acc);
+            res = accumulate_pair(src, live_normals, px, vx, e, ep, p, pred_depth, pred_normals, acc, photo);
         }
         if (residuals) src.store(residuals, p, px, res);  // the last iteration
+        if constexpr (SRC::kPhoto)
+            if (src.intensity) src.store(src.intensity, p, px, photo);
     }
     store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * K);
 }
@@ -335,9 +411,12 @@ int launch_run(const Run& r, int levels, const int32_t* iterations, SourceOf sou
     using SRC = decltype(source_of(0));
     int k = 0, prev_blocks = 0, prev_level = 0;
     for (int l = 0; l < levels; ++l) {
-        const SRC src = source_of(l);
-        const int blocks = src.grid.tiles < kMaxBlocks ? src.grid.tiles : kMaxBlocks;
+        const SRC level = source_of(l);
+        const int blocks = level.grid.tiles < kMaxBlocks ? level.grid.tiles : kMaxBlocks;
         for (int it = 0; it < iterations[l]; ++it, ++k) {
+            SRC src = level;
+            if constexpr (SRC::kPhoto)  // like the residuals: from the last iteration only
+                if (k != r.total - 1) src.intensity = nullptr;
             hipLaunchKernelGGL(icp_iterate_kernel<SRC>, dim3(blocks), dim3(kBlock), 0, r.stream, src,
                                reinterpret_cast<const typename SRC::Live*>(r.live) + src.offset,
                                r.live_normals + src.offset * 3, r.pred_depth,
@@ -411,6 +490,23 @@ Run run_of(const Q* q, double ratio, const void* live, const float* live_normals
     return r;
 }
 
+// the checks of the strided parameter structs (lsf_icp_params, lsf_icp_photometric_params): sum(iterations), or -1
+template <typename Q>
+long long strided_total(const Q* q, const double* records) {
+    if (!camera_ok(q) || !std::isfinite(q->depth_unit_ratio) || !depth_dtype_ok(q->depth_dtype)) return -1;
+    if (q->levels < 1 || q->levels > LSF_ICP_MAX_LEVELS) return -1;
+    for (int l = 0; l < q->levels; ++l)
+        if (q->strides[l] < 1) return -1;
+    return iteration_total(q->iterations, q->levels, records);
+}
+
+template <typename Q>
+Grid strided_grid(const Q* q, int stride) {
+    return grid_of((q->width + stride - 1) / stride, (q->height + stride - 1) / stride);
+}
+
+const size_t kDepthBytes[3] = {2, 4, 8};
+
 }  // namespace
 
 extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, const float* pred_normals,
@@ -419,14 +515,8 @@ extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, cons
     (void)hipGetLastError();
     if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params) return LSF_ERR_BAD_ARGUMENT;
     const lsf_icp_params* q = params;
-    if (!camera_ok(q) || !std::isfinite(q->depth_unit_ratio) || !depth_dtype_ok(q->depth_dtype))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (q->levels < 1 || q->levels > LSF_ICP_MAX_LEVELS) return LSF_ERR_BAD_ARGUMENT;
-    for (int l = 0; l < q->levels; ++l)
-        if (q->strides[l] < 1) return LSF_ERR_BAD_ARGUMENT;
-    const long long total = iteration_total(q->iterations, q->levels, records);
+    const long long total = strided_total(q, records);
     if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    static const size_t kDepthBytes[3] = {2, 4, 8};
     const size_t pixels = (size_t)q->height * q->width;
     if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_ICP_SCRATCH_BYTES},
                  {residuals_out, pixels * 4}},
@@ -439,9 +529,41 @@ extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, cons
     return dispatch_depth(q->depth_dtype, [&](auto dt) {
         using DT = decltype(dt);
         return launch_run(r, q->levels, q->iterations, [&](int l) {
-            const int stride = q->strides[l];
-            return StridedSource<DT>{grid_of((q->width + stride - 1) / stride, (q->height + stride - 1) / stride),
-                                     stride};
+            return StridedSource<DT>{strided_grid(q, q->strides[l]), q->strides[l]};
+        });
+    });
+}
+
+extern "C" int lsf_icp_run_photometric(const void* live_depth, const uint8_t* live_colour, const float* pred_depth,
+                                       const float* pred_normals, const float* pred_colour, double* twist_inout,
+                                       double* records, void* scratch, float* residuals_out,
+                                       float* intensity_residuals_out, const lsf_icp_photometric_params* params,
+                                       void* stream) {
+    (void)hipGetLastError();
+    if (!live_depth || !live_colour || !pred_depth || !pred_normals || !pred_colour || !twist_inout || !scratch ||
+        !params)
+        return LSF_ERR_BAD_ARGUMENT;
+    const lsf_icp_photometric_params* q = params;
+    if (!(std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0))
+        return LSF_ERR_BAD_ARGUMENT;
+    const long long total = strided_total(q, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t pixels = (size_t)q->height * q->width;
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
+                 {scratch, LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES}, {residuals_out, pixels * 4},
+                 {intensity_residuals_out, pixels * 4}},
+                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {live_colour, pixels * 3}, {pred_depth, pixels * 4},
+                 {pred_normals, pixels * 12}, {pred_colour, pixels * 16}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
+                         scratch, residuals_out, total, stream);
+    return dispatch_depth(q->depth_dtype, [&](auto dt) {
+        using DT = decltype(dt);
+        return launch_run(r, q->levels, q->iterations, [&](int l) {
+            return PhotometricSource<DT>{{strided_grid(q, q->strides[l]), q->strides[l]}, live_colour, pred_colour,
+                                         intensity_residuals_out, q->photometric_weight,
+                                         q->max_intensity_difference};
         });
     });
 }

@@ -7,6 +7,8 @@
 // fixed step of voxel_size / 2 in camera z on a grid of sample positions shared by all rays (s = m * step), clipped to
 // the volume's box with a one-step pad: the clip decides only where a lane starts and stops, never what a sample is.
 // The 8 corner weights of a sample are read first; its 8 tsdf values only when all weights are > 0.
+// lsf_raycast_colour is the same kernel with COLOUR set: after the march a hit pixel also samples the model's colour
+// records at its hit point ("Ray-cast colour"), the 8 colour weights first.
 #include "lsf_device.h"
 #include "lsf_tsdf_typed.h"
 
@@ -65,14 +67,52 @@ __device__ inline bool sample(const Volume& vol, double gx, double gy, double gz
     return true;
 }
 
+// the trilinear sample of R, G, B (records of 4 floats, the colour weight last) at voxel coordinates g, in sample()'s
+// order per channel; false when a corner lies outside the volume or a colour weight is not > 0
+__device__ inline bool sample_colour(const Volume& vol, const float* __restrict__ colour, double gx, double gy,
+                                     double gz, double (&rgb)[3]) {
+    if (!(gx >= 0.0 && gx < (double)(vol.nx - 1) && gy >= 0.0 && gy < (double)(vol.ny - 1) && gz >= 0.0 &&
+          gz < (double)(vol.nz - 1)))
+        return false;
+    const int x0 = (int)floor(gx), y0 = (int)floor(gy), z0 = (int)floor(gz);
+    const long long sx = 1, sy = vol.nx, sz = (long long)vol.nx * vol.ny;
+    const long long i = (long long)z0 * sz + (long long)y0 * sy + x0;
+    const long long c[8] = {i, i + sx, i + sy, i + sy + sx, i + sz, i + sz + sx, i + sz + sy, i + sz + sy + sx};
+    float w[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w[q] = colour[c[q] * 4 + 3];
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) ok = ok && w[q] > 0.0f;  // NaN is not > 0
+    if (!ok) return false;
+    const double fx = gx - (double)x0, fy = gy - (double)y0, fz = gz - (double)z0;
+    const double hx = 1.0 - fx, hy = 1.0 - fy, hz = 1.0 - fz;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float t[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = colour[c[q] * 4 + ch];
+        const double c00 = (double)t[0] * hx + (double)t[1] * fx;
+        const double c01 = (double)t[2] * hx + (double)t[3] * fx;
+        const double c10 = (double)t[4] * hx + (double)t[5] * fx;
+        const double c11 = (double)t[6] * hx + (double)t[7] * fx;
+        const double c0 = c00 * hy + c01 * fy;
+        const double c1 = c10 * hy + c11 * fy;
+        rgb[ch] = c0 * hz + c1 * fz;
+    }
+    return true;
+}
+
 __device__ inline double dmin(double a, double b) { return b < a ? b : a; }
 __device__ inline double dmax(double a, double b) { return b > a ? b : a; }
 
-template <typename DT>
+template <typename DT, bool COLOUR>
 __global__ __launch_bounds__(kBlock) void raycast_kernel(Volume vol, const DT* __restrict__ fallback,
                                                          float* __restrict__ depth_out,
                                                          float* __restrict__ normals_out,
-                                                         unsigned long long* __restrict__ hit_count, RayDev p) {
+                                                         unsigned long long* __restrict__ hit_count, RayDev p,
+                                                         const float* __restrict__ colour,
+                                                         float* __restrict__ colour_out) {
     __shared__ double e_sh[12];
     if (threadIdx.x == 0) live_extrinsic(p.twist, e_sh);
     __syncthreads();
@@ -138,6 +178,18 @@ __global__ __launch_bounds__(kBlock) void raycast_kernel(Volume vol, const DT* _
     float out = (float)s_hit;
     if (!hit) out = fallback ? (float)scaled_depth(fallback, px, p.ratio) : 0.0f;
     depth_out[px] = out;
+    if constexpr (COLOUR) {  // (R, G, B, Y) at the unrounded hit point, four NaNs without a hit or a colour
+        float rgby[4] = {NAN, NAN, NAN, NAN};
+        double rgb[3];
+        if (hit && sample_colour(vol, colour, a[0] + s_hit * b[0], a[1] + s_hit * b[1], a[2] + s_hit * b[2], rgb)) {
+            const double y = ((0.299 * rgb[0] + 0.587 * rgb[1]) + 0.114 * rgb[2]) / 255.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) rgby[i] = (float)rgb[i];
+            rgby[3] = (float)y;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) colour_out[px * 4 + i] = rgby[i];
+    }
     if (!normals_out) return;
     float nrm[3] = {0.0f, 0.0f, 0.0f};
     if (hit) {
@@ -199,21 +251,24 @@ int convert(const lsf_raycast_params* q, bool with_fallback, RayDev& p) {
     return 0;
 }
 
-template <typename DT>
+template <typename DT, bool COLOUR>
 int launch(const Volume& vol, const void* fallback, float* depth_out, float* normals_out, uint64_t* hits,
-           const RayDev& p, hipStream_t s) {
+           const RayDev& p, const float* colour, float* colour_out, hipStream_t s) {
     const dim3 grid((unsigned)((p.width + kTile - 1) / kTile), (unsigned)((p.height + kTile - 1) / kTile));
-    hipLaunchKernelGGL(raycast_kernel<DT>, grid, dim3(kBlock), 0, s, vol, reinterpret_cast<const DT*>(fallback),
-                       depth_out, normals_out, reinterpret_cast<unsigned long long*>(hits), p);
+    hipLaunchKernelGGL((raycast_kernel<DT, COLOUR>), grid, dim3(kBlock), 0, s, vol,
+                       reinterpret_cast<const DT*>(fallback), depth_out, normals_out,
+                       reinterpret_cast<unsigned long long*>(hits), p, colour, colour_out);
     return launch_status();
 }
 
-}  // namespace
-
-extern "C" int lsf_raycast(const float* tsdf, const float* weight, const void* fallback_depth, float* depth_out,
-                           float* normals_out, uint64_t* hit_count, const lsf_raycast_params* params, void* stream) {
+// both entry points: colour and colour_out are NULL from lsf_raycast
+template <bool COLOUR>
+int raycast(const float* tsdf, const float* weight, const float* colour, const void* fallback_depth, float* depth_out,
+            float* normals_out, float* colour_out, uint64_t* hit_count, const lsf_raycast_params* params,
+            void* stream) {
     (void)hipGetLastError();
     if (!tsdf || !weight || !depth_out || tsdf == weight) return LSF_ERR_BAD_ARGUMENT;
+    if (COLOUR && (!colour || !colour_out)) return LSF_ERR_BAD_ARGUMENT;
     RayDev p;
     if (int e = convert(params, fallback_depth != nullptr, p)) return e;
     const size_t voxels = (size_t)params->depth * params->height * params->width * 4;
@@ -221,20 +276,37 @@ extern "C" int lsf_raycast(const float* tsdf, const float* weight, const void* f
     static const size_t kDepthBytes[3] = {2, 4, 8};
     const size_t fb = fallback_depth ? pixels * kDepthBytes[params->fallback_dtype] : 0;
     // no output may alias an input or another output
-    const void* outs[3] = {depth_out, normals_out, hit_count};
-    const size_t out_bytes[3] = {pixels * 4, pixels * 12, 8};
-    const void* ins[3] = {tsdf, weight, fallback_depth};
-    const size_t in_bytes[3] = {voxels, voxels, fb};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j)
+    const void* outs[4] = {depth_out, normals_out, hit_count, colour_out};
+    const size_t out_bytes[4] = {pixels * 4, pixels * 12, 8, pixels * 16};
+    const void* ins[4] = {tsdf, weight, fallback_depth, colour};
+    const size_t in_bytes[4] = {voxels, voxels, fb, voxels * 4};
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 4; ++j)
             if (overlaps(outs[i], out_bytes[i], ins[j], in_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-        for (int j = i + 1; j < 3; ++j)
+        for (int j = i + 1; j < 4; ++j)
             if (overlaps(outs[i], out_bytes[i], outs[j], out_bytes[j])) return LSF_ERR_BAD_ARGUMENT;
     }
     const Volume vol{tsdf, weight, params->width, params->height, params->depth};
     hipStream_t s = as_stream(stream);
-    if (!fallback_depth) return launch<float>(vol, nullptr, depth_out, normals_out, hit_count, p, s);
+    if (!fallback_depth)
+        return launch<float, COLOUR>(vol, nullptr, depth_out, normals_out, hit_count, p, colour, colour_out, s);
     return dispatch_depth(params->fallback_dtype, [&](auto dt) {
-        return launch<decltype(dt)>(vol, fallback_depth, depth_out, normals_out, hit_count, p, s);
+        return launch<decltype(dt), COLOUR>(vol, fallback_depth, depth_out, normals_out, hit_count, p, colour,
+                                            colour_out, s);
     });
+}
+
+}  // namespace
+
+extern "C" int lsf_raycast(const float* tsdf, const float* weight, const void* fallback_depth, float* depth_out,
+                           float* normals_out, uint64_t* hit_count, const lsf_raycast_params* params, void* stream) {
+    return raycast<false>(tsdf, weight, nullptr, fallback_depth, depth_out, normals_out, nullptr, hit_count, params,
+                          stream);
+}
+
+extern "C" int lsf_raycast_colour(const float* tsdf, const float* weight, const float* colour,
+                                  const void* fallback_depth, float* depth_out, float* normals_out, float* colour_out,
+                                  uint64_t* hit_count, const lsf_raycast_params* params, void* stream) {
+    return raycast<true>(tsdf, weight, colour, fallback_depth, depth_out, normals_out, colour_out, hit_count, params,
+                         stream);
 }

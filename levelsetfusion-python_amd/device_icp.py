@@ -2,15 +2,18 @@
 the host before the launches; a call enqueues sum(iterations) + 1 launches with no host wait and copies the twist and
 the records back once.  The public interfaces are rigid_opt.ProjectiveIcp3d and
 fusion.SequenceFusion3d(tracking_reference="icp").  icp_run_pyramid (lsf_icp_run_pyramid) is the same schedule over a
-live depth pyramid (device_depth_pyramid), with an optional normal-angle gate."""
+live depth pyramid (device_depth_pyramid), with an optional normal-angle gate.  icp_run_photometric
+(lsf_icp_run_photometric) is icp_run with an intensity term against the ray-cast colour image
+(device_raycast.raycast(..., colour=)) in the same normal equations."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, IcpPyramidParams, lib
+from ._lib import IcpParams, IcpPhotometricParams, IcpPyramidParams, lib
 from .device_core import require_gpu
+from .device_fusion import check_colour_image
 from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
 from .device_rigid import enqueue_run, twist6
 
@@ -48,13 +51,33 @@ def _common(p, camera, image_shape, twist_p, max_distance, iterations):
 
 
 def params(camera, image_shape, twist_p, depth_code, iterations=ITERATIONS, strides=STRIDES,
-           max_distance=MAX_DISTANCE):
-    """the lsf_icp_params of a call, after the host checks"""
+           max_distance=MAX_DISTANCE, into=None):
+    """the lsf_icp_params of a call, after the host checks (into: another struct with its members to fill instead)"""
     it, st = levels(iterations, strides)
-    p = _common(IcpParams(), camera, image_shape, twist_p, max_distance, it)
+    p = _common(IcpParams() if into is None else into, camera, image_shape, twist_p, max_distance, it)
     p.depth_unit_ratio = checked_depth_unit_ratio(camera)
     p.depth_dtype = int(depth_code)
     p.strides[:len(st)] = list(st)
+    return p
+
+
+def photometric_settings(photometric_weight, max_intensity_difference=math.inf):
+    """(lambda, gate) as floats after the checks: lambda finite and > 0, the gate > 0 (inf allowed)"""
+    lam, gate = float(photometric_weight), float(max_intensity_difference)
+    if not (math.isfinite(lam) and lam > 0):
+        raise ValueError("photometric_weight must be finite and positive, got %r" % (photometric_weight,))
+    if not gate > 0:
+        raise ValueError("max_intensity_difference must be positive (inf allowed), got %r"
+                         % (max_intensity_difference,))
+    return lam, gate
+
+
+def photometric_params(camera, image_shape, twist_p, depth_code, photometric_weight, max_intensity_difference=math.inf,
+                       iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE):
+    """the lsf_icp_photometric_params of a call, after the host checks"""
+    p = params(camera, image_shape, twist_p, depth_code, iterations, strides, max_distance, IcpPhotometricParams())
+    p.photometric_weight, p.max_intensity_difference = photometric_settings(photometric_weight,
+                                                                            max_intensity_difference)
     return p
 
 
@@ -66,16 +89,21 @@ def _prediction(x, name, shape):
     return x
 
 
-def _run(entry, name, live, pred_depth, pred_normals, p, twist, scratch_bytes, residual_shape):
-    """the run of p enqueued (device_rigid.enqueue_run) after the checks of the prediction: icp_run's triple"""
+def _run(entry, name, live, pred_depth, pred_normals, p, twist, scratch_bytes, residual_shape, pred_colour=None):
+    """the run of p enqueued (device_rigid.enqueue_run) after the checks of the prediction: icp_run's triple, and with
+    pred_colour (lsf_icp_run_photometric) the intensity residual image as a fourth value"""
     h, w = p.height, p.width
     inputs = live + (_prediction(pred_depth, "pred_depth", (h, w)), _prediction(pred_normals, "pred_normals", (h, w, 3)))
-    res = None
+    if pred_colour is not None:
+        inputs += (_prediction(pred_colour, "pred_colour", (h, w, 4)),)
+    res = intensity = None
     if residual_shape is not None:
         res = torch.empty(residual_shape, dtype=torch.float32, device=pred_depth.device)
+        if pred_colour is not None:
+            intensity = torch.empty(residual_shape, dtype=torch.float32, device=pred_depth.device)
     out, records = enqueue_run(entry, name, inputs, p, twist, 6, 8, RECORD, scratch_bytes,
-                               sum(p.iterations[:p.levels]), (res,))
-    return out, records, res
+                               sum(p.iterations[:p.levels]), (res,) if pred_colour is None else (res, intensity))
+    return (out, records, res) if pred_colour is None else (out, records, res, intensity)
 
 
 def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, twist=None, iterations=ITERATIONS,
@@ -92,6 +120,28 @@ def icp_run(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, t
     p = params(camera, (h, w), twist_p, depth_code, iterations, strides, max_distance)
     return _run(lib.lsf_icp_run, "lsf_icp_run", (live_depth,), pred_depth, pred_normals, p,
                 twist_p if twist is None else twist, _lib.ICP_SCRATCH_BYTES, (h, w) if residuals else None)
+
+
+def icp_run_photometric(live_depth, depth_code, live_colour, pred_depth, pred_normals, pred_colour, camera, twist_p,
+                        photometric_weight, twist=None, iterations=ITERATIONS, strides=STRIDES,
+                        max_distance=MAX_DISTANCE, max_intensity_difference=math.inf, residuals=False):
+    """icp_run with the photometric term (lsf_icp_run_photometric): the same launches and one copy back.  live_colour:
+    the frame's uint8 (H, W, 3) device image, registered to live_depth; pred_colour: the float32 (H, W, 4) device image
+    of device_raycast.raycast(..., colour=) at twist_p; photometric_weight: lambda, finite and > 0;
+    max_intensity_difference: the gate on |r_I| in units of Y.  Returns icp_run's triple and, fourth, the last
+    iteration's intensity residual image (H, W) with residuals=True, else None; the records carry photometric_count
+    and photometric_energy (unpack_record)."""
+    require_gpu()
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
+        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+    h, w = (int(v) for v in live_depth.shape)
+    p = photometric_params(camera, (h, w), twist_p, depth_code, photometric_weight, max_intensity_difference,
+                           iterations, strides, max_distance)
+    check_colour_image(live_colour, live_depth, (("pred_depth", pred_depth), ("pred_normals", pred_normals),
+                                                 ("pred_colour", pred_colour)))
+    return _run(lib.lsf_icp_run_photometric, "lsf_icp_run_photometric", (live_depth, live_colour), pred_depth,
+                pred_normals, p, twist_p if twist is None else twist, _lib.ICP_PHOTOMETRIC_SCRATCH_BYTES,
+                (h, w) if residuals else None, pred_colour)
 
 
 def pyramid_iterations(iterations, pyramid_levels):
@@ -157,7 +207,9 @@ def icp_run_pyramid(pyramid_depth, pyramid_normals, pyramid_levels, pred_depth, 
 
 def unpack_record(r):
     """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES); angle_rejected is 0 on
-    every lsf_icp_run record"""
+    every lsf_icp_run record, photometric_count and photometric_energy are 0 on every record that is not
+    lsf_icp_run_photometric's"""
     return {"delta": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
             "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
-            "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57]), "angle_rejected": int(r[58])}
+            "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57]), "angle_rejected": int(r[58]),
+            "photometric_count": int(r[59]), "photometric_energy": float(r[60])}

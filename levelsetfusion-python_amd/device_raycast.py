@@ -1,6 +1,8 @@
 """Torch-facing wrapper of the ray-caster (include/lsf_hip.h: lsf_raycast).  Every argument is checked on the host
 before the launch; a call enqueues one launch and returns device tensors without waiting.  The public interface is
-fusion.CanonicalVolume.raycast; fusion.SequenceFusion3d(tracking_reference="raycast") tracks against its output."""
+fusion.CanonicalVolume.raycast; fusion.SequenceFusion3d(tracking_reference="raycast") tracks against its output.
+With the model's colour volume the call is lsf_raycast_colour: the same march, and a float32 (H, W, 4) image of
+(R, G, B, Y) at the hit points beside it."""
 import ctypes
 
 import numpy as np
@@ -8,7 +10,7 @@ import torch
 
 from ._lib import RaycastParams, check, lib
 from .device_core import require_gpu, stream_ptr
-from .device_fusion import check_model
+from .device_fusion import check_colour_volume, check_model
 from .device_rigid import twist6
 from .tsdf.generation import offsets_of
 
@@ -60,13 +62,17 @@ def params(shape, camera, twist, array_offset, voxel_size, image_shape, fallback
 
 
 def raycast(tsdf, weight, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
-            fallback_depth=None, fallback_code=None, hit_count=None):
+            fallback_depth=None, fallback_code=None, hit_count=None, colour=None):
     """one launch of lsf_raycast on the (Z, Y, X) model.  fallback_depth: a contiguous device depth image of
     image_shape (tsdf.generation.device_depth) and its LSF_DEPTH_* code, scaled by camera.depth_unit_ratio where a ray
     hits nothing.  hit_count: a device int64 tensor of one element the hit count is added to, or None for a fresh
-    one.  Returns (depth (H, W), normals (H, W, 3) or None, hit_count) as device tensors; nothing waits."""
+    one.  Returns (depth (H, W), normals (H, W, 3) or None, hit_count) as device tensors; nothing waits.  colour: the
+    model's float32 (Z, Y, X, 4) colour volume; with it the launch is lsf_raycast_colour's and the float32 (H, W, 4)
+    image of (R, G, B, Y), NaN where a pixel has no hit or no colour, is returned as a fourth value."""
     require_gpu()
     check_model(tsdf, weight)
+    if colour is not None:
+        check_colour_volume(colour, tsdf, weight)
     p = params(tuple(tsdf.shape), camera, twist, array_offset, voxel_size, image_shape,
                None if fallback_depth is None else fallback_code)
     h, w = p.image_height, p.image_width
@@ -87,9 +93,16 @@ def raycast(tsdf, weight, camera, twist, array_offset, voxel_size=0.004, image_s
         raise ValueError("hit_count must be a device int64 tensor of one element")
     depth = torch.empty((h, w), dtype=torch.float32, device=tsdf.device)
     out_normals = torch.empty((h, w, 3), dtype=torch.float32, device=tsdf.device) if normals else None
-    check(lib.lsf_raycast(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()),
-                          None if fallback_depth is None else ctypes.c_void_p(fallback_depth.data_ptr()),
-                          ctypes.c_void_p(depth.data_ptr()),
-                          None if out_normals is None else ctypes.c_void_p(out_normals.data_ptr()),
-                          ctypes.c_void_p(hit_count.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_raycast")
-    return depth, out_normals, hit_count
+    fb = None if fallback_depth is None else ctypes.c_void_p(fallback_depth.data_ptr())
+    nrm = None if out_normals is None else ctypes.c_void_p(out_normals.data_ptr())
+    if colour is None:
+        check(lib.lsf_raycast(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), fb,
+                              ctypes.c_void_p(depth.data_ptr()), nrm, ctypes.c_void_p(hit_count.data_ptr()),
+                              ctypes.byref(p), stream_ptr()), "lsf_raycast")
+        return depth, out_normals, hit_count
+    out_colour = torch.empty((h, w, 4), dtype=torch.float32, device=tsdf.device)
+    check(lib.lsf_raycast_colour(ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()),
+                                 ctypes.c_void_p(colour.data_ptr()), fb, ctypes.c_void_p(depth.data_ptr()), nrm,
+                                 ctypes.c_void_p(out_colour.data_ptr()), ctypes.c_void_p(hit_count.data_ptr()),
+                                 ctypes.byref(p), stream_ptr()), "lsf_raycast_colour")
+    return depth, out_normals, hit_count, out_colour

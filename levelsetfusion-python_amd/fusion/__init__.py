@@ -62,7 +62,16 @@ confidence image comes from the frame's own pyramid -- the tracker's, built once
 with the filter settings of `confidence.pyramid`, else a one-level pyramid of those settings.
 With `colour` the model holds a colour volume, integrate(depth_image, colour_image) needs a colour image on every frame
 and fuses it through the colour entry point, with `carve` and `confidence` as set, in every tracking mode; tracking
-does not read the colour.
+does not read the colour unless `photometric_weight` is set.
+With `photometric_weight` (lambda; it needs colour=True and tracking_reference="icp", and no `icp_pyramid`) frames
+k >= 1 are tracked by the joint geometric and photometric solve (INTEGRATION.md section 3, "Photometric ICP";
+rigid_opt.ProjectiveIcp3d, device_icp.icp_run_photometric; tests/photometric_restatement.py restates it) against the
+model ray-cast with normals and colour at the previous twist (CanonicalVolume.raycast(..., colours=True),
+lsf_raycast_colour: (R, G, B, Y) trilinear in the colour volume at each hit point, NaN without a colour).  Every live
+pixel with a geometric pair adds lambda times its intensity residual against the bilinear interpolant of the
+prediction's Y, so a flat textured wall, whose geometry leaves t_x, t_y and r_z free, is tracked.
+`icp_max_intensity_difference` gates |r_I|; `prediction_colour` keeps the last colour image.  lambda has no default
+other than off: no value is right across scenes.
 With a `nonrigid_optimizer` that is a HierarchicalOptimizer3d, every frame k >= 1 is fused through its warp field
 ("Warped depth fusion"; tests/warped_fusion_restatement.py restates it).  After tracking, the
 live volume under the twist is generated (device_rigid.live_volume_3d), `psi = optimizer.optimize(model.tsdf, live)` is
@@ -92,9 +101,9 @@ vertex and face totals.
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SlavchevaOptimizer3d, a carve-distance
 limit, keeping the warp field between frames as a warm start, ray-casting or meshing in the live frame, a whole frame
 enqueued without host synchronisations, z-slab / multi-GPU fusion, a 2-D depth-mode row generator, fusing the filtered
-depth, a downsampled prediction pyramid, robust ICP weights (Huber / Tukey), ICP combined with SDF-2-SDF,
-an adaptive ray-casting step, a colour or confidence image in the
-prediction, photometric (colour) tracking, a colour image of another
+depth, a downsampled prediction pyramid, robust ICP weights (Huber / Tukey) on either term, ICP combined with
+SDF-2-SDF, an adaptive ray-casting step, a confidence image in the prediction, the photometric term on the depth
+pyramid (an intensity pyramid), a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
 import math
@@ -264,19 +273,26 @@ class CanonicalVolume:
                                                       _pixel_weight(pixel_weight), carve)
 
     def raycast(self, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
-                fallback_depth=None, as_tensor=False):
+                fallback_depth=None, as_tensor=False, colours=False):
         """the model seen from a pinhole camera at twist (the generator's convention: twist_vector_to_matrix3d of the
         float32-rounded twist maps world to camera): float32 depth (H, W) in metres, 0 where a ray hits nothing, and
         with normals=True the unit normals (H, W, 3) in camera coordinates.  fallback_depth (uint16 / float32 /
         float64, numpy or device, scaled by camera.depth_unit_ratio) fills the pixels without a hit.  Returns depth or
-        (depth, normals): device tensors with as_tensor=True, enqueued without waiting; numpy copies otherwise."""
+        (depth, normals): device tensors with as_tensor=True, enqueued without waiting; numpy copies otherwise.  With
+        colours=True (a volume made with colour=True) the float32 (H, W, 4) image of (R, G, B, Y) at the hit points is
+        appended -- R, G, B in units of the 8-bit image, Y = (0.299 R + 0.587 G + 0.114 B) / 255, four NaNs where a
+        pixel has no hit or its hit point no colour -- and the result is always a tuple."""
         fb, code = (None, None) if fallback_depth is None else device_depth(fallback_depth)
-        depth, out_normals, _ = device_raycast.raycast(self.tsdf, self.weight, camera, twist, array_offset, voxel_size,
-                                                       image_shape, normals, fb, code)
-        out = (depth, out_normals) if normals else (depth,)
+        if colours and self.colour is None:
+            raise ValueError("colours=True needs a volume made with colour=True")
+        cast = device_raycast.raycast(self.tsdf, self.weight, camera, twist, array_offset, voxel_size, image_shape,
+                                      normals, fb, code, colour=self.colour if colours else None)
+        out = (cast[0], cast[1]) if normals else (cast[0],)
+        if colours:
+            out += (cast[3],)
         if not as_tensor:
             out = tuple(t.cpu().numpy() for t in out)
-        return out if normals else out[0]
+        return out if normals or colours else out[0]
 
     def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False,
                      colours=False, default_colour=device_mesh.DEFAULT_COLOUR):
@@ -313,13 +329,15 @@ class SequenceFusion3d:
     (the last predicted depth image, a float32 device tensor in metres) and, with a HierarchicalOptimizer3d as the
     non-rigid step, `warp` (the last frame's displacement field, a float32 (Z, Y, X, 3) device tensor; None before
     frame 1).  In "icp" mode rigid_records holds the ICP
-    records (device_icp.unpack_record)."""
+    records (device_icp.unpack_record); with photometric_weight they carry photometric_count and photometric_energy,
+    and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
-                 icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0):
+                 icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
+                 photometric_weight=None, icp_max_intensity_difference=math.inf):
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
@@ -345,9 +363,16 @@ class SequenceFusion3d:
             raise ValueError("rigid_iterations must be >= 0")
         if tracking_reference not in TRACKING_MODES:
             raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_MODES, tracking_reference))
+        if photometric_weight is not None:
+            if not self.colour or tracking_reference != "icp":
+                raise ValueError("photometric_weight needs colour=True and tracking_reference=\"icp\"")
+            if icp_pyramid is not None:
+                raise ValueError("photometric_weight does not combine with an icp_pyramid: there is no intensity "
+                                 "pyramid")
         # the "icp" tracker; its arguments are checked in every mode
         t = self.icp = ProjectiveIcp3d(camera, icp_iterations, icp_strides, icp_max_distance, icp_pyramid,
-                                       icp_max_normal_angle)
+                                       icp_max_normal_angle, photometric_weight, icp_max_intensity_difference)
+        self.photometric_weight, self.icp_max_intensity_difference = t.photometric_weight, t.max_intensity_difference
         self.icp_iterations, self.icp_strides, self.icp_max_distance = t.iterations, t.strides, t.max_distance
         self.icp_pyramid, self.icp_max_normal_angle = t.pyramid, t.max_normal_angle
         self.voxel_size = voxel_size
@@ -362,6 +387,7 @@ class SequenceFusion3d:
         self.twists = []
         self.frame_records = []
         self.prediction = None  # "raycast", "icp": the last prediction, a float32 device depth image in metres
+        self.prediction_colour = None  # photometric_weight: the last prediction's float32 (H, W, 4) colour image
         self.warp = None  # a HierarchicalOptimizer3d step: the last frame's psi, a float32 (Z, Y, X, 3) device tensor
         self._previous = None  # "raycast": the previous frame's (device depth, LSF_DEPTH_* code)
         P = camera.intrinsics.intrinsic_matrix
@@ -380,10 +406,18 @@ class SequenceFusion3d:
                                            self.array_offset, twist, self.voxel_size, self.narrow_band_width_voxels)
         return live, hits
 
-    def _track_icp(self, depth, code, twist):
+    def _track_icp(self, depth, code, twist, colour_image=None):
         """ICP of the frame against the model ray-cast with normals at twist (no fallback), started from twist: the
-        new twist, the unpacked ICP records and the prediction's device hit count"""
+        new twist, the unpacked ICP records and the prediction's device hit count.  With photometric_weight the
+        prediction carries the model's colour and the solve is the joint one, on the frame's colour_image"""
         model = self.canonical
+        if self.photometric_weight is not None:
+            self.prediction, normals, hits, self.prediction_colour = device_raycast.raycast(
+                model.tsdf, model.weight, self.camera, twist, self.array_offset, self.voxel_size, tuple(depth.shape),
+                normals=True, colour=model.colour)
+            twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist,
+                                               colour_image=colour_image, prediction_colour=self.prediction_colour)
+            return twist, records, hits
         self.prediction, normals, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
                                                                 self.array_offset, self.voxel_size, tuple(depth.shape),
                                                                 normals=True)
@@ -409,6 +443,8 @@ class SequenceFusion3d:
             raise ValueError("colour_image needs a sequence made with colour=True")
         k = len(self.twists)
         depth, code = device_depth(depth_image)
+        if self.photometric_weight is not None:
+            colour_image = _colour_image(colour_image)  # on the device once: the tracker and the fusion both read it
         model = self.canonical
         rigid_records, nonrigid, hits, tracked = [], None, None, False
         gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
@@ -418,7 +454,8 @@ class SequenceFusion3d:
             twist = self.twists[-1].copy()
             if self.tracking_reference == "icp":
                 if sum(self.icp_iterations) > 0:
-                    twist, rigid_records, hits = self._track_icp(depth, code, twist)
+                    twist, rigid_records, hits = self._track_icp(
+                        depth, code, twist, None if self.photometric_weight is None else colour_image)
                     tracked = True
             elif self.rigid_iterations > 0:
                 reference = model.tsdf

@@ -13,7 +13,19 @@ list of dicts: delta, twist, energy, matrix_a, vector_b, skipped, count, level, 
 
 With a DepthPyramid (pyramid=...) the live frame is first turned into a filtered pyramid on the device, and level k of
 the iterations (coarse first) uses every pixel of pyramid level len(iterations) - 1 - k instead of a stride;
-max_normal_angle (radians) adds the normal-angle gate.  The pyramid of the last call stays as `last_pyramid`."""
+max_normal_angle (radians) adds the normal-angle gate.  The pyramid of the last call stays as `last_pyramid`.
+
+With photometric_weight (lambda; strided path only) the solve is the joint geometric and photometric one of
+INTEGRATION.md section 3 ("Photometric ICP"; tests/photometric_restatement.py restates it): every live pixel with a
+geometric pair also compares its own intensity with the bilinear interpolant of the prediction's intensity image --
+the Y channel of the model's ray-cast colour (CanonicalVolume.raycast with colours=True) -- at its unrounded projection,
+and lambda times that residual and its Jacobian go into the same normal equations.  It holds the pose where geometry
+does not: on a flat wall t_x, t_y and r_z leave the geometric A singular.  track and optimize then take the frame's
+uint8 (H, W, 3) colour image and the prediction's (H, W, 4) colour image; max_intensity_difference gates |r_I|; the
+records carry photometric_count and photometric_energy, and `last_intensity_residuals` keeps r_I beside
+`last_residuals`.  lambda has no default: no value is right across scenes."""
+import math
+
 import numpy as np
 import torch
 
@@ -30,15 +42,19 @@ def _prediction(x, trailing):
     t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     t = t.to("cuda").to(torch.float32).contiguous()
     if t.dim() != 2 + len(trailing) or tuple(t.shape[2:]) != trailing:
-        raise ValueError("the prediction must be depth (H, W) and normals (H, W, 3), got shape %s" % (tuple(t.shape),))
+        raise ValueError("the prediction must be depth (H, W), normals (H, W, 3) and colour (H, W, 4), got shape %s"
+                         % (tuple(t.shape),))
     return t
 
 
 class ProjectiveIcp3d:
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
-                 max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None):
+                 max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None, photometric_weight=None,
+                 max_intensity_difference=math.inf):
         """pyramid: None (the strided live image) or a DepthPyramid, with which strides is not used and iterations has
-        one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only)"""
+        one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only);
+        photometric_weight: None (geometric only) or lambda, finite and > 0 (strided only); max_intensity_difference:
+        the gate on |r_I|, > 0"""
         self.camera = camera
         if pyramid is not None and not isinstance(pyramid, DepthPyramid):
             raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
@@ -56,14 +72,33 @@ class ProjectiveIcp3d:
         if not float(max_distance) > 0:
             raise ValueError("max_distance must be positive")
         self.max_distance = float(max_distance)
+        self.photometric_weight = None
+        _, self.max_intensity_difference = device_icp.photometric_settings(1.0, max_intensity_difference)
+        if photometric_weight is not None:
+            if pyramid is not None:
+                raise ValueError("photometric_weight needs the strided path: there is no intensity pyramid")
+            self.photometric_weight, _ = device_icp.photometric_settings(photometric_weight)
         self.last_records = []
         self.last_residuals = None
+        self.last_intensity_residuals = None
         self.last_pyramid = None
 
-    def track(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals=False):
+    def track(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals=False,
+              colour_image=None, prediction_colour=None):
         """optimize() on device inputs (tsdf.generation.device_depth's depth and LSF_DEPTH_* code, the prediction's
-        float32 device depth and normals at twist_p): (final twist, the unpacked records, the residual image or None)"""
-        if self.pyramid is None:
+        float32 device depth and normals at twist_p): (final twist, the unpacked records, the residual image or None).
+        With a photometric_weight also the frame's uint8 (H, W, 3) device colour image and the prediction's float32
+        (H, W, 4) one; the intensity residual image is kept as `last_intensity_residuals`"""
+        if (self.photometric_weight is None) != (colour_image is None) or \
+                (colour_image is None) != (prediction_colour is None):
+            raise ValueError("colour_image and prediction_colour go with a tracker made with photometric_weight, and "
+                             "only with one")
+        if self.photometric_weight is not None:
+            out, records, res, self.last_intensity_residuals = device_icp.icp_run_photometric(
+                depth, code, colour_image, prediction_depth, prediction_normals, prediction_colour, self.camera,
+                twist_p, self.photometric_weight, twist, self.iterations, self.strides, self.max_distance,
+                self.max_intensity_difference, residuals)
+        elif self.pyramid is None:
             out, records, res = device_icp.icp_run(depth, code, prediction_depth, prediction_normals, self.camera,
                                                    twist_p, twist, self.iterations, self.strides, self.max_distance,
                                                    residuals)
@@ -75,15 +110,25 @@ class ProjectiveIcp3d:
         return out, [device_icp.unpack_record(r) for r in records], res
 
     def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
-                 residuals=False):
+                 residuals=False, colour_image=None, prediction_colour=None):
         """the float64 (6,) twist of the live depth frame (uint16 / float32 / float64, scaled by the camera's
         depth_unit_ratio), started from twist (prediction_twist by default).  residuals=True also keeps the last
         iteration's residual image (float32 device tensor, NaN without a correspondence) as `last_residuals`; with a
-        pyramid it has the extents of the last iteration's level."""
+        pyramid it has the extents of the last iteration's level.  A tracker made with photometric_weight also takes
+        colour_image (uint8 (H, W, 3), numpy or device) and prediction_colour ((H, W, 4) float32, numpy or device)."""
         require_gpu()
         depth, code = device_depth(live_depth)
         twist_p = twist6(prediction_twist)
+        if colour_image is not None and not isinstance(colour_image, torch.Tensor):
+            a = np.asarray(colour_image)
+            if a.dtype != np.uint8:
+                raise ValueError("colour_image must be uint8, got %s" % a.dtype)
+            colour_image = torch.from_numpy(np.ascontiguousarray(a))
+        if colour_image is not None:
+            colour_image = colour_image.to("cuda")
+        if prediction_colour is not None:
+            prediction_colour = _prediction(prediction_colour, (4,))
         out, self.last_records, self.last_residuals = self.track(
             depth, code, _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,)), twist_p,
-            twist_p if twist is None else twist, residuals)
+            twist_p if twist is None else twist, residuals, colour_image, prediction_colour)
         return out
