@@ -1205,7 +1205,7 @@ typedef struct lsf_icp_params {
  *   row-major   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)
  *   [56] correspondence count   [57] level   [58] pairs the normal-angle gate rejected (lsf_icp_run_pyramid; 0 from
  *   lsf_icp_run)   [59] photometric pair count   [60] photometric energy, sum r_I^2 (lsf_icp_run_photometric; 0 from
- *   the other two)   [61, 64) reserved */
+ *   the other two; lsf_icp_run_pyramid_photometric writes 58, 59 and 60)   [61, 64) reserved */
 #define LSF_ICP_RECORD_DOUBLES 64
 /* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
  * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
@@ -1318,6 +1318,68 @@ int lsf_icp_run_photometric(const void *live_depth, const uint8_t *live_colour, 
                             const float *pred_normals, const float *pred_colour, double *twist_inout, double *records,
                             void *scratch, float *residuals_out, float *intensity_residuals_out,
                             const lsf_icp_photometric_params *params, void *stream);
+
+/* ---- the intensity pyramids of photometric ICP over the depth pyramid ------------------------------------------------
+ * Extends lsf_depth_pyramid's layout to intensities ("Intensity pyramid"), every step one
+ * float64 operation.  Level 0 of a LSF_INTENSITY_SOURCE_COLOUR pyramid is float32(((0.299 R + 0.587 G) + 0.114 B) /
+ * 255) of the image's bytes, lsf_icp_run_photometric's I_l; level 0 of a LSF_INTENSITY_SOURCE_PREDICTION pyramid is the
+ * fourth channel (Y) of lsf_raycast_colour's image, copied bit for bit, NaNs included.  Level l + 1 has extents
+ * (height >> (l + 1), width >> (l + 1)); with the 2 x 2 block q00, q10 (one row) and q01, q11 (the next) of level l
+ * its value is float32(((q00 + q10) + (q01 + q11)) / 4), and NaN when one of the four is not finite.  Levels are stored
+ * back to back, level 0 first. */
+#define LSF_INTENSITY_SOURCE_COLOUR 0     /* image: DEVICE uint8 [height][width][3] */
+#define LSF_INTENSITY_SOURCE_PREDICTION 1 /* image: DEVICE float32 [height][width][4], Y last */
+typedef struct lsf_intensity_pyramid_params {
+    int32_t height, width;     /* level-0 extents, >= 1 each, at most 2^31 - 1 pixels */
+    int32_t levels;            /* 1 .. LSF_ICP_MAX_LEVELS; height >> (levels - 1) and width >> (levels - 1) >= 1 */
+    int32_t source;            /* LSF_INTENSITY_SOURCE_* */
+} lsf_intensity_pyramid_params;
+
+/* image: as params->source says.  pyramid_intensity: DEVICE float32, sum over levels of (height >> l) (width >> l)
+ * values, overlapping image nowhere.  `levels` launches on stream, one lane per output pixel, with no host wait and
+ * no atomics. */
+int lsf_intensity_pyramid(const void *image, float *pyramid_intensity, const lsf_intensity_pyramid_params *params,
+                          void *stream);
+
+/* ---- joint geometric and photometric ICP over the depth pyramid ------------------------------------------------------
+ * Extends lsf_icp_run_pyramid by lsf_icp_run_photometric's term ("Photometric ICP").  The
+ * geometric pair of a pixel of pyramid level L is lsf_icp_run_pyramid's exactly, gate included, against the
+ * full-resolution prediction.  A pixel with a pair gets the intensity term at its own level: with the level's
+ * intrinsics fx_L, fy_L, cx_L, cy_L and extents (w_L, h_L) = (width >> L, height >> L), pu = (fx_L q_x) / q_z + cx_L,
+ * pv = (fy_L q_y) / q_z + cy_L, x0 = floor(pu), y0 = floor(pv); the term needs 0 <= x0, x0 + 1 <= w_L - 1, 0 <= y0,
+ * y0 + 1 <= h_L - 1 and the four values of level L of pred_intensity at (x0, y0) .. (x0 + 1, y0 + 1) finite.  I_p, I_u
+ * and I_v are lsf_icp_run_photometric's, I_l is level L of live_intensity at the live pixel, r_I = I_p - I_l is kept
+ * when |r_I| <= max_intensity_difference, and the Jacobian is lsf_icp_run_photometric's with fx_L, fy_L.  32 partial
+ * sums per workgroup: lsf_icp_run's 29, the gate's rejections (record slot 58), the photometric pair count (59) and
+ * sum r_I^2 (60). */
+typedef struct lsf_icp_pyramid_photometric_params {
+    double fx, fy, cx, cy;             /* as lsf_icp_pyramid_params */
+    double max_distance;
+    double cos_max_angle;
+    double photometric_weight;         /* lambda: finite and > 0 */
+    double max_intensity_difference;   /* the gate on |r_I|, units of Y (0 .. 1): > 0 (inf allowed) */
+    double twist_p[6];
+    int32_t height, width;
+    int32_t pyramid_levels;            /* levels the three live and prediction pyramids hold */
+    int32_t levels;
+    int32_t angle_gate;
+    int32_t reserved;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+} lsf_icp_pyramid_photometric_params;
+#define LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 32 * 8)
+
+/* live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, residuals_out: as lsf_icp_run_pyramid.
+ * live_intensity, pred_intensity: lsf_intensity_pyramid's outputs for (height, width, pyramid_levels), of the frame's
+ * colour image and of lsf_raycast_colour's image at twist_p; scratch: DEVICE,
+ * LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES; intensity_residuals_out: NULL, or DEVICE float32 of the last iteration's
+ * level extents, r_I there, NaN where a pixel has no photometric term.  sum(iterations) + 1 launches, none when
+ * sum(iterations) == 0; no float atomics, no host wait, a rerun is bit-identical.  No output may alias an input or
+ * another output. */
+int lsf_icp_run_pyramid_photometric(const float *live_depth, const float *live_normals, const float *live_intensity,
+                                    const float *pred_depth, const float *pred_normals, const float *pred_intensity,
+                                    double *twist_inout, double *records, void *scratch, float *residuals_out,
+                                    float *intensity_residuals_out,
+                                    const lsf_icp_pyramid_photometric_params *params, void *stream);
 
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "92edb0e3afe3c3d5"
+HEADER_ABI_HASH = "83026f016e850731"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -301,6 +301,29 @@ class IcpPhotometricParams(ctypes.Structure):
                [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS), ("strides", ctypes.c_int32 * ICP_MAX_LEVELS)]
 
 
+INTENSITY_SOURCE_COLOUR, INTENSITY_SOURCE_PREDICTION = 0, 1
+
+
+class IntensityPyramidParams(ctypes.Structure):
+    """lsf_intensity_pyramid_params: an intensity pyramid of a colour image or a ray-cast colour image
+    (lsf_intensity_pyramid)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("height", "width", "levels", "source")]
+
+
+ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 32 * 8
+
+
+class IcpPyramidPhotometricParams(ctypes.Structure):
+    """lsf_icp_pyramid_photometric_params: joint geometric and photometric ICP over a live depth pyramid and two
+    intensity pyramids (lsf_icp_run_pyramid_photometric)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "max_distance", "cos_max_angle",
+                                               "photometric_weight", "max_intensity_difference")] + \
+               [("twist_p", ctypes.c_double * 6)] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "pyramid_levels", "levels", "angle_gate",
+                                              "reserved")] + \
+               [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -431,6 +454,9 @@ PROTOTYPES = {
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),
     "lsf_icp_run_photometric": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _P(IcpPhotometricParams), _vp]),
+    "lsf_intensity_pyramid": (ctypes.c_int, [_vp, _vp, _P(IntensityPyramidParams), _vp]),
+    "lsf_icp_run_pyramid_photometric": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                       _P(IcpPyramidPhotometricParams), _vp]),
 }
 
 

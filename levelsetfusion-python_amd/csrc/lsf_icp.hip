@@ -1,9 +1,9 @@
-// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run, lsf_icp_run_pyramid
-// and lsf_icp_run_photometric): the KinectFusion tracker, which the reference does not have.  The arithmetic is INTEGRATION.md
-// section 3 ("Projective ICP"); tests/icp_restatement.py restates it.  Every per-pixel step is one float64 operation in
-// the order written there; -ffp-contract=off keeps products and sums separately rounded, so the residual image and
-// the correspondence count equal the restatement bit for bit.  One iteration kernel over a live source, and the 3-D
-// rigid tracker's schedule (lsf_rigid_solve.h):
+// Projective point-to-plane ICP against the ray-cast prediction (include/lsf_hip.h, lsf_icp_run, lsf_icp_run_pyramid,
+// lsf_icp_run_photometric and lsf_icp_run_pyramid_photometric): the KinectFusion tracker, which the reference does not
+// have.  The arithmetic is INTEGRATION.md section 3 ("Projective ICP"); tests/icp_restatement.py restates it.  Every
+// per-pixel step is one float64 operation in the order written there; -ffp-contract=off keeps products and sums
+// separately rounded, so the residual image and the correspondence count equal the restatement bit for bit.  One
+// iteration kernel over a live source, and the 3-D rigid tracker's schedule (lsf_rigid_solve.h):
 //   iterate  iteration k: prologue = combine iteration k-1's per-block partial sums in a fixed order, solve the 6 x 6
 //            system, compose the step into the twist (every block computes the same twist bit for bit, block 0 writes
 //            record k-1); body = one lane per pixel of the source's level, a wave per 8 x 8 block of them, a
@@ -20,6 +20,9 @@
 //                  intensity term of INTEGRATION.md section 3 ("Photometric ICP") against the ray-cast colour image,
 //                  scaled by lambda into the same 27 sums, and two more: the photometric pairs and sum r_I^2 (record
 //                  slots 59 and 60)
+//   PyramidPhotometricSource  lsf_icp_run_pyramid_photometric: PyramidSource's pixels and gate; the intensity term is
+//                  taken at the pixel's own level, between that level of two lsf_intensity_pyramid outputs (the live
+//                  frame's and the prediction's) with the level's intrinsics; 32 sums, slots 58, 59 and 60
 #include <initializer_list>
 #include <type_traits>
 
@@ -36,6 +39,7 @@ constexpr int kSub = 8;    // a wave's block is kSub x kSub of them
 constexpr int kSums = 29;  // A's upper triangle (21, row by row), b (6), energy, count
 constexpr int kPyrSums = 30;  // lsf_icp_run_pyramid: and the pairs the angle gate rejected
 constexpr int kPhotoSums = 31;  // lsf_icp_run_photometric: kSums, then the photometric pairs and sum r_I^2
+constexpr int kPyrPhotoSums = 32;  // lsf_icp_run_pyramid_photometric: kPyrSums, then the same two
 constexpr int kMaxBlocks = LSF_ICP_MAX_BLOCKS;
 constexpr int kRecord = LSF_ICP_RECORD_DOUBLES;
 constexpr int kDelta = 0, kTwist = 6, kEnergy = 12, kA = 13, kB = 49, kSkipped = 55, kCount = 56, kLevel = 57,
@@ -44,6 +48,7 @@ static_assert(kSub * kSub == kWave && (kTile / kSub) * (kTile / kSub) * kWave ==
 static_assert(LSF_ICP_SCRATCH_BYTES == 2 * kMaxBlocks * kSums * 8, "two ping-pong buffers of kMaxBlocks partials");
 static_assert(LSF_ICP_PYRAMID_SCRATCH_BYTES == 2 * kMaxBlocks * kPyrSums * 8, "the same with the 30th sum");
 static_assert(LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES == 2 * kMaxBlocks * kPhotoSums * 8, "the same with 31 sums");
+static_assert(LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES == 2 * kMaxBlocks * kPyrPhotoSums * 8, "the same with 32 sums");
 static_assert(kMaxBlocks <= kBlock, "the prologue gives every partial one thread");
 static_assert(kPhotoEnergy < kRecord && kRejected < kRecord && kB == kA + 36 && kSkipped == kB + 6, "the record holds every field");
 
@@ -123,15 +128,59 @@ struct PyramidSource {
     }
 };
 
-// lsf_icp_run_photometric: the strided pixels, and what the intensity term reads
+// What photometric_term asks of a source with kPhoto: the image the term is taken in -- its intrinsics and extents,
+// the pixel's unrounded projection into it, the prediction's intensity at one of its pixels -- and the live pixel's own
+// intensity; the last two sums of its K are the photometric pairs and sum r_I^2.
+
+// lsf_icp_run_photometric: the strided pixels; the term is taken in the full-resolution prediction
 template <typename DT>
 struct PhotometricSource : StridedSource<DT> {
+    using Pixel = typename StridedSource<DT>::Pixel;
     static constexpr int K = kPhotoSums;
     static constexpr bool kPhoto = true;
     const uint8_t* live_colour;  // [height][width][3]
     const float* pred_colour;    // [height][width][4], Y last
     float* intensity;            // r_I of the launch, or NULL: launch_run keeps it for the last iteration
     double lambda, max_difference;
+
+    __device__ double photo_fx(const IcpDev& p) const { return p.fx; }
+    __device__ double photo_fy(const IcpDev& p) const { return p.fy; }
+    __device__ int photo_width(const IcpDev& p) const { return p.width; }
+    __device__ int photo_height(const IcpDev& p) const { return p.height; }
+    // the geometric pair's own projection, before rint
+    __device__ void project(const IcpDev&, const double (&)[3], double pu, double pv, double& iu, double& iv) const {
+        iu = pu;
+        iv = pv;
+    }
+    __device__ double predicted(long long at) const { return (double)pred_colour[at * 4 + 3]; }
+    __device__ double observed(const IcpDev& p, Pixel px) const {
+        const uint8_t* lc = live_colour + ((long long)px.v * p.width + px.u) * 3;
+        return ((0.299 * (double)lc[0] + 0.587 * (double)lc[1]) + 0.114 * (double)lc[2]) / 255.0;
+    }
+};
+
+// lsf_icp_run_pyramid_photometric: the pixels of one pyramid level; the term is taken in that level of the
+// prediction's intensity pyramid, against the same level of the live one
+template <bool GATE>
+struct PyramidPhotometricSource : PyramidSource<GATE> {
+    using Pixel = typename PyramidSource<GATE>::Pixel;
+    static constexpr int K = kPyrPhotoSums;
+    static constexpr bool kPhoto = true;
+    const float* live_intensity;  // the level's [nj][ni] of the live frame's lsf_intensity_pyramid output
+    const float* pred_intensity;  // the same level of the prediction's
+    float* intensity;             // r_I of the launch at the level's extents, or NULL
+    double lambda, max_difference;
+
+    __device__ double photo_fx(const IcpDev&) const { return this->fx; }
+    __device__ double photo_fy(const IcpDev&) const { return this->fy; }
+    __device__ int photo_width(const IcpDev&) const { return this->grid.ni; }
+    __device__ int photo_height(const IcpDev&) const { return this->grid.nj; }
+    __device__ void project(const IcpDev&, const double (&q)[3], double, double, double& iu, double& iv) const {
+        iu = (this->fx * q[0]) / q[2] + this->cx;
+        iv = (this->fy * q[1]) / q[2] + this->cy;
+    }
+    __device__ double predicted(long long at) const { return (double)pred_intensity[at]; }
+    __device__ double observed(const IcpDev&, Pixel px) const { return (double)live_intensity[px.at]; }
 };
 
 // the twist after the step delta = (tau, omega): R' = R Rodrigues(omega)^T, t' = t - R' tau, out = (t', log R')
@@ -159,7 +208,7 @@ __device__ inline void compose(const double* tw, const double* delta, double* ou
 // solved and composed onto the twist before it (record k-2's, or twist_io); block 0 writes record k-1 and, with
 // twist_final, the final twist.  The finishing launch has one block, which reads twist_io before it writes it.
 // K = kPyrSums also writes the gate's rejections to record slot kRejected, K = kPhotoSums the photometric pairs and
-// energy to kPhotoCount and kPhotoEnergy.
+// energy to kPhotoCount and kPhotoEnergy, K = kPyrPhotoSums all three.
 template <int K>
 __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_level, double* __restrict__ twist_io,
                                              double* __restrict__ records, const double* __restrict__ scratch,
@@ -190,10 +239,10 @@ __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_le
             r[kLevel] = (double)prev_level;
             int i = kLevel + 1;
             if constexpr (K == kPyrSums) r[i++] = v[kSums];
-            if constexpr (K == kPhotoSums) {
-                r[kRejected] = 0.0;
-                r[kPhotoCount] = v[kSums];
-                r[kPhotoEnergy] = v[kSums + 1];
+            if constexpr (K == kPhotoSums || K == kPyrPhotoSums) {
+                r[kRejected] = K == kPyrPhotoSums ? v[kSums] : 0.0;
+                r[kPhotoCount] = v[K - 2];
+                r[kPhotoEnergy] = v[K - 1];
                 i = kPhotoEnergy + 1;
             }
             for (; i < kRecord; ++i) r[i] = 0.0;
@@ -223,31 +272,34 @@ __device__ __forceinline__ void load_poses(const double* tw, const IcpDev& p, do
 }
 
 // the intensity term of a pixel that has a geometric pair (q: its point in the prediction's camera, before the
-// projection is rounded; g: its world point): r_I, its scaled terms added to acc; NaN and nothing added when the 2 x 2
-// neighbourhood leaves the image, one of its four Y is not finite, or |r_I| exceeds the gate
+// projection is rounded, (gu, gv) that projection; g: its world point): r_I, its scaled terms added to acc; NaN and
+// nothing added when the 2 x 2 neighbourhood leaves the source's intensity image, one of its four Y is not finite, or
+// |r_I| exceeds the gate
 template <typename SRC>
-__device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::Pixel px, double pu, double pv,
+__device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::Pixel px, double gu, double gv,
                                                   const double (&q)[3], const double (&g)[3], const double (&ep)[12],
                                                   const IcpDev& p, double (&acc)[SRC::K]) {
+    double pu, pv;
+    src.project(p, q, gu, gv, pu, pv);
+    const int width = src.photo_width(p), height = src.photo_height(p);
     const double x0 = floor(pu), y0 = floor(pv);
     // compared as doubles first: NaN and far-off values never reach the integer conversion
-    if (!(0.0 <= x0 && x0 + 1.0 <= (double)(p.width - 1) && 0.0 <= y0 && y0 + 1.0 <= (double)(p.height - 1)))
+    if (!(0.0 <= x0 && x0 + 1.0 <= (double)(width - 1) && 0.0 <= y0 && y0 + 1.0 <= (double)(height - 1)))
         return NAN;
-    const long long at = (long long)(int)y0 * p.width + (int)x0;
-    const double I00 = (double)src.pred_colour[at * 4 + 3], I10 = (double)src.pred_colour[(at + 1) * 4 + 3];
-    const double I01 = (double)src.pred_colour[(at + p.width) * 4 + 3];
-    const double I11 = (double)src.pred_colour[(at + p.width + 1) * 4 + 3];
+    const long long at = (long long)(int)y0 * width + (int)x0;
+    const double I00 = src.predicted(at), I10 = src.predicted(at + 1);
+    const double I01 = src.predicted(at + width);
+    const double I11 = src.predicted(at + width + 1);
     if (!(isfinite(I00) && isfinite(I10) && isfinite(I01) && isfinite(I11))) return NAN;
     const double al = pu - x0, be = pv - y0;
     const double ha = 1.0 - al, hb = 1.0 - be;
     const double Ip = hb * (ha * I00 + al * I10) + be * (ha * I01 + al * I11);
     const double Iu = hb * (I10 - I00) + be * (I11 - I01);
     const double Iv = ha * (I01 - I00) + al * (I11 - I10);
-    const uint8_t* lc = src.live_colour + ((long long)px.v * p.width + px.u) * 3;
-    const double Il = ((0.299 * (double)lc[0] + 0.587 * (double)lc[1]) + 0.114 * (double)lc[2]) / 255.0;
+    const double Il = src.observed(p, px);
     const double rI = Ip - Il;
     if (!(fabs(rI) <= src.max_difference)) return NAN;
-    const double su = Iu * p.fx, sv = Iv * p.fy;
+    const double su = Iu * src.photo_fx(p), sv = Iv * src.photo_fy(p);
     const double c[3] = {su / q[2], sv / q[2], -((su * q[0] + sv * q[1]) / (q[2] * q[2]))};
     double a[3];
 #pragma unroll
@@ -263,8 +315,8 @@ __device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::
         for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc[21 + i] -= J[i] * r;
-    acc[kSums] += 1.0;
-    acc[kSums + 1] += rI * rI;
+    acc[SRC::K - 2] += 1.0;
+    acc[SRC::K - 1] += rI * rI;
     return (float)rI;
 }
 
@@ -507,6 +559,51 @@ Grid strided_grid(const Q* q, int stride) {
 
 const size_t kDepthBytes[3] = {2, 4, 8};
 
+// the checks of the pyramid parameter structs (lsf_icp_pyramid_params, lsf_icp_pyramid_photometric_params):
+// sum(iterations), or -1
+template <typename Q>
+long long pyramid_total(const Q* q, const double* records) {
+    if (!camera_ok(q) || !(q->cos_max_angle >= -1.0 && q->cos_max_angle <= 1.0)) return -1;
+    if (q->pyramid_levels < 1 || q->pyramid_levels > LSF_ICP_MAX_LEVELS || q->levels < 1 ||
+        q->levels > q->pyramid_levels || (q->height >> (q->pyramid_levels - 1)) < 1 ||
+        (q->width >> (q->pyramid_levels - 1)) < 1)
+        return -1;
+    return iteration_total(q->iterations, q->levels, records);
+}
+
+// the pixels of the last iteration's pyramid level: the extents of the residual images
+template <typename Q>
+size_t last_level_pixels(const Q* q) {
+    int last = 0;
+    for (int l = 0; l < q->levels; ++l)
+        if (q->iterations[l] > 0) last = q->levels - 1 - l;
+    return (size_t)(q->height >> last) * (q->width >> last);
+}
+
+template <typename Q>
+size_t pyramid_pixels(const Q* q) {
+    size_t n = 0;
+    for (int l = 0; l < q->pyramid_levels; ++l) n += (size_t)(q->height >> l) * (q->width >> l);
+    return n;
+}
+
+// the source of iterations entry l: lsf_depth_pyramid's layout and level intrinsics
+template <bool GATE, typename Q>
+PyramidSource<GATE> pyramid_level(const Q* q, int l) {
+    PyramidSource<GATE> src = {q->fx, q->fy, q->cx, q->cy, q->cos_max_angle, 0, {}};
+    const int level = q->levels - 1 - l;
+    for (int c = 0; c < level; ++c) {
+        const long long n = (long long)(q->height >> c) * (q->width >> c);
+        src.offset += n;
+        src.fx = src.fx / 2.0;
+        src.fy = src.fy / 2.0;
+        src.cx = (src.cx - 0.5) / 2.0;
+        src.cy = (src.cy - 0.5) / 2.0;
+    }
+    src.grid = grid_of(q->width >> level, q->height >> level);
+    return src;
+}
+
 }  // namespace
 
 extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, const float* pred_normals,
@@ -575,44 +672,58 @@ extern "C" int lsf_icp_run_pyramid(const float* live_depth, const float* live_no
     if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params)
         return LSF_ERR_BAD_ARGUMENT;
     const lsf_icp_pyramid_params* q = params;
-    if (!camera_ok(q) || !(q->cos_max_angle >= -1.0 && q->cos_max_angle <= 1.0)) return LSF_ERR_BAD_ARGUMENT;
-    if (q->pyramid_levels < 1 || q->pyramid_levels > LSF_ICP_MAX_LEVELS || q->levels < 1 ||
-        q->levels > q->pyramid_levels || (q->height >> (q->pyramid_levels - 1)) < 1 ||
-        (q->width >> (q->pyramid_levels - 1)) < 1)
-        return LSF_ERR_BAD_ARGUMENT;
-    const long long total = iteration_total(q->iterations, q->levels, records);
+    const long long total = pyramid_total(q, records);
     if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    int last = 0;  // the pyramid level of the last iteration
-    for (int l = 0; l < q->levels; ++l)
-        if (q->iterations[l] > 0) last = q->levels - 1 - l;
-    size_t pyramid_pixels = 0;
-    for (int l = 0; l < q->pyramid_levels; ++l) pyramid_pixels += (size_t)(q->height >> l) * (q->width >> l);
-    const size_t pixels = (size_t)q->height * q->width;
+    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
     if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_ICP_PYRAMID_SCRATCH_BYTES},
-                 {residuals_out, (size_t)(q->height >> last) * (q->width >> last) * 4}},
-                {{live_depth, pyramid_pixels * 4}, {live_normals, pyramid_pixels * 12}, {pred_depth, pixels * 4},
+                 {scratch, LSF_ICP_PYRAMID_SCRATCH_BYTES}, {residuals_out, last_level_pixels(q) * 4}},
+                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12}, {pred_depth, pixels * 4},
                  {pred_normals, pixels * 12}}))
         return LSF_ERR_BAD_ARGUMENT;
     if (total == 0) return 0;
     const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
                          residuals_out, total, stream);
     auto run = [&](auto gate) {
+        return launch_run(r, q->levels, q->iterations,
+                          [&](int l) { return pyramid_level<decltype(gate)::value>(q, l); });
+    };
+    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
+}
+
+extern "C" int lsf_icp_run_pyramid_photometric(const float* live_depth, const float* live_normals,
+                                               const float* live_intensity, const float* pred_depth,
+                                               const float* pred_normals, const float* pred_intensity,
+                                               double* twist_inout, double* records, void* scratch,
+                                               float* residuals_out, float* intensity_residuals_out,
+                                               const lsf_icp_pyramid_photometric_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!live_depth || !live_normals || !live_intensity || !pred_depth || !pred_normals || !pred_intensity ||
+        !twist_inout || !scratch || !params)
+        return LSF_ERR_BAD_ARGUMENT;
+    const lsf_icp_pyramid_photometric_params* q = params;
+    if (!(std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0))
+        return LSF_ERR_BAD_ARGUMENT;
+    const long long total = pyramid_total(q, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
+    const size_t last_bytes = last_level_pixels(q) * 4;
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
+                 {scratch, LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES}, {residuals_out, last_bytes},
+                 {intensity_residuals_out, last_bytes}},
+                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12},
+                 {live_intensity, levels_pixels * 4}, {pred_depth, pixels * 4}, {pred_normals, pixels * 12},
+                 {pred_intensity, levels_pixels * 4}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
+                         residuals_out, total, stream);
+    auto run = [&](auto gate) {
         return launch_run(r, q->levels, q->iterations, [&](int l) {
-            // lsf_depth_pyramid's layout and level intrinsics
-            PyramidSource<decltype(gate)::value> src = {q->fx, q->fy, q->cx, q->cy,
-                                                        q->cos_max_angle, 0, {}};
-            const int level = q->levels - 1 - l;
-            for (int c = 0; c < level; ++c) {
-                const long long n = (long long)(q->height >> c) * (q->width >> c);
-                src.offset += n;
-                src.fx = src.fx / 2.0;
-                src.fy = src.fy / 2.0;
-                src.cx = (src.cx - 0.5) / 2.0;
-                src.cy = (src.cy - 0.5) / 2.0;
-            }
-            src.grid = grid_of(q->width >> level, q->height >> level);
-            return src;
+            const PyramidSource<decltype(gate)::value> level = pyramid_level<decltype(gate)::value>(q, l);
+            return PyramidPhotometricSource<decltype(gate)::value>{level, live_intensity + level.offset,
+                                                                   pred_intensity + level.offset,
+                                                                   intensity_residuals_out, q->photometric_weight,
+                                                                   q->max_intensity_difference};
         });
     };
     return q->angle_gate ? run(std::true_type()) : run(std::false_type());

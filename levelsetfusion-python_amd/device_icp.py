@@ -4,14 +4,16 @@ the records back once.  The public interfaces are rigid_opt.ProjectiveIcp3d and
 fusion.SequenceFusion3d(tracking_reference="icp").  icp_run_pyramid (lsf_icp_run_pyramid) is the same schedule over a
 live depth pyramid (device_depth_pyramid), with an optional normal-angle gate.  icp_run_photometric
 (lsf_icp_run_photometric) is icp_run with an intensity term against the ray-cast colour image
-(device_raycast.raycast(..., colour=)) in the same normal equations."""
+(device_raycast.raycast(..., colour=)) in the same normal equations; icp_run_pyramid_photometric
+(lsf_icp_run_pyramid_photometric) is icp_run_pyramid with that term taken at each pixel's own level, between two
+intensity pyramids (device_intensity_pyramid)."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, IcpPhotometricParams, IcpPyramidParams, lib
+from ._lib import IcpParams, IcpPhotometricParams, IcpPyramidParams, IcpPyramidPhotometricParams, lib
 from .device_core import require_gpu
 from .device_fusion import check_colour_image
 from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
@@ -89,13 +91,16 @@ def _prediction(x, name, shape):
     return x
 
 
-def _run(entry, name, live, pred_depth, pred_normals, p, twist, scratch_bytes, residual_shape, pred_colour=None):
+def _run(entry, name, live, pred_depth, pred_normals, p, twist, scratch_bytes, residual_shape, pred_colour=None,
+         pred_colour_shape=None):
     """the run of p enqueued (device_rigid.enqueue_run) after the checks of the prediction: icp_run's triple, and with
-    pred_colour (lsf_icp_run_photometric) the intensity residual image as a fourth value"""
+    pred_colour (lsf_icp_run_photometric's colour image; with pred_colour_shape, lsf_icp_run_pyramid_photometric's
+    intensity pyramid) the intensity residual image as a fourth value"""
     h, w = p.height, p.width
     inputs = live + (_prediction(pred_depth, "pred_depth", (h, w)), _prediction(pred_normals, "pred_normals", (h, w, 3)))
     if pred_colour is not None:
-        inputs += (_prediction(pred_colour, "pred_colour", (h, w, 4)),)
+        inputs += (_prediction(pred_colour, "pred_colour" if pred_colour_shape is None else "pred_intensity",
+                               (h, w, 4) if pred_colour_shape is None else pred_colour_shape),)
     res = intensity = None
     if residual_shape is not None:
         res = torch.empty(residual_shape, dtype=torch.float32, device=pred_depth.device)
@@ -163,9 +168,10 @@ def cos_max_angle(max_normal_angle):
 
 
 def pyramid_params(camera, image_shape, pyramid_levels, twist_p, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
-                   max_normal_angle=None):
-    """the lsf_icp_pyramid_params of a call, after the host checks; max_normal_angle None: no gate"""
-    p = IcpPyramidParams()
+                   max_normal_angle=None, into=None):
+    """the lsf_icp_pyramid_params of a call, after the host checks; max_normal_angle None: no gate (into: another
+    struct with its members to fill instead)"""
+    p = IcpPyramidParams() if into is None else into
     p.height, p.width = image_extents(image_shape)
     p.pyramid_levels = int(pyramid_levels)
     if not 1 <= p.pyramid_levels <= _lib.ICP_MAX_LEVELS or (p.height >> (p.pyramid_levels - 1)) < 1 or \
@@ -205,10 +211,46 @@ def icp_run_pyramid(pyramid_depth, pyramid_normals, pyramid_levels, pred_depth, 
                 (h >> last, w >> last) if residuals else None)
 
 
+def pyramid_photometric_params(camera, image_shape, pyramid_levels, twist_p, photometric_weight,
+                               max_intensity_difference=math.inf, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
+                               max_normal_angle=None):
+    """the lsf_icp_pyramid_photometric_params of a call, after the host checks"""
+    p = pyramid_params(camera, image_shape, pyramid_levels, twist_p, iterations, max_distance, max_normal_angle,
+                       IcpPyramidPhotometricParams())
+    p.photometric_weight, p.max_intensity_difference = photometric_settings(photometric_weight,
+                                                                            max_intensity_difference)
+    return p
+
+
+def icp_run_pyramid_photometric(pyramid_depth, pyramid_normals, pyramid_intensity, pyramid_levels, pred_depth,
+                                pred_normals, pred_intensity, camera, twist_p, photometric_weight, twist=None,
+                                iterations=ITERATIONS, max_distance=MAX_DISTANCE, max_normal_angle=None,
+                                max_intensity_difference=math.inf, residuals=False):
+    """icp_run_pyramid with the photometric term at every pixel's own level (lsf_icp_run_pyramid_photometric): the
+    same launches and one copy back.  pyramid_intensity and pred_intensity: the buffers of
+    device_intensity_pyramid.intensity_pyramid for the frame's colour image ("colour") and for the ray-cast colour
+    image at twist_p ("prediction"), both of pyramid_levels levels at the prediction's extents.  Returns
+    icp_run_photometric's four values; both residual images have the extents of the last iteration's level."""
+    require_gpu()
+    if not (isinstance(pred_depth, torch.Tensor) and pred_depth.dim() == 2):
+        raise ValueError("pred_depth must be an (H, W) device tensor (device_raycast.raycast)")
+    h, w = (int(v) for v in pred_depth.shape)
+    p = pyramid_photometric_params(camera, (h, w), pyramid_levels, twist_p, photometric_weight,
+                                   max_intensity_difference, iterations, max_distance, max_normal_angle)
+    pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
+    live = (_prediction(pyramid_depth, "pyramid_depth", (pixels,)),
+            _prediction(pyramid_normals, "pyramid_normals", (pixels, 3)),
+            _prediction(pyramid_intensity, "pyramid_intensity", (pixels,)))
+    last = last_level(p.iterations[:p.levels])
+    return _run(lib.lsf_icp_run_pyramid_photometric, "lsf_icp_run_pyramid_photometric", live, pred_depth, pred_normals,
+                p, twist_p if twist is None else twist, _lib.ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES,
+                (h >> last, w >> last) if residuals else None, pred_intensity, (pixels,))
+
+
 def unpack_record(r):
     """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES); angle_rejected is 0 on
     every lsf_icp_run record, photometric_count and photometric_energy are 0 on every record that is not
-    lsf_icp_run_photometric's"""
+    lsf_icp_run_photometric's or lsf_icp_run_pyramid_photometric's"""
     return {"delta": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
             "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
             "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57]), "angle_rejected": int(r[58]),

@@ -63,7 +63,8 @@ with the filter settings of `confidence.pyramid`, else a one-level pyramid of th
 With `colour` the model holds a colour volume, integrate(depth_image, colour_image) needs a colour image on every frame
 and fuses it through the colour entry point, with `carve` and `confidence` as set, in every tracking mode; tracking
 does not read the colour unless `photometric_weight` is set.
-With `photometric_weight` (lambda; it needs colour=True and tracking_reference="icp", and no `icp_pyramid`) frames
+With `photometric_weight` (lambda; it needs colour=True and tracking_reference="icp", and with an `icp_pyramid` also
+an `icp_intensity_pyramid`) frames
 k >= 1 are tracked by the joint geometric and photometric solve (INTEGRATION.md section 3, "Photometric ICP";
 rigid_opt.ProjectiveIcp3d, device_icp.icp_run_photometric; tests/photometric_restatement.py restates it) against the
 model ray-cast with normals and colour at the previous twist (CanonicalVolume.raycast(..., colours=True),
@@ -72,6 +73,14 @@ pixel with a geometric pair adds lambda times its intensity residual against the
 prediction's Y, so a flat textured wall, whose geometry leaves t_x, t_y and r_z free, is tracked.
 `icp_max_intensity_difference` gates |r_I|; `prediction_colour` keeps the last colour image.  lambda has no default
 other than off: no value is right across scenes.
+With `icp_pyramid`, `icp_intensity_pyramid` (a rigid_opt.IntensityPyramid of the same levels) and `photometric_weight`
+the joint solve runs on the depth pyramid (device_icp.icp_run_pyramid_photometric;
+tests/pyramid_photometric_restatement.py restates it): the tracker builds an intensity pyramid of the frame's colour
+image and one of the prediction's Y (2 x 2 means, NaN where one of the four has no colour), and a pixel of level L takes
+its intensity term at level L of both with that level's intrinsics; `icp_max_normal_angle` still gates the geometric
+pairs.  Without an `icp_intensity_pyramid` the combination is refused, since then there is no intensity pyramid to
+take the term from.  Fusion still integrates the raw depth, `confidence` still shares the tracker's depth pyramid and
+`prediction_colour` is kept.
 With a `nonrigid_optimizer` that is a HierarchicalOptimizer3d, every frame k >= 1 is fused through its warp field
 ("Warped depth fusion"; tests/warped_fusion_restatement.py restates it).  After tracking, the
 live volume under the twist is generated (device_rigid.live_volume_3d), `psi = optimizer.optimize(model.tsdf, live)` is
@@ -101,9 +110,9 @@ vertex and face totals.
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SlavchevaOptimizer3d, a carve-distance
 limit, keeping the warp field between frames as a warm start, ray-casting or meshing in the live frame, a whole frame
 enqueued without host synchronisations, z-slab / multi-GPU fusion, a 2-D depth-mode row generator, fusing the filtered
-depth, a downsampled prediction pyramid, robust ICP weights (Huber / Tukey) on either term, ICP combined with
-SDF-2-SDF, an adaptive ray-casting step, a confidence image in the prediction, the photometric term on the depth
-pyramid (an intensity pyramid), a colour image of another
+depth, a downsampled prediction depth and normal pyramid (every level still pairs into the full-resolution
+prediction), robust ICP weights (Huber / Tukey) on either term, smoothing the intensity before level 0, ICP combined
+with SDF-2-SDF, an adaptive ray-casting step, a confidence image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
 import math
@@ -330,14 +339,15 @@ class SequenceFusion3d:
     non-rigid step, `warp` (the last frame's displacement field, a float32 (Z, Y, X, 3) device tensor; None before
     frame 1).  In "icp" mode rigid_records holds the ICP
     records (device_icp.unpack_record); with photometric_weight they carry photometric_count and photometric_energy,
-    and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image."""
+    and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image; with icp_intensity_pyramid the
+    joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids)."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
-                 photometric_weight=None, icp_max_intensity_difference=math.inf):
+                 photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None):
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
@@ -366,15 +376,17 @@ class SequenceFusion3d:
         if photometric_weight is not None:
             if not self.colour or tracking_reference != "icp":
                 raise ValueError("photometric_weight needs colour=True and tracking_reference=\"icp\"")
-            if icp_pyramid is not None:
+            if icp_pyramid is not None and icp_intensity_pyramid is None:
                 raise ValueError("photometric_weight does not combine with an icp_pyramid: there is no intensity "
                                  "pyramid")
         # the "icp" tracker; its arguments are checked in every mode
         t = self.icp = ProjectiveIcp3d(camera, icp_iterations, icp_strides, icp_max_distance, icp_pyramid,
-                                       icp_max_normal_angle, photometric_weight, icp_max_intensity_difference)
+                                       icp_max_normal_angle, photometric_weight, icp_max_intensity_difference,
+                                       icp_intensity_pyramid)
         self.photometric_weight, self.icp_max_intensity_difference = t.photometric_weight, t.max_intensity_difference
         self.icp_iterations, self.icp_strides, self.icp_max_distance = t.iterations, t.strides, t.max_distance
         self.icp_pyramid, self.icp_max_normal_angle = t.pyramid, t.max_normal_angle
+        self.icp_intensity_pyramid = t.intensity_pyramid
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)

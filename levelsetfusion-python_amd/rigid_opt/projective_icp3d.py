@@ -15,15 +15,23 @@ With a DepthPyramid (pyramid=...) the live frame is first turned into a filtered
 the iterations (coarse first) uses every pixel of pyramid level len(iterations) - 1 - k instead of a stride;
 max_normal_angle (radians) adds the normal-angle gate.  The pyramid of the last call stays as `last_pyramid`.
 
-With photometric_weight (lambda; strided path only) the solve is the joint geometric and photometric one of
-INTEGRATION.md section 3 ("Photometric ICP"; tests/photometric_restatement.py restates it): every live pixel with a
+With photometric_weight (lambda; on the strided path, or on a pyramid with an intensity_pyramid) the solve is the
+joint geometric and photometric one of INTEGRATION.md section 3 ("Photometric ICP"; tests/photometric_restatement.py restates it): every live pixel with a
 geometric pair also compares its own intensity with the bilinear interpolant of the prediction's intensity image --
 the Y channel of the model's ray-cast colour (CanonicalVolume.raycast with colours=True) -- at its unrounded projection,
 and lambda times that residual and its Jacobian go into the same normal equations.  It holds the pose where geometry
 does not: on a flat wall t_x, t_y and r_z leave the geometric A singular.  track and optimize then take the frame's
 uint8 (H, W, 3) colour image and the prediction's (H, W, 4) colour image; max_intensity_difference gates |r_I|; the
 records carry photometric_count and photometric_energy, and `last_intensity_residuals` keeps r_I beside
-`last_residuals`.  lambda has no default: no value is right across scenes."""
+`last_residuals`.  lambda has no default: no value is right across scenes.
+
+With pyramid, intensity_pyramid (an IntensityPyramid of the pyramid's levels) and photometric_weight together the joint
+solve runs on the depth pyramid (device_icp.icp_run_pyramid_photometric; tests/pyramid_photometric_restatement.py
+restates it): track builds an intensity pyramid of the frame's colour image and one of the prediction's Y, and a pixel
+of level L with a geometric pair takes its intensity term at level L of both, with that level's intrinsics.
+max_normal_angle still applies.  The two pyramids of the last call stay as `last_intensity_pyramids` (live,
+prediction).  A pyramid with photometric_weight and without an intensity_pyramid is refused: there is no intensity
+pyramid to take the term from."""
 import math
 
 import numpy as np
@@ -33,6 +41,7 @@ from .. import device_icp
 from ..device_core import require_gpu
 from ..device_rigid import twist6
 from .depth_pyramid import DepthPyramid
+from .intensity_pyramid import IntensityPyramid
 from ..tsdf.generation import device_depth
 
 __all__ = ["ProjectiveIcp3d"]
@@ -50,11 +59,12 @@ def _prediction(x, trailing):
 class ProjectiveIcp3d:
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
                  max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None, photometric_weight=None,
-                 max_intensity_difference=math.inf):
+                 max_intensity_difference=math.inf, intensity_pyramid=None):
         """pyramid: None (the strided live image) or a DepthPyramid, with which strides is not used and iterations has
         one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only);
-        photometric_weight: None (geometric only) or lambda, finite and > 0 (strided only); max_intensity_difference:
-        the gate on |r_I|, > 0"""
+        photometric_weight: None (geometric only) or lambda, finite and > 0 (with a pyramid it needs an
+        intensity_pyramid); max_intensity_difference: the gate on |r_I|, > 0; intensity_pyramid: None or an
+        IntensityPyramid of pyramid.levels levels, which needs both a pyramid and a photometric_weight"""
         self.camera = camera
         if pyramid is not None and not isinstance(pyramid, DepthPyramid):
             raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
@@ -74,14 +84,25 @@ class ProjectiveIcp3d:
         self.max_distance = float(max_distance)
         self.photometric_weight = None
         _, self.max_intensity_difference = device_icp.photometric_settings(1.0, max_intensity_difference)
+        if intensity_pyramid is not None:
+            if not isinstance(intensity_pyramid, IntensityPyramid):
+                raise ValueError("intensity_pyramid must be a rigid_opt.IntensityPyramid or None, got %r"
+                                 % (intensity_pyramid,))
+            if pyramid is None or photometric_weight is None:
+                raise ValueError("intensity_pyramid needs both a pyramid and a photometric_weight")
+            if intensity_pyramid.levels != pyramid.levels:
+                raise ValueError("intensity_pyramid has %d levels, the pyramid %d: they must be equal"
+                                 % (intensity_pyramid.levels, pyramid.levels))
+        self.intensity_pyramid = intensity_pyramid
         if photometric_weight is not None:
-            if pyramid is not None:
+            if pyramid is not None and intensity_pyramid is None:
                 raise ValueError("photometric_weight needs the strided path: there is no intensity pyramid")
             self.photometric_weight, _ = device_icp.photometric_settings(photometric_weight)
         self.last_records = []
         self.last_residuals = None
         self.last_intensity_residuals = None
         self.last_pyramid = None
+        self.last_intensity_pyramids = None  # (live, prediction) IntensityLevels of the last joint pyramid call
 
     def track(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals=False,
               colour_image=None, prediction_colour=None):
@@ -93,7 +114,15 @@ class ProjectiveIcp3d:
                 (colour_image is None) != (prediction_colour is None):
             raise ValueError("colour_image and prediction_colour go with a tracker made with photometric_weight, and "
                              "only with one")
-        if self.photometric_weight is not None:
+        if self.intensity_pyramid is not None:
+            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
+            live, pred = self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
+                                                         self.intensity_pyramid.build_prediction(prediction_colour))
+            out, records, res, self.last_intensity_residuals = device_icp.icp_run_pyramid_photometric(
+                *self.last_pyramid.buffers, live.buffer, self.pyramid.levels, prediction_depth, prediction_normals,
+                pred.buffer, self.camera, twist_p, self.photometric_weight, twist, self.iterations, self.max_distance,
+                self.max_normal_angle, self.max_intensity_difference, residuals)
+        elif self.photometric_weight is not None:
             out, records, res, self.last_intensity_residuals = device_icp.icp_run_photometric(
                 depth, code, colour_image, prediction_depth, prediction_normals, prediction_colour, self.camera,
                 twist_p, self.photometric_weight, twist, self.iterations, self.strides, self.max_distance,
