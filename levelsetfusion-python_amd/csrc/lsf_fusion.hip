@@ -1,27 +1,28 @@
 // Fusion of aligned frames into a canonical TSDF volume (include/lsf_hip.h, lsf_fusion_*): the model update of
-// KillingFusion / SobolevFusion, which the reference does not have; the rule is this project's (INTEGRATION.md
-// section 3, "Fusion"; tests/fusion_restatement.py restates it).  One kernel, two live sources, one update:
-//   VOLUME  the live value of a voxel is read from a given float32 field (flat index, 16-byte accesses per lane)
-//   DEPTH   the live value is generated from a depth image under a twist by the rigid 3-D tracker's own code
-//           (live_extrinsic + typed_tsdf_voxel, lsf_tsdf_typed.h, with its host setup and dispatch) and fused in the
-//           same pass; no live volume is written
-// Every lane takes four consecutive voxels per step of a grid-stride loop; the grid depends on the voxel count alone,
-// so both sources visit the voxels in one order and sum the record identically.  Per-workgroup partials go to
-// scratch; a finishing one-workgroup launch combines them in a fixed order (the sums by the trackers' butterfly,
-// wave_sum_xor in lsf_rigid_solve.h): no atomics, reruns are bit-identical.
+// KillingFusion / SobolevFusion, which the reference does not have; the rules are this project's (INTEGRATION.md
+// section 3, "Fusion" and what follows it; tests/*_restatement.py restate them).
+// One kernel, fusion_kernel<RULE>, walks the voxels for every entry point.  Every lane takes four consecutive voxels per
+// step of a grid-stride loop: it asks the rule what the four observe, loads their tsdf and weight in one 16-byte access
+// each (scalar ones off alignment), lets the rule fuse each in the order k = 0..3, and stores only when one of them
+// changed.  The n % 4 voxels after the last step are the tail, taken by lane 0 of workgroup 0 after its own steps.  The
+// grid depends on the voxel count alone, so every rule visits the voxels in one order and sums its record identically.
+// Per-workgroup partials go to scratch; a finishing one-workgroup launch combines them in a fixed order (the sums by the
+// trackers' butterfly, wave_sum_xor in lsf_rigid_solve.h): no atomics, reruns are bit-identical.
 // -ffp-contract=off keeps W t + w l two roundings and an add, as numpy computes it.
-// lsf_fusion_integrate_depth_weighted is the DEPTH kernel with the weighted rule ("Weighted
-// fusion and carving"; tests/fusion_weighted_restatement.py): the same four voxels per lane, 16-byte accesses, grid and
-// finishing launch, with the pixel a voxel projects to (typed_tsdf_sample) selecting its weight from a float32 image,
-// +1 fused in the seen free space in front of the band, and six partials per workgroup instead of four.
-// lsf_fusion_integrate_depth_colour is that kernel again with a colour volume beside the model (INTEGRATION.md section 3,
-// "Colour fusion"; tests/colour_restatement.py): one float32 (R, G, B, Wc) record per voxel, loaded and stored in one
-// 16-byte access each and only where the voxel lies inside the colour band, three byte reads of the colour image at the
-// voxel's pixel, and eight partials per workgroup.  The geometry code is fuse_voxel_weighted itself.
-// lsf_fusion_integrate_depth_warped is the non-rigid step's fusion ("Warped depth fusion";
-// tests/warped_fusion_restatement.py): a voxel observes the frame at its point displaced by a warp field, float32
-// (Z, Y, X, 3) interleaved -- 12 floats per four-voxel step, three 16-byte loads -- and fuse_voxel_weighted and
-// colour_voxel run unchanged on what that point sees (typed_tsdf_sample_at); nine partials per workgroup.
+// A rule says what a voxel observes and what is done with it:
+//   VolumeRule    lsf_fusion_integrate_volume: the live value is read from a given float32 field (flat index)
+//   DepthRule     lsf_fusion_integrate_depth: the live value is generated from a depth image under a twist by the rigid
+//                 3-D tracker's own code (live_extrinsic + typed_tsdf_voxel, lsf_tsdf_typed.h, with its host setup and
+//                 dispatch); no live volume is written.  Both fuse by fuse_voxel; four partials per workgroup
+//   WeightedRule  the other three entry points: the voxel keeps the pixel it projects to (typed_tsdf_sample), which
+//                 selects its weight from a float32 image, and +1 is fused in the seen free space in front of the band
+//                 (fuse_voxel_weighted; six partials).  With WARP the voxel observes the frame at its point displaced by
+//                 a warp field, float32 (Z, Y, X, 3) interleaved -- 12 floats per step, three 16-byte loads
+//                 (typed_tsdf_sample_at; nine partials).  With COLOUR an updated voxel inside the colour band also
+//                 averages its (R, G, B, Wc) record, one 16-byte load and store, with three byte reads of the colour
+//                 image at its pixel (colour_voxel; eight partials); outside the band colour memory is not touched
+#include <initializer_list>
+
 #include "lsf_device.h"
 #include "lsf_rigid_solve.h"
 #include "lsf_tsdf_typed.h"
@@ -43,8 +44,6 @@ static_assert(LSF_FUSION_WEIGHTED_SCRATCH_BYTES == kMaxBlocks * kWParts * 8, "a 
 static_assert(LSF_FUSION_COLOUR_SCRATCH_BYTES == kMaxBlocks * kCParts * 8, "a workgroup's partials");
 static_assert(LSF_FUSION_WARPED_SCRATCH_BYTES == kMaxBlocks * kXParts * 8, "a workgroup's partials");
 static_assert(LSF_FUSION_WARPED_RECORD_DOUBLES == kXParts, "the warped record is its partials");
-
-enum Source { VOLUME = 0, DEPTH = 1 };
 
 struct FusionDev {
     TypedTsdf t;        // DEPTH
@@ -71,6 +70,12 @@ struct WeightedAcc {
 struct ColourAcc {
     WeightedAcc w;
     int coloured, first;
+};
+
+// the weighted rule's: a counter that an instantiation never touches costs nothing
+struct WarpedAcc {
+    ColourAcc c;
+    int rejected;
 };
 
 // the colour side of a call: the volume of (R, G, B, Wc) records, the uint8 (R, G, B) image, the band
@@ -207,152 +212,6 @@ __device__ inline void block_combine(double (&v)[N], double (*red)[N]) {
         }
 }
 
-template <int SOURCE, typename DT, typename PT>
-__global__ __launch_bounds__(kBlock) void fusion_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
-                                                        const float* __restrict__ live,
-                                                        const DT* __restrict__ depth, double* __restrict__ scratch,
-                                                        FusionDev p) {
-    __shared__ double e[12];
-    __shared__ double red[kBlock / kWave][kParts];
-    if (SOURCE == DEPTH) {
-        if (threadIdx.x == 0) live_extrinsic(p.twist, e);
-        __syncthreads();
-    }
-    const bool aligned = p.aligned != 0;
-    Acc a = {0, 0, 0.0, 0.0f};
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
-        const long long i = g * 4;
-        float l[4], t[4], W[4];
-        if (SOURCE == VOLUME) {
-            load4(live, i, l, aligned);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) l[k] = depth_voxel<DT, PT>(depth, p, e, i + k);
-        }
-        load4(tsdf, i, t, aligned);
-        load4(weight, i, W, aligned);
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) any = fuse_voxel(l[k], t[k], W[k], p, a) || any;
-        if (any) {  // a step without an observed voxel stores nothing; the stored values would equal the loaded ones
-            store4(tsdf, i, t, aligned);
-            store4(weight, i, W, aligned);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
-        for (long long i = p.groups * 4; i < p.n; ++i) {
-            const float l = SOURCE == VOLUME ? live[i] : depth_voxel<DT, PT>(depth, p, e, i);
-            float t = tsdf[i], W = weight[i];
-            if (fuse_voxel(l, t, W, p, a)) {
-                tsdf[i] = t;
-                weight[i] = W;
-            }
-        }
-    double v[kParts] = {(double)a.fused, (double)a.first, a.sum, (double)a.max};
-    block_combine(v, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int c = 0; c < kParts; ++c) scratch[(size_t)blockIdx.x * kParts + c] = v[c];
-}
-
-// the weighted rule on a depth image: fusion_kernel<DEPTH>'s walk, stores and partials with fuse_voxel_weighted
-template <typename DT, typename PT>
-__global__ __launch_bounds__(kBlock) void fusion_weighted_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
-                                                                 const DT* __restrict__ depth,
-                                                                 const float* __restrict__ pixel_weight,
-                                                                 double* __restrict__ scratch, FusionDev p, int carve) {
-    __shared__ double e[12];
-    __shared__ double red[kBlock / kWave][kWParts];
-    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
-    __syncthreads();
-    const bool aligned = p.aligned != 0, carving = carve != 0;
-    WeightedAcc a = {{0, 0, 0.0, 0.0f}, 0, 0};
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
-        const long long i = g * 4;
-        TsdfSample s[4];
-        float t[4], W[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = depth_sample<DT, PT>(depth, p, e, i + k);
-        load4(tsdf, i, t, aligned);
-        load4(weight, i, W, aligned);
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) any = fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a) || any;
-        if (any) {  // a step without an updated voxel stores nothing
-            store4(tsdf, i, t, aligned);
-            store4(weight, i, W, aligned);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
-        for (long long i = p.groups * 4; i < p.n; ++i) {
-            float t = tsdf[i], W = weight[i];
-            if (fuse_voxel_weighted(depth_sample<DT, PT>(depth, p, e, i), pixel_weight, carving, t, W, p, a)) {
-                tsdf[i] = t;
-                weight[i] = W;
-            }
-        }
-    double v[kWParts] = {(double)a.a.fused, (double)a.a.first, a.a.sum, (double)a.a.max, (double)a.carved,
-                         (double)a.rejected};
-    block_combine(v, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int c = 0; c < kWParts; ++c) scratch[(size_t)blockIdx.x * kWParts + c] = v[c];
-}
-
-// the weighted rule with colour: fusion_weighted_kernel's walk, stores and partials, and colour_voxel at every updated voxel
-template <typename DT, typename PT>
-__global__ __launch_bounds__(kBlock) void fusion_colour_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
-                                                               const DT* __restrict__ depth,
-                                                               const float* __restrict__ pixel_weight,
-                                                               double* __restrict__ scratch, FusionDev p, int carve,
-                                                               ColourDev c) {
-    __shared__ double e[12];
-    __shared__ double red[kBlock / kWave][kCParts];
-    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
-    __syncthreads();
-    const bool aligned = p.aligned != 0, carving = carve != 0;
-    ColourAcc a = {{{0, 0, 0.0, 0.0f}, 0, 0}, 0, 0};
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
-        const long long i = g * 4;
-        TsdfSample s[4];
-        float t[4], W[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = depth_sample<DT, PT>(depth, p, e, i + k);
-        load4(tsdf, i, t, aligned);
-        load4(weight, i, W, aligned);
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a.w)) {
-                any = true;
-                colour_voxel(s[k], pixel_weight, c, i + k, p, a);
-            }
-        if (any) {  // a step without an updated voxel stores nothing
-            store4(tsdf, i, t, aligned);
-            store4(weight, i, W, aligned);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
-        for (long long i = p.groups * 4; i < p.n; ++i) {
-            float t = tsdf[i], W = weight[i];
-            const TsdfSample s = depth_sample<DT, PT>(depth, p, e, i);
-            if (fuse_voxel_weighted(s, pixel_weight, carving, t, W, p, a.w)) {
-                tsdf[i] = t;
-                weight[i] = W;
-                colour_voxel(s, pixel_weight, c, i, p, a);
-            }
-        }
-    double v[kCParts] = {(double)a.w.a.fused, (double)a.w.a.first,  a.w.a.sum,          (double)a.w.a.max,
-                         (double)a.w.carved,  (double)a.w.rejected, (double)a.coloured, (double)a.first};
-    block_combine(v, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int c8 = 0; c8 < kCParts; ++c8) scratch[(size_t)blockIdx.x * kCParts + c8] = v[c8];
-}
-
 // the twelve warp floats of the four voxels from i on: three 16-byte loads, or scalar ones off alignment
 __device__ inline void load_warp4(const float* __restrict__ warp, long long i, float (&v)[12], bool aligned) {
     const float* f = warp + i * 3;
@@ -388,64 +247,138 @@ __device__ inline TsdfSample warped_sample(const DT* __restrict__ depth, const F
     return typed_tsdf_sample_at<3, double, PT, DT>(depth, p.t, e, xv, yv, zv);
 }
 
-// the weighted rule (and colour, when c.volume is given) at the warped point of every voxel: fusion_colour_kernel's
-// walk, stores and partials
+// ---- the rules.  A rule has N partials, an accumulator Acc, an observation Obs, kExtrinsic (whether e is needed), and
+//   observe4(i, p, e, o, a)    what the four voxels from i on observe
+//   observe(i, p, e, a)        what the tail voxel i observes
+//   fuse(o, i, t, W, p, a)     the update of voxel i, which observed o; true when its tsdf and weight may have changed
+//   parts(a, v)                the lane's partials
+
+struct PlainRule {
+    static constexpr int N = kParts;
+    using Acc = ::Acc;
+    using Obs = float;
+    __device__ static bool fuse(float l, long long, float& t, float& W, const FusionDev& p, Acc& a) {
+        return fuse_voxel(l, t, W, p, a);
+    }
+    __device__ static void parts(const Acc& a, double (&v)[N]) {
+        v[0] = (double)a.fused; v[1] = (double)a.first; v[2] = a.sum; v[3] = (double)a.max;
+    }
+};
+
+struct VolumeRule : PlainRule {
+    static constexpr bool kExtrinsic = false;
+    const float* __restrict__ live;
+    __device__ void observe4(long long i, const FusionDev& p, const double*, float (&l)[4], Acc&) const {
+        load4(live, i, l, p.aligned != 0);
+    }
+    __device__ float observe(long long i, const FusionDev&, const double*, Acc&) const { return live[i]; }
+};
+
 template <typename DT, typename PT>
-__global__ __launch_bounds__(kBlock) void fusion_warped_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
-                                                               const float* __restrict__ warp,
-                                                               const DT* __restrict__ depth,
-                                                               const float* __restrict__ pixel_weight,
-                                                               double* __restrict__ scratch, FusionDev p, int carve,
-                                                               ColourDev c, int warp_aligned) {
+struct DepthRule : PlainRule {
+    static constexpr bool kExtrinsic = true;
+    const DT* __restrict__ depth;
+    __device__ void observe4(long long i, const FusionDev& p, const double* e, float (&l)[4], Acc&) const {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) l[k] = depth_voxel<DT, PT>(depth, p, e, i + k);
+    }
+    __device__ float observe(long long i, const FusionDev& p, const double* e, Acc&) const {
+        return depth_voxel<DT, PT>(depth, p, e, i);
+    }
+};
+
+enum Colour { NEVER = 0, ALWAYS = 1, IF_GIVEN = 2 };  // IF_GIVEN: when c.volume is given, one instantiation for both
+
+template <typename DT, typename PT, bool WARP, int COLOUR, int PARTS>
+struct WeightedRule {
+    static_assert(PARTS == kWParts || PARTS == kCParts || PARTS == kXParts, "the three weighted records");
+    static constexpr int N = PARTS;
+    static constexpr bool kExtrinsic = true;
+    using Acc = WarpedAcc;
+    using Obs = TsdfSample;
+    const DT* __restrict__ depth;
+    const float* __restrict__ pixel_weight;
+    const float* __restrict__ warp;  // WARP
+    ColourDev c;                     // COLOUR
+    int carve, warp_aligned;
+    __device__ void observe4(long long i, const FusionDev& p, const double* e, TsdfSample (&s)[4], Acc& a) const {
+        if constexpr (WARP) {
+            float psi[12];
+            load_warp4(warp, i, psi, warp_aligned != 0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                s[k] = warped_sample<DT, PT>(depth, p, e, i + k, psi[3 * k], psi[3 * k + 1], psi[3 * k + 2], a.rejected);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] = depth_sample<DT, PT>(depth, p, e, i + k);
+        }
+    }
+    __device__ TsdfSample observe(long long i, const FusionDev& p, const double* e, Acc& a) const {
+        if constexpr (WARP) {
+            const float* f = warp + i * 3;
+            return warped_sample<DT, PT>(depth, p, e, i, f[0], f[1], f[2], a.rejected);
+        } else {
+            return depth_sample<DT, PT>(depth, p, e, i);
+        }
+    }
+    __device__ bool fuse(const TsdfSample& s, long long i, float& t, float& W, const FusionDev& p, Acc& a) const {
+        if (!fuse_voxel_weighted(s, pixel_weight, carve != 0, t, W, p, a.c.w)) return false;
+        if (COLOUR == ALWAYS || (COLOUR == IF_GIVEN && c.volume != nullptr)) colour_voxel(s, pixel_weight, c, i, p, a.c);
+        return true;
+    }
+    __device__ static void parts(const Acc& a, double (&v)[N]) {
+        const WeightedAcc& w = a.c.w;
+        v[0] = (double)w.a.fused; v[1] = (double)w.a.first; v[2] = w.a.sum; v[3] = (double)w.a.max;
+        v[4] = (double)w.carved; v[5] = (double)w.rejected;
+        if constexpr (N >= kCParts) { v[6] = (double)a.c.coloured; v[7] = (double)a.c.first; }
+        if constexpr (N >= kXParts) v[8] = (double)a.rejected;
+    }
+};
+
+// the walk
+template <typename RULE>
+__global__ __launch_bounds__(kBlock) void fusion_kernel(float* __restrict__ tsdf, float* __restrict__ weight, RULE rule,
+                                                        double* __restrict__ scratch, FusionDev p) {
+    constexpr int N = RULE::N;
     __shared__ double e[12];
-    __shared__ double red[kBlock / kWave][kXParts];
-    if (threadIdx.x == 0) live_extrinsic(p.twist, e);
-    __syncthreads();
-    const bool aligned = p.aligned != 0, carving = carve != 0, psi_aligned = warp_aligned != 0;
-    const bool colouring = c.volume != nullptr;
-    ColourAcc a = {{{0, 0, 0.0, 0.0f}, 0, 0}, 0, 0};
-    int rejected = 0;
+    __shared__ double red[kBlock / kWave][N];
+    if constexpr (RULE::kExtrinsic) {
+        if (threadIdx.x == 0) live_extrinsic(p.twist, e);
+        __syncthreads();
+    }
+    const bool aligned = p.aligned != 0;
+    typename RULE::Acc a = {};
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += stride) {
         const long long i = g * 4;
-        TsdfSample s[4];
-        float psi[12], t[4], W[4];
-        load_warp4(warp, i, psi, psi_aligned);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            s[k] = warped_sample<DT, PT>(depth, p, e, i + k, psi[3 * k], psi[3 * k + 1], psi[3 * k + 2], rejected);
+        typename RULE::Obs o[4];
+        float t[4], W[4];
+        rule.observe4(i, p, e, o, a);
         load4(tsdf, i, t, aligned);
         load4(weight, i, W, aligned);
         bool any = false;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (fuse_voxel_weighted(s[k], pixel_weight, carving, t[k], W[k], p, a.w)) {
-                any = true;
-                if (colouring) colour_voxel(s[k], pixel_weight, c, i + k, p, a);
-            }
-        if (any) {  // a step without an updated voxel stores nothing
+        for (int k = 0; k < 4; ++k) any = rule.fuse(o[k], i + k, t[k], W[k], p, a) || any;
+        if (any) {  // a step without an updated voxel stores nothing; the stored values would equal the loaded ones
             store4(tsdf, i, t, aligned);
             store4(weight, i, W, aligned);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)  // the tail, after this lane's steps
         for (long long i = p.groups * 4; i < p.n; ++i) {
+            const typename RULE::Obs o = rule.observe(i, p, e, a);
             float t = tsdf[i], W = weight[i];
-            const float* f = warp + i * 3;
-            const TsdfSample s = warped_sample<DT, PT>(depth, p, e, i, f[0], f[1], f[2], rejected);
-            if (fuse_voxel_weighted(s, pixel_weight, carving, t, W, p, a.w)) {
+            if (rule.fuse(o, i, t, W, p, a)) {
                 tsdf[i] = t;
                 weight[i] = W;
-                if (colouring) colour_voxel(s, pixel_weight, c, i, p, a);
             }
         }
-    double v[kXParts] = {(double)a.w.a.fused, (double)a.w.a.first,  a.w.a.sum,          (double)a.w.a.max,
-                         (double)a.w.carved,  (double)a.w.rejected, (double)a.coloured, (double)a.first,
-                         (double)rejected};
+    double v[N];
+    RULE::parts(a, v);
     block_combine(v, red);
     if (threadIdx.x == 0)
 #pragma unroll
-        for (int c9 = 0; c9 < kXParts; ++c9) scratch[(size_t)blockIdx.x * kXParts + c9] = v[c9];
+        for (int c = 0; c < N; ++c) scratch[(size_t)blockIdx.x * N + c] = v[c];
 }
 
 // one workgroup: lane q combines partials q, q + kBlock, ... in order, then the block in a fixed order
@@ -491,47 +424,13 @@ int convert(const lsf_fusion_params* params, FusionDev& p) {
     return 0;
 }
 
-template <int SOURCE, typename DT, typename PT>
-int launch(float* tsdf, float* weight, const float* live, const void* depth, double* record, double* scratch,
-           const FusionDev& p, hipStream_t s) {
-    hipLaunchKernelGGL((fusion_kernel<SOURCE, DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, live,
-                       reinterpret_cast<const DT*>(depth), scratch, p);
+// the walk under a rule, then the combination of its partials into the record
+template <typename RULE>
+int launch(float* tsdf, float* weight, const RULE& rule, double* record, double* scratch, const FusionDev& p,
+           hipStream_t s) {
+    hipLaunchKernelGGL(fusion_kernel<RULE>, dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, rule, scratch, p);
     if (int e = launch_status()) return e;
-    hipLaunchKernelGGL(fusion_finish_kernel<kParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
-                       p.nblocks);
-    return launch_status();
-}
-
-template <typename DT, typename PT>
-int launch_weighted(float* tsdf, float* weight, const void* depth, const float* pixel_weight, double* record,
-                    double* scratch, const FusionDev& p, int carve, hipStream_t s) {
-    hipLaunchKernelGGL((fusion_weighted_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight,
-                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve);
-    if (int e = launch_status()) return e;
-    hipLaunchKernelGGL(fusion_finish_kernel<kWParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
-                       p.nblocks);
-    return launch_status();
-}
-
-template <typename DT, typename PT>
-int launch_colour(float* tsdf, float* weight, const void* depth, const float* pixel_weight, double* record,
-                  double* scratch, const FusionDev& p, int carve, const ColourDev& c, hipStream_t s) {
-    hipLaunchKernelGGL((fusion_colour_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight,
-                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve, c);
-    if (int e = launch_status()) return e;
-    hipLaunchKernelGGL(fusion_finish_kernel<kCParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
-                       p.nblocks);
-    return launch_status();
-}
-
-template <typename DT, typename PT>
-int launch_warped(float* tsdf, float* weight, const float* warp, const void* depth, const float* pixel_weight,
-                  double* record, double* scratch, const FusionDev& p, int carve, const ColourDev& c, int warp_aligned,
-                  hipStream_t s) {
-    hipLaunchKernelGGL((fusion_warped_kernel<DT, PT>), dim3(p.nblocks), dim3(kBlock), 0, s, tsdf, weight, warp,
-                       reinterpret_cast<const DT*>(depth), pixel_weight, scratch, p, carve, c, warp_aligned);
-    if (int e = launch_status()) return e;
-    hipLaunchKernelGGL(fusion_finish_kernel<kXParts>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
+    hipLaunchKernelGGL(fusion_finish_kernel<RULE::N>, dim3(1), dim3(kBlock), 0, s, (const double*)scratch, record,
                        p.nblocks);
     return launch_status();
 }
@@ -544,6 +443,67 @@ int check_buffers(const float* tsdf, const float* weight, const void* source, co
     return 0;
 }
 
+struct Buffer {
+    const void* at;  // may be NULL: overlaps nothing
+    size_t bytes;
+};
+
+// whether any two of the buffers share a byte
+bool any_overlap(std::initializer_list<Buffer> buffers) {
+    for (const Buffer* a = buffers.begin(); a != buffers.end(); ++a)
+        for (const Buffer* b = a + 1; b != buffers.end(); ++b)
+            if (overlaps(a->at, a->bytes, b->at, b->bytes)) return true;
+    return false;
+}
+
+// a depth-mode call after the checks its four entry points share
+struct DepthCall {
+    FusionDev p;
+    const lsf_fusion_params* f;
+    double* scratch;
+    hipStream_t s;
+    size_t model, pixels, depth_bytes;  // the bytes of tsdf (and of weight), the image's pixels, the depth image's bytes
+    int carve;
+};
+
+// those checks.  wp: the weighted parameters around f, NULL for the unweighted rule
+int depth_call(const float* tsdf, const float* weight, const void* depth_image, const float* pixel_weight,
+               const double* record, void* scratch, const lsf_fusion_params* f, const lsf_fusion_weighted_params* wp,
+               void* stream, DepthCall& d) {
+    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
+    if (int e = convert(f, d.p)) return e;
+    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
+    if (wp && (wp->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    d.p.aligned = aligned16(tsdf) && aligned16(weight);
+    d.f = f;
+    d.scratch = reinterpret_cast<double*>(scratch);
+    d.s = as_stream(stream);
+    d.model = (size_t)d.p.n * 4;
+    d.pixels = (size_t)f->tsdf.image_width * f->tsdf.image_height;
+    d.depth_bytes = d.pixels * kDepthBytes[f->depth_dtype];
+    d.carve = wp && wp->carve != 0;
+    return 0;
+}
+
+// make(DT(), PT()) gives the rule of the call's (depth dtype, intrinsics dtype); launched
+template <typename MAKE>
+int dispatch_rule(float* tsdf, float* weight, double* record, const DepthCall& d, MAKE&& make) {
+    return dispatch_typed(d.f->depth_dtype, d.f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
+        return launch(tsdf, weight, make(dt, pt), record, d.scratch, d.p, d.s);
+    });
+}
+
+// the weighted rule with its buffers
+template <bool WARP, int COLOUR, int PARTS>
+int dispatch_weighted(float* tsdf, float* weight, const void* depth_image, const float* pixel_weight, const float* warp,
+                    const ColourDev& c, double* record, const DepthCall& d) {
+    return dispatch_rule(tsdf, weight, record, d, [&](auto dt, auto pt) {
+        using DT = decltype(dt);
+        return WeightedRule<DT, decltype(pt), WARP, COLOUR, PARTS>{reinterpret_cast<const DT*>(depth_image),
+                                                                   pixel_weight, warp, c, d.carve, aligned16(warp)};
+    });
+}
+
 }  // namespace
 
 extern "C" int lsf_fusion_integrate_volume(float* tsdf, float* weight, const float* live, double* record,
@@ -553,23 +513,18 @@ extern "C" int lsf_fusion_integrate_volume(float* tsdf, float* weight, const flo
     FusionDev p;
     if (int e = convert(params, p)) return e;
     p.aligned = aligned16(tsdf) && aligned16(weight) && aligned16(live);
-    return launch<VOLUME, float, double>(tsdf, weight, live, nullptr, record, reinterpret_cast<double*>(scratch), p,
-                                         as_stream(stream));
+    return launch(tsdf, weight, VolumeRule{{}, live}, record, reinterpret_cast<double*>(scratch), p,
+                  as_stream(stream));
 }
 
 extern "C" int lsf_fusion_integrate_depth(float* tsdf, float* weight, const void* depth_image, double* record,
                                           void* scratch, const lsf_fusion_params* params, void* stream) {
     (void)hipGetLastError();
-    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
-    FusionDev p;
-    if (int e = convert(params, p)) return e;
-    if (!depth_dtype_ok(params->depth_dtype) || !typed_tsdf_ok(params->tsdf, false, true))
-        return LSF_ERR_BAD_ARGUMENT;
-    p.aligned = aligned16(tsdf) && aligned16(weight);
-    hipStream_t s = as_stream(stream);
-    double* sc = reinterpret_cast<double*>(scratch);
-    return dispatch_typed(params->depth_dtype, params->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
-        return launch<DEPTH, decltype(dt), decltype(pt)>(tsdf, weight, nullptr, depth_image, record, sc, p, s);
+    DepthCall d;
+    if (int e = depth_call(tsdf, weight, depth_image, nullptr, record, scratch, params, nullptr, stream, d)) return e;
+    return dispatch_rule(tsdf, weight, record, d, [&](auto dt, auto pt) {
+        using DT = decltype(dt);
+        return DepthRule<DT, decltype(pt)>{{}, reinterpret_cast<const DT*>(depth_image)};
     });
 }
 
@@ -578,25 +533,13 @@ extern "C" int lsf_fusion_integrate_depth_weighted(float* tsdf, float* weight, c
                                                    const lsf_fusion_weighted_params* params, void* stream) {
     (void)hipGetLastError();
     if (!params) return LSF_ERR_BAD_ARGUMENT;
-    const lsf_fusion_params* f = &params->fusion;
-    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
-    FusionDev p;
-    if (int e = convert(f, p)) return e;
-    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
-    if ((params->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
-    if (pixel_weight) {
-        const size_t image = (size_t)f->tsdf.image_width * f->tsdf.image_height * 4, model = (size_t)p.n * 4;
-        if (overlaps(pixel_weight, image, tsdf, model) || overlaps(pixel_weight, image, weight, model))
-            return LSF_ERR_BAD_ARGUMENT;
-    }
-    p.aligned = aligned16(tsdf) && aligned16(weight);
-    hipStream_t s = as_stream(stream);
-    double* sc = reinterpret_cast<double*>(scratch);
-    const int carve = params->carve != 0;
-    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
-        return launch_weighted<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p,
-                                                           carve, s);
-    });
+    DepthCall d;
+    if (int e = depth_call(tsdf, weight, depth_image, pixel_weight, record, scratch, &params->fusion, params, stream, d))
+        return e;
+    if (overlaps(pixel_weight, d.pixels * 4, tsdf, d.model) || overlaps(pixel_weight, d.pixels * 4, weight, d.model))
+        return LSF_ERR_BAD_ARGUMENT;
+    return dispatch_weighted<false, NEVER, kWParts>(tsdf, weight, depth_image, pixel_weight, nullptr, ColourDev{}, record,
+                                                  d);
 }
 
 extern "C" int lsf_fusion_integrate_depth_colour(float* tsdf, float* weight, float* colour, const void* depth_image,
@@ -606,31 +549,17 @@ extern "C" int lsf_fusion_integrate_depth_colour(float* tsdf, float* weight, flo
     (void)hipGetLastError();
     if (!params || !colour || !colour_image) return LSF_ERR_BAD_ARGUMENT;
     const lsf_fusion_weighted_params* wp = &params->weighted;
-    const lsf_fusion_params* f = &wp->fusion;
-    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
-    FusionDev p;
-    if (int e = convert(f, p)) return e;
-    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
-    if ((wp->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    DepthCall d;
+    if (int e = depth_call(tsdf, weight, depth_image, pixel_weight, record, scratch, &wp->fusion, wp, stream, d))
+        return e;
     const float band = params->colour_band;
     if (!(band > 0.0f && band <= 1.0f)) return LSF_ERR_BAD_ARGUMENT;  // NaN fails
     if (((uintptr_t)colour & 15) != 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)f->tsdf.image_width * f->tsdf.image_height, model = (size_t)p.n * 4;
-    const size_t depth_bytes = pixels * (f->depth_dtype == LSF_DEPTH_U16 ? 2 : (f->depth_dtype == LSF_DEPTH_F32 ? 4 : 8));
-    const void* const buffers[6] = {tsdf, weight, colour, colour_image, pixel_weight, depth_image};
-    const size_t bytes[6] = {model, model, model * 4, pixels * 3, pixels * 4, depth_bytes};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            if (overlaps(buffers[i], bytes[i], buffers[j], bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-    p.aligned = aligned16(tsdf) && aligned16(weight);
-    hipStream_t s = as_stream(stream);
-    double* sc = reinterpret_cast<double*>(scratch);
-    const int carve = wp->carve != 0;
+    if (any_overlap({{tsdf, d.model}, {weight, d.model}, {colour, d.model * 4}, {colour_image, d.pixels * 3},
+                     {pixel_weight, d.pixels * 4}, {depth_image, d.depth_bytes}}))
+        return LSF_ERR_BAD_ARGUMENT;
     const ColourDev c{reinterpret_cast<float4*>(colour), colour_image, band};
-    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
-        return launch_colour<decltype(dt), decltype(pt)>(tsdf, weight, depth_image, pixel_weight, record, sc, p, carve,
-                                                         c, s);
-    });
+    return dispatch_weighted<false, ALWAYS, kCParts>(tsdf, weight, depth_image, pixel_weight, nullptr, c, record, d);
 }
 
 extern "C" int lsf_fusion_integrate_depth_warped(float* tsdf, float* weight, float* colour, const float* warp,
@@ -640,12 +569,9 @@ extern "C" int lsf_fusion_integrate_depth_warped(float* tsdf, float* weight, flo
     (void)hipGetLastError();
     if (!params || !warp) return LSF_ERR_BAD_ARGUMENT;
     const lsf_fusion_weighted_params* wp = &params->colour.weighted;
-    const lsf_fusion_params* f = &wp->fusion;
-    if (int e = check_buffers(tsdf, weight, depth_image, record, scratch)) return e;
-    FusionDev p;
-    if (int e = convert(f, p)) return e;
-    if (!depth_dtype_ok(f->depth_dtype) || !typed_tsdf_ok(f->tsdf, false, true)) return LSF_ERR_BAD_ARGUMENT;
-    if ((wp->has_pixel_weight != 0) != (pixel_weight != nullptr)) return LSF_ERR_BAD_ARGUMENT;
+    DepthCall d;
+    if (int e = depth_call(tsdf, weight, depth_image, pixel_weight, record, scratch, &wp->fusion, wp, stream, d))
+        return e;
     const bool has_colour = params->has_colour != 0;
     if (has_colour != (colour != nullptr) || has_colour != (colour_image != nullptr)) return LSF_ERR_BAD_ARGUMENT;
     const float band = params->colour.colour_band;
@@ -653,20 +579,9 @@ extern "C" int lsf_fusion_integrate_depth_warped(float* tsdf, float* weight, flo
         if (!(band > 0.0f && band <= 1.0f)) return LSF_ERR_BAD_ARGUMENT;  // NaN fails
         if (((uintptr_t)colour & 15) != 0) return LSF_ERR_BAD_ARGUMENT;
     }
-    const size_t pixels = (size_t)f->tsdf.image_width * f->tsdf.image_height, model = (size_t)p.n * 4;
-    const size_t depth_bytes = pixels * (f->depth_dtype == LSF_DEPTH_U16 ? 2 : (f->depth_dtype == LSF_DEPTH_F32 ? 4 : 8));
-    const void* const buffers[7] = {tsdf, weight, colour, warp, depth_image, pixel_weight, colour_image};
-    const size_t bytes[7] = {model, model, model * 4, model * 3, depth_bytes, pixels * 4, pixels * 3};
-    for (int i = 0; i < 7; ++i)
-        for (int j = i + 1; j < 7; ++j)
-            if (overlaps(buffers[i], bytes[i], buffers[j], bytes[j])) return LSF_ERR_BAD_ARGUMENT;
-    p.aligned = aligned16(tsdf) && aligned16(weight);
-    hipStream_t s = as_stream(stream);
-    double* sc = reinterpret_cast<double*>(scratch);
-    const int carve = wp->carve != 0, warp_aligned = aligned16(warp);
+    if (any_overlap({{tsdf, d.model}, {weight, d.model}, {colour, d.model * 4}, {warp, d.model * 3},
+                     {depth_image, d.depth_bytes}, {pixel_weight, d.pixels * 4}, {colour_image, d.pixels * 3}}))
+        return LSF_ERR_BAD_ARGUMENT;
     const ColourDev c{reinterpret_cast<float4*>(colour), colour_image, has_colour ? band : 1.0f};
-    return dispatch_typed(f->depth_dtype, f->tsdf.intrinsics_are_f32 != 0, [&](auto dt, auto pt) {
-        return launch_warped<decltype(dt), decltype(pt)>(tsdf, weight, warp, depth_image, pixel_weight, record, sc, p,
-                                                         carve, c, warp_aligned, s);
-    });
+    return dispatch_weighted<true, IF_GIVEN, kXParts>(tsdf, weight, depth_image, pixel_weight, warp, c, record, d);
 }

@@ -557,8 +557,6 @@ Grid strided_grid(const Q* q, int stride) {
     return grid_of((q->width + stride - 1) / stride, (q->height + stride - 1) / stride);
 }
 
-const size_t kDepthBytes[3] = {2, 4, 8};
-
 // the checks of the pyramid parameter structs (lsf_icp_pyramid_params, lsf_icp_pyramid_photometric_params):
 // sum(iterations), or -1
 template <typename Q>

@@ -122,6 +122,9 @@ __device__ inline void live_extrinsic(const double* tw, double* e) {
 
 inline bool depth_dtype_ok(int32_t dt) { return dt == LSF_DEPTH_U16 || dt == LSF_DEPTH_F32 || dt == LSF_DEPTH_F64; }
 
+// a depth element's bytes, by its checked LSF_DEPTH_* code
+constexpr size_t kDepthBytes[3] = {2, 4, 8};
+
 // the image and band checks of a typed-TSDF entry point.  image_y: the depth row must lie in the image (2-D);
 // pixels: width x height must fit an int32.  Each entry point keeps the set of checks it has always made.
 inline bool typed_tsdf_ok(const lsf_tsdf_params& t, bool image_y, bool pixels) {

@@ -136,45 +136,35 @@ def integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist
     return _launch(lib.lsf_fusion_integrate_depth, "lsf_fusion_integrate_depth", tsdf, weight, depth, p, record)
 
 
+def _check_tensor(name, t, dtype, device_name, device_like, shape_name, shape_like, extra, rule):
+    """what every optional buffer of a call is checked for before its aliasing: a torch tensor of `dtype`, on
+    device_like's device, contiguous, of shape_like's shape + extra; `rule` words the shape's refusal"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise ValueError("%s must be %s, got %s" % (name, str(dtype).split(".")[-1], t.dtype))
+    if t.device != device_like.device:
+        raise ValueError("%s is on %s, %s on %s: all buffers must be on one device"
+                         % (name, t.device, device_name, device_like.device))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if tuple(t.shape) != tuple(shape_like.shape) + extra:
+        raise ValueError("%s has shape %s, %s %s: %s" % (name, tuple(t.shape), shape_name, tuple(shape_like.shape), rule))
+
+
+def _check_others(name, t, others):
+    for other, o in others:
+        if o is not None and _overlap(t, o):
+            raise ValueError("%s must not alias %s" % (name, other))
+
+
 def check_pixel_weight(pixel_weight, depth, tsdf, weight):
     """a weight image: a float32 contiguous tensor on the model's device, of the depth image's shape, aliasing neither
     the model nor the depth image"""
-    if not isinstance(pixel_weight, torch.Tensor):
-        raise TypeError("pixel_weight must be a torch tensor, got %s" % type(pixel_weight).__name__)
-    if pixel_weight.dtype != torch.float32:
-        raise ValueError("pixel_weight must be float32, got %s" % pixel_weight.dtype)
-    if pixel_weight.device != tsdf.device:
-        raise ValueError("pixel_weight is on %s, tsdf on %s: all buffers must be on one device"
-                         % (pixel_weight.device, tsdf.device))
-    if not pixel_weight.is_contiguous():
-        raise ValueError("pixel_weight must be contiguous")
-    if tuple(pixel_weight.shape) != tuple(depth.shape):
-        raise ValueError("pixel_weight has shape %s, the depth image %s: they must have one shape"
-                         % (tuple(pixel_weight.shape), tuple(depth.shape)))
+    _check_tensor("pixel_weight", pixel_weight, torch.float32, "tsdf", tsdf, "the depth image", depth, (),
+                  "they must have one shape")
     if _overlap(pixel_weight, tsdf) or _overlap(pixel_weight, weight) or _overlap(pixel_weight, depth):
         raise ValueError("pixel_weight must not alias tsdf, weight or the depth image")
-
-
-def integrate_depth_weighted(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
-                             narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None, carve=False,
-                             record=None):
-    """integrate_depth with the weighted rule (INTEGRATION.md section 3, "Weighted fusion and carving"): a voxel's
-    weight is w times pixel_weight at the pixel it projects to (a float32 device image of depth's shape; None: w
-    itself), and with carve the seen free space in front of the band (live value exactly 1 at a valid pixel) is fused
-    with +1.  Two launches, no host wait; returns the record (unpack_weighted_record once it is on the host)"""
-    require_gpu()
-    p = FusionWeightedParams()
-    p.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
-                             narrow_band_width_voxels, w, max_weight, 1)
-    if pixel_weight is not None:
-        check_pixel_weight(pixel_weight, depth, tsdf, weight)
-    p.carve, p.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
-    record, scratch = _record_and_scratch(tsdf, record, _lib.FUSION_WEIGHTED_SCRATCH_BYTES)
-    check(lib.lsf_fusion_integrate_depth_weighted(
-        ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(depth.data_ptr()),
-        ctypes.c_void_p(None if pixel_weight is None else pixel_weight.data_ptr()), ctypes.c_void_p(record.data_ptr()),
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_weighted")
-    return record
 
 
 def colour_band_of(colour_band):
@@ -188,17 +178,8 @@ def colour_band_of(colour_band):
 def check_colour_volume(colour, tsdf, weight):
     """a colour volume: a float32 contiguous tensor of shape tsdf.shape + (4,) on the model's device, 16-byte aligned,
     aliasing neither tsdf nor weight"""
-    if not isinstance(colour, torch.Tensor):
-        raise TypeError("colour must be a torch tensor, got %s" % type(colour).__name__)
-    if colour.dtype != torch.float32:
-        raise ValueError("colour must be float32, got %s" % colour.dtype)
-    if colour.device != tsdf.device:
-        raise ValueError("colour is on %s, tsdf on %s: all buffers must be on one device" % (colour.device, tsdf.device))
-    if not colour.is_contiguous():
-        raise ValueError("colour must be contiguous")
-    if tuple(colour.shape) != tuple(tsdf.shape) + (4,):
-        raise ValueError("colour has shape %s, the model %s: it must be the model's shape + (4,)"
-                         % (tuple(colour.shape), tuple(tsdf.shape)))
+    _check_tensor("colour", colour, torch.float32, "tsdf", tsdf, "the model", tsdf, (4,),
+                  "it must be the model's shape + (4,)")
     if colour.data_ptr() % 16:
         raise ValueError("colour must be 16-byte aligned: a voxel's record is one 16-byte access")
     if _overlap(colour, tsdf) or _overlap(colour, weight):
@@ -208,21 +189,81 @@ def check_colour_volume(colour, tsdf, weight):
 def check_colour_image(colour_image, depth, others):
     """a colour image: a uint8 contiguous (H, W, 3) tensor on the depth image's device, H and W the depth image's,
     aliasing none of `others` ((name, tensor) pairs; None tensors are skipped)"""
-    if not isinstance(colour_image, torch.Tensor):
-        raise TypeError("colour_image must be a torch tensor, got %s" % type(colour_image).__name__)
-    if colour_image.dtype != torch.uint8:
-        raise ValueError("colour_image must be uint8, got %s" % colour_image.dtype)
-    if colour_image.device != depth.device:
-        raise ValueError("colour_image is on %s, the depth image on %s: all buffers must be on one device"
-                         % (colour_image.device, depth.device))
-    if not colour_image.is_contiguous():
-        raise ValueError("colour_image must be contiguous")
-    if tuple(colour_image.shape) != tuple(depth.shape) + (3,):
-        raise ValueError("colour_image has shape %s, the depth image %s: it must be (H, W, 3) with the depth image's H, W"
-                         % (tuple(colour_image.shape), tuple(depth.shape)))
-    for name, t in others:
-        if t is not None and _overlap(colour_image, t):
-            raise ValueError("colour_image must not alias %s" % name)
+    _check_tensor("colour_image", colour_image, torch.uint8, "the depth image", depth, "the depth image", depth, (3,),
+                  "it must be (H, W, 3) with the depth image's H, W")
+    _check_others("colour_image", colour_image, others)
+
+
+def check_warp(warp, tsdf, others):
+    """a warp field: a float32 contiguous tensor of shape tsdf.shape + (3,) on the model's device (what
+    HierarchicalOptimizer3d.optimize returns for device inputs), aliasing none of `others` ((name, tensor) pairs; None
+    tensors are skipped)"""
+    _check_tensor("warp", warp, torch.float32, "tsdf", tsdf, "the model", tsdf, (3,),
+                  "it must be the model's shape + (3,)")
+    _check_others("warp", warp, others)
+
+
+# the three entry points of the weighted rule: the C function, its parameter struct (lsf_fusion_weighted_params, and what
+# is nested around it), its scratch bytes and its record's doubles
+_WEIGHTED = ("lsf_fusion_integrate_depth_weighted", FusionWeightedParams, _lib.FUSION_WEIGHTED_SCRATCH_BYTES, RECORD)
+_COLOUR = ("lsf_fusion_integrate_depth_colour", FusionColourParams, _lib.FUSION_COLOUR_SCRATCH_BYTES, RECORD)
+_WARPED = ("lsf_fusion_integrate_depth_warped", FusionWarpedParams, _lib.FUSION_WARPED_SCRATCH_BYTES, WARPED_RECORD)
+
+
+def _integrate_depth_weighted(entry, tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                              narrow_band_width_voxels, w, max_weight, pixel_weight, carve, record, colour=None,
+                              colour_image=None, colour_band=1.0, warp=None):
+    """the checks, the parameters and the call of one of the three: _COLOUR needs colour and colour_image, _WARPED takes
+    them together or not at all and needs warp, _WEIGHTED takes none of the three"""
+    name, params, scratch_bytes, doubles = entry
+    require_gpu()
+    if entry is _WARPED and (colour is None) != (colour_image is None):
+        raise ValueError("colour and colour_image are given together or not at all")
+    p = params()
+    cp = p.colour if entry is _WARPED else p  # lsf_fusion_colour_params, where there is one
+    wp = p if entry is _WEIGHTED else cp.weighted
+    wp.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                              narrow_band_width_voxels, w, max_weight, 1)
+    if pixel_weight is not None:
+        check_pixel_weight(pixel_weight, depth, tsdf, weight)
+    if entry is _COLOUR or colour is not None:
+        check_colour_volume(colour, tsdf, weight)
+        check_colour_image(colour_image, depth, (("tsdf", tsdf), ("weight", weight), ("colour", colour),
+                                                 ("depth", depth), ("pixel_weight", pixel_weight)))
+        if _overlap(colour, depth) or (pixel_weight is not None and _overlap(colour, pixel_weight)):
+            raise ValueError("colour must not alias the depth image or pixel_weight")
+    if entry is _WARPED:
+        check_warp(warp, tsdf, (("tsdf", tsdf), ("weight", weight), ("colour", colour), ("depth", depth),
+                                ("pixel_weight", pixel_weight), ("colour_image", colour_image)))
+        p.has_colour = int(colour is not None)
+    wp.carve, wp.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
+    ptr = ctypes.c_void_p
+    pw = ptr(None if pixel_weight is None else pixel_weight.data_ptr())
+    if entry is _WEIGHTED:
+        between = (ptr(depth.data_ptr()), pw)
+    else:  # colour, [warp,] depth, pixel_weight, colour_image
+        cp.colour_band = colour_band_of(colour_band)
+        between = (ptr(depth.data_ptr()), pw, ptr(None if colour_image is None else colour_image.data_ptr()))
+        if entry is _WARPED:
+            between = (ptr(warp.data_ptr()),) + between
+        between = (ptr(None if colour is None else colour.data_ptr()),) + between
+    if record is None:
+        record = torch.empty(doubles, dtype=torch.float64, device=tsdf.device)
+    scratch = torch.empty(scratch_bytes // 8, dtype=torch.float64, device=tsdf.device)
+    check(getattr(lib, name)(ptr(tsdf.data_ptr()), ptr(weight.data_ptr()), *between, ptr(record.data_ptr()),
+                             ptr(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), name)
+    return record
+
+
+def integrate_depth_weighted(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                             narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None, carve=False,
+                             record=None):
+    """integrate_depth with the weighted rule (INTEGRATION.md section 3, "Weighted fusion and carving"): a voxel's
+    weight is w times pixel_weight at the pixel it projects to (a float32 device image of depth's shape; None: w
+    itself), and with carve the seen free space in front of the band (live value exactly 1 at a valid pixel) is fused
+    with +1.  Two launches, no host wait; returns the record (unpack_weighted_record once it is on the host)"""
+    return _integrate_depth_weighted(_WEIGHTED, tsdf, weight, depth, depth_code, camera, array_offset, twist,
+                                     voxel_size, narrow_band_width_voxels, w, max_weight, pixel_weight, carve, record)
 
 
 def integrate_depth_colour(tsdf, weight, colour, depth, depth_code, camera, array_offset, twist, colour_image,
@@ -233,46 +274,9 @@ def integrate_depth_colour(tsdf, weight, colour, depth, depth_code, camera, arra
     whose live value lies strictly inside (-colour_band, colour_band) ("Colour fusion").
     tsdf, weight and record slots 0..5 are integrate_depth_weighted's bit for bit.  Two launches, no host wait; returns
     the record (unpack_colour_record once it is on the host)"""
-    require_gpu()
-    p = FusionColourParams()
-    p.weighted.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
-                                      narrow_band_width_voxels, w, max_weight, 1)
-    if pixel_weight is not None:
-        check_pixel_weight(pixel_weight, depth, tsdf, weight)
-    check_colour_volume(colour, tsdf, weight)
-    check_colour_image(colour_image, depth, [("tsdf", tsdf), ("weight", weight), ("colour", colour), ("depth", depth),
-                                             ("pixel_weight", pixel_weight)])
-    if _overlap(colour, depth) or (pixel_weight is not None and _overlap(colour, pixel_weight)):
-        raise ValueError("colour must not alias the depth image or pixel_weight")
-    p.weighted.carve, p.weighted.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
-    p.colour_band = colour_band_of(colour_band)
-    record, scratch = _record_and_scratch(tsdf, record, _lib.FUSION_COLOUR_SCRATCH_BYTES)
-    check(lib.lsf_fusion_integrate_depth_colour(
-        ctypes.c_void_p(tsdf.data_ptr()), ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(colour.data_ptr()),
-        ctypes.c_void_p(depth.data_ptr()), ctypes.c_void_p(None if pixel_weight is None else pixel_weight.data_ptr()),
-        ctypes.c_void_p(colour_image.data_ptr()), ctypes.c_void_p(record.data_ptr()),
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_colour")
-    return record
-
-
-def check_warp(warp, tsdf, others):
-    """a warp field: a float32 contiguous tensor of shape tsdf.shape + (3,) on the model's device (what
-    HierarchicalOptimizer3d.optimize returns for device inputs), aliasing none of `others` ((name, tensor) pairs; None
-    tensors are skipped)"""
-    if not isinstance(warp, torch.Tensor):
-        raise TypeError("warp must be a torch tensor, got %s" % type(warp).__name__)
-    if warp.dtype != torch.float32:
-        raise ValueError("warp must be float32, got %s" % warp.dtype)
-    if warp.device != tsdf.device:
-        raise ValueError("warp is on %s, tsdf on %s: all buffers must be on one device" % (warp.device, tsdf.device))
-    if not warp.is_contiguous():
-        raise ValueError("warp must be contiguous")
-    if tuple(warp.shape) != tuple(tsdf.shape) + (3,):
-        raise ValueError("warp has shape %s, the model %s: it must be the model's shape + (3,)"
-                         % (tuple(warp.shape), tuple(tsdf.shape)))
-    for name, t in others:
-        if t is not None and _overlap(warp, t):
-            raise ValueError("warp must not alias %s" % name)
+    return _integrate_depth_weighted(_COLOUR, tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                                     narrow_band_width_voxels, w, max_weight, pixel_weight, carve, record, colour,
+                                     colour_image, colour_band)
 
 
 def integrate_depth_warped(tsdf, weight, depth, depth_code, camera, array_offset, twist, warp, voxel_size=0.004,
@@ -284,64 +288,55 @@ def integrate_depth_warped(tsdf, weight, depth, depth_code, camera, array_offset
     v + warp[v] in place of its centre, and a voxel whose displacement is not finite is left alone and counted.  With a
     zero warp the result equals those calls bit for bit.  Two launches, no host wait; returns the record, WARPED_RECORD
     doubles (unpack_warped_record once it is on the host)"""
-    require_gpu()
-    if (colour is None) != (colour_image is None):
-        raise ValueError("colour and colour_image are given together or not at all")
-    p = FusionWarpedParams()
-    p.colour.weighted.fusion = _depth_params(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
-                                             narrow_band_width_voxels, w, max_weight, 1)
-    if pixel_weight is not None:
-        check_pixel_weight(pixel_weight, depth, tsdf, weight)
-    if colour is not None:
-        check_colour_volume(colour, tsdf, weight)
-        check_colour_image(colour_image, depth, [("tsdf", tsdf), ("weight", weight), ("colour", colour),
-                                                 ("depth", depth), ("pixel_weight", pixel_weight)])
-        if _overlap(colour, depth) or (pixel_weight is not None and _overlap(colour, pixel_weight)):
-            raise ValueError("colour must not alias the depth image or pixel_weight")
-    check_warp(warp, tsdf, [("tsdf", tsdf), ("weight", weight), ("colour", colour), ("depth", depth),
-                            ("pixel_weight", pixel_weight), ("colour_image", colour_image)])
-    p.colour.weighted.carve, p.colour.weighted.has_pixel_weight = int(bool(carve)), int(pixel_weight is not None)
-    p.colour.colour_band = colour_band_of(colour_band)
-    p.has_colour = int(colour is not None)
-    if record is None:
-        record = torch.empty(WARPED_RECORD, dtype=torch.float64, device=tsdf.device)
-    scratch = torch.empty(_lib.FUSION_WARPED_SCRATCH_BYTES // 8, dtype=torch.float64, device=tsdf.device)
+    return _integrate_depth_weighted(_WARPED, tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size,
+                                     narrow_band_width_voxels, w, max_weight, pixel_weight, carve, record, colour,
+                                     colour_image, colour_band, warp)
 
-    def ptr(t):
-        return ctypes.c_void_p(None if t is None else t.data_ptr())
 
-    check(lib.lsf_fusion_integrate_depth_warped(
-        ptr(tsdf), ptr(weight), ptr(colour), ptr(warp), ptr(depth), ptr(pixel_weight), ptr(colour_image), ptr(record),
-        ptr(scratch), ctypes.byref(p), stream_ptr()), "lsf_fusion_integrate_depth_warped")
-    return record
+def integrate_depth_by_arguments(tsdf, weight, depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                                 narrow_band_width_voxels=20., w=1.0, max_weight=math.inf, pixel_weight=None, carve=False,
+                                 colour=None, colour_image=None, colour_band=1.0, warp=None):
+    """the depth-mode call that the arguments ask for: integrate_depth_warped with a warp, else integrate_depth_colour
+    with a colour_image, else integrate_depth_weighted with a pixel_weight or carve, else integrate_depth.  `colour`,
+    the model's colour volume, is used with a colour_image only.  Returns (record, unpack): the device record and the
+    unpack_* function that reads a host copy of it"""
+    gen = (voxel_size, narrow_band_width_voxels, w, max_weight)
+    if warp is not None:
+        coloured = colour_image is not None
+        return integrate_depth_warped(tsdf, weight, depth, depth_code, camera, array_offset, twist, warp, *gen,
+                                      pixel_weight, carve, colour if coloured else None, colour_image,
+                                      colour_band), unpack_warped_record
+    if colour_image is not None:
+        return integrate_depth_colour(tsdf, weight, colour, depth, depth_code, camera, array_offset, twist,
+                                      colour_image, *gen, pixel_weight, carve, colour_band), unpack_colour_record
+    if pixel_weight is not None or carve:
+        return integrate_depth_weighted(tsdf, weight, depth, depth_code, camera, array_offset, twist, *gen,
+                                        pixel_weight, carve), unpack_weighted_record
+    return integrate_depth(tsdf, weight, depth, depth_code, camera, array_offset, twist, *gen), unpack_record
+
+
+def _unpack(r, fields):
+    """the host record as a dict of `fields`: exact counts as ints, the float64 sum and the max as floats"""
+    r = np.asarray(r, dtype=np.float64).reshape(-1)
+    return {f: (float if f in ("sum_abs_change", "max_abs_change") else int)(r[i]) for i, f in enumerate(fields)}
 
 
 def unpack_record(r):
     """the host record (RECORD float64) as a dict: exact counts as ints, the float64 sum and the max"""
-    r = np.asarray(r, dtype=np.float64).reshape(-1)
-    return {"fused": int(r[0]), "first_seen": int(r[1]), "sum_abs_change": float(r[2]),
-            "max_abs_change": float(r[3])}
+    return _unpack(r, RECORD_FIELDS)
 
 
 def unpack_weighted_record(r):
     """unpack_record of a weighted call, with its two further exact counts: carved and weight_rejected"""
-    out = unpack_record(r)
-    r = np.asarray(r, dtype=np.float64).reshape(-1)
-    out["carved"], out["weight_rejected"] = int(r[4]), int(r[5])
-    return out
+    return _unpack(r, WEIGHTED_RECORD_FIELDS)
 
 
 def unpack_colour_record(r):
     """unpack_weighted_record of a colour call, with its two further exact counts: coloured and first_coloured"""
-    out = unpack_weighted_record(r)
-    r = np.asarray(r, dtype=np.float64).reshape(-1)
-    out["coloured"], out["first_coloured"] = int(r[6]), int(r[7])
-    return out
+    return _unpack(r, COLOUR_RECORD_FIELDS)
 
 
 def unpack_warped_record(r):
     """unpack_colour_record of a warped call (coloured and first_coloured are 0 without colour), with the exact count of
     voxels whose displacement was not finite: warp_rejected"""
-    out = unpack_colour_record(r)
-    out["warp_rejected"] = int(np.asarray(r, dtype=np.float64).reshape(-1)[8])
-    return out
+    return _unpack(r, WARPED_RECORD_FIELDS)

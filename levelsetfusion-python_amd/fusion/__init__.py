@@ -194,31 +194,19 @@ class DepthConfidence:
         return self.build_device(*device_depth(depth_image), camera)
 
 
-def _pixel_weight(pixel_weight):
-    if pixel_weight is None or isinstance(pixel_weight, torch.Tensor):
-        return pixel_weight
-    a = np.asarray(pixel_weight)
-    if a.dtype != np.float32:
-        raise ValueError("pixel_weight must be float32, got %s" % a.dtype)
+def _on_device(x, name, dtype, move=True):
+    """x, a numpy array of `dtype` or a tensor, as a device tensor.  move=False leaves a tensor where it is: a CPU
+    tensor is then refused by the device check of the call, not moved"""
+    if isinstance(x, torch.Tensor):
+        return x.to("cuda") if move and not x.is_cuda else x
+    a = np.asarray(x)
+    if a.dtype != dtype:
+        raise ValueError("%s must be %s, got %s" % (name, np.dtype(dtype).name, a.dtype))
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
 def _colour_image(colour_image):
-    if isinstance(colour_image, torch.Tensor):
-        return colour_image if colour_image.is_cuda else colour_image.to("cuda")
-    a = np.asarray(colour_image)
-    if a.dtype != np.uint8:
-        raise ValueError("colour_image must be uint8, got %s" % a.dtype)
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
-
-
-def _warp(warp):
-    if isinstance(warp, torch.Tensor):
-        return warp if warp.is_cuda else warp.to("cuda")
-    a = np.asarray(warp)
-    if a.dtype != np.float32:
-        raise ValueError("warp must be float32, got %s" % a.dtype)
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    return _on_device(colour_image, "colour_image", np.uint8)
 
 
 class CanonicalVolume:
@@ -263,23 +251,15 @@ class CanonicalVolume:
         depth, code = device_depth(depth_image)
         if colour_image is not None and self.colour is None:
             raise ValueError("colour_image needs a volume made with colour=True")
-        if warp is not None:
-            coloured = colour_image is not None
-            return device_fusion.integrate_depth_warped(
-                self.tsdf, self.weight, depth, code, camera, array_offset, twist, _warp(warp), voxel_size,
-                narrow_band_width_voxels, weight, self.max_weight, _pixel_weight(pixel_weight), carve,
-                self.colour if coloured else None, _colour_image(colour_image) if coloured else None, colour_band)
+        if pixel_weight is not None:
+            pixel_weight = _on_device(pixel_weight, "pixel_weight", np.float32, move=False)
         if colour_image is not None:
-            return device_fusion.integrate_depth_colour(self.tsdf, self.weight, self.colour, depth, code, camera,
-                                                        array_offset, twist, _colour_image(colour_image), voxel_size,
-                                                        narrow_band_width_voxels, weight, self.max_weight,
-                                                        _pixel_weight(pixel_weight), carve, colour_band)
-        if pixel_weight is None and not carve:
-            return device_fusion.integrate_depth(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
-                                                 voxel_size, narrow_band_width_voxels, weight, self.max_weight)
-        return device_fusion.integrate_depth_weighted(self.tsdf, self.weight, depth, code, camera, array_offset, twist,
-                                                      voxel_size, narrow_band_width_voxels, weight, self.max_weight,
-                                                      _pixel_weight(pixel_weight), carve)
+            colour_image = _colour_image(colour_image)
+        if warp is not None:
+            warp = _on_device(warp, "warp", np.float32)
+        return device_fusion.integrate_depth_by_arguments(
+            self.tsdf, self.weight, depth, code, camera, array_offset, twist, voxel_size, narrow_band_width_voxels,
+            weight, self.max_weight, pixel_weight, carve, self.colour, colour_image, colour_band, warp)[0]
 
     def raycast(self, camera, twist, array_offset, voxel_size=0.004, image_shape=(480, 640), normals=False,
                 fallback_depth=None, as_tensor=False, colours=False):
@@ -478,41 +458,25 @@ class SequenceFusion3d:
                     self.eta, self.voxel_size, self.voxel_size, self.narrow_band_width_voxels, twist=twist)
                 rigid_records = [unpack_rigid_record(r) for r in records]
                 del reference
-        unpack = unpack_record
-        if self.warped and k > 0:
+        through = self.nonrigid_optimizer is not None and k > 0  # the frame takes the non-rigid step
+        if through:
             live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
                                                **gen)
-            self.warp = self.nonrigid_optimizer.optimize(model.tsdf, live)
+            if self.warped:
+                self.warp = self.nonrigid_optimizer.optimize(model.tsdf, live)
+                del live
+            else:
+                self.nonrigid_optimizer.optimize(live, model.tsdf)
             nonrigid = self.nonrigid_optimizer.engine.last_call
-            del live
-            record = device_fusion.integrate_depth_warped(
-                model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, self.warp, w=1.0,
-                max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
-                colour=model.colour, colour_image=_colour_image(colour_image) if self.colour else None,
-                colour_band=self.colour_band, **gen)
-            unpack = unpack_warped_record
-        elif self.colour:
-            record = device_fusion.integrate_depth_colour(
-                model.tsdf, model.weight, model.colour, depth, code, self.camera, self.array_offset, twist,
-                _colour_image(colour_image), w=1.0, max_weight=model.max_weight,
-                pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve, colour_band=self.colour_band,
-                **gen)
-            unpack = unpack_colour_record
-        elif self.carve or self.confidence is not None:
-            record = device_fusion.integrate_depth_weighted(
+        if through and not self.warped:  # the live volume, warped into the model, is fused in volume mode
+            record, unpack = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0,
+                                                            model.max_weight), unpack_record
+        else:  # depth mode, through the frame's warp field when it has one
+            record, unpack = device_fusion.integrate_depth_by_arguments(
                 model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, w=1.0,
                 max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
-                **gen)
-            unpack = unpack_weighted_record
-        elif k == 0 or self.nonrigid_optimizer is None:
-            record = device_fusion.integrate_depth(model.tsdf, model.weight, depth, code, self.camera,
-                                                   self.array_offset, twist, w=1.0, max_weight=model.max_weight, **gen)
-        else:
-            live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
-                                               **gen)
-            self.nonrigid_optimizer.optimize(live, model.tsdf)
-            nonrigid = self.nonrigid_optimizer.engine.last_call
-            record = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0, model.max_weight)
+                colour=model.colour, colour_image=_colour_image(colour_image) if self.colour else None,
+                colour_band=self.colour_band, warp=self.warp if through else None, **gen)
         frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
                  "fusion": unpack(record.cpu().numpy()),

@@ -140,8 +140,9 @@ FUSION_TWIST = np.array([0.013, -0.021, 0.008, 0.05, -0.17, 0.11])
 
 
 def _fusion_split(shape):
-    """convert() of csrc/lsf_fusion.hip: (4-voxel groups, tail voxels, workgroups = partials).  The three kernels loop
-    `for (g = blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += gridDim.x * kBlock)`, and fusion_finish_kernel
+    """convert() of csrc/lsf_fusion.hip: (4-voxel groups, tail voxels, workgroups = partials).  The one walk kernel,
+    fusion_kernel<RULE>, loops `for (g = blockIdx.x * kBlock + threadIdx.x; g < p.groups; g += gridDim.x * kBlock)`
+    under every rule, and fusion_finish_kernel
     `for (q = threadIdx.x; q < nblocks; q += kBlock)`"""
     n = int(np.prod(shape))
     groups = n // 4
