@@ -424,6 +424,29 @@ int lsf_slavcheva_state_iteration(const float *state_in, const float *canonical,
                                   lsf_iteration_record *record, const int32_t *band_list, int64_t band_count,
                                   int32_t band_subset, void *stream);
 
+/* ---- the cumulative warp of a call on the state layout ("Cumulative warp") -----------------------
+ * Every iteration re-warps the live field by its own update, live_{k+1}(v) = live_k(v + u_k(v)), so the call's total
+ * displacement PSI with live_0(v + PSI(v)) ~ canonical(v) is the composition PSI_0 = 0, PSI_{k+1}(v) = u_k(v) +
+ * PSI_k(v + u_k(v)).  lsf_cumulative_warp_compose is one step of it, launched behind the iteration whose output state it
+ * reads.  The rule, D = 2 and 3, for every listed voxel v and component c, with u the update `state` holds at v (the
+ * post-snap update: zero where the re-warped live value snapped to +-1):
+ *     psi_out_c(v) = float32( u_c(v) + S_c ),   S_c = sample_linear(psi_in_c, position(v, u), oob = 0)
+ * position(v, u) = float32(coordinate) + u per axis in float32 (z from the GLOBAL coordinate, z + z_global_offset);
+ * sample_linear lerps z, then y, then x, every tap outside the array reads 0, multiply and add rounded separately;
+ * positions are clamped before the integer conversion, so a non-finite or huge update addresses valid cells only.
+ * Outside the band u = 0 and PSI stays 0: only listed voxels are written, psi_in AND psi_out must hold zeros at every
+ * unlisted voxel (two zero-filled buffers, ping-pong).  An iteration the gate skips composes nothing: `gate` is the gate
+ * of the iteration this launch follows (both read record i - 1 and decide alike); min_iterations == 0 leaves PSI = 0.
+ * state, psi_in, psi_out: float4 [z][y][x], 16-byte aligned, psi = (unused, x, y, z) in the state's channel order, so
+ * lsf_state_unpack(psi, NULL, NULL, interleaved) gives the API layout [z][y][x][c].  psi_in, psi_out and state must not
+ * overlap.  band_list (NULL = every voxel of the z-range, band_count 0) / band_count (> 0 with a list) as
+ * lsf_slavcheva_state_iteration, any subset.  One launch, no host synchronisation, no atomics, no record.
+ * Refused before any launch, all with LSF_ERR_BAD_ARGUMENT: a NULL buffer, a base off 16-byte alignment, psi_in ==
+ * psi_out or any overlap among state, psi_in and psi_out, a grid with bad dims, extents or z range or cut along y, a
+ * negative band_count or one past int32, a list with band_count <= 0, a band_count without a list. */
+int lsf_cumulative_warp_compose(const float *state, const float *psi_in, float *psi_out, const lsf_grid *grid,
+                                const lsf_gate *gate, const int32_t *band_list, int64_t band_count, void *stream);
+
 /* ---- the fused iteration over BOXES (3-D, INTERIOR band voxels) -----------------------------
  * The same pass of slavcheva_optimizer2d.py:238-330 as lsf_slavcheva_state_iteration over an INTERIOR band list, same
  * results, with the work cut differently: a box is 4 x 4 x 4 voxels whose lowest corner (x0, y0, z0) has coordinates that

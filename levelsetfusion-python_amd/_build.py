@@ -9,7 +9,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liblsf_hip.so")
 SOURCES = ["lsf_fields.hip", "lsf_hierarchical.hip", "lsf_slavcheva.hip", "lsf_slavcheva_state.hip",
-           "lsf_slavcheva_run.hip", "lsf_slavcheva_box.hip", "lsf_sobolev_state.hip", "lsf_sobolev_box.hip", "lsf_slab.hip", "lsf_tsdf.hip",
+           "lsf_slavcheva_run.hip", "lsf_slavcheva_box.hip", "lsf_cumulative_warp.hip", "lsf_sobolev_state.hip", "lsf_sobolev_box.hip", "lsf_slab.hip", "lsf_tsdf.hip",
            "lsf_terms.hip", "lsf_rigid.hip", "lsf_rigid3d.hip", "lsf_fusion.hip",
            "lsf_raycast.hip", "lsf_mesh.hip", "lsf_icp.hip", "lsf_depth_pyramid.hip", "lsf_depth_confidence.hip",
            "lsf_intensity_pyramid.hip"]

@@ -393,6 +393,18 @@ def slavcheva_state_iteration(state_in, canonical, state_out, grid, params, gate
           "lsf_slavcheva_state_iteration")
 
 
+def cumulative_warp_compose(state, psi_in, psi_out, grid, gate=None, band=None):
+    """one step of the cumulative warp behind an iteration: psi_out = u + psi_in(id + u) at the listed voxels (every voxel
+    without a list), u the update `state` holds; state, psi_in, psi_out: float4 tensors [z,]y,x,4, psi = (unused, x, y, z),
+    zeros at unlisted voxels (lsf_cumulative_warp_compose)"""
+    n = n_voxels(grid)
+    check(lib.lsf_cumulative_warp_compose(_ptr(state, 4 * n, "state"), _ptr(psi_in, 4 * n, "psi_in"),
+                                          _ptr(psi_out, 4 * n, "psi_out"), ctypes.byref(grid), _gate_ref(gate),
+                                          band.pointer if band is not None else ctypes.c_void_p(0),
+                                          band.count if band is not None else 0, stream_ptr()),
+          "lsf_cumulative_warp_compose")
+
+
 def slavcheva_update_rewarp(live, canonical, g, warp_out, live_out, grid, params, gate, records, index, band=None):
     n = n_voxels(grid)
     nd = n * grid.dims

@@ -26,12 +26,23 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
                  smoothing_term_method, gradient_descent_rate, data_term_weight, smoothing_term_weight,
                  isomorphic_enforcement_factor, level_set_term_weight, lower_threshold, upper_threshold,
                  max_iterations, min_iterations, sobolev_kernel, compute_energies=True, check_interval=32,
-                 comm=None, options=None):
+                 comm=None, options=None, cumulative_warp=False):
         self.direct = bool(direct)
         self.sobolev = bool(sobolev_smoothing_enabled)
         self.sobolev_kernel = sobolev_kernel
         if self.sobolev and sobolev_kernel is None:
             raise ValueError("sobolev_smoothing_enabled requires a sobolev_kernel")
+        # the call also composes its iterations' updates into the cumulative displacement PSI with
+        # live_0(v + PSI(v)) ~ canonical(v) ("Cumulative warp"): a keyword, not an engine
+        # option, since it changes what a call leaves behind
+        self.cumulative_warp = bool(cumulative_warp)
+        if self.cumulative_warp and self.sobolev:
+            raise ValueError("cumulative_warp does not combine with sobolev_smoothing_enabled: the planar and float4 "
+                             "Sobolev launch plans do not compose the warp")
+        if self.cumulative_warp and comm is not None and comm.active:
+            raise ValueError("cumulative_warp does not combine with an active comm: slab runs would need a halo of the "
+                             "cumulative warp")
+        self._cumulative_state = None
         lam = float(isomorphic_enforcement_factor)
         # VECTORIZED ignores the Killing / level-set / thresholded options (slavcheva_optimizer2d.py:163-190)
         smoothing = smoothing_term_method if self.direct else _lib.SMOOTHING_TIKHONOV
@@ -103,6 +114,20 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
             return
         return self._enqueue_slab_state_iteration(i, states, limit)
 
+    def _enqueue_composition(self, i):
+        """cumulative_warp: PSI_{i+1} = u_i + PSI_i(id + u_i) at the voxels of every band list, from the state iteration i
+        has just written, under iteration i's gate (lsf_cumulative_warp_compose)"""
+        f = self._fast
+        gate_ref = None if i < self.min_iterations else f.gate_ref(i - 1)
+        run = _lib.lib.lsf_cumulative_warp_compose
+        for band in f.bands:
+            if band.indices is not None and band.count == 0:
+                continue  # an empty list: nothing to compose
+            status = run(f.p_state[(i + 1) % 2], f.p_psi[i % 2], f.p_psi[(i + 1) % 2], f.grid_ref, gate_ref, band.pointer,
+                         band.count, f.stream)
+            if status:
+                _lib.check(status, "lsf_cumulative_warp_compose")
+
     def optimize(self, live, canonical, finalize=None):
         """live, canonical: float32 device tensors (z-slab runs: the local slab incl. halos).  Returns a
         SlavchevaOutcome holding the final fields on the device; the caller's tensors are not modified.
@@ -149,6 +174,7 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
         # the footprint doubles and the first three calls of an optimizer each pay device allocations: 120 / 131 / 70 ms
         # against 9 ms at 512^3, tools/step_times.py)
         self._gradient_state = None
+        self._cumulative_state = None
         self._fast = None
         self.last_call = engine_options.new_call_report()
         grid = self._grid(live)
@@ -159,8 +185,10 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
         watched = self.iteration_hook is not None or self.focus_voxels is not None
         if self.focus_voxels is not None:
             self._focus_begin(live, canonical)
+        # cumulative_warp: the general path below, where a composition launch follows every iteration's launches
         run_ok = (self.library_run and finalize is not None and not self.sobolev and self.use_band_list
-                  and not watched and self.min_iterations > 0 and dev.buffer_addressing_ok(grid))
+                  and not watched and self.min_iterations > 0 and dev.buffer_addressing_ok(grid)
+                  and not self.cumulative_warp)
         if (self.library_run and finalize is not None and self.sobolev and self.sobolev_boxes and self.use_band_list
                 and not watched and self.min_iterations > 0 and not slab and grid.dims == 3
                 and dev.boxes_ok(grid) and dev.n_voxels(grid) < (1 << 27) and dev.buffer_addressing_ok(grid)
@@ -239,7 +267,7 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
             live_at_entry = finalize[0].clone()
         records = dev.new_records(n_rec, live.device)
         self._last_g = None
-        lives = warps = gbufs = states = sob = None
+        lives = warps = gbufs = states = sob = psi = None
         if planar_sobolev:
             lives = [live.clone(), live.clone()]
             warps = [torch.zeros((dims,) + tuple(live.shape), dtype=torch.float32, device=live.device)
@@ -283,6 +311,11 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
                 bands = dev.band_lists(live, canonical, whole) if self.use_band_list else [dev.BandList.none()]
             f.bands = bands
             self._fast = f
+            if self.cumulative_warp:
+                # two zero-filled PSI buffers in the state's layout, ping-pong with the states; allocated per attempt, so
+                # a call that runs again on fully initialised states composes from zeros again
+                psi = [torch.zeros(tuple(live.shape) + (4,), dtype=torch.float32, device=live.device) for _ in range(2)]
+                f.p_psi = [f.pointer(t, 4 * n, "cumulative warp") for t in psi]
             if sob_state:
                 g4 = [torch.zeros(tuple(live.shape) + (4,), dtype=torch.float32, device=live.device)
                       for _ in range(2 if _SobolevStatePlan.fuses_x(grid) else 3)]
@@ -320,6 +353,8 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
                     sob.enqueue(i)
                 else:
                     self._enqueue_state_iteration(i, states, limit)
+                    if psi is not None:
+                        self._enqueue_composition(i)
             # z-slab: a gated run's device-side gate reads the records, so they are all-reduced (global max: idempotent;
             # once per record the energy sums of this batch); a fixed count only needs them on the host: every rank's
             # partial slots are gathered when they are read
@@ -361,6 +396,8 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
             if n_exec >= self.min_iterations and not (np.float32(self.lo) < m < np.float32(self.hi)):
                 break
         self.iteration_count = n_exec
+        if psi is not None:  # gated launches behind the stop composed nothing: n_exec compositions have run
+            self._cumulative_state = ("state", psi[n_exec % 2], grid)
         wd, ws, wl = self.weights
         if dec is None:
             dec = dev.decode_records(dev.records_to_host(records[:1]))
@@ -409,6 +446,20 @@ class SlavchevaEngine(RunMixin, SlabMixin, PlanarSobolevMixin, FocusMixin):
         own = (slice(None), self.comm.layout.owned_local()) if self._slab() else (slice(None),)
         self.iteration_hook(0, i, dev.interleave(warp_planar[own].contiguous()), dev.interleave(g[own].contiguous()),
                             max_warp)
+
+    def cumulative_warp_field(self):
+        """PSI of the last call in the API layout [..., D] (x, y[, z] channels), a float32 device tensor built when first
+        read; None before the first call and without cumulative_warp"""
+        st = self._cumulative_state
+        if st is None:
+            return None
+        if st[0] == "ready":
+            return st[1]
+        _, psi, grid = st
+        out = torch.empty(tuple(psi.shape[:-1]) + (grid.dims,), dtype=torch.float32, device=psi.device)
+        dev.state_unpack(psi, grid, warp_interleaved_out=out)
+        self._cumulative_state = ("ready", out)
+        return out
 
     def gradient_field(self):
         """planar gradient of the last executed iteration (zeroed where the live field snapped, DIRECT only).

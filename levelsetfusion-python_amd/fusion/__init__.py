@@ -89,14 +89,29 @@ channels), and the frame is fused in depth mode with "the voxel's centre" replac
     point(v) = float32((float64(v) + float64(psi(v)) + array_offset) * voxel_size),   per axis
 is transformed by the twist, projected, and the depth, the pixel weight and the colour are read at its pixel; the
 weighted, carving and colour rules then apply unchanged (csrc/lsf_fusion.hip, lsf_fusion_integrate_depth_warped).  Nothing
-is warped as a volume, so `carve`, `confidence` and `colour` combine with this optimizer, and with this one only.  A voxel
+is warped as a volume, so `carve`, `confidence` and `colour` combine with this optimizer (and with the one of the next
+paragraph), and with no other.  A voxel
 whose psi is not finite is left alone and counted in the record's warp_rejected (unpack_warped_record); psi = 0 gives
 the unwarped calls bit for bit.  Frame 0 is fused as without an optimizer; `warp` keeps the last psi.
 CanonicalVolume.integrate_depth(..., warp=) is the same call for a given field.  In 3-D the optimizer's default
 tikhonov_strength = 0.2 diverges: its recursion g <- data - s * laplace(g) has gain 12 s at the highest frequency of the
 7-point Laplacian, so s must lie below 1 / 12; 0.05 is stable.
-With any other non-rigid optimizer (a SlavchevaOptimizer3d in a KillingFusion or SobolevFusion configuration: its final
-warp_field is the last iteration's update only, not a cumulative warp) the live volume under the twist is generated,
+With a SlavchevaOptimizer3d made with `cumulative_warp=True` (the KillingFusion iteration; INTEGRATION.md section 3,
+"Cumulative warp"; tests/cumulative_warp_restatement.py restates it) frames k >= 1 are fused the same way: after tracking,
+the live volume under the twist is generated, `optimizer.optimize(live, model.tsdf)` runs -- every iteration re-warps the
+live volume by its own update u_k, and a composition launch behind it (csrc/lsf_cumulative_warp.hip) keeps
+PSI_{k+1}(v) = u_k(v) + PSI_k(v + u_k(v)), PSI_0 = 0 --, `warp` takes `optimizer.cumulative_warp_field`, the total
+displacement with live(v + PSI(v)) ~ model(v), and the frame is fused in depth mode through it, with `carve`, `confidence`
+and `colour` as set.  The warped live volume itself is dropped.  On a model fused from depth the level-set term is best
+left off (level_set_term_enabled=False): the voxels behind the model's band were never observed and keep the initial +1
+where the live volume has -1, the term's gradient of the live field is huge across that step, and on
+tests/deforming_scene.py it produces updates of 14 voxels per iteration, after which the chain changes the model by 0.17
+per voxel near the surface, against 0.070 with the term off and 0.212 fused rigidly.  That is the reference's term doing
+what it does on such a field, not a fault of the composition.  The keyword is refused together with
+sobolev_smoothing_enabled and with a slab `comm`.
+With any other non-rigid optimizer (a SlavchevaOptimizer3d without that keyword, in a KillingFusion or SobolevFusion
+configuration: its final warp_field is the last iteration's update only, not a cumulative warp) the live volume under the
+twist is generated,
 warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fused in volume mode: unweighted,
 uncarved, uncoloured -- `carve`, `confidence` and `colour` raise with it, since the observation mask, the weights and
 the colour would have to be warped with the live field.
@@ -107,7 +122,8 @@ count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals.
 
-Not covered: carving, weights or colour in volume mode, a cumulative warp out of SlavchevaOptimizer3d, a carve-distance
+Not covered: carving, weights or colour in volume mode, a cumulative warp out of SobolevFusion
+(sobolev_smoothing_enabled) or out of a z-slab / multi-GPU run (`comm`), a carve-distance
 limit, keeping the warp field between frames as a warm start, ray-casting or meshing in the live frame, a whole frame
 enqueued without host synchronisations, z-slab / multi-GPU fusion, a 2-D depth-mode row generator, fusing the filtered
 depth, a downsampled prediction depth and normal pyramid (every level still pairs into the full-resolution
@@ -125,6 +141,7 @@ from ..device_core import require_gpu
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
                              unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
 from ..nonrigid_opt.hierarchical.hierarchical_optimizer3d import HierarchicalOptimizer3d
+from ..nonrigid_opt.slavcheva.slavcheva_optimizer3d import SlavchevaOptimizer3d
 from ..rigid_opt.depth_pyramid import DepthPyramid
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
@@ -316,8 +333,8 @@ class SequenceFusion3d:
     `frame_records` (one dict per frame: frame, twist, rigid_records, nonrigid, fusion, prediction_hits -- the pixels
     of the prediction that hit the model, None without a prediction), in "raycast" and "icp" mode `prediction`
     (the last predicted depth image, a float32 device tensor in metres) and, with a HierarchicalOptimizer3d as the
-    non-rigid step, `warp` (the last frame's displacement field, a float32 (Z, Y, X, 3) device tensor; None before
-    frame 1).  In "icp" mode rigid_records holds the ICP
+    non-rigid step, or a SlavchevaOptimizer3d made with cumulative_warp=True, `warp` (the last frame's displacement
+    field, a float32 (Z, Y, X, 3) device tensor; None before frame 1).  In "icp" mode rigid_records holds the ICP
     records (device_icp.unpack_record); with photometric_weight they carry photometric_count and photometric_energy,
     and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image; with icp_intensity_pyramid the
     joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids)."""
@@ -331,8 +348,9 @@ class SequenceFusion3d:
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
-        # the one optimizer that returns a cumulative warp: its frames are fused through it, in depth mode
-        self.warped = isinstance(nonrigid_optimizer, HierarchicalOptimizer3d)
+        # the optimizers that give a cumulative warp: their frames are fused through it, in depth mode
+        self._composed = isinstance(nonrigid_optimizer, SlavchevaOptimizer3d) and nonrigid_optimizer.cumulative_warp
+        self.warped = isinstance(nonrigid_optimizer, HierarchicalOptimizer3d) or self._composed
         volume_mode = nonrigid_optimizer is not None and not self.warped
         if volume_mode and (self.carve or confidence is not None):
             raise ValueError("carve and confidence need depth-mode fusion and do not combine with a nonrigid_optimizer: "
@@ -380,7 +398,7 @@ class SequenceFusion3d:
         self.frame_records = []
         self.prediction = None  # "raycast", "icp": the last prediction, a float32 device depth image in metres
         self.prediction_colour = None  # photometric_weight: the last prediction's float32 (H, W, 4) colour image
-        self.warp = None  # a HierarchicalOptimizer3d step: the last frame's psi, a float32 (Z, Y, X, 3) device tensor
+        self.warp = None  # a warped step: the last frame's psi, a float32 (Z, Y, X, 3) device tensor
         self._previous = None  # "raycast": the previous frame's (device depth, LSF_DEPTH_* code)
         P = camera.intrinsics.intrinsic_matrix
         # the prediction is in metres: its live volume is generated with ratio 1
@@ -462,7 +480,11 @@ class SequenceFusion3d:
         if through:
             live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
                                                **gen)
-            if self.warped:
+            if self._composed:  # the live volume is warped in place and dropped: the frame is fused through PSI
+                self.nonrigid_optimizer.optimize(live, model.tsdf)
+                self.warp = self.nonrigid_optimizer.cumulative_warp_field
+                del live
+            elif self.warped:
                 self.warp = self.nonrigid_optimizer.optimize(model.tsdf, live)
                 del live
             else:

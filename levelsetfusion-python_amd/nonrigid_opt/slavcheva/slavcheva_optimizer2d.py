@@ -107,7 +107,8 @@ class _SlavchevaOptimizerBase:
                  level_set_term_weight=0.2, maximum_warp_length_lower_threshold=0.1,
                  maximum_warp_length_upper_threshold=10000, max_iterations=100, min_iterations=1,
                  sobolev_kernel=None, visualization_settings=None, enable_convergence_status_logging=True,
-                 verbose=False, check_interval=32, comm=None, engine_options=None, focus_coordinates=None):
+                 verbose=False, check_interval=32, comm=None, engine_options=None, focus_coordinates=None,
+                 cumulative_warp=False):
         self.visualization_settings = visualization_settings  # accepted, unused
         self.field_size = field_size
         self.out_path = out_path
@@ -139,6 +140,10 @@ class _SlavchevaOptimizerBase:
         self._warp_field = None
         self.focus_coordinates = focus_coordinates
         self.focus_neighborhood_log = None
+        # cumulative_warp=True: every call also leaves `cumulative_warp_field`, the composition of its iterations' updates
+        # (refused with sobolev_smoothing_enabled and with an active comm); False changes nothing
+        self.cumulative_warp = bool(cumulative_warp)
+        self._cumulative_on_device = True
         self._engine = SlavchevaEngine(
             direct=compute_method == ComputeMethod.DIRECT, level_set_term_enabled=level_set_term_enabled,
             sobolev_smoothing_enabled=sobolev_smoothing_enabled,
@@ -152,7 +157,7 @@ class _SlavchevaOptimizerBase:
             upper_threshold=maximum_warp_length_upper_threshold, max_iterations=max_iterations,
             min_iterations=min_iterations,
             sobolev_kernel=None if sobolev_kernel is None else np.asarray(sobolev_kernel, dtype=np.float64),
-            check_interval=check_interval, comm=comm, options=engine_options)
+            check_interval=check_interval, comm=comm, options=engine_options, cumulative_warp=self.cumulative_warp)
 
     def _run_checks(self, live_field, canonical_field):
         # slavcheva_optimizer2d.py:157-161,339: equal shapes, square/cubic, side == field_size
@@ -208,6 +213,18 @@ class _SlavchevaOptimizerBase:
         self._warp_field = value
 
     @property
+    def cumulative_warp_field(self):
+        """with cumulative_warp=True, the last call's total displacement PSI [..., D] in voxels (x, y[, z] channels) with
+        live_at_entry(v + PSI(v)) ~ canonical(v): PSI_0 = 0, PSI_{k+1}(v) = u_k(v) + PSI_k(v + u_k(v)) over the executed
+        iterations' post-snap updates u_k ("Cumulative warp") -- what
+        CanonicalVolume.integrate_depth(..., warp=) takes.  numpy for numpy inputs, a device tensor for device inputs, built
+        when read like warp_field; None before the first call and without the keyword"""
+        psi = self._engine.cumulative_warp_field()
+        if psi is None or self._cumulative_on_device:
+            return psi
+        return psi.cpu().numpy()
+
+    @property
     def gradient_field(self):
         """gradient of the last iteration, interleaved numpy array (reference attribute of the same name)"""
         g = self._engine.gradient_field()
@@ -215,6 +232,7 @@ class _SlavchevaOptimizerBase:
 
     def optimize(self, live_field, canonical_field):
         on_device = isinstance(live_field, torch.Tensor) and live_field.is_cuda
+        self._cumulative_on_device = on_device
         if self._engine.comm is None or not self._engine.comm.active:
             self._run_checks(live_field, canonical_field)
         live = as_device_field(live_field)
