@@ -1228,7 +1228,9 @@ typedef struct lsf_icp_params {
  *   row-major   [49, 55) b   [55] skipped: 0 updated, 1 singular (not finite, or an exact zero pivot)
  *   [56] correspondence count   [57] level   [58] pairs the normal-angle gate rejected (lsf_icp_run_pyramid; 0 from
  *   lsf_icp_run)   [59] photometric pair count   [60] photometric energy, sum r_I^2 (lsf_icp_run_photometric; 0 from
- *   the other two; lsf_icp_run_pyramid_photometric writes 58, 59 and 60)   [61, 64) reserved */
+ *   the other two; lsf_icp_run_pyramid_photometric writes 58, 59 and 60)   [61] sum of the geometric weights w
+ *   [62] sum of the photometric weights w_I   [63] geometric outliers (lsf_icp_run_robust and
+ *   lsf_icp_run_pyramid_robust; 0 from the other four) */
 #define LSF_ICP_RECORD_DOUBLES 64
 /* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
  * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
@@ -1403,6 +1405,87 @@ int lsf_icp_run_pyramid_photometric(const float *live_depth, const float *live_n
                                     double *twist_inout, double *records, void *scratch, float *residuals_out,
                                     float *intensity_residuals_out,
                                     const lsf_icp_pyramid_photometric_params *params, void *stream);
+
+/* ---- robust ICP: Huber and Tukey weights on both terms, strided and pyramid ------------------------------------------
+ * An iteratively reweighted solve ("Robust ICP"): the pairs, gates, schedule and records of
+ * lsf_icp_run_photometric (lsf_icp_run's without the images), with every pair's rows of the normal equations scaled by
+ * a weight of its own residual at the current twist, every step one float64 operation.  With a = |r| and the scale s:
+ *   LSF_ICP_LOSS_HUBER  w = (a <= s) ? 1 : s / a               outlier: a > s
+ *   LSF_ICP_LOSS_TUKEY  t = r / s, u = 1 - t t, w = (a < s) ? u u : 0   outlier: a >= s
+ * A geometric pair (J, r) adds wJ_i = w J_i, A_ij += wJ_i J_j, b_i -= wJ_i r and (w r) r to the energy.  A photometric
+ * term takes w_I from the unscaled r_I and intensity_scale, applies it to lambda J_I and lambda r_I in the same way and
+ * adds (w_I r_I) r_I to the photometric energy.  The distance gate, the normal-angle gate and max_intensity_difference
+ * stay hard gates in front of the weight; a pair with w = 0 still counts; the residual images keep the unweighted r and
+ * r_I.  An infinite scale makes every weight exactly 1 and every product above exact, so a call with both scales
+ * infinite equals the plain entry point's twist, residuals and record slots 0 .. 60 bit for bit.  Record slot 61 is
+ * sum w over the geometric pairs, 62 sum w_I over the photometric pairs, 63 the geometric outliers.  No default scale
+ * is right across sensors: the caller chooses both. */
+#define LSF_ICP_LOSS_HUBER 1
+#define LSF_ICP_LOSS_TUKEY 2
+typedef struct lsf_icp_robust_params {
+    double fx, fy, cx, cy;             /* as lsf_icp_photometric_params, member for member */
+    double depth_unit_ratio;
+    double max_distance;
+    double photometric_weight;         /* lambda: finite and > 0 with the colour images, 0 without them */
+    double max_intensity_difference;   /* with the colour images: > 0 (inf allowed); not read without them */
+    double twist_p[6];
+    int32_t height, width;
+    int32_t depth_dtype;
+    int32_t levels;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    int32_t strides[LSF_ICP_MAX_LEVELS];
+    int32_t loss;                      /* LSF_ICP_LOSS_* */
+    double scale;                      /* of r, metres: > 0 (inf allowed: least squares) */
+    double intensity_scale;            /* of r_I, units of Y (0 .. 1): > 0 (inf allowed: least squares) */
+} lsf_icp_robust_params;
+/* at most 34 partial sums per workgroup: lsf_icp_run_photometric's 31, sum w, sum w_I, the outliers */
+#define LSF_ICP_ROBUST_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 34 * 8)
+
+/* lsf_icp_run_photometric's arguments, and weights_out: NULL, or DEVICE float32 [height][width] that receives the last
+ * iteration's geometric w, laid out like residuals_out (NaN where a pixel has no correspondence or is not on the last
+ * level's stride), written by the launch that writes the residuals.  live_colour and pred_colour are optional: with
+ * both NULL, photometric_weight == 0 and intensity_residuals_out NULL the call is the geometric solve of lsf_icp_run
+ * with weights.  One of the two NULL without the other, a non-zero photometric_weight without them, an unknown loss, a
+ * scale or intensity_scale that is NaN or <= 0 return LSF_ERR_BAD_ARGUMENT.  scratch: DEVICE,
+ * LSF_ICP_ROBUST_SCRATCH_BYTES.  sum(iterations) + 1 launches, none when sum(iterations) == 0; no float atomics, no host
+ * wait, a rerun is bit-identical.  No output (weights_out included) may alias an input or another output. */
+int lsf_icp_run_robust(const void *live_depth, const uint8_t *live_colour, const float *pred_depth,
+                       const float *pred_normals, const float *pred_colour, double *twist_inout, double *records,
+                       void *scratch, float *residuals_out, float *intensity_residuals_out, float *weights_out,
+                       const lsf_icp_robust_params *params, void *stream);
+
+typedef struct lsf_icp_pyramid_robust_params {
+    double fx, fy, cx, cy;             /* as lsf_icp_pyramid_photometric_params, member for member */
+    double max_distance;
+    double cos_max_angle;
+    double photometric_weight;         /* lambda: finite and > 0 with the intensity pyramids, 0 without them */
+    double max_intensity_difference;   /* with the intensity pyramids: > 0 (inf allowed); not read without them */
+    double twist_p[6];
+    int32_t height, width;
+    int32_t pyramid_levels;
+    int32_t levels;
+    int32_t angle_gate;
+    int32_t reserved;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    int32_t loss;                      /* LSF_ICP_LOSS_* */
+    double scale;                      /* of r, metres: > 0 (inf allowed: least squares) */
+    double intensity_scale;            /* of r_I, units of Y (0 .. 1): > 0 (inf allowed: least squares) */
+} lsf_icp_pyramid_robust_params;
+/* at most 35 partial sums per workgroup: lsf_icp_run_pyramid_photometric's 32, sum w, sum w_I, the outliers */
+#define LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 35 * 8)
+
+/* lsf_icp_run_pyramid_photometric's arguments, and weights_out: NULL, or DEVICE float32 of the last iteration's level
+ * extents, the geometric w there, NaN where a pixel has no correspondence.  live_intensity and pred_intensity are
+ * optional under lsf_icp_run_robust's rules: with both NULL, photometric_weight == 0 and intensity_residuals_out NULL
+ * the call is lsf_icp_run_pyramid with weights.  The refusals are lsf_icp_run_pyramid's and lsf_icp_run_robust's.
+ * scratch: DEVICE, LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES.  sum(iterations) + 1 launches, none when sum(iterations) == 0;
+ * no float atomics, no host wait, a rerun is bit-identical.  No output (weights_out included) may alias an input or
+ * another output. */
+int lsf_icp_run_pyramid_robust(const float *live_depth, const float *live_normals, const float *live_intensity,
+                               const float *pred_depth, const float *pred_normals, const float *pred_intensity,
+                               double *twist_inout, double *records, void *scratch, float *residuals_out,
+                               float *intensity_residuals_out, float *weights_out,
+                               const lsf_icp_pyramid_robust_params *params, void *stream);
 
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):

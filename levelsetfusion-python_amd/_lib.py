@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "892cc19a0c12c0b0"
+HEADER_ABI_HASH = "8a5ce59b8dece352"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -324,6 +324,23 @@ class IcpPyramidPhotometricParams(ctypes.Structure):
                [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS)]
 
 
+ICP_LOSS_HUBER, ICP_LOSS_TUKEY = 1, 2
+ICP_ROBUST_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 34 * 8
+ICP_PYRAMID_ROBUST_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 35 * 8
+_ROBUST_FIELDS = [("loss", ctypes.c_int32), ("scale", ctypes.c_double), ("intensity_scale", ctypes.c_double)]
+
+
+class IcpRobustParams(ctypes.Structure):
+    """lsf_icp_robust_params: lsf_icp_photometric_params' members, then the loss and its two scales (lsf_icp_run_robust)"""
+    _fields_ = IcpPhotometricParams._fields_ + _ROBUST_FIELDS
+
+
+class IcpPyramidRobustParams(ctypes.Structure):
+    """lsf_icp_pyramid_robust_params: lsf_icp_pyramid_photometric_params' members, then the loss and its two scales
+    (lsf_icp_run_pyramid_robust)"""
+    _fields_ = IcpPyramidPhotometricParams._fields_ + _ROBUST_FIELDS
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -458,6 +475,10 @@ PROTOTYPES = {
     "lsf_intensity_pyramid": (ctypes.c_int, [_vp, _vp, _P(IntensityPyramidParams), _vp]),
     "lsf_icp_run_pyramid_photometric": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                        _P(IcpPyramidPhotometricParams), _vp]),
+    "lsf_icp_run_robust": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpRobustParams),
+                                          _vp]),
+    "lsf_icp_run_pyramid_robust": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _P(IcpPyramidRobustParams), _vp]),
 }
 
 

@@ -23,6 +23,12 @@
 //   PyramidPhotometricSource  lsf_icp_run_pyramid_photometric: PyramidSource's pixels and gate; the intensity term is
 //                  taken at the pixel's own level, between that level of two lsf_intensity_pyramid outputs (the live
 //                  frame's and the prediction's) with the level's intrinsics; 32 sums, slots 58, 59 and 60
+//   RobustSource<S>  lsf_icp_run_robust and lsf_icp_run_pyramid_robust: any of the four with every pair's rows scaled
+//                  by a Huber or Tukey weight of its own residual ("Robust ICP";
+//                  tests/robust_icp_restatement.py); the loss is a wave-uniform run-time select; three more sums: sum w,
+//                  sum w_I and the geometric outliers (record slots 61, 62 and 63), and the weight image of the last
+//                  iteration beside the residuals
+#include <cstddef>
 #include <initializer_list>
 #include <type_traits>
 
@@ -40,17 +46,42 @@ constexpr int kSums = 29;  // A's upper triangle (21, row by row), b (6), energy
 constexpr int kPyrSums = 30;  // lsf_icp_run_pyramid: and the pairs the angle gate rejected
 constexpr int kPhotoSums = 31;  // lsf_icp_run_photometric: kSums, then the photometric pairs and sum r_I^2
 constexpr int kPyrPhotoSums = 32;  // lsf_icp_run_pyramid_photometric: kPyrSums, then the same two
+constexpr int kRobustSums = 3;     // a robust source: its base's, then sum w, sum w_I and the geometric outliers
 constexpr int kMaxBlocks = LSF_ICP_MAX_BLOCKS;
 constexpr int kRecord = LSF_ICP_RECORD_DOUBLES;
 constexpr int kDelta = 0, kTwist = 6, kEnergy = 12, kA = 13, kB = 49, kSkipped = 55, kCount = 56, kLevel = 57,
-              kRejected = 58, kPhotoCount = 59, kPhotoEnergy = 60;
+              kRejected = 58, kPhotoCount = 59, kPhotoEnergy = 60, kWeightSum = 61, kPhotoWeightSum = 62,
+              kOutliers = 63;
 static_assert(kSub * kSub == kWave && (kTile / kSub) * (kTile / kSub) * kWave == kBlock, "4 waves of 8 x 8 pixels");
 static_assert(LSF_ICP_SCRATCH_BYTES == 2 * kMaxBlocks * kSums * 8, "two ping-pong buffers of kMaxBlocks partials");
 static_assert(LSF_ICP_PYRAMID_SCRATCH_BYTES == 2 * kMaxBlocks * kPyrSums * 8, "the same with the 30th sum");
 static_assert(LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES == 2 * kMaxBlocks * kPhotoSums * 8, "the same with 31 sums");
 static_assert(LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES == 2 * kMaxBlocks * kPyrPhotoSums * 8, "the same with 32 sums");
+static_assert(LSF_ICP_ROBUST_SCRATCH_BYTES == 2 * kMaxBlocks * (kPhotoSums + kRobustSums) * 8, "the same with 34 sums");
+static_assert(LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES == 2 * kMaxBlocks * (kPyrPhotoSums + kRobustSums) * 8, "the same with 35 sums");
+// the robust structs are the photometric ones with the loss behind them: tests/test_robust_icp_host.py holds the
+// ctypes mirrors to the same numbers
+static_assert(sizeof(lsf_icp_photometric_params) == 160 && offsetof(lsf_icp_robust_params, loss) == 160 &&
+              offsetof(lsf_icp_robust_params, scale) == 168 && offsetof(lsf_icp_robust_params, intensity_scale) == 176 &&
+              sizeof(lsf_icp_robust_params) == 184, "lsf_icp_robust_params");
+static_assert(sizeof(lsf_icp_pyramid_photometric_params) == 152 && offsetof(lsf_icp_pyramid_robust_params, loss) == 152 &&
+              offsetof(lsf_icp_pyramid_robust_params, scale) == 160 &&
+              offsetof(lsf_icp_pyramid_robust_params, intensity_scale) == 168 &&
+              sizeof(lsf_icp_pyramid_robust_params) == 176, "lsf_icp_pyramid_robust_params");
 static_assert(kMaxBlocks <= kBlock, "the prologue gives every partial one thread");
-static_assert(kPhotoEnergy < kRecord && kRejected < kRecord && kB == kA + 36 && kSkipped == kB + 6, "the record holds every field");
+static_assert(kOutliers < kRecord && kRejected < kRecord && kB == kA + 36 && kSkipped == kB + 6, "the record holds every field");
+
+// where a source keeps its sums: kSums, then the gate's rejections (a pyramid source), the photometric pairs and
+// sum r_I^2 (a photometric one), and sum w, sum w_I and the geometric outliers (a robust one)
+template <bool PYRAMID, bool PHOTO, bool ROBUST>
+struct Sums {
+    static constexpr bool kPyramid = PYRAMID, kPhoto = PHOTO, kRobust = ROBUST;
+    static constexpr int kPhotoAt = kSums + (PYRAMID ? 1 : 0), kRobustAt = kPhotoAt + (PHOTO ? 2 : 0),
+                         K = kRobustAt + (ROBUST ? kRobustSums : 0);
+};
+static_assert(Sums<false, false, false>::K == kSums && Sums<true, false, false>::K == kPyrSums &&
+              Sums<false, true, false>::K == kPhotoSums && Sums<true, true, false>::K == kPyrPhotoSums,
+              "the four plain sources keep their sums");
 
 struct IcpDev {
     double fx, fy, cx, cy, ratio, max_distance;
@@ -71,8 +102,9 @@ Grid grid_of(int ni, int nj) {
 // lsf_icp_run: pixel (i, j) is the live image's (stride i, stride j), its depth scaled by the ratio
 template <typename DT>
 struct StridedSource {
-    static constexpr int K = kSums;
-    static constexpr bool kGate = false, kPhoto = false;
+    using Layout = Sums<false, false, false>;
+    static constexpr int K = Layout::K;
+    static constexpr bool kGate = false, kPhoto = false, kRobust = false;
     using Live = DT;
     Grid grid;
     int stride;
@@ -102,8 +134,9 @@ struct StridedSource {
 // lsf_icp_run_pyramid: every pixel of one pyramid level, float32 metres at live[j ni + i], normals beside them
 template <bool GATE>
 struct PyramidSource {
-    static constexpr int K = kPyrSums;
-    static constexpr bool kGate = GATE, kPhoto = false;
+    using Layout = Sums<true, false, false>;
+    static constexpr int K = Layout::K;
+    static constexpr bool kGate = GATE, kPhoto = false, kRobust = false;
     using Live = float;
     double fx, fy, cx, cy, cos_max;
     long long offset;  // of the level in the live buffers: the launch passes their pointers advanced by it
@@ -136,7 +169,8 @@ struct PyramidSource {
 template <typename DT>
 struct PhotometricSource : StridedSource<DT> {
     using Pixel = typename StridedSource<DT>::Pixel;
-    static constexpr int K = kPhotoSums;
+    using Layout = Sums<false, true, false>;
+    static constexpr int K = Layout::K;
     static constexpr bool kPhoto = true;
     const uint8_t* live_colour;  // [height][width][3]
     const float* pred_colour;    // [height][width][4], Y last
@@ -164,7 +198,8 @@ struct PhotometricSource : StridedSource<DT> {
 template <bool GATE>
 struct PyramidPhotometricSource : PyramidSource<GATE> {
     using Pixel = typename PyramidSource<GATE>::Pixel;
-    static constexpr int K = kPyrPhotoSums;
+    using Layout = Sums<true, true, false>;
+    static constexpr int K = Layout::K;
     static constexpr bool kPhoto = true;
     const float* live_intensity;  // the level's [nj][ni] of the live frame's lsf_intensity_pyramid output
     const float* pred_intensity;  // the same level of the prediction's
@@ -181,6 +216,32 @@ struct PyramidPhotometricSource : PyramidSource<GATE> {
     }
     __device__ double predicted(long long at) const { return (double)pred_intensity[at]; }
     __device__ double observed(const IcpDev&, Pixel px) const { return (double)live_intensity[px.at]; }
+};
+
+// lsf_icp_run_robust and lsf_icp_run_pyramid_robust: BASE's pixels, pairs and gates; a pair's rows are scaled by the
+// weight of its own residual, w from r and scale, w_I from the unscaled r_I and intensity_scale.  The loss is the same
+// for every lane of a launch, so the select is wave-uniform
+template <typename BASE>
+struct RobustSource : BASE {
+    using Layout = Sums<BASE::Layout::kPyramid, BASE::kPhoto, true>;
+    static constexpr int K = Layout::K;
+    static constexpr bool kRobust = true;
+    int loss;  // LSF_ICP_LOSS_*
+    double scale, intensity_scale;
+    float* weights;  // w of the launch, laid out like the residuals, or NULL: launch_run keeps it for the last iteration
+
+    // the weight of the residual r at the scale s (> 0, inf allowed), and whether the pair is an outlier
+    __device__ double weight(double r, double s, bool& outlier) const {
+        const double a = fabs(r);
+        if (loss == LSF_ICP_LOSS_HUBER) {
+            outlier = a > s;
+            return a <= s ? 1.0 : s / a;
+        }
+        const double t = r / s;
+        const double u = 1.0 - t * t;
+        outlier = a >= s;
+        return a < s ? u * u : 0.0;
+    }
 };
 
 // the twist after the step delta = (tau, omega): R' = R Rodrigues(omega)^T, t' = t - R' tau, out = (t', log R')
@@ -207,18 +268,20 @@ __device__ inline void compose(const double* tw, const double* delta, double* ou
 // the twist of launch k into tw (LDS): twist_io (k = 0), or iteration k-1's partials (prev_blocks of them) combined,
 // solved and composed onto the twist before it (record k-2's, or twist_io); block 0 writes record k-1 and, with
 // twist_final, the final twist.  The finishing launch has one block, which reads twist_io before it writes it.
-// K = kPyrSums also writes the gate's rejections to record slot kRejected, K = kPhotoSums the photometric pairs and
-// energy to kPhotoCount and kPhotoEnergy, K = kPyrPhotoSums all three.
-template <int K>
+// L (a Sums): a pyramid source's also writes the gate's rejections to record slot kRejected, a photometric one's the
+// photometric pairs and energy to kPhotoCount and kPhotoEnergy, a robust one's sum w, sum w_I and the outliers to
+// kWeightSum, kPhotoWeightSum and kOutliers; the slots a source does not have are 0.
+template <typename L>
 __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_level, double* __restrict__ twist_io,
                                              double* __restrict__ records, const double* __restrict__ scratch,
-                                             double (*red)[K], double* tw, double* twist_final) {
+                                             double (*red)[L::K], double* tw, double* twist_final) {
     if (k == 0) {
         if (threadIdx.x == 0)
             for (int i = 0; i < 6; ++i) tw[i] = twist_io[i];
         __syncthreads();
         return;
     }
+    constexpr int K = L::K;
     double v[K];
     combine_partials(scratch + (size_t)((k - 1) & 1) * kMaxBlocks * K, prev_blocks, v, red);
     if (threadIdx.x == 0) {
@@ -237,15 +300,17 @@ __device__ __forceinline__ void icp_prologue(int k, int prev_blocks, int prev_le
             r[kSkipped] = (double)skipped;
             r[kCount] = v[28];
             r[kLevel] = (double)prev_level;
-            int i = kLevel + 1;
-            if constexpr (K == kPyrSums) r[i++] = v[kSums];
-            if constexpr (K == kPhotoSums || K == kPyrPhotoSums) {
-                r[kRejected] = K == kPyrPhotoSums ? v[kSums] : 0.0;
-                r[kPhotoCount] = v[K - 2];
-                r[kPhotoEnergy] = v[K - 1];
-                i = kPhotoEnergy + 1;
+            for (int i = kLevel + 1; i < kRecord; ++i) r[i] = 0.0;
+            if constexpr (L::kPyramid) r[kRejected] = v[kSums];
+            if constexpr (L::kPhoto) {
+                r[kPhotoCount] = v[L::kPhotoAt];
+                r[kPhotoEnergy] = v[L::kPhotoAt + 1];
             }
-            for (; i < kRecord; ++i) r[i] = 0.0;
+            if constexpr (L::kRobust) {
+                r[kWeightSum] = v[L::kRobustAt];
+                r[kPhotoWeightSum] = v[L::kRobustAt + 1];
+                r[kOutliers] = v[L::kRobustAt + 2];
+            }
             if (twist_final)
                 for (int i = 0; i < 6; ++i) twist_final[i] = next[i];
         }
@@ -309,28 +374,45 @@ __device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::
                          src.lambda * (g[0] * a[1] - g[1] * a[0])};
     const double r = src.lambda * rI;
     int s = 0;
+    if constexpr (SRC::kRobust) {  // w_I of the unscaled r_I on the lambda-scaled row and residual
+        bool outlier;
+        const double w = src.weight(rI, src.intensity_scale, outlier);
+        double wJ[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
+        for (int i = 0; i < 6; ++i) wJ[i] = w * J[i];
 #pragma unroll
-        for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
+        for (int i = 0; i < 6; ++i)
 #pragma unroll
-    for (int i = 0; i < 6; ++i) acc[21 + i] -= J[i] * r;
-    acc[SRC::K - 2] += 1.0;
-    acc[SRC::K - 1] += rI * rI;
+            for (int j = i; j < 6; ++j) acc[s++] += wJ[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] -= wJ[i] * r;
+        acc[SRC::Layout::kPhotoAt + 1] += (w * rI) * rI;
+        acc[SRC::Layout::kRobustAt + 1] += w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] -= J[i] * r;
+        acc[SRC::Layout::kPhotoAt + 1] += rI * rI;
+    }
+    acc[SRC::Layout::kPhotoAt] += 1.0;
     return (float)rI;
 }
 
 // the live vertex vx (camera coordinates) of the source's pixel px against the prediction at the estimate e: its
 // residual r, the pair's terms added to acc, when the pair is valid and (SRC::kGate) the live normal passes the angle
 // gate; NaN otherwise.  A pair that passes the distance test and fails the gate counts in acc[kSums].  SRC::kPhoto:
-// a pixel with a pair also gets photometric_term, its r_I into photo.
+// a pixel with a pair also gets photometric_term, its r_I into photo.  SRC::kRobust: the pair's terms are scaled by
+// its weight w, which goes into weight; a pair with w = 0 still counts.
 template <typename SRC>
 __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __restrict__ live_normals,
                                                  typename SRC::Pixel px, const double (&vx)[3],
                                                  const double (&e)[12], const double (&ep)[12], const IcpDev& p,
                                                  const float* __restrict__ pred_depth,
                                                  const float* __restrict__ pred_normals, double (&acc)[SRC::K],
-                                                 float& photo) {
+                                                 float& photo, float& weight) {
     double dv[3], g[3], q[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) dv[c] = vx[c] - e[c * 4 + 3];
@@ -380,13 +462,31 @@ __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __
     const double J[6] = {Nw[0], Nw[1], Nw[2], g[1] * Nw[2] - g[2] * Nw[1], g[2] * Nw[0] - g[0] * Nw[2],
                          g[0] * Nw[1] - g[1] * Nw[0]};
     int s = 0;
+    if constexpr (SRC::kRobust) {
+        bool outlier;
+        const double w = src.weight(r, src.scale, outlier);
+        double wJ[6];
 #pragma unroll
-    for (int a = 0; a < 6; ++a)
+        for (int a = 0; a < 6; ++a) wJ[a] = w * J[a];
 #pragma unroll
-        for (int b = a; b < 6; ++b) acc[s++] += J[a] * J[b];
+        for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
-    acc[27] += r * r;
+            for (int b = a; b < 6; ++b) acc[s++] += wJ[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] -= wJ[a] * r;
+        acc[27] += (w * r) * r;
+        acc[SRC::Layout::kRobustAt] += w;
+        acc[SRC::Layout::kRobustAt + 2] += outlier ? 1.0 : 0.0;
+        weight = (float)w;
+    } else {
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[s++] += J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
+        acc[27] += r * r;
+    }
     acc[28] += 1.0;
     if constexpr (SRC::kPhoto) photo = photometric_term(src, px, pu, pv, q, g, ep, p, acc);
     return (float)r;
@@ -404,7 +504,7 @@ __global__ __launch_bounds__(kBlock) void icp_iterate_kernel(SRC src, const type
     __shared__ double red[kBlock / kWave][K];
     __shared__ double tw[6], pose[12], pose_p[12];
 
-    icp_prologue<K>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, nullptr);
+    icp_prologue<typename SRC::Layout>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, nullptr);
     double e[12], ep[12];
     load_poses(tw, p, pose, pose_p, e, ep);
 
@@ -418,27 +518,30 @@ __global__ __launch_bounds__(kBlock) void icp_iterate_kernel(SRC src, const type
         if (i >= src.grid.ni || j >= src.grid.nj) continue;
         const auto px = src.pixel(i, j);
         const double d = src.depth(live, p, px);
-        float res = NAN, photo = NAN;
+        float res = NAN, photo = NAN, weight = NAN;
         if (d > 0.0) {  // NaN is not > 0
             double vx[3];
             src.vertex(p, px, d, vx);
-            res = accumulate_pair(src, live_normals, px, vx, e, ep, p, pred_depth, pred_normals, acc, photo);
+            res = accumulate_pair(src, live_normals, px, vx, e, ep, p, pred_depth, pred_normals, acc, photo,
+                                  weight);
         }
         if (residuals) src.store(residuals, p, px, res);  // the last iteration
         if constexpr (SRC::kPhoto)
             if (src.intensity) src.store(src.intensity, p, px, photo);
+        if constexpr (SRC::kRobust)
+            if (src.weights) src.store(src.weights, p, px, weight);
     }
     store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * K);
 }
 
-// the prologue alone, one block: the last iteration's record and the final twist.  K: the sums of the run's source
-template <int K>
+// the prologue alone, one block: the last iteration's record and the final twist.  L: the sums of the run's source
+template <typename L>
 __global__ __launch_bounds__(kBlock) void icp_finish_kernel(double* __restrict__ twist_io, double* __restrict__ records,
                                                             const double* __restrict__ scratch, int k, int prev_blocks,
                                                             int prev_level) {
-    __shared__ double red[kBlock / kWave][K];
+    __shared__ double red[kBlock / kWave][L::K];
     __shared__ double tw[6];
-    icp_prologue<K>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, twist_io);
+    icp_prologue<L>(k, prev_blocks, prev_level, twist_io, records, scratch, red, tw, twist_io);
 }
 
 // what every launch of a run shares
@@ -469,6 +572,8 @@ int launch_run(const Run& r, int levels, const int32_t* iterations, SourceOf sou
             SRC src = level;
             if constexpr (SRC::kPhoto)  // like the residuals: from the last iteration only
                 if (k != r.total - 1) src.intensity = nullptr;
+            if constexpr (SRC::kRobust)
+                if (k != r.total - 1) src.weights = nullptr;
             hipLaunchKernelGGL(icp_iterate_kernel<SRC>, dim3(blocks), dim3(kBlock), 0, r.stream, src,
                                reinterpret_cast<const typename SRC::Live*>(r.live) + src.offset,
                                r.live_normals + src.offset * 3, r.pred_depth,
@@ -479,8 +584,8 @@ int launch_run(const Run& r, int levels, const int32_t* iterations, SourceOf sou
             prev_level = l;
         }
     }
-    hipLaunchKernelGGL(icp_finish_kernel<SRC::K>, dim3(1), dim3(kBlock), 0, r.stream, r.twist, r.records, r.scratch,
-                       r.total, prev_blocks, prev_level);
+    hipLaunchKernelGGL(icp_finish_kernel<typename SRC::Layout>, dim3(1), dim3(kBlock), 0, r.stream, r.twist, r.records,
+                       r.scratch, r.total, prev_blocks, prev_level);
     return launch_status();
 }
 
@@ -722,6 +827,105 @@ extern "C" int lsf_icp_run_pyramid_photometric(const float* live_depth, const fl
                                                                    pred_intensity + level.offset,
                                                                    intensity_residuals_out, q->photometric_weight,
                                                                    q->max_intensity_difference};
+        });
+    };
+    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
+}
+
+namespace {
+
+// the checks the two robust parameter structs share: the loss, both scales, and the optional intensity term (a, b: its
+// two images, both or neither; without them lambda is 0 and there is no intensity residual image).  1 with the term,
+// 0 without, -1 refused
+template <typename Q>
+int robust_term(const Q* q, const void* a, const void* b, const float* intensity_residuals_out) {
+    if (q->loss != LSF_ICP_LOSS_HUBER && q->loss != LSF_ICP_LOSS_TUKEY) return -1;
+    if (!(q->scale > 0.0 && q->intensity_scale > 0.0)) return -1;  // NaN is not > 0
+    if ((a == nullptr) != (b == nullptr)) return -1;
+    if (!a) return q->photometric_weight == 0.0 && !intensity_residuals_out ? 0 : -1;
+    return std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0
+               ? 1 : -1;
+}
+
+template <typename BASE, typename Q>
+RobustSource<BASE> robust_of(const BASE& base, const Q* q, float* weights_out) {
+    return RobustSource<BASE>{base, q->loss, q->scale, q->intensity_scale, weights_out};
+}
+
+}  // namespace
+
+extern "C" int lsf_icp_run_robust(const void* live_depth, const uint8_t* live_colour, const float* pred_depth,
+                                  const float* pred_normals, const float* pred_colour, double* twist_inout,
+                                  double* records, void* scratch, float* residuals_out,
+                                  float* intensity_residuals_out, float* weights_out,
+                                  const lsf_icp_robust_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params) return LSF_ERR_BAD_ARGUMENT;
+    const lsf_icp_robust_params* q = params;
+    const int term = robust_term(q, live_colour, pred_colour, intensity_residuals_out);
+    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
+    const long long total = strided_total(q, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t pixels = (size_t)q->height * q->width;
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_ICP_ROBUST_SCRATCH_BYTES},
+                 {residuals_out, pixels * 4}, {intensity_residuals_out, pixels * 4}, {weights_out, pixels * 4}},
+                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {live_colour, pixels * 3}, {pred_depth, pixels * 4},
+                 {pred_normals, pixels * 12}, {pred_colour, pixels * 16}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
+                         scratch, residuals_out, total, stream);
+    return dispatch_depth(q->depth_dtype, [&](auto dt) {
+        using DT = decltype(dt);
+        auto level = [&](int l) { return StridedSource<DT>{strided_grid(q, q->strides[l]), q->strides[l]}; };
+        if (!term)
+            return launch_run(r, q->levels, q->iterations,
+                              [&](int l) { return robust_of(level(l), q, weights_out); });
+        return launch_run(r, q->levels, q->iterations, [&](int l) {
+            return robust_of(PhotometricSource<DT>{level(l), live_colour, pred_colour, intensity_residuals_out,
+                                                   q->photometric_weight, q->max_intensity_difference},
+                             q, weights_out);
+        });
+    });
+}
+
+extern "C" int lsf_icp_run_pyramid_robust(const float* live_depth, const float* live_normals,
+                                          const float* live_intensity, const float* pred_depth,
+                                          const float* pred_normals, const float* pred_intensity, double* twist_inout,
+                                          double* records, void* scratch, float* residuals_out,
+                                          float* intensity_residuals_out, float* weights_out,
+                                          const lsf_icp_pyramid_robust_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params)
+        return LSF_ERR_BAD_ARGUMENT;
+    const lsf_icp_pyramid_robust_params* q = params;
+    const int term = robust_term(q, live_intensity, pred_intensity, intensity_residuals_out);
+    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
+    const long long total = pyramid_total(q, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
+    const size_t last_bytes = last_level_pixels(q) * 4;
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
+                 {scratch, LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES}, {residuals_out, last_bytes},
+                 {intensity_residuals_out, last_bytes}, {weights_out, last_bytes}},
+                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12},
+                 {live_intensity, levels_pixels * 4}, {pred_depth, pixels * 4}, {pred_normals, pixels * 12},
+                 {pred_intensity, levels_pixels * 4}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
+                         residuals_out, total, stream);
+    auto run = [&](auto gate) {
+        constexpr bool GATE = decltype(gate)::value;
+        if (!term)
+            return launch_run(r, q->levels, q->iterations,
+                              [&](int l) { return robust_of(pyramid_level<GATE>(q, l), q, weights_out); });
+        return launch_run(r, q->levels, q->iterations, [&](int l) {
+            const PyramidSource<GATE> level = pyramid_level<GATE>(q, l);
+            return robust_of(PyramidPhotometricSource<GATE>{level, live_intensity + level.offset,
+                                                            pred_intensity + level.offset, intensity_residuals_out,
+                                                            q->photometric_weight, q->max_intensity_difference},
+                             q, weights_out);
         });
     };
     return q->angle_gate ? run(std::true_type()) : run(std::false_type());

@@ -6,14 +6,17 @@ live depth pyramid (device_depth_pyramid), with an optional normal-angle gate.  
 (lsf_icp_run_photometric) is icp_run with an intensity term against the ray-cast colour image
 (device_raycast.raycast(..., colour=)) in the same normal equations; icp_run_pyramid_photometric
 (lsf_icp_run_pyramid_photometric) is icp_run_pyramid with that term taken at each pixel's own level, between two
-intensity pyramids (device_intensity_pyramid)."""
+intensity pyramids (device_intensity_pyramid).  icp_run_robust (lsf_icp_run_robust) and icp_run_pyramid_robust
+(lsf_icp_run_pyramid_robust) are the strided and the pyramid run, with or without the photometric term, with every
+pair scaled by the Huber or Tukey weight of a rigid_opt.RobustLoss."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, IcpPhotometricParams, IcpPyramidParams, IcpPyramidPhotometricParams, lib
+from ._lib import (IcpParams, IcpPhotometricParams, IcpPyramidParams, IcpPyramidPhotometricParams,
+                   IcpPyramidRobustParams, IcpRobustParams, lib)
 from .device_core import require_gpu
 from .device_fusion import check_colour_image
 from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
@@ -247,11 +250,125 @@ def icp_run_pyramid_photometric(pyramid_depth, pyramid_normals, pyramid_intensit
                 (h >> last, w >> last) if residuals else None, pred_intensity, (pixels,))
 
 
+def robust_settings(robust):
+    """(loss code, scale, intensity_scale) of a rigid_opt.RobustLoss after the checks: a known loss, both scales > 0
+    (inf allowed)"""
+    code = getattr(robust, "code", None)
+    scale, intensity_scale = getattr(robust, "scale", None), getattr(robust, "intensity_scale", None)
+    if code not in (_lib.ICP_LOSS_HUBER, _lib.ICP_LOSS_TUKEY) or not isinstance(scale, float) or \
+            not isinstance(intensity_scale, float):
+        raise ValueError("robust must be a rigid_opt.RobustLoss, got %r" % (robust,))
+    if not (scale > 0 and intensity_scale > 0):
+        raise ValueError("the scales of a RobustLoss must be positive (inf allowed), got %r" % (robust,))
+    return code, scale, intensity_scale
+
+
+def _robust_into(p, robust, photometric_weight, max_intensity_difference):
+    """the members a robust struct has beyond its geometric twin: the loss and, with a photometric_weight, lambda and
+    its gate (without one lambda is 0 and the gate is not read)"""
+    p.loss, p.scale, p.intensity_scale = robust_settings(robust)
+    p.photometric_weight, p.max_intensity_difference = 0.0, math.inf
+    if photometric_weight is not None:
+        p.photometric_weight, p.max_intensity_difference = photometric_settings(photometric_weight,
+                                                                                max_intensity_difference)
+    return p
+
+
+def robust_params(camera, image_shape, twist_p, depth_code, robust, photometric_weight=None,
+                  max_intensity_difference=math.inf, iterations=ITERATIONS, strides=STRIDES,
+                  max_distance=MAX_DISTANCE):
+    """the lsf_icp_robust_params of a call, after the host checks; photometric_weight None: the geometric solve"""
+    p = params(camera, image_shape, twist_p, depth_code, iterations, strides, max_distance, IcpRobustParams())
+    return _robust_into(p, robust, photometric_weight, max_intensity_difference)
+
+
+def pyramid_robust_params(camera, image_shape, pyramid_levels, twist_p, robust, photometric_weight=None,
+                          max_intensity_difference=math.inf, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
+                          max_normal_angle=None):
+    """the lsf_icp_pyramid_robust_params of a call, after the host checks"""
+    p = pyramid_params(camera, image_shape, pyramid_levels, twist_p, iterations, max_distance, max_normal_angle,
+                       IcpPyramidRobustParams())
+    return _robust_into(p, robust, photometric_weight, max_intensity_difference)
+
+
+def _run_robust(entry, name, live, pred, p, twist, scratch_bytes, residual_shape, photometric):
+    """a robust run enqueued (device_rigid.enqueue_run): live and pred are the entry point's inputs in its order, None
+    for the optional ones.  Returns (twist, records, residual image, intensity residual image, weight image); the
+    images are None without residual_shape, the intensity one also without the photometric term"""
+    device = pred[0].device
+    res = intensity = weights = None
+    if residual_shape is not None:
+        res = torch.empty(residual_shape, dtype=torch.float32, device=device)
+        weights = torch.empty(residual_shape, dtype=torch.float32, device=device)
+        if photometric:
+            intensity = torch.empty(residual_shape, dtype=torch.float32, device=device)
+    out, records = enqueue_run(entry, name, live + pred, p, twist, 6, 8, RECORD, scratch_bytes,
+                               sum(p.iterations[:p.levels]), (res, intensity, weights))
+    return out, records, res, intensity, weights
+
+
+def icp_run_robust(live_depth, depth_code, pred_depth, pred_normals, camera, twist_p, robust, twist=None,
+                   iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE, live_colour=None,
+                   pred_colour=None, photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
+    """icp_run, or with live_colour, pred_colour and photometric_weight icp_run_photometric, with robust weights
+    (lsf_icp_run_robust): the same launches and one copy back.  robust: a rigid_opt.RobustLoss.  Returns (final twist,
+    records, and with residuals=True the last iteration's residual image, intensity residual image (None without the
+    photometric term) and weight image -- w where the residual is finite, NaN elsewhere -- else three Nones); the
+    records carry weight_sum, photometric_weight_sum and outliers (unpack_record)."""
+    require_gpu()
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
+        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+    h, w = (int(v) for v in live_depth.shape)
+    photometric = photometric_weight is not None
+    if (live_colour is None) == photometric or (pred_colour is None) == photometric:
+        raise ValueError("live_colour, pred_colour and photometric_weight go together")
+    p = robust_params(camera, (h, w), twist_p, depth_code, robust, photometric_weight, max_intensity_difference,
+                      iterations, strides, max_distance)
+    pred = (_prediction(pred_depth, "pred_depth", (h, w)), _prediction(pred_normals, "pred_normals", (h, w, 3)), None)
+    if photometric:
+        check_colour_image(live_colour, live_depth, (("pred_depth", pred_depth), ("pred_normals", pred_normals),
+                                                     ("pred_colour", pred_colour)))
+        pred = pred[:2] + (_prediction(pred_colour, "pred_colour", (h, w, 4)),)
+    return _run_robust(lib.lsf_icp_run_robust, "lsf_icp_run_robust", (live_depth, live_colour), pred, p,
+                       twist_p if twist is None else twist, _lib.ICP_ROBUST_SCRATCH_BYTES,
+                       (h, w) if residuals else None, photometric)
+
+
+def icp_run_pyramid_robust(pyramid_depth, pyramid_normals, pyramid_levels, pred_depth, pred_normals, camera, twist_p,
+                           robust, twist=None, iterations=ITERATIONS, max_distance=MAX_DISTANCE,
+                           max_normal_angle=None, pyramid_intensity=None, pred_intensity=None,
+                           photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
+    """icp_run_pyramid, or with pyramid_intensity, pred_intensity and photometric_weight
+    icp_run_pyramid_photometric, with robust weights (lsf_icp_run_pyramid_robust).  Returns icp_run_robust's five
+    values; the three images have the extents of the last iteration's level."""
+    require_gpu()
+    if not (isinstance(pred_depth, torch.Tensor) and pred_depth.dim() == 2):
+        raise ValueError("pred_depth must be an (H, W) device tensor (device_raycast.raycast)")
+    h, w = (int(v) for v in pred_depth.shape)
+    photometric = photometric_weight is not None
+    if (pyramid_intensity is None) == photometric or (pred_intensity is None) == photometric:
+        raise ValueError("pyramid_intensity, pred_intensity and photometric_weight go together")
+    p = pyramid_robust_params(camera, (h, w), pyramid_levels, twist_p, robust, photometric_weight,
+                              max_intensity_difference, iterations, max_distance, max_normal_angle)
+    pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
+    live = (_prediction(pyramid_depth, "pyramid_depth", (pixels,)),
+            _prediction(pyramid_normals, "pyramid_normals", (pixels, 3)),
+            _prediction(pyramid_intensity, "pyramid_intensity", (pixels,)) if photometric else None)
+    pred = (_prediction(pred_depth, "pred_depth", (h, w)), _prediction(pred_normals, "pred_normals", (h, w, 3)),
+            _prediction(pred_intensity, "pred_intensity", (pixels,)) if photometric else None)
+    last = last_level(p.iterations[:p.levels])
+    return _run_robust(lib.lsf_icp_run_pyramid_robust, "lsf_icp_run_pyramid_robust", live, pred, p,
+                       twist_p if twist is None else twist, _lib.ICP_PYRAMID_ROBUST_SCRATCH_BYTES,
+                       (h >> last, w >> last) if residuals else None, photometric)
+
+
 def unpack_record(r):
     """one host record as a dict: the layout of include/lsf_hip.h (LSF_ICP_RECORD_DOUBLES); angle_rejected is 0 on
     every lsf_icp_run record, photometric_count and photometric_energy are 0 on every record that is not
-    lsf_icp_run_photometric's or lsf_icp_run_pyramid_photometric's"""
+    lsf_icp_run_photometric's or lsf_icp_run_pyramid_photometric's; weight_sum, photometric_weight_sum and outliers
+    are 0 on every record that is not lsf_icp_run_robust's or lsf_icp_run_pyramid_robust's"""
     return {"delta": r[0:6].reshape(6, 1).copy(), "twist": r[6:12].reshape(6, 1).copy(), "energy": float(r[12]),
             "matrix_a": r[13:49].reshape(6, 6).copy(), "vector_b": r[49:55].reshape(6, 1).copy(),
             "skipped": int(r[55]), "count": int(r[56]), "level": int(r[57]), "angle_rejected": int(r[58]),
-            "photometric_count": int(r[59]), "photometric_energy": float(r[60])}
+            "photometric_count": int(r[59]), "photometric_energy": float(r[60]), "weight_sum": float(r[61]),
+            "photometric_weight_sum": float(r[62]), "outliers": int(r[63])}

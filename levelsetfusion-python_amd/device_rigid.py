@@ -51,7 +51,7 @@ def twist6(twist):
 def enqueue_run(entry, name, inputs, p, twist, n, head, record, scratch_bytes, iterations, outputs=()):
     """a whole tracker run enqueued by `entry` (lsf_rigid_run / lsf_rigid3d_run / lsf_icp_run / lsf_icp_run_pyramid):
     iterations + 1 launches into one buffer [twist (n)][pad to head][records (iterations x record)], and one copy back.
-    inputs: the device tensors the entry point reads, in its order; outputs: what it takes after the scratch buffer
+    inputs: the device tensors the entry point reads, in its order (None after the first for an optional one); outputs: what it takes after the scratch buffer
     (device tensors, or None for a NULL).  Returns (final twist float64 (n,), records float64 (iterations, record))."""
     device = inputs[0].device
     out = torch.zeros(head + iterations * record, dtype=torch.float64, device=device)
@@ -59,7 +59,7 @@ def enqueue_run(entry, name, inputs, p, twist, n, head, record, scratch_bytes, i
         out[:n] = torch.from_numpy(twist_n(twist, n).copy())
     scratch = torch.empty(scratch_bytes // 8, dtype=torch.float64, device=device)
     base = out.data_ptr()
-    ptr = [ctypes.c_void_p(t.data_ptr()) for t in inputs]
+    ptr = [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in inputs]
     ptr += [ctypes.c_void_p(base), ctypes.c_void_p(base + head * 8), ctypes.c_void_p(scratch.data_ptr())]
     ptr += [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in outputs]
     check(entry(*ptr, ctypes.byref(p), stream_ptr()), name)

@@ -81,6 +81,13 @@ its intensity term at level L of both with that level's intrinsics; `icp_max_nor
 pairs.  Without an `icp_intensity_pyramid` the combination is refused, since then there is no intensity pyramid to
 take the term from.  Fusion still integrates the raw depth, `confidence` still shares the tracker's depth pyramid and
 `prediction_colour` is kept.
+With `icp_robust` (a rigid_opt.RobustLoss; tracking_reference="icp" only) the tracker's solve, in any of the
+configurations above, is iteratively reweighted ("Robust ICP"; device_icp.icp_run_robust and
+icp_run_pyramid_robust; tests/robust_icp_restatement.py restates it): every pair's rows are scaled by the Huber or
+Tukey weight of its own residual at the current twist, so a part of the scene that moves against the rest -- whose
+pairs sit inside the distance gate -- does not drag the pose the non-rigid step then has to undo.  The ICP records carry
+weight_sum, photometric_weight_sum and outliers.  The scale has no default: none is right across sensors.  Fusion
+itself is unchanged.
 With a `nonrigid_optimizer` that is a HierarchicalOptimizer3d, every frame k >= 1 is fused through its warp field
 ("Warped depth fusion"; tests/warped_fusion_restatement.py restates it).  After tracking, the
 live volume under the twist is generated (device_rigid.live_volume_3d), `psi = optimizer.optimize(model.tsdf, live)` is
@@ -127,7 +134,9 @@ Not covered: carving, weights or colour in volume mode, a cumulative warp out of
 limit, keeping the warp field between frames as a warm start, ray-casting or meshing in the live frame, a whole frame
 enqueued without host synchronisations, z-slab / multi-GPU fusion, a 2-D depth-mode row generator, fusing the filtered
 depth, a downsampled prediction depth and normal pyramid (every level still pairs into the full-resolution
-prediction), robust ICP weights (Huber / Tukey) on either term, smoothing the intensity before level 0, ICP combined
+prediction), for the robust ICP weights a scale estimated from the residuals (MAD or the previous iteration's RMS),
+the weight image used as `pixel_weight` in fusion and robust weights in the SDF-2-SDF trackers, smoothing the intensity
+before level 0, ICP combined
 with SDF-2-SDF, an adaptive ray-casting step, a confidence image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
@@ -337,14 +346,17 @@ class SequenceFusion3d:
     field, a float32 (Z, Y, X, 3) device tensor; None before frame 1).  In "icp" mode rigid_records holds the ICP
     records (device_icp.unpack_record); with photometric_weight they carry photometric_count and photometric_energy,
     and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image; with icp_intensity_pyramid the
-    joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids)."""
+    joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids); with
+    icp_robust the solve is reweighted by that RobustLoss and the records carry weight_sum, photometric_weight_sum
+    and outliers."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
                  initial_twist=None, tracking_reference="model", icp_iterations=device_icp.ITERATIONS,
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
-                 photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None):
+                 photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None,
+                 icp_robust=None):
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
@@ -377,14 +389,17 @@ class SequenceFusion3d:
             if icp_pyramid is not None and icp_intensity_pyramid is None:
                 raise ValueError("photometric_weight does not combine with an icp_pyramid: there is no intensity "
                                  "pyramid")
+        if icp_robust is not None and tracking_reference != "icp":
+            raise ValueError("icp_robust needs tracking_reference=\"icp\": the SDF-2-SDF trackers have no robust "
+                             "weights")
         # the "icp" tracker; its arguments are checked in every mode
         t = self.icp = ProjectiveIcp3d(camera, icp_iterations, icp_strides, icp_max_distance, icp_pyramid,
                                        icp_max_normal_angle, photometric_weight, icp_max_intensity_difference,
-                                       icp_intensity_pyramid)
+                                       icp_intensity_pyramid, icp_robust)
         self.photometric_weight, self.icp_max_intensity_difference = t.photometric_weight, t.max_intensity_difference
         self.icp_iterations, self.icp_strides, self.icp_max_distance = t.iterations, t.strides, t.max_distance
         self.icp_pyramid, self.icp_max_normal_angle = t.pyramid, t.max_normal_angle
-        self.icp_intensity_pyramid = t.intensity_pyramid
+        self.icp_intensity_pyramid, self.icp_robust = t.intensity_pyramid, t.robust
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)

@@ -31,7 +31,15 @@ restates it): track builds an intensity pyramid of the frame's colour image and 
 of level L with a geometric pair takes its intensity term at level L of both, with that level's intrinsics.
 max_normal_angle still applies.  The two pyramids of the last call stay as `last_intensity_pyramids` (live,
 prediction).  A pyramid with photometric_weight and without an intensity_pyramid is refused: there is no intensity
-pyramid to take the term from."""
+pyramid to take the term from.
+
+With robust (a RobustLoss) every configuration above becomes an iteratively reweighted solve (INTEGRATION.md section 3,
+"Robust ICP"; tests/robust_icp_restatement.py restates it): each pair's rows are scaled by the Huber or Tukey weight of
+its own residual at the current twist, the geometric term by `scale`, the photometric one by `intensity_scale`.  A part
+of the scene that moves against the rest sits inside the distance gate and drags a least-squares pose; a Tukey weight
+takes it out of the solve.  The gates stay in front of the weights, a pair with weight 0 still counts, and the records
+carry weight_sum, photometric_weight_sum and outliers; `last_weights` keeps the geometric weight image beside
+`last_residuals`.  The scale has no default: none is right across sensors."""
 import math
 
 import numpy as np
@@ -42,6 +50,7 @@ from ..device_core import require_gpu
 from ..device_rigid import twist6
 from .depth_pyramid import DepthPyramid
 from .intensity_pyramid import IntensityPyramid
+from .robust_loss import RobustLoss
 from ..tsdf.generation import device_depth
 
 __all__ = ["ProjectiveIcp3d"]
@@ -59,12 +68,13 @@ def _prediction(x, trailing):
 class ProjectiveIcp3d:
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
                  max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None, photometric_weight=None,
-                 max_intensity_difference=math.inf, intensity_pyramid=None):
+                 max_intensity_difference=math.inf, intensity_pyramid=None, robust=None):
         """pyramid: None (the strided live image) or a DepthPyramid, with which strides is not used and iterations has
         one entry per tracked level, at most pyramid.levels; max_normal_angle: the gate in radians (pyramid only);
         photometric_weight: None (geometric only) or lambda, finite and > 0 (with a pyramid it needs an
         intensity_pyramid); max_intensity_difference: the gate on |r_I|, > 0; intensity_pyramid: None or an
-        IntensityPyramid of pyramid.levels levels, which needs both a pyramid and a photometric_weight"""
+        IntensityPyramid of pyramid.levels levels, which needs both a pyramid and a photometric_weight; robust: None
+        (least squares) or a RobustLoss, with any of the above"""
         self.camera = camera
         if pyramid is not None and not isinstance(pyramid, DepthPyramid):
             raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
@@ -98,8 +108,12 @@ class ProjectiveIcp3d:
             if pyramid is not None and intensity_pyramid is None:
                 raise ValueError("photometric_weight needs the strided path: there is no intensity pyramid")
             self.photometric_weight, _ = device_icp.photometric_settings(photometric_weight)
+        if robust is not None and not isinstance(robust, RobustLoss):
+            raise ValueError("robust must be a rigid_opt.RobustLoss or None, got %r" % (robust,))
+        self.robust = robust
         self.last_records = []
         self.last_residuals = None
+        self.last_weights = None  # the geometric weight image of the last robust call with residuals=True
         self.last_intensity_residuals = None
         self.last_pyramid = None
         self.last_intensity_pyramids = None  # (live, prediction) IntensityLevels of the last joint pyramid call
@@ -114,6 +128,9 @@ class ProjectiveIcp3d:
                 (colour_image is None) != (prediction_colour is None):
             raise ValueError("colour_image and prediction_colour go with a tracker made with photometric_weight, and "
                              "only with one")
+        if self.robust is not None:
+            return self._track_robust(depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals,
+                                      colour_image, prediction_colour)
         if self.intensity_pyramid is not None:
             self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
             live, pred = self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
@@ -136,6 +153,27 @@ class ProjectiveIcp3d:
             out, records, res = device_icp.icp_run_pyramid(
                 *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
                 twist_p, twist, self.iterations, self.max_distance, self.max_normal_angle, residuals)
+        return out, [device_icp.unpack_record(r) for r in records], res
+
+    def _track_robust(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals,
+                      colour_image, prediction_colour):
+        """track() through the robust entry points: the same four configurations"""
+        if self.pyramid is None:
+            out, records, res, self.last_intensity_residuals, self.last_weights = device_icp.icp_run_robust(
+                depth, code, prediction_depth, prediction_normals, self.camera, twist_p, self.robust, twist,
+                self.iterations, self.strides, self.max_distance, colour_image, prediction_colour,
+                self.photometric_weight, self.max_intensity_difference, residuals)
+        else:
+            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
+            live = pred = None
+            if self.intensity_pyramid is not None:
+                live, pred = self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
+                                                             self.intensity_pyramid.build_prediction(prediction_colour))
+                live, pred = live.buffer, pred.buffer
+            out, records, res, self.last_intensity_residuals, self.last_weights = device_icp.icp_run_pyramid_robust(
+                *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
+                twist_p, self.robust, twist, self.iterations, self.max_distance, self.max_normal_angle, live, pred,
+                self.photometric_weight, self.max_intensity_difference, residuals)
         return out, [device_icp.unpack_record(r) for r in records], res
 
     def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
