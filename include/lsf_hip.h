@@ -1230,7 +1230,8 @@ typedef struct lsf_icp_params {
  *   lsf_icp_run)   [59] photometric pair count   [60] photometric energy, sum r_I^2 (lsf_icp_run_photometric; 0 from
  *   the other two; lsf_icp_run_pyramid_photometric writes 58, 59 and 60)   [61] sum of the geometric weights w
  *   [62] sum of the photometric weights w_I   [63] geometric outliers (lsf_icp_run_robust and
- *   lsf_icp_run_pyramid_robust; 0 from the other four) */
+ *   lsf_icp_run_pyramid_robust; 0 from the other four).  lsf_point_sdf_run writes the same record: [58] its pixels
+ *   with a depth and no valid sample, [61] and [63] with a loss */
 #define LSF_ICP_RECORD_DOUBLES 64
 /* the launches of lsf_icp_run use at most LSF_ICP_MAX_BLOCKS workgroups; scratch holds two ping-pong buffers of 29
  * float64 partial sums per workgroup (21 of A's upper triangle, 6 of b, energy, count) */
@@ -1486,6 +1487,55 @@ int lsf_icp_run_pyramid_robust(const float *live_depth, const float *live_normal
                                double *twist_inout, double *records, void *scratch, float *residuals_out,
                                float *intensity_residuals_out, float *weights_out,
                                const lsf_icp_pyramid_robust_params *params, void *stream);
+
+/* ---- point-to-SDF tracking: the live points against the canonical TSDF itself ------------------------------------------
+ * The tracker of Bylow et al. (RSS 2013); the reference has none, the arithmetic is this project's (INTEGRATION.md
+ * section 3, "Point-to-SDF tracking"), every step one float64 operation.  The estimate, the live vertex v, the world
+ * point g = R^T (v - xi_t), the strided levels, the schedule, the solve and the composed update are lsf_icp_run's.
+ * There is no prediction: g is taken to voxel coordinates p_j = g_j / voxel_size - offset_j (lsf_raycast's convention)
+ * and the model is sampled there exactly as lsf_raycast samples it -- valid only for p_j in [0, n_j - 1) on every axis
+ * and all 8 corner weights > 0 (read first), phi lerped x, then y, then z.  The same 8 corners t0 .. t7 (x fastest)
+ * give the gradient in voxel units,
+ *   d_x = ((t1 - t0) hy + (t3 - t2) fy) hz + ((t5 - t4) hy + (t7 - t6) fy) fz
+ *   d_y = (c01 - c00) hz + (c11 - c10) fz        d_z = c1 - c0
+ * with the sample's f, h = 1 - f and its intermediate lerps c00 .. c11, c0, c1.  With mu = narrow_band_width_voxels *
+ * voxel_size: r = mu phi, grad_j = (mu d_j) / voxel_size.  A pixel is a pair when its depth is > 0, the sample is
+ * valid, |r| <= max_distance and grad != 0; J = (grad, g x grad), A += J J^T, b -= J r, energy += r^2.  With a loss
+ * (LSF_ICP_LOSS_HUBER / _TUKEY) a pair's rows are scaled by w(r) as in lsf_icp_run_robust; an infinite scale gives
+ * the loss-free call bit for bit.  Records: lsf_icp_run's LSF_ICP_RECORD_DOUBLES and slots; [58] counts the pixels that
+ * had a depth but no valid sample, [61] and [63] are sum w and the outliers with a loss, every other slot past 57 is
+ * 0.  One lane per strided live pixel, a wave per 8 x 8 block of them (its 16 gathers per pixel share cache lines), a
+ * grid-stride loop over at most LSF_ICP_MAX_BLOCKS workgroups. */
+#define LSF_POINT_SDF_LOSS_NONE 0
+typedef struct lsf_point_sdf_params {
+    double fx, fy, cx, cy;             /* intrinsics, pixels; finite, fx and fy non-zero */
+    double depth_unit_ratio;           /* metres per unit of the live depth image, finite */
+    double max_distance;               /* metres, > 0 (inf allowed): the gate on |r| */
+    double voxel_size;                 /* metres, finite and > 0 */
+    double offset_x, offset_y, offset_z; /* array offset, voxels, finite, fractional allowed */
+    double narrow_band_width_voxels;   /* the truncation distance in voxels, finite and > 0 */
+    double scale;                      /* of r, metres, > 0 (inf allowed); not read without a loss */
+    int32_t depth, height, width;      /* volume extents z, y, x, >= 2 each */
+    int32_t image_height, image_width; /* live image extents, >= 1 each, at most 2^31 - 1 pixels */
+    int32_t depth_dtype;               /* LSF_DEPTH_* of the live depth image */
+    int32_t levels;                    /* 1 .. LSF_ICP_MAX_LEVELS */
+    int32_t iterations[LSF_ICP_MAX_LEVELS]; /* per level, coarse first, >= 0 */
+    int32_t strides[LSF_ICP_MAX_LEVELS];    /* per level, >= 1 */
+    int32_t loss;                      /* LSF_POINT_SDF_LOSS_NONE, LSF_ICP_LOSS_HUBER or LSF_ICP_LOSS_TUKEY */
+} lsf_point_sdf_params;
+/* at most 33 partial sums per workgroup: lsf_icp_run's 29, the pixels without a valid sample, sum w, (sum w_I, not
+ * used,) the outliers */
+#define LSF_POINT_SDF_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 33 * 8)
+
+/* tsdf, weight: DEVICE float32 [depth][height][width], two distinct buffers, read only.  live_depth, twist_inout,
+ * records: as lsf_icp_run; scratch: DEVICE, LSF_POINT_SDF_SCRATCH_BYTES; residuals_out: NULL, or DEVICE float32
+ * [image_height][image_width] that receives the last iteration's r, NaN where a pixel has no pair (or is not on the
+ * last level's stride); weights_out: NULL, or (with a loss only) DEVICE float32 of the same extents, w where
+ * residuals_out has r.  sum(iterations) + 1 launches back to back, none when sum(iterations) == 0; no float atomics,
+ * no host wait, a rerun is bit-identical.  No output may alias an input or another output. */
+int lsf_point_sdf_run(const float *tsdf, const float *weight, const void *live_depth, double *twist_inout,
+                      double *records, void *scratch, float *residuals_out, float *weights_out,
+                      const lsf_point_sdf_params *params, void *stream);
 
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):

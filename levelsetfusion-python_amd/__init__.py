@@ -4,7 +4,8 @@ Drop-in for the numpy path of Algomorph/LevelSetFusion-Python's warp-field gradi
     SlavchevaOptimizer2d(...).optimize(live_field, canonical_field)
     HierarchicalOptimizer2d(...).optimize(canonical_field, live_field)
 plus their 3-D generalisations, the SDF-2-SDF rigid 2-D tracker rigid_opt.Sdf2SdfOptimizer2d and its 6-DoF 3-D
-form rigid_opt.Sdf2SdfOptimizer3d, the point-to-plane ICP tracker rigid_opt.ProjectiveIcp3d, and
+form rigid_opt.Sdf2SdfOptimizer3d, the point-to-plane ICP tracker rigid_opt.ProjectiveIcp3d, the point-to-SDF tracker
+rigid_opt.PointToSdf3d, and
 fusion.SequenceFusion3d, which tracks a depth sequence against a weighted canonical TSDF (fusion.CanonicalVolume) and fuses every frame into it; the model's surface comes out as a triangle mesh
 (CanonicalVolume.extract_mesh, written by mesh_io.write_ply).  Host code is Python; device buffers are
 PyTorch-ROCm tensors; every per-voxel operation is a hand-written HIP kernel (gfx950) behind the C ABI in include/lsf_hip.h.  There is no CPU
@@ -30,11 +31,13 @@ from .rigid_opt import (sdf_2_sdf_optimizer2d, sdf_2_sdf_optimizer3d, sdf_2_sdf_
 from .rigid_opt.sdf_2_sdf_optimizer2d import Sdf2SdfOptimizer2d
 from .rigid_opt.sdf_2_sdf_optimizer3d import Sdf2SdfOptimizer3d
 from .rigid_opt.projective_icp3d import ProjectiveIcp3d
+from .rigid_opt.point_to_sdf3d import PointToSdf3d
 from . import fusion, mesh_io
 from .fusion import CanonicalVolume, DepthConfidence, SequenceFusion3d
 
 __all__ = ["HierarchicalOptimizer2d", "HierarchicalOptimizer3d", "SlavchevaOptimizer2d", "SlavchevaOptimizer3d",
            "ComputeMethod", "AdaptiveLearningRateMethod", "DataTermMethod", "SmoothingTermMethod",
            "generate_1d_sobolev_kernel", "data_term", "smoothing_term", "level_set_term", "rigid_opt",
-           "transformation", "Sdf2SdfOptimizer2d", "Sdf2SdfOptimizer3d", "ProjectiveIcp3d", "fusion", "CanonicalVolume",
+           "transformation", "Sdf2SdfOptimizer2d", "Sdf2SdfOptimizer3d", "ProjectiveIcp3d", "PointToSdf3d", "fusion",
+           "CanonicalVolume",
            "SequenceFusion3d", "DepthConfidence", "mesh_io"]

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "8a5ce59b8dece352"
+HEADER_ABI_HASH = "7203c09dd7362540"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -341,6 +341,21 @@ class IcpPyramidRobustParams(ctypes.Structure):
     _fields_ = IcpPyramidPhotometricParams._fields_ + _ROBUST_FIELDS
 
 
+POINT_SDF_LOSS_NONE = 0
+POINT_SDF_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 33 * 8
+
+
+class PointSdfParams(ctypes.Structure):
+    """lsf_point_sdf_params: point-to-SDF tracking of a live depth frame against the canonical TSDF (lsf_point_sdf_run)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_unit_ratio", "max_distance", "voxel_size",
+                                               "offset_x", "offset_y", "offset_z", "narrow_band_width_voxels",
+                                               "scale")] + \
+               [(n, ctypes.c_int32) for n in ("depth", "height", "width", "image_height", "image_width", "depth_dtype",
+                                              "levels")] + \
+               [("iterations", ctypes.c_int32 * ICP_MAX_LEVELS), ("strides", ctypes.c_int32 * ICP_MAX_LEVELS),
+                ("loss", ctypes.c_int32)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -479,6 +494,7 @@ PROTOTYPES = {
                                           _vp]),
     "lsf_icp_run_pyramid_robust": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _P(IcpPyramidRobustParams), _vp]),
+    "lsf_point_sdf_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PointSdfParams), _vp]),
 }
 
 

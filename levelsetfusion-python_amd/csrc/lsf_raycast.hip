@@ -10,6 +10,7 @@
 // lsf_raycast_colour is the same kernel with COLOUR set: after the march a hit pixel also samples the model's colour
 // records at its hit point ("Ray-cast colour"), the 8 colour weights first.
 #include "lsf_device.h"
+#include "lsf_tsdf_sample.h"
 #include "lsf_tsdf_typed.h"
 
 using namespace lsf;
@@ -28,44 +29,6 @@ struct RayDev {
     int height, width;
     long long max_steps;    // a defensive bound on a ray's steps, above what any ray through the box takes
 };
-
-struct Volume {
-    const float* __restrict__ tsdf;
-    const float* __restrict__ weight;
-    int nx, ny, nz;
-};
-
-// the trilinear sample at voxel coordinates g; false when g is outside [0, n - 1) on an axis or a corner weight is
-// not > 0
-__device__ inline bool sample(const Volume& vol, double gx, double gy, double gz, double& value) {
-    if (!(gx >= 0.0 && gx < (double)(vol.nx - 1) && gy >= 0.0 && gy < (double)(vol.ny - 1) && gz >= 0.0 &&
-          gz < (double)(vol.nz - 1)))
-        return false;
-    const int x0 = (int)floor(gx), y0 = (int)floor(gy), z0 = (int)floor(gz);
-    const long long sx = 1, sy = vol.nx, sz = (long long)vol.nx * vol.ny;
-    const long long i = (long long)z0 * sz + (long long)y0 * sy + x0;
-    const long long c[8] = {i, i + sx, i + sy, i + sy + sx, i + sz, i + sz + sx, i + sz + sy, i + sz + sy + sx};
-    float w[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) w[q] = vol.weight[c[q]];
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) ok = ok && w[q] > 0.0f;  // NaN is not > 0
-    if (!ok) return false;
-    float t[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t[q] = vol.tsdf[c[q]];
-    const double fx = gx - (double)x0, fy = gy - (double)y0, fz = gz - (double)z0;
-    const double hx = 1.0 - fx, hy = 1.0 - fy, hz = 1.0 - fz;
-    const double c00 = (double)t[0] * hx + (double)t[1] * fx;  // z0 y0
-    const double c01 = (double)t[2] * hx + (double)t[3] * fx;  // z0 y1
-    const double c10 = (double)t[4] * hx + (double)t[5] * fx;  // z1 y0
-    const double c11 = (double)t[6] * hx + (double)t[7] * fx;  // z1 y1
-    const double c0 = c00 * hy + c01 * fy;
-    const double c1 = c10 * hy + c11 * fy;
-    value = c0 * hz + c1 * fz;
-    return true;
-}
 
 // the trilinear sample of R, G, B (records of 4 floats, the colour weight last) at voxel coordinates g, in sample()'s
 // order per channel; false when a corner lies outside the volume or a colour weight is not > 0

@@ -56,6 +56,13 @@ by ICP against the model's prediction:
                `icp_pyramid` (a rigid_opt.DepthPyramid) the frame's filtered depth pyramid is built on the device and
                `icp_iterations` runs over its levels (device_icp.icp_run_pyramid), `icp_strides` not used;
                `icp_max_normal_angle` (radians) adds the normal-angle gate.  Fusion still integrates the raw depth.
+    "sdf"      point-to-SDF tracking (rigid_opt.PointToSdf3d, device_point_sdf.point_sdf_run; INTEGRATION.md section 3,
+               "Point-to-SDF tracking"; tests/point_sdf_restatement.py restates it) of the frame's points against the
+               model's tsdf and weight themselves: no prediction is ray-cast, `prediction_hits` is None, and
+               `sdf_tracker` (a PointToSdf3d, PointToSdf3d(camera) by default) sets the levels, the gate and the
+               loss.  `rigid_iterations` and the `icp_*` settings are not used, and `photometric_weight`,
+               `icp_robust`, `icp_pyramid`, `icp_max_normal_angle` and `icp_intensity_pyramid` are refused: they belong
+               to the "icp" tracker, which has a prediction image to pair into.
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
 With `carve` or `confidence` (a DepthConfidence) every frame, frame 0 included, is fused by the weighted rule; the
 confidence image comes from the frame's own pyramid -- the tracker's, built once, when "icp" mode has an `icp_pyramid`
@@ -137,7 +144,9 @@ depth, a downsampled prediction depth and normal pyramid (every level still pair
 prediction), for the robust ICP weights a scale estimated from the residuals (MAD or the previous iteration's RMS),
 the weight image used as `pixel_weight` in fusion and robust weights in the SDF-2-SDF trackers, smoothing the intensity
 before level 0, ICP combined
-with SDF-2-SDF, an adaptive ray-casting step, a confidence image in the prediction, a colour image of another
+with SDF-2-SDF, for the "sdf" tracker a depth pyramid or filtered depth as the point source, a colour term against the
+colour volume, a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casting step, a confidence
+image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
 import math
@@ -152,6 +161,7 @@ from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_
 from ..nonrigid_opt.hierarchical.hierarchical_optimizer3d import HierarchicalOptimizer3d
 from ..nonrigid_opt.slavcheva.slavcheva_optimizer3d import SlavchevaOptimizer3d
 from ..rigid_opt.depth_pyramid import DepthPyramid
+from ..rigid_opt.point_to_sdf3d import PointToSdf3d
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
@@ -160,11 +170,13 @@ from ..tsdf.generation import DepthCamera, device_depth
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
-           "TRACKING_REFERENCES", "TRACKING_MODES"]
+           "TRACKING_REFERENCES", "TRACKING_MODES", "DIRECT_TRACKING_MODES"]
 
-# the trackers with a reference volume (rigid_run_3d), and every tracking mode SequenceFusion3d accepts
+# the trackers with a reference volume (rigid_run_3d), with them the one that tracks against a prediction image, and
+# the ones that read the model directly; SequenceFusion3d accepts the union
 TRACKING_REFERENCES = ("model", "raycast")
 TRACKING_MODES = TRACKING_REFERENCES + ("icp",)
+DIRECT_TRACKING_MODES = ("sdf",)
 
 
 def _model_shape(shape):
@@ -337,8 +349,9 @@ class CanonicalVolume:
 
 class SequenceFusion3d:
     """track each depth frame against the model (tracking_reference "model"), the live volume of its ray-cast
-    prediction ("raycast") or, by point-to-plane ICP, the prediction's depth and normals ("icp"), and fuse it (module
-    docstring).  Keeps `canonical` (the CanonicalVolume), `twists` (one float64 (6,) per frame),
+    prediction ("raycast"), by point-to-plane ICP the prediction's depth and normals ("icp") or, point to signed
+    distance, the model's tsdf and weight ("sdf"), and fuse it (module docstring).  Keeps `canonical` (the
+    CanonicalVolume), `twists` (one float64 (6,) per frame),
     `frame_records` (one dict per frame: frame, twist, rigid_records, nonrigid, fusion, prediction_hits -- the pixels
     of the prediction that hit the model, None without a prediction), in "raycast" and "icp" mode `prediction`
     (the last predicted depth image, a float32 device tensor in metres) and, with a HierarchicalOptimizer3d as the
@@ -348,7 +361,7 @@ class SequenceFusion3d:
     and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image; with icp_intensity_pyramid the
     joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids); with
     icp_robust the solve is reweighted by that RobustLoss and the records carry weight_sum, photometric_weight_sum
-    and outliers."""
+    and outliers.  In "sdf" mode rigid_records holds `sdf_tracker`'s records, in the same layout."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
@@ -356,7 +369,7 @@ class SequenceFusion3d:
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
                  photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None,
-                 icp_robust=None):
+                 icp_robust=None, sdf_tracker=None):
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
@@ -381,8 +394,21 @@ class SequenceFusion3d:
             raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
         if int(rigid_iterations) < 0:
             raise ValueError("rigid_iterations must be >= 0")
-        if tracking_reference not in TRACKING_MODES:
-            raise ValueError("tracking_reference must be one of %s, got %r" % (TRACKING_MODES, tracking_reference))
+        modes = TRACKING_MODES + DIRECT_TRACKING_MODES
+        if tracking_reference not in modes:
+            raise ValueError("tracking_reference must be one of %s, got %r" % (modes, tracking_reference))
+        if tracking_reference in DIRECT_TRACKING_MODES:
+            for name, value in (("photometric_weight", photometric_weight), ("icp_robust", icp_robust),
+                                ("icp_pyramid", icp_pyramid), ("icp_max_normal_angle", icp_max_normal_angle),
+                                ("icp_intensity_pyramid", icp_intensity_pyramid)):
+                if value is not None:
+                    raise ValueError("%s belongs to the \"icp\" tracker, which pairs into a prediction image; "
+                                     "tracking_reference=%r reads the model itself (a loss goes on the sdf_tracker: "
+                                     "PointToSdf3d(robust=))" % (name, tracking_reference))
+            if sdf_tracker is not None and not isinstance(sdf_tracker, PointToSdf3d):
+                raise ValueError("sdf_tracker must be a rigid_opt.PointToSdf3d or None, got %r" % (sdf_tracker,))
+        elif sdf_tracker is not None:
+            raise ValueError("sdf_tracker needs tracking_reference=\"sdf\"")
         if photometric_weight is not None:
             if not self.colour or tracking_reference != "icp":
                 raise ValueError("photometric_weight needs colour=True and tracking_reference=\"icp\"")
@@ -400,6 +426,9 @@ class SequenceFusion3d:
         self.icp_iterations, self.icp_strides, self.icp_max_distance = t.iterations, t.strides, t.max_distance
         self.icp_pyramid, self.icp_max_normal_angle = t.pyramid, t.max_normal_angle
         self.icp_intensity_pyramid, self.icp_robust = t.intensity_pyramid, t.robust
+        self.sdf_tracker = None
+        if tracking_reference in DIRECT_TRACKING_MODES:
+            self.sdf_tracker = PointToSdf3d(camera) if sdf_tracker is None else sdf_tracker
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -482,6 +511,10 @@ class SequenceFusion3d:
                     twist, rigid_records, hits = self._track_icp(
                         depth, code, twist, None if self.photometric_weight is None else colour_image)
                     tracked = True
+            elif self.tracking_reference == "sdf":
+                if sum(self.sdf_tracker.iterations) > 0:
+                    twist, rigid_records, _ = self.sdf_tracker.track(
+                        depth, code, model.tsdf, model.weight, self.array_offset, twist, **gen)
             elif self.rigid_iterations > 0:
                 reference = model.tsdf
                 if self.tracking_reference == "raycast":
