@@ -1537,6 +1537,98 @@ int lsf_point_sdf_run(const float *tsdf, const float *weight, const void *live_d
                       double *records, void *scratch, float *residuals_out, float *weights_out,
                       const lsf_point_sdf_params *params, void *stream);
 
+/* ---- point-to-SDF tracking with a colour term against the colour volume, strided and on the depth pyramid --------------
+ * INTEGRATION.md section 3 ("Point-to-SDF tracking", "The colour term" and "The pyramid source").  The geometric pair is
+ * lsf_point_sdf_run's, unchanged.  A pixel with a geometric pair also gets a colour term at the same voxel coordinates
+ * p, hence the same cell and fractions f, h: the 8 corner records (R, G, B, W) of the colour volume (x fastest, then y,
+ * then z; one 16-byte load each) must all have W > 0; y_k = ((0.299 R_k + 0.587 G_k) + 0.114 B_k) / 255 in float64;
+ * Y and dY are the formulas of phi and d above on the corner values y_k.  r_I = Y - I_l, kept when
+ * |r_I| <= max_intensity_difference (NaN fails), with I_l the live pixel's own intensity: on the strided source
+ * ((0.299 R + 0.587 G) + 0.114 B) / 255 of its three bytes, unrounded, on the pyramid the pixel of its level of
+ * lsf_intensity_pyramid's output.  gI_j = dY_j / voxel_size, J_I = (gI, g x gI); lambda = photometric_weight scales
+ * first, J^ = lambda J_I, r^ = lambda r_I, then A += J^ J^^T, b -= J^ r^ into the same 27 sums.  Record slots 59 and 60
+ * are the photometric pairs and the unscaled sum r_I^2.  With a loss w_I comes from the unscaled r_I and
+ * intensity_scale, scales J^ and r^ as in lsf_icp_run_robust, (w_I r_I) r_I goes to slot 60 and sum w_I to slot 62; an
+ * infinite scale gives the loss-free run bit for bit.
+ * The pyramid source: entry k of iterations runs on level levels - 1 - k of lsf_depth_pyramid's depth output, every
+ * pixel (u, v) of it, float32 metres valid when > 0, back-projected with that level's intrinsics; from the vertex on
+ * the body is the strided one.  There is no normal-angle gate and the pyramid's normals are not read.  Record slot 57
+ * is the entry index, slot 58 still the pixels with a depth and no valid sample. */
+typedef struct lsf_point_sdf_photometric_params {
+    double fx, fy, cx, cy;             /* lsf_point_sdf_params, member for member */
+    double depth_unit_ratio;
+    double max_distance;
+    double voxel_size;
+    double offset_x, offset_y, offset_z;
+    double narrow_band_width_voxels;
+    double scale;
+    int32_t depth, height, width;
+    int32_t image_height, image_width;
+    int32_t depth_dtype;
+    int32_t levels;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    int32_t strides[LSF_ICP_MAX_LEVELS];
+    int32_t loss;
+    double photometric_weight;         /* lambda: finite and > 0 with the colour inputs, 0 without them */
+    double max_intensity_difference;   /* the gate on |r_I|, units of Y (0 .. 1): > 0 (inf allowed) */
+    double intensity_scale;            /* of r_I, units of Y, > 0 (inf allowed); not read without a loss */
+} lsf_point_sdf_photometric_params;
+/* at most 35 partial sums per workgroup: lsf_point_sdf_run's 30, the photometric pairs, sum r_I^2, sum w, sum w_I,
+ * the outliers */
+#define LSF_POINT_SDF_COLOUR_SCRATCH_BYTES (2 * LSF_ICP_MAX_BLOCKS * 35 * 8)
+
+/* lsf_point_sdf_run's arguments, and colour: NULL, or the model's DEVICE float32 [depth][height][width][4] colour
+ * volume (lsf_fusion's (R, G, B, W) records), 16-byte aligned; live_colour: NULL, or the frame's DEVICE uint8
+ * [image_height][image_width][3]; both or neither: with both NULL, photometric_weight == 0 and
+ * intensity_residuals_out NULL the call is lsf_point_sdf_run.  intensity_residuals_out: NULL, or DEVICE float32
+ * [image_height][image_width] that receives the last iteration's r_I, NaN where a pixel has no colour term.  scratch:
+ * DEVICE, LSF_POINT_SDF_COLOUR_SCRATCH_BYTES.  Refused (LSF_ERR_BAD_ARGUMENT, before any launch): what
+ * lsf_point_sdf_run refuses, one colour input without the other, a non-zero photometric_weight without both or a zero
+ * one with them, a photometric_weight that is negative or not finite, a max_intensity_difference that is NaN or <= 0,
+ * an intensity_scale that is NaN or <= 0 with a loss, a colour volume off 16-byte alignment.  sum(iterations) + 1
+ * launches, none when sum(iterations) == 0; no float atomics, no host wait, a rerun is bit-identical.  No output may
+ * alias an input or another output. */
+int lsf_point_sdf_run_photometric(const float *tsdf, const float *weight, const float *colour, const void *live_depth,
+                                  const uint8_t *live_colour, double *twist_inout, double *records, void *scratch,
+                                  float *residuals_out, float *intensity_residuals_out, float *weights_out,
+                                  const lsf_point_sdf_photometric_params *params, void *stream);
+
+typedef struct lsf_point_sdf_pyramid_params {
+    double fx, fy, cx, cy;             /* lsf_point_sdf_params, member for member; level 0's intrinsics */
+    double depth_unit_ratio;           /* not read: the pyramid is in metres */
+    double max_distance;
+    double voxel_size;
+    double offset_x, offset_y, offset_z;
+    double narrow_band_width_voxels;
+    double scale;
+    int32_t depth, height, width;
+    int32_t image_height, image_width; /* level 0's extents */
+    int32_t depth_dtype;               /* not read: the pyramid is float32 */
+    int32_t levels;                    /* tracked levels, 1 .. pyramid_levels: entry k runs on level levels - 1 - k */
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    int32_t strides[LSF_ICP_MAX_LEVELS]; /* not read */
+    int32_t loss;
+    double photometric_weight;         /* as lsf_point_sdf_photometric_params */
+    double max_intensity_difference;
+    double intensity_scale;
+    int32_t pyramid_levels;            /* levels the pyramids hold, 1 .. LSF_ICP_MAX_LEVELS, the last not empty */
+    int32_t reserved;
+} lsf_point_sdf_pyramid_params;
+
+/* lsf_point_sdf_run_photometric on the depth pyramid.  pyramid_depth: lsf_depth_pyramid's DEVICE float32 depth output
+ * for (image_height, image_width, pyramid_levels); pyramid_intensity: NULL, or lsf_intensity_pyramid's output of the
+ * frame's colour image for the same extents and levels, optional together with colour under
+ * lsf_point_sdf_run_photometric's rules.  residuals_out, intensity_residuals_out, weights_out: NULL, or DEVICE float32
+ * of the last iteration's level extents.  scratch: DEVICE, LSF_POINT_SDF_COLOUR_SCRATCH_BYTES.  Refused: what
+ * lsf_point_sdf_run_photometric refuses (the depth type, the ratio and the strides are not read), pyramid_levels
+ * outside 1 .. LSF_ICP_MAX_LEVELS, levels above pyramid_levels, a level whose extents reach 0.  sum(iterations) + 1
+ * launches, none when sum(iterations) == 0; no float atomics, no host wait, a rerun is bit-identical.  No output may
+ * alias an input or another output. */
+int lsf_point_sdf_run_pyramid(const float *tsdf, const float *weight, const float *colour, const float *pyramid_depth,
+                              const float *pyramid_intensity, double *twist_inout, double *records, void *scratch,
+                              float *residuals_out, float *intensity_residuals_out, float *weights_out,
+                              const lsf_point_sdf_pyramid_params *params, void *stream);
+
 /* ---- a triangle mesh of the canonical TSDF's level set iso ------------------------------------------------------------
  * The reference has no mesh extraction; the contract is this project's ("Mesh extraction"):
  * marching cubes over the cells whose 8 corners have weight > min_weight and a finite tsdf, with the generated case

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "7203c09dd7362540"
+HEADER_ABI_HASH = "d72dd95c04440bad"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -356,6 +356,23 @@ class PointSdfParams(ctypes.Structure):
                 ("loss", ctypes.c_int32)]
 
 
+POINT_SDF_COLOUR_SCRATCH_BYTES = 2 * ICP_MAX_BLOCKS * 35 * 8
+_POINT_SDF_COLOUR_FIELDS = [(n, ctypes.c_double) for n in ("photometric_weight", "max_intensity_difference",
+                                                           "intensity_scale")]
+
+
+class PointSdfPhotometricParams(ctypes.Structure):
+    """lsf_point_sdf_photometric_params: lsf_point_sdf_params' members, then the colour term's
+    (lsf_point_sdf_run_photometric)"""
+    _fields_ = PointSdfParams._fields_ + _POINT_SDF_COLOUR_FIELDS
+
+
+class PointSdfPyramidParams(ctypes.Structure):
+    """lsf_point_sdf_pyramid_params: lsf_point_sdf_photometric_params' members, then the levels the pyramids hold
+    (lsf_point_sdf_run_pyramid)"""
+    _fields_ = PointSdfPhotometricParams._fields_ + [("pyramid_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class EwaParams(ctypes.Structure):
     _fields_ = [("covariance_camera_space", ctypes.c_double * 9), ("squared_radius_threshold", ctypes.c_double),
                 ("intrinsic_matrix", ctypes.c_float * 9), ("method", ctypes.c_int32)]
@@ -495,6 +512,8 @@ PROTOTYPES = {
     "lsf_icp_run_pyramid_robust": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _P(IcpPyramidRobustParams), _vp]),
     "lsf_point_sdf_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PointSdfParams), _vp]),
+    "lsf_point_sdf_run_photometric": (ctypes.c_int, [_vp] * 11 + [_P(PointSdfPhotometricParams), _vp]),
+    "lsf_point_sdf_run_pyramid": (ctypes.c_int, [_vp] * 11 + [_P(PointSdfPyramidParams), _vp]),
 }
 
 

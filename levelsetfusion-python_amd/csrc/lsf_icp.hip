@@ -29,8 +29,8 @@
 //                  sum w_I and the geometric outliers (record slots 61, 62 and 63), and the weight image of the last
 //                  iteration beside the residuals
 // What this file shares with the point-to-SDF tracker (lsf_point_sdf.hip) -- the sums' layout, StridedSource,
-// RobustSource, compose, the prologue, load_poses, the finishing kernel, the schedule, the host checks -- is in
-// lsf_icp_shared.h.
+// PyramidSource, RobustSource, compose, the prologue, load_poses, the finishing kernel, the schedule, the host
+// checks -- is in lsf_icp_shared.h.
 #include <type_traits>
 
 #include "lsf_icp_shared.h"
@@ -59,36 +59,6 @@ static_assert(sizeof(lsf_icp_pyramid_photometric_params) == 152 && offsetof(lsf_
 static_assert(Sums<false, false, false>::K == kSums && Sums<true, false, false>::K == kPyrSums &&
               Sums<false, true, false>::K == kPhotoSums && Sums<true, true, false>::K == kPyrPhotoSums,
               "the four plain sources keep their sums");
-
-// lsf_icp_run_pyramid: every pixel of one pyramid level, float32 metres at live[j ni + i], normals beside them
-template <bool GATE>
-struct PyramidSource {
-    using Layout = Sums<true, false, false>;
-    static constexpr int K = Layout::K;
-    static constexpr bool kGate = GATE, kPhoto = false, kRobust = false;
-    using Live = float;
-    double fx, fy, cx, cy, cos_max;
-    long long offset;  // of the level in the live buffers: the launch passes their pointers advanced by it
-    Grid grid;
-
-    struct Pixel {
-        int i, j;
-        long long at;  // in the level's arrays
-    };
-    __device__ Pixel pixel(int i, int j) const { return {i, j, (long long)j * grid.ni + i}; }
-    __device__ double depth(const float* __restrict__ live, const IcpDev&, Pixel px) const {
-        return (double)live[px.at];
-    }
-    __device__ void vertex(const IcpDev&, Pixel px, double d, double (&vx)[3]) const {
-        vx[0] = d * (((double)px.i - cx) / fx);
-        vx[1] = d * (((double)px.j - cy) / fy);
-        vx[2] = d * 1.0;
-    }
-    __device__ const float* normal(const float* __restrict__ normals, Pixel px) const { return normals + px.at * 3; }
-    __device__ void store(float* __restrict__ residuals, const IcpDev&, Pixel px, float res) const {
-        residuals[px.at] = res;
-    }
-};
 
 // What photometric_term asks of a source with kPhoto: the image the term is taken in -- its intrinsics and extents,
 // the pixel's unrounded projection into it, the prediction's intensity at one of its pixels -- and the live pixel's own

@@ -1,6 +1,6 @@
 // What the Gauss-Newton trackers over a live depth image share (lsf_icp.hip: projective point-to-plane ICP against the
 // ray-cast prediction; lsf_point_sdf.hip: point-to-SDF against the model itself): the layout of the per-block sums and
-// of the record, the strided source, the robust weight, the composed update, the launch-boundary prologue, the
+// of the record, the strided and the pyramid source, the robust weight, the composed update, the launch-boundary prologue, the
 // finishing kernel, the launch schedule and the host checks.  Each tracker keeps its own per-pixel body.
 // Everything here has internal linkage, as it had inside lsf_icp.hip before it moved: the kernels of that file
 // compile to the code they compiled to there (profiles/point_sdf_cost.md).
@@ -85,6 +85,36 @@ struct StridedSource {
         for (int y = px.v; y < min(px.v + stride, p.height); ++y)
             for (int x = px.u; x < min(px.u + stride, p.width); ++x)
                 residuals[(long long)y * p.width + x] = (x == px.u && y == px.v) ? res : NAN;
+    }
+};
+
+// lsf_icp_run_pyramid: every pixel of one pyramid level, float32 metres at live[j ni + i], normals beside them
+template <bool GATE>
+struct PyramidSource {
+    using Layout = Sums<true, false, false>;
+    static constexpr int K = Layout::K;
+    static constexpr bool kGate = GATE, kPhoto = false, kRobust = false;
+    using Live = float;
+    double fx, fy, cx, cy, cos_max;
+    long long offset;  // of the level in the live buffers: the launch passes their pointers advanced by it
+    Grid grid;
+
+    struct Pixel {
+        int i, j;
+        long long at;  // in the level's arrays
+    };
+    __device__ Pixel pixel(int i, int j) const { return {i, j, (long long)j * grid.ni + i}; }
+    __device__ double depth(const float* __restrict__ live, const IcpDev&, Pixel px) const {
+        return (double)live[px.at];
+    }
+    __device__ void vertex(const IcpDev&, Pixel px, double d, double (&vx)[3]) const {
+        vx[0] = d * (((double)px.i - cx) / fx);
+        vx[1] = d * (((double)px.j - cy) / fy);
+        vx[2] = d * 1.0;
+    }
+    __device__ const float* normal(const float* __restrict__ normals, Pixel px) const { return normals + px.at * 3; }
+    __device__ void store(float* __restrict__ residuals, const IcpDev&, Pixel px, float res) const {
+        residuals[px.at] = res;
     }
 };
 

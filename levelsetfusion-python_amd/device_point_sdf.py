@@ -1,30 +1,36 @@
-"""Torch-facing wrapper of point-to-SDF tracking (include/lsf_hip.h: lsf_point_sdf_run).  Every pointer, dtype and
+"""Torch-facing wrappers of point-to-SDF tracking (include/lsf_hip.h: lsf_point_sdf_run, and with a colour term
+against the colour volume lsf_point_sdf_run_photometric on the strided image and lsf_point_sdf_run_pyramid on the
+depth pyramid).  Every pointer, dtype and
 element count is checked on the host before the launches; a call enqueues sum(iterations) + 1 launches with no host
 wait and copies the twist and the records back once (device_rigid.enqueue_run).  The public interfaces are
 rigid_opt.PointToSdf3d and fusion.SequenceFusion3d(tracking_reference="sdf").  The records are device_icp's
 (device_icp.unpack_record): angle_rejected holds the pixels that had a depth but no valid sample, weight_sum and
-outliers are written with a rigid_opt.RobustLoss, the photometric slots are 0."""
+outliers are written with a rigid_opt.RobustLoss, the photometric slots are 0 without a colour term."""
+import math
+
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PointSdfParams, lib
+from ._lib import PointSdfParams, PointSdfPhotometricParams, PointSdfPyramidParams, lib
 from .device_core import require_gpu
-from .device_fusion import check_model
-from .device_icp import ITERATIONS, MAX_DISTANCE, RECORD, STRIDES, levels, robust_settings, unpack_record  # noqa: F401
+from .device_fusion import check_colour_image, check_colour_volume, check_model
+from .device_icp import (ITERATIONS, MAX_DISTANCE, RECORD, STRIDES, last_level, levels,  # noqa: F401
+                         photometric_settings, pyramid_iterations, robust_settings, unpack_record)
 from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
 from .device_rigid import enqueue_run, twist6
 from .tsdf.generation import offsets_of
 
 
 def params(shape, camera, image_shape, depth_code, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
-           iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE, robust=None):
-    """the lsf_point_sdf_params of a call, after the host checks; robust: None or a rigid_opt.RobustLoss"""
+           iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE, robust=None, into=None):
+    """the lsf_point_sdf_params of a call, after the host checks; robust: None or a rigid_opt.RobustLoss (into: another
+    struct with its members to fill instead; with strides None the iterations are taken as they are, for a pyramid)"""
     shape = tuple(int(v) for v in shape)
     if len(shape) != 3 or min(shape) < 2:
         raise ValueError("point-to-SDF tracking needs a 3-D (Z, Y, X) volume of extents >= 2, got shape %s" % (shape,))
-    it, st = levels(iterations, strides)
-    p = PointSdfParams()
+    it, st = (tuple(iterations), ()) if strides is None else levels(iterations, strides)
+    p = PointSdfParams() if into is None else into
     p.fx, p.fy, p.cx, p.cy = checked_intrinsics(camera)
     p.depth_unit_ratio = checked_depth_unit_ratio(camera)
     p.max_distance = float(max_distance)
@@ -87,3 +93,141 @@ def point_sdf_run(tsdf, weight, live_depth, depth_code, camera, array_offset, tw
     out, records = enqueue_run(lib.lsf_point_sdf_run, "lsf_point_sdf_run", (tsdf, weight, live_depth), p, start, 6, 8,
                                RECORD, _lib.POINT_SDF_SCRATCH_BYTES, sum(p.iterations[:p.levels]), (res, weights))
     return out, records, res, weights
+
+
+def _colour_into(p, robust, photometric_weight, max_intensity_difference):
+    """the members the two colour structs have beyond lsf_point_sdf_params: lambda and its gate (0 and the gate alone
+    without a photometric_weight) and the loss's intensity scale"""
+    p.photometric_weight, p.max_intensity_difference = 0.0, photometric_settings(1.0, max_intensity_difference)[1]
+    if photometric_weight is not None:
+        p.photometric_weight, _ = photometric_settings(photometric_weight)
+    p.intensity_scale = math.inf if robust is None else robust_settings(robust)[2]
+    return p
+
+
+def photometric_params(shape, camera, image_shape, depth_code, array_offset, voxel_size=0.004,
+                       narrow_band_width_voxels=20, iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE,
+                       robust=None, photometric_weight=None, max_intensity_difference=math.inf):
+    """the lsf_point_sdf_photometric_params of a call, after the host checks; photometric_weight None: geometry only"""
+    p = params(shape, camera, image_shape, depth_code, array_offset, voxel_size, narrow_band_width_voxels, iterations,
+               strides, max_distance, robust, PointSdfPhotometricParams())
+    return _colour_into(p, robust, photometric_weight, max_intensity_difference)
+
+
+def pyramid_params(shape, camera, image_shape, pyramid_levels, array_offset, voxel_size=0.004,
+                   narrow_band_width_voxels=20, iterations=ITERATIONS, max_distance=MAX_DISTANCE, robust=None,
+                   photometric_weight=None, max_intensity_difference=math.inf):
+    """the lsf_point_sdf_pyramid_params of a call, after the host checks: image_shape is level 0's, iterations has one
+    entry per tracked level, at most pyramid_levels"""
+    levels_ = int(pyramid_levels)
+    h, w = image_extents(image_shape)
+    if not 1 <= levels_ <= _lib.ICP_MAX_LEVELS or (h >> (levels_ - 1)) < 1 or (w >> (levels_ - 1)) < 1:
+        raise ValueError("a %d x %d image has no %d-level pyramid" % (h, w, levels_))
+    p = params(shape, camera, (h, w), _lib.DEPTH_F32, array_offset, voxel_size, narrow_band_width_voxels,
+               pyramid_iterations(iterations, levels_), None, max_distance, robust, PointSdfPyramidParams())
+    p.depth_unit_ratio = 1.0  # the pyramid is in metres
+    p.pyramid_levels = levels_
+    return _colour_into(p, robust, photometric_weight, max_intensity_difference)
+
+
+def _check_colour_inputs(tsdf, weight, colour, live, photometric_weight, live_name):
+    """the colour volume and the live colour input go with a photometric_weight, and only with one"""
+    photometric = photometric_weight is not None
+    if (colour is None) == photometric or (live is None) == photometric:
+        raise ValueError("colour, %s and photometric_weight go together" % live_name)
+    if photometric:
+        check_colour_volume(colour, tsdf, weight)
+    return photometric
+
+
+def _level_buffer(x, name, pixels, device):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise ValueError("%s must be a contiguous float32 device tensor (device_depth_pyramid / "
+                         "device_intensity_pyramid)" % name)
+    if tuple(x.shape) != (pixels,):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(x.shape), (pixels,)))
+    if x.device != device:
+        raise ValueError("%s is on %s, tsdf on %s" % (name, x.device, device))
+    return x
+
+
+def _run_colour(entry, name, inputs, p, twist, residual_shape, photometric, robust):
+    """a run of one of the two colour entry points enqueued (device_rigid.enqueue_run): (twist, records, residual
+    image, intensity residual image, weight image); the images are None without residual_shape, the intensity one also
+    without the colour term, the weight image without a loss"""
+    start = twist6(twist)
+    if not np.all(np.isfinite(start)):
+        raise ValueError("twist must be finite")
+    device = inputs[0].device
+    res = intensity = weights = None
+    if residual_shape is not None:
+        res = torch.empty(residual_shape, dtype=torch.float32, device=device)
+        if photometric:
+            intensity = torch.empty(residual_shape, dtype=torch.float32, device=device)
+        if robust is not None:
+            weights = torch.empty(residual_shape, dtype=torch.float32, device=device)
+    out, records = enqueue_run(entry, name, inputs, p, start, 6, 8, RECORD, _lib.POINT_SDF_COLOUR_SCRATCH_BYTES,
+                               sum(p.iterations[:p.levels]), (res, intensity, weights))
+    return out, records, res, intensity, weights
+
+
+def point_sdf_run_photometric(tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                              narrow_band_width_voxels=20, iterations=ITERATIONS, strides=STRIDES,
+                              max_distance=MAX_DISTANCE, robust=None, colour=None, live_colour=None,
+                              photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
+    """point_sdf_run with the colour term (lsf_point_sdf_run_photometric): the same launches and one copy back.
+    colour: the model's float32 (Z, Y, X, 4) device colour volume; live_colour: the frame's uint8 (H, W, 3) device
+    image, registered to live_depth; photometric_weight: lambda, finite and > 0; the three go together, and without
+    them the call is point_sdf_run's.  max_intensity_difference: the gate on |r_I| in units of Y.  Returns (final
+    twist, records, and with residuals=True the last iteration's residual image, intensity residual image (None
+    without the colour term) and weight image (None without a loss), else three Nones); the records carry
+    photometric_count and photometric_energy, with a loss also photometric_weight_sum (unpack_record)."""
+    require_gpu()
+    check_model(tsdf, weight)
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
+        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+    if live_depth.dim() != 2:
+        raise ValueError("live_depth must be an (H, W) image, got shape %s" % (tuple(live_depth.shape),))
+    if live_depth.device != tsdf.device:
+        raise ValueError("live_depth is on %s, tsdf on %s" % (live_depth.device, tsdf.device))
+    h, w = (int(v) for v in live_depth.shape)
+    p = photometric_params(tuple(tsdf.shape), camera, (h, w), depth_code, array_offset, voxel_size,
+                           narrow_band_width_voxels, iterations, strides, max_distance, robust, photometric_weight,
+                           max_intensity_difference)
+    if live_depth.dtype != _DEPTH_DTYPES[p.depth_dtype]:
+        raise ValueError("live_depth is %s, its depth_code says %s" % (live_depth.dtype, _DEPTH_DTYPES[p.depth_dtype]))
+    photometric = _check_colour_inputs(tsdf, weight, colour, live_colour, photometric_weight, "live_colour")
+    if photometric:
+        check_colour_image(live_colour, live_depth, (("tsdf", tsdf), ("weight", weight), ("colour", colour)))
+    return _run_colour(lib.lsf_point_sdf_run_photometric, "lsf_point_sdf_run_photometric",
+                       (tsdf, weight, colour, live_depth, live_colour), p, twist, (h, w) if residuals else None,
+                       photometric, robust)
+
+
+def point_sdf_run_pyramid(tsdf, weight, pyramid_depth, pyramid_levels, image_shape, camera, array_offset, twist,
+                          voxel_size=0.004, narrow_band_width_voxels=20, iterations=ITERATIONS,
+                          max_distance=MAX_DISTANCE, robust=None, colour=None, pyramid_intensity=None,
+                          photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
+    """point-to-SDF tracking over a live depth pyramid (lsf_point_sdf_run_pyramid), enqueued: sum(iterations) + 1
+    launches and one copy back.  pyramid_depth: device_depth_pyramid.depth_pyramid's depth buffer of pyramid_levels
+    levels for a frame of image_shape (H, W); iterations: one entry per tracked level, coarse first, entry k on level
+    len(iterations) - 1 - k.  colour, pyramid_intensity (device_intensity_pyramid.intensity_pyramid's buffer of the
+    frame's colour image, "colour") and photometric_weight go together: the colour term at every pixel's own level.
+    There is no normal-angle gate.  Returns point_sdf_run_photometric's five values; the three images have the extents
+    of the last iteration's level."""
+    require_gpu()
+    check_model(tsdf, weight)
+    h, w = image_extents(image_shape)
+    p = pyramid_params(tuple(tsdf.shape), camera, (h, w), pyramid_levels, array_offset, voxel_size,
+                       narrow_band_width_voxels, iterations, max_distance, robust, photometric_weight,
+                       max_intensity_difference)
+    pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
+    _level_buffer(pyramid_depth, "pyramid_depth", pixels, tsdf.device)
+    photometric = _check_colour_inputs(tsdf, weight, colour, pyramid_intensity, photometric_weight,
+                                       "pyramid_intensity")
+    if photometric:
+        _level_buffer(pyramid_intensity, "pyramid_intensity", pixels, tsdf.device)
+    last = last_level(p.iterations[:p.levels])
+    return _run_colour(lib.lsf_point_sdf_run_pyramid, "lsf_point_sdf_run_pyramid",
+                       (tsdf, weight, colour, pyramid_depth, pyramid_intensity), p, twist,
+                       (h >> last, w >> last) if residuals else None, photometric, robust)

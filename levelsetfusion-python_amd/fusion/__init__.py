@@ -62,7 +62,12 @@ by ICP against the model's prediction:
                `sdf_tracker` (a PointToSdf3d, PointToSdf3d(camera) by default) sets the levels, the gate and the
                loss.  `rigid_iterations` and the `icp_*` settings are not used, and `photometric_weight`,
                `icp_robust`, `icp_pyramid`, `icp_max_normal_angle` and `icp_intensity_pyramid` are refused: they belong
-               to the "icp" tracker, which has a prediction image to pair into.
+               to the "icp" tracker, which has a prediction image to pair into.  The tracker's own settings do the
+               same here: PointToSdf3d(pyramid=) tracks on the frame's filtered depth pyramid, built once per frame
+               (`confidence` shares it under "icp" mode's rule; fusion still integrates the raw depth), and
+               PointToSdf3d(photometric_weight=) adds a colour term against the model's colour volume (it needs
+               colour=True; with a pyramid also intensity_pyramid=), which holds the pose on a flat textured wall
+               (tests/point_sdf_colour_restatement.py restates both; profiles/point_sdf_colour_cost.md).
 Without a non-rigid optimizer the frame is then fused in depth mode under its twist: one launch pair, no live volume.
 With `carve` or `confidence` (a DepthConfidence) every frame, frame 0 included, is fused by the weighted rule; the
 confidence image comes from the frame's own pyramid -- the tracker's, built once, when "icp" mode has an `icp_pyramid`
@@ -144,8 +149,10 @@ depth, a downsampled prediction depth and normal pyramid (every level still pair
 prediction), for the robust ICP weights a scale estimated from the residuals (MAD or the previous iteration's RMS),
 the weight image used as `pixel_weight` in fusion and robust weights in the SDF-2-SDF trackers, smoothing the intensity
 before level 0, ICP combined
-with SDF-2-SDF, for the "sdf" tracker a depth pyramid or filtered depth as the point source, a colour term against the
-colour volume, a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casting step, a confidence
+with SDF-2-SDF, for the "sdf" tracker through the sequence's own `icp_*` and `photometric_weight` keywords a depth
+pyramid or filtered depth as the point source and a colour term against the colour volume (both are settings of the
+`sdf_tracker`), a normal-angle gate from the SDF gradient,
+a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casting step, a confidence
 image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
@@ -429,6 +436,9 @@ class SequenceFusion3d:
         self.sdf_tracker = None
         if tracking_reference in DIRECT_TRACKING_MODES:
             self.sdf_tracker = PointToSdf3d(camera) if sdf_tracker is None else sdf_tracker
+            if self.sdf_tracker.photometric_weight is not None and not self.colour:
+                raise ValueError("an sdf_tracker with a photometric_weight needs colour=True: its colour term reads "
+                                 "the model's colour volume")
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -486,6 +496,8 @@ class SequenceFusion3d:
             return None
         if tracked and self.tracking_reference == "icp" and c.shares(self.icp_pyramid):
             return c.from_levels(self.icp.last_pyramid, self.camera)
+        if tracked and self.tracking_reference == "sdf" and c.shares(self.sdf_tracker.pyramid):
+            return c.from_levels(self.sdf_tracker.last_pyramid, self.camera)
         return c.build_device(depth, code, self.camera)
 
     def integrate(self, depth_image, colour_image=None):
@@ -497,7 +509,8 @@ class SequenceFusion3d:
             raise ValueError("colour_image needs a sequence made with colour=True")
         k = len(self.twists)
         depth, code = device_depth(depth_image)
-        if self.photometric_weight is not None:
+        sdf_joint = self.sdf_tracker is not None and self.sdf_tracker.photometric_weight is not None
+        if self.photometric_weight is not None or sdf_joint:
             colour_image = _colour_image(colour_image)  # on the device once: the tracker and the fusion both read it
         model = self.canonical
         rigid_records, nonrigid, hits, tracked = [], None, None, False
@@ -513,8 +526,10 @@ class SequenceFusion3d:
                     tracked = True
             elif self.tracking_reference == "sdf":
                 if sum(self.sdf_tracker.iterations) > 0:
+                    joint = dict(colour=model.colour, colour_image=colour_image) if sdf_joint else {}
                     twist, rigid_records, _ = self.sdf_tracker.track(
-                        depth, code, model.tsdf, model.weight, self.array_offset, twist, **gen)
+                        depth, code, model.tsdf, model.weight, self.array_offset, twist, **gen, **joint)
+                    tracked = True
             elif self.rigid_iterations > 0:
                 reference = model.tsdf
                 if self.tracking_reference == "raycast":
