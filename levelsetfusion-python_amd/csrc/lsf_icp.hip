@@ -29,8 +29,11 @@
 //                  sum w_I and the geometric outliers (record slots 61, 62 and 63), and the weight image of the last
 //                  iteration beside the residuals
 // What this file shares with the point-to-SDF tracker (lsf_point_sdf.hip) -- the sums' layout, StridedSource,
-// PyramidSource, RobustSource, compose, the prologue, load_poses, the finishing kernel, the schedule, the host
-// checks -- is in lsf_icp_shared.h.
+// PyramidSource and their levels, RobustSource, add_rows, compose, the prologue, load_poses, the finishing kernel, the
+// schedule, launch_selected, the host checks -- is in lsf_icp_shared.h.
+// On the host the six entry points are two runs, run_strided and run_pyramid, over one Settings filled from any of the
+// six parameter structs (settings_of) and one Images of pointers; an entry point keeps its required pointers and its
+// rule for the intensity term.
 #include <type_traits>
 
 #include "lsf_icp_shared.h"
@@ -154,28 +157,14 @@ __device__ __forceinline__ float photometric_term(const SRC& src, typename SRC::
                          src.lambda * (g[1] * a[2] - g[2] * a[1]), src.lambda * (g[2] * a[0] - g[0] * a[2]),
                          src.lambda * (g[0] * a[1] - g[1] * a[0])};
     const double r = src.lambda * rI;
-    int s = 0;
     if constexpr (SRC::kRobust) {  // w_I of the unscaled r_I on the lambda-scaled row and residual
         bool outlier;
         const double w = src.weight(rI, src.intensity_scale, outlier);
-        double wJ[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) wJ[i] = w * J[i];
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = i; j < 6; ++j) acc[s++] += wJ[i] * J[j];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[21 + i] -= wJ[i] * r;
+        add_rows<true>(J, r, w, acc);
         acc[SRC::Layout::kPhotoAt + 1] += (w * rI) * rI;
         acc[SRC::Layout::kRobustAt + 1] += w;
     } else {
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = i; j < 6; ++j) acc[s++] += J[i] * J[j];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[21 + i] -= J[i] * r;
+        add_rows<false>(J, r, 1.0, acc);
         acc[SRC::Layout::kPhotoAt + 1] += rI * rI;
     }
     acc[SRC::Layout::kPhotoAt] += 1.0;
@@ -242,30 +231,16 @@ __device__ __forceinline__ float accumulate_pair(const SRC& src, const float* __
     const double r = (Nw[0] * diff[0] + Nw[1] * diff[1]) + Nw[2] * diff[2];
     const double J[6] = {Nw[0], Nw[1], Nw[2], g[1] * Nw[2] - g[2] * Nw[1], g[2] * Nw[0] - g[0] * Nw[2],
                          g[0] * Nw[1] - g[1] * Nw[0]};
-    int s = 0;
     if constexpr (SRC::kRobust) {
         bool outlier;
         const double w = src.weight(r, src.scale, outlier);
-        double wJ[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) wJ[a] = w * J[a];
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[s++] += wJ[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] -= wJ[a] * r;
+        add_rows<true>(J, r, w, acc);
         acc[27] += (w * r) * r;
         acc[SRC::Layout::kRobustAt] += w;
         acc[SRC::Layout::kRobustAt + 2] += outlier ? 1.0 : 0.0;
         weight = (float)w;
     } else {
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[s++] += J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
+        add_rows<false>(J, r, 1.0, acc);
         acc[27] += r * r;
     }
     acc[28] += 1.0;
@@ -315,6 +290,72 @@ __global__ __launch_bounds__(kBlock) void icp_iterate_kernel(SRC src, const type
     store_partial(acc, red, scratch + (size_t)(k & 1) * kMaxBlocks * K);
 }
 
+constexpr int kNoLoss = 0;  // a Settings without weights: no loss code an entry point accepts
+static_assert(kNoLoss != LSF_ICP_LOSS_HUBER && kNoLoss != LSF_ICP_LOSS_TUKEY, "no loss is not a loss");
+
+// what a run reads of its parameter struct: the union of the six public structs.  settings_of fills it from any of
+// them, and the members a struct lacks get the neutral value: lambda 0, the gate inf, no loss, the scales inf.  The
+// strided run reads depth_unit_ratio, depth_dtype and strides, the pyramid run cos_max_angle, pyramid_levels and
+// angle_gate
+struct Settings {
+    double fx, fy, cx, cy, max_distance, twist_p[6];
+    int height, width, levels;
+    int32_t iterations[LSF_ICP_MAX_LEVELS];
+    double depth_unit_ratio;
+    int depth_dtype;
+    int32_t strides[LSF_ICP_MAX_LEVELS];
+    double cos_max_angle;
+    int pyramid_levels, angle_gate;
+    double photometric_weight, max_intensity_difference;
+    Loss loss;  // weights_out: the run's
+};
+
+template <typename Q, typename = void> struct is_pyramid : std::false_type {};
+template <typename Q> struct is_pyramid<Q, std::void_t<decltype(Q::pyramid_levels)>> : std::true_type {};
+template <typename Q, typename = void> struct has_term : std::false_type {};
+template <typename Q> struct has_term<Q, std::void_t<decltype(Q::photometric_weight)>> : std::true_type {};
+template <typename Q, typename = void> struct has_loss : std::false_type {};
+template <typename Q> struct has_loss<Q, std::void_t<decltype(Q::loss)>> : std::true_type {};
+
+template <typename Q>
+Settings settings_of(const Q* q, float* weights_out) {
+    Settings s = {q->fx, q->fy, q->cx, q->cy, q->max_distance, {}, q->height, q->width, q->levels, {}, 1.0, 0, {},
+                  -1.0, 0, 0, 0.0, INFINITY, {kNoLoss, INFINITY, INFINITY, weights_out}};
+    for (int i = 0; i < 6; ++i) s.twist_p[i] = q->twist_p[i];
+    for (int l = 0; l < LSF_ICP_MAX_LEVELS; ++l) s.iterations[l] = q->iterations[l];
+    if constexpr (is_pyramid<Q>::value) {
+        s.cos_max_angle = q->cos_max_angle;
+        s.pyramid_levels = q->pyramid_levels;
+        s.angle_gate = q->angle_gate;
+    } else {
+        s.depth_unit_ratio = q->depth_unit_ratio;
+        s.depth_dtype = q->depth_dtype;
+        for (int l = 0; l < LSF_ICP_MAX_LEVELS; ++l) s.strides[l] = q->strides[l];
+    }
+    if constexpr (has_term<Q>::value) {
+        s.photometric_weight = q->photometric_weight;
+        s.max_intensity_difference = q->max_intensity_difference;
+    }
+    if constexpr (has_loss<Q>::value) {
+        s.loss.loss = q->loss;
+        s.loss.scale = q->scale;
+        s.loss.intensity_scale = q->intensity_scale;
+    }
+    return s;
+}
+
+// a run's pointers, the absent ones NULL.  live_term and pred_term: the two images of the intensity term, the strided
+// run's uint8 colour image and float32 [h][w][4] prediction, the pyramid run's two float32 intensity pyramids
+struct Images {
+    const void* live_depth;
+    const float* live_normals;
+    const void* live_term;
+    const float *pred_depth, *pred_normals, *pred_term;
+    double *twist, *records;
+    void* scratch;
+    float *residuals_out, *intensity_residuals_out;
+};
+
 // what every launch of a run shares
 struct Run {
     const void* live;           // the source's Live type
@@ -345,118 +386,130 @@ int launch_run(const Run& r, int levels, const int32_t* iterations, SourceOf sou
     });
 }
 
-// the checks the two parameter structs share: the extents, finite intrinsics and twist_p, max_distance
-template <typename Q>
-bool camera_ok(const Q* q) {
-    if (q->height < 1 || q->width < 1 || (long long)q->height * q->width > 0x7fffffffll) return false;
-    const double all[] = {q->fx, q->fy, q->cx, q->cy, q->twist_p[0], q->twist_p[1], q->twist_p[2], q->twist_p[3],
-                          q->twist_p[4], q->twist_p[5]};
+// the checks every run shares: the extents, finite intrinsics and twist_p, max_distance
+bool camera_ok(const Settings& q) {
+    if (q.height < 1 || q.width < 1 || (long long)q.height * q.width > 0x7fffffffll) return false;
+    const double all[] = {q.fx, q.fy, q.cx, q.cy, q.twist_p[0], q.twist_p[1], q.twist_p[2], q.twist_p[3],
+                          q.twist_p[4], q.twist_p[5]};
     for (double x : all)
         if (!std::isfinite(x)) return false;
-    return q->fx != 0.0 && q->fy != 0.0 && q->max_distance > 0.0;
+    return q.fx != 0.0 && q.fy != 0.0 && q.max_distance > 0.0;
 }
 
-template <typename Q>
-Run run_of(const Q* q, double ratio, const void* live, const float* live_normals, const float* pred_depth,
-           const float* pred_normals, double* twist,
-           double* records, void* scratch, float* residuals, long long total, void* stream) {
-    Run r = {live, live_normals, pred_depth, pred_normals, twist, records, reinterpret_cast<double*>(scratch),
-             residuals, {}, (int)total,
-             as_stream(stream)};
-    r.p.fx = q->fx; r.p.fy = q->fy; r.p.cx = q->cx; r.p.cy = q->cy;
-    r.p.ratio = ratio;
-    r.p.max_distance = q->max_distance;
-    for (int i = 0; i < 6; ++i) r.p.twist_p[i] = q->twist_p[i];
-    r.p.height = q->height;
-    r.p.width = q->width;
+Run run_of(const Settings& q, const Images& m, long long total, void* stream) {
+    Run r = {m.live_depth, m.live_normals, m.pred_depth, m.pred_normals, m.twist, m.records,
+             reinterpret_cast<double*>(m.scratch), m.residuals_out, {}, (int)total, as_stream(stream)};
+    r.p.fx = q.fx; r.p.fy = q.fy; r.p.cx = q.cx; r.p.cy = q.cy;
+    r.p.ratio = q.depth_unit_ratio;
+    r.p.max_distance = q.max_distance;
+    for (int i = 0; i < 6; ++i) r.p.twist_p[i] = q.twist_p[i];
+    r.p.height = q.height;
+    r.p.width = q.width;
     return r;
 }
 
-// the checks of the strided parameter structs (lsf_icp_params, lsf_icp_photometric_params): sum(iterations), or -1
-template <typename Q>
-long long strided_total(const Q* q, const double* records) {
-    if (!camera_ok(q) || !std::isfinite(q->depth_unit_ratio) || !depth_dtype_ok(q->depth_dtype)) return -1;
-    if (q->levels < 1 || q->levels > LSF_ICP_MAX_LEVELS) return -1;
-    for (int l = 0; l < q->levels; ++l)
-        if (q->strides[l] < 1) return -1;
-    return iteration_total(q->iterations, q->levels, records);
+// the strided run of the three strided entry points (scratch_bytes: the caller's LSF_*_SCRATCH_BYTES): the checks of
+// the settings, the alias check, and the launches over the source that the term (live_term) and the loss select
+int run_strided(const Settings& q, const Images& m, size_t scratch_bytes, void* stream) {
+    if (!camera_ok(q) || !std::isfinite(q.depth_unit_ratio) || !depth_dtype_ok(q.depth_dtype)) return LSF_ERR_BAD_ARGUMENT;
+    if (q.levels < 1 || q.levels > LSF_ICP_MAX_LEVELS) return LSF_ERR_BAD_ARGUMENT;
+    for (int l = 0; l < q.levels; ++l)
+        if (q.strides[l] < 1) return LSF_ERR_BAD_ARGUMENT;
+    const long long total = iteration_total(q.iterations, q.levels, m.records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t pixels = (size_t)q.height * q.width;
+    if (aliased({{m.twist, 6 * 8}, {m.records, (size_t)total * kRecord * 8}, {m.scratch, scratch_bytes},
+                 {m.residuals_out, pixels * 4}, {m.intensity_residuals_out, pixels * 4},
+                 {q.loss.weights_out, pixels * 4}},
+                {{m.live_depth, pixels * kDepthBytes[q.depth_dtype]}, {m.live_term, pixels * 3},
+                 {m.pred_depth, pixels * 4}, {m.pred_normals, pixels * 12}, {m.pred_term, pixels * 16}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, m, total, stream);
+    return dispatch_depth(q.depth_dtype, [&](auto dt) {
+        using DT = decltype(dt);
+        return launch_selected(
+            m.live_term != nullptr, q.loss,
+            [&](auto source_of) { return launch_run(r, q.levels, q.iterations, source_of); },
+            [&](int l) { return strided_level<DT>(q.height, q.width, q.strides[l]); },
+            [&](const StridedSource<DT>& level) {
+                return PhotometricSource<DT>{level, reinterpret_cast<const uint8_t*>(m.live_term), m.pred_term,
+                                             m.intensity_residuals_out, q.photometric_weight,
+                                             q.max_intensity_difference};
+            });
+    });
 }
 
-template <typename Q>
-Grid strided_grid(const Q* q, int stride) {
-    return grid_of((q->width + stride - 1) / stride, (q->height + stride - 1) / stride);
+// the same for the three pyramid entry points
+int run_pyramid(const Settings& q, const Images& m, size_t scratch_bytes, void* stream) {
+    if (!camera_ok(q) || !(q.cos_max_angle >= -1.0 && q.cos_max_angle <= 1.0)) return LSF_ERR_BAD_ARGUMENT;
+    if (q.pyramid_levels < 1 || q.pyramid_levels > LSF_ICP_MAX_LEVELS || q.levels < 1 ||
+        q.levels > q.pyramid_levels || (q.height >> (q.pyramid_levels - 1)) < 1 ||
+        (q.width >> (q.pyramid_levels - 1)) < 1)
+        return LSF_ERR_BAD_ARGUMENT;
+    const long long total = iteration_total(q.iterations, q.levels, m.records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t levels_pixels = pyramid_pixels(q.height, q.width, q.pyramid_levels);
+    const size_t pixels = (size_t)q.height * q.width;
+    const size_t last_bytes = last_level_pixels(q.height, q.width, q.levels, q.iterations) * 4;
+    if (aliased({{m.twist, 6 * 8}, {m.records, (size_t)total * kRecord * 8}, {m.scratch, scratch_bytes},
+                 {m.residuals_out, last_bytes}, {m.intensity_residuals_out, last_bytes},
+                 {q.loss.weights_out, last_bytes}},
+                {{m.live_depth, levels_pixels * 4}, {m.live_normals, levels_pixels * 12},
+                 {m.live_term, levels_pixels * 4}, {m.pred_depth, pixels * 4}, {m.pred_normals, pixels * 12},
+                 {m.pred_term, levels_pixels * 4}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const Run r = run_of(q, m, total, stream);
+    auto run = [&](auto gate) {
+        constexpr bool GATE = decltype(gate)::value;
+        return launch_selected(
+            m.live_term != nullptr, q.loss,
+            [&](auto source_of) { return launch_run(r, q.levels, q.iterations, source_of); },
+            [&](int l) {
+                return pyramid_level<GATE>(q.fx, q.fy, q.cx, q.cy, q.cos_max_angle, q.height, q.width, q.levels, l);
+            },
+            [&](const PyramidSource<GATE>& level) {
+                return PyramidPhotometricSource<GATE>{level,
+                                                      reinterpret_cast<const float*>(m.live_term) + level.offset,
+                                                      m.pred_term + level.offset, m.intensity_residuals_out,
+                                                      q.photometric_weight, q.max_intensity_difference};
+            });
+    };
+    return q.angle_gate ? run(std::true_type()) : run(std::false_type());
 }
 
-// the checks of the pyramid parameter structs (lsf_icp_pyramid_params, lsf_icp_pyramid_photometric_params):
-// sum(iterations), or -1
+// the photometric entry points' rule: lambda finite and > 0, the gate > 0 (NaN is not)
 template <typename Q>
-long long pyramid_total(const Q* q, const double* records) {
-    if (!camera_ok(q) || !(q->cos_max_angle >= -1.0 && q->cos_max_angle <= 1.0)) return -1;
-    if (q->pyramid_levels < 1 || q->pyramid_levels > LSF_ICP_MAX_LEVELS || q->levels < 1 ||
-        q->levels > q->pyramid_levels || (q->height >> (q->pyramid_levels - 1)) < 1 ||
-        (q->width >> (q->pyramid_levels - 1)) < 1)
-        return -1;
-    return iteration_total(q->iterations, q->levels, records);
+bool term_ok(const Q* q) {
+    return std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0;
 }
 
-// the pixels of the last iteration's pyramid level: the extents of the residual images
+// the robust entry points' rule: the loss, both scales, and the optional intensity term (a, b: its two images, both or
+// neither; without them lambda is 0 and there is no intensity residual image)
 template <typename Q>
-size_t last_level_pixels(const Q* q) {
-    int last = 0;
-    for (int l = 0; l < q->levels; ++l)
-        if (q->iterations[l] > 0) last = q->levels - 1 - l;
-    return (size_t)(q->height >> last) * (q->width >> last);
-}
-
-template <typename Q>
-size_t pyramid_pixels(const Q* q) {
-    size_t n = 0;
-    for (int l = 0; l < q->pyramid_levels; ++l) n += (size_t)(q->height >> l) * (q->width >> l);
-    return n;
-}
-
-// the source of iterations entry l: lsf_depth_pyramid's layout and level intrinsics
-template <bool GATE, typename Q>
-PyramidSource<GATE> pyramid_level(const Q* q, int l) {
-    PyramidSource<GATE> src = {q->fx, q->fy, q->cx, q->cy, q->cos_max_angle, 0, {}};
-    const int level = q->levels - 1 - l;
-    for (int c = 0; c < level; ++c) {
-        const long long n = (long long)(q->height >> c) * (q->width >> c);
-        src.offset += n;
-        src.fx = src.fx / 2.0;
-        src.fy = src.fy / 2.0;
-        src.cx = (src.cx - 0.5) / 2.0;
-        src.cy = (src.cy - 0.5) / 2.0;
-    }
-    src.grid = grid_of(q->width >> level, q->height >> level);
-    return src;
+bool robust_term(const Q* q, const void* a, const void* b, const float* intensity_residuals_out) {
+    if (q->loss != LSF_ICP_LOSS_HUBER && q->loss != LSF_ICP_LOSS_TUKEY) return false;
+    if (!(q->scale > 0.0 && q->intensity_scale > 0.0)) return false;  // NaN is not > 0
+    if ((a == nullptr) != (b == nullptr)) return false;
+    if (!a) return q->photometric_weight == 0.0 && !intensity_residuals_out;
+    return term_ok(q);
 }
 
 }  // namespace
+
+// Each entry point keeps what is its own -- the pointers it requires and its rule for the intensity term -- and hands
+// its settings, its pointers and its scratch size to the run of its source.
 
 extern "C" int lsf_icp_run(const void* live_depth, const float* pred_depth, const float* pred_normals,
                            double* twist_inout, double* records, void* scratch, float* residuals_out,
                            const lsf_icp_params* params, void* stream) {
     (void)hipGetLastError();
     if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params) return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_params* q = params;
-    const long long total = strided_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)q->height * q->width;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_ICP_SCRATCH_BYTES},
-                 {residuals_out, pixels * 4}},
-                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {pred_depth, pixels * 4},
-                 {pred_normals, pixels * 12}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
-                         scratch, residuals_out, total, stream);
-    return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        using DT = decltype(dt);
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            return StridedSource<DT>{strided_grid(q, q->strides[l]), q->strides[l]};
-        });
-    });
+    return run_strided(settings_of(params, nullptr),
+                       {live_depth, nullptr, nullptr, pred_depth, pred_normals, nullptr, twist_inout, records, scratch,
+                        residuals_out, nullptr},
+                       LSF_ICP_SCRATCH_BYTES, stream);
 }
 
 extern "C" int lsf_icp_run_photometric(const void* live_depth, const uint8_t* live_colour, const float* pred_depth,
@@ -466,31 +519,27 @@ extern "C" int lsf_icp_run_photometric(const void* live_depth, const uint8_t* li
                                        void* stream) {
     (void)hipGetLastError();
     if (!live_depth || !live_colour || !pred_depth || !pred_normals || !pred_colour || !twist_inout || !scratch ||
-        !params)
+        !params || !term_ok(params))
         return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_photometric_params* q = params;
-    if (!(std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0))
+    return run_strided(settings_of(params, nullptr),
+                       {live_depth, nullptr, live_colour, pred_depth, pred_normals, pred_colour, twist_inout, records,
+                        scratch, residuals_out, intensity_residuals_out},
+                       LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES, stream);
+}
+
+extern "C" int lsf_icp_run_robust(const void* live_depth, const uint8_t* live_colour, const float* pred_depth,
+                                  const float* pred_normals, const float* pred_colour, double* twist_inout,
+                                  double* records, void* scratch, float* residuals_out,
+                                  float* intensity_residuals_out, float* weights_out,
+                                  const lsf_icp_robust_params* params, void* stream) {
+    (void)hipGetLastError();
+    if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params ||
+        !robust_term(params, live_colour, pred_colour, intensity_residuals_out))
         return LSF_ERR_BAD_ARGUMENT;
-    const long long total = strided_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)q->height * q->width;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_ICP_PHOTOMETRIC_SCRATCH_BYTES}, {residuals_out, pixels * 4},
-                 {intensity_residuals_out, pixels * 4}},
-                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {live_colour, pixels * 3}, {pred_depth, pixels * 4},
-                 {pred_normals, pixels * 12}, {pred_colour, pixels * 16}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
-                         scratch, residuals_out, total, stream);
-    return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        using DT = decltype(dt);
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            return PhotometricSource<DT>{{strided_grid(q, q->strides[l]), q->strides[l]}, live_colour, pred_colour,
-                                         intensity_residuals_out, q->photometric_weight,
-                                         q->max_intensity_difference};
-        });
-    });
+    return run_strided(settings_of(params, weights_out),
+                       {live_depth, nullptr, live_colour, pred_depth, pred_normals, pred_colour, twist_inout, records,
+                        scratch, residuals_out, intensity_residuals_out},
+                       LSF_ICP_ROBUST_SCRATCH_BYTES, stream);
 }
 
 extern "C" int lsf_icp_run_pyramid(const float* live_depth, const float* live_normals, const float* pred_depth,
@@ -499,23 +548,10 @@ extern "C" int lsf_icp_run_pyramid(const float* live_depth, const float* live_no
     (void)hipGetLastError();
     if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params)
         return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_pyramid_params* q = params;
-    const long long total = pyramid_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_ICP_PYRAMID_SCRATCH_BYTES}, {residuals_out, last_level_pixels(q) * 4}},
-                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12}, {pred_depth, pixels * 4},
-                 {pred_normals, pixels * 12}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
-                         residuals_out, total, stream);
-    auto run = [&](auto gate) {
-        return launch_run(r, q->levels, q->iterations,
-                          [&](int l) { return pyramid_level<decltype(gate)::value>(q, l); });
-    };
-    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
+    return run_pyramid(settings_of(params, nullptr),
+                       {live_depth, live_normals, nullptr, pred_depth, pred_normals, nullptr, twist_inout, records,
+                        scratch, residuals_out, nullptr},
+                       LSF_ICP_PYRAMID_SCRATCH_BYTES, stream);
 }
 
 extern "C" int lsf_icp_run_pyramid_photometric(const float* live_depth, const float* live_normals,
@@ -526,92 +562,12 @@ extern "C" int lsf_icp_run_pyramid_photometric(const float* live_depth, const fl
                                                const lsf_icp_pyramid_photometric_params* params, void* stream) {
     (void)hipGetLastError();
     if (!live_depth || !live_normals || !live_intensity || !pred_depth || !pred_normals || !pred_intensity ||
-        !twist_inout || !scratch || !params)
+        !twist_inout || !scratch || !params || !term_ok(params))
         return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_pyramid_photometric_params* q = params;
-    if (!(std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0))
-        return LSF_ERR_BAD_ARGUMENT;
-    const long long total = pyramid_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
-    const size_t last_bytes = last_level_pixels(q) * 4;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES}, {residuals_out, last_bytes},
-                 {intensity_residuals_out, last_bytes}},
-                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12},
-                 {live_intensity, levels_pixels * 4}, {pred_depth, pixels * 4}, {pred_normals, pixels * 12},
-                 {pred_intensity, levels_pixels * 4}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
-                         residuals_out, total, stream);
-    auto run = [&](auto gate) {
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            const PyramidSource<decltype(gate)::value> level = pyramid_level<decltype(gate)::value>(q, l);
-            return PyramidPhotometricSource<decltype(gate)::value>{level, live_intensity + level.offset,
-                                                                   pred_intensity + level.offset,
-                                                                   intensity_residuals_out, q->photometric_weight,
-                                                                   q->max_intensity_difference};
-        });
-    };
-    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
-}
-
-namespace {
-
-// the checks the two robust parameter structs share: the loss, both scales, and the optional intensity term (a, b: its
-// two images, both or neither; without them lambda is 0 and there is no intensity residual image).  1 with the term,
-// 0 without, -1 refused
-template <typename Q>
-int robust_term(const Q* q, const void* a, const void* b, const float* intensity_residuals_out) {
-    if (q->loss != LSF_ICP_LOSS_HUBER && q->loss != LSF_ICP_LOSS_TUKEY) return -1;
-    if (!(q->scale > 0.0 && q->intensity_scale > 0.0)) return -1;  // NaN is not > 0
-    if ((a == nullptr) != (b == nullptr)) return -1;
-    if (!a) return q->photometric_weight == 0.0 && !intensity_residuals_out ? 0 : -1;
-    return std::isfinite(q->photometric_weight) && q->photometric_weight > 0.0 && q->max_intensity_difference > 0.0
-               ? 1 : -1;
-}
-
-template <typename BASE, typename Q>
-RobustSource<BASE> robust_of(const BASE& base, const Q* q, float* weights_out) {
-    return RobustSource<BASE>{base, q->loss, q->scale, q->intensity_scale, weights_out};
-}
-
-}  // namespace
-
-extern "C" int lsf_icp_run_robust(const void* live_depth, const uint8_t* live_colour, const float* pred_depth,
-                                  const float* pred_normals, const float* pred_colour, double* twist_inout,
-                                  double* records, void* scratch, float* residuals_out,
-                                  float* intensity_residuals_out, float* weights_out,
-                                  const lsf_icp_robust_params* params, void* stream) {
-    (void)hipGetLastError();
-    if (!live_depth || !pred_depth || !pred_normals || !twist_inout || !scratch || !params) return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_robust_params* q = params;
-    const int term = robust_term(q, live_colour, pred_colour, intensity_residuals_out);
-    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
-    const long long total = strided_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)q->height * q->width;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_ICP_ROBUST_SCRATCH_BYTES},
-                 {residuals_out, pixels * 4}, {intensity_residuals_out, pixels * 4}, {weights_out, pixels * 4}},
-                {{live_depth, pixels * kDepthBytes[q->depth_dtype]}, {live_colour, pixels * 3}, {pred_depth, pixels * 4},
-                 {pred_normals, pixels * 12}, {pred_colour, pixels * 16}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, q->depth_unit_ratio, live_depth, nullptr, pred_depth, pred_normals, twist_inout, records,
-                         scratch, residuals_out, total, stream);
-    return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        using DT = decltype(dt);
-        auto level = [&](int l) { return StridedSource<DT>{strided_grid(q, q->strides[l]), q->strides[l]}; };
-        if (!term)
-            return launch_run(r, q->levels, q->iterations,
-                              [&](int l) { return robust_of(level(l), q, weights_out); });
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            return robust_of(PhotometricSource<DT>{level(l), live_colour, pred_colour, intensity_residuals_out,
-                                                   q->photometric_weight, q->max_intensity_difference},
-                             q, weights_out);
-        });
-    });
+    return run_pyramid(settings_of(params, nullptr),
+                       {live_depth, live_normals, live_intensity, pred_depth, pred_normals, pred_intensity,
+                        twist_inout, records, scratch, residuals_out, intensity_residuals_out},
+                       LSF_ICP_PYRAMID_PHOTOMETRIC_SCRATCH_BYTES, stream);
 }
 
 extern "C" int lsf_icp_run_pyramid_robust(const float* live_depth, const float* live_normals,
@@ -621,37 +577,11 @@ extern "C" int lsf_icp_run_pyramid_robust(const float* live_depth, const float* 
                                           float* intensity_residuals_out, float* weights_out,
                                           const lsf_icp_pyramid_robust_params* params, void* stream) {
     (void)hipGetLastError();
-    if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params)
+    if (!live_depth || !live_normals || !pred_depth || !pred_normals || !twist_inout || !scratch || !params ||
+        !robust_term(params, live_intensity, pred_intensity, intensity_residuals_out))
         return LSF_ERR_BAD_ARGUMENT;
-    const lsf_icp_pyramid_robust_params* q = params;
-    const int term = robust_term(q, live_intensity, pred_intensity, intensity_residuals_out);
-    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
-    const long long total = pyramid_total(q, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t levels_pixels = pyramid_pixels(q), pixels = (size_t)q->height * q->width;
-    const size_t last_bytes = last_level_pixels(q) * 4;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES}, {residuals_out, last_bytes},
-                 {intensity_residuals_out, last_bytes}, {weights_out, last_bytes}},
-                {{live_depth, levels_pixels * 4}, {live_normals, levels_pixels * 12},
-                 {live_intensity, levels_pixels * 4}, {pred_depth, pixels * 4}, {pred_normals, pixels * 12},
-                 {pred_intensity, levels_pixels * 4}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const Run r = run_of(q, 1.0, live_depth, live_normals, pred_depth, pred_normals, twist_inout, records, scratch,
-                         residuals_out, total, stream);
-    auto run = [&](auto gate) {
-        constexpr bool GATE = decltype(gate)::value;
-        if (!term)
-            return launch_run(r, q->levels, q->iterations,
-                              [&](int l) { return robust_of(pyramid_level<GATE>(q, l), q, weights_out); });
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            const PyramidSource<GATE> level = pyramid_level<GATE>(q, l);
-            return robust_of(PyramidPhotometricSource<GATE>{level, live_intensity + level.offset,
-                                                            pred_intensity + level.offset, intensity_residuals_out,
-                                                            q->photometric_weight, q->max_intensity_difference},
-                             q, weights_out);
-        });
-    };
-    return q->angle_gate ? run(std::true_type()) : run(std::false_type());
+    return run_pyramid(settings_of(params, weights_out),
+                       {live_depth, live_normals, live_intensity, pred_depth, pred_normals, pred_intensity,
+                        twist_inout, records, scratch, residuals_out, intensity_residuals_out},
+                       LSF_ICP_PYRAMID_ROBUST_SCRATCH_BYTES, stream);
 }

@@ -1,7 +1,8 @@
 // What the Gauss-Newton trackers over a live depth image share (lsf_icp.hip: projective point-to-plane ICP against the
 // ray-cast prediction; lsf_point_sdf.hip: point-to-SDF against the model itself): the layout of the per-block sums and
-// of the record, the strided and the pyramid source, the robust weight, the composed update, the launch-boundary prologue, the
-// finishing kernel, the launch schedule and the host checks.  Each tracker keeps its own per-pixel body.
+// of the record, the strided and the pyramid source and their levels, the robust weight, a term's rows (add_rows), the
+// composed update, the launch-boundary prologue, the finishing kernel, the launch schedule, the select over (colour
+// term, loss) and the host checks.  Each tracker keeps its own per-pixel body.
 // Everything here has internal linkage, as it had inside lsf_icp.hip before it moved: the kernels of that file
 // compile to the code they compiled to there (profiles/point_sdf_cost.md).
 #pragma once
@@ -144,6 +145,30 @@ struct RobustSource : BASE {
     }
 };
 
+// the rows of one term, J and r with the weight w (1 without a loss), into A's upper triangle, b
+template <bool ROBUST, int K>
+__device__ __forceinline__ void add_rows(const double (&J)[6], double r, double w, double (&acc)[K]) {
+    int n = 0;
+    if constexpr (ROBUST) {
+        double wJ[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) wJ[a] = w * J[a];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[n++] += wJ[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] -= wJ[a] * r;
+    } else {
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[n++] += J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
+    }
+}
+
 // the twist after the step delta = (tau, omega): R' = R Rodrigues(omega)^T, t' = t - R' tau, out = (t', log R')
 __device__ inline void compose(const double* tw, const double* delta, double* out) {
     double R[9], D[9], Rn[9];
@@ -270,6 +295,65 @@ int launch_schedule(int levels, const int32_t* iterations, int total, double* tw
     hipLaunchKernelGGL(icp_finish_kernel<typename SRC::Layout>, dim3(1), dim3(kBlock), 0, stream, twist, records,
                        scratch, total, prev_blocks, prev_level);
     return launch_status();
+}
+
+// a strided level of a height x width live image: the pixels (stride i, stride j)
+template <typename DT>
+StridedSource<DT> strided_level(int height, int width, int stride) {
+    return {grid_of((width + stride - 1) / stride, (height + stride - 1) / stride), stride};
+}
+
+// the source of iterations entry l of a pyramid run of `levels` tracked levels over a height x width level 0:
+// lsf_depth_pyramid's layout and level intrinsics
+template <bool GATE>
+PyramidSource<GATE> pyramid_level(double fx, double fy, double cx, double cy, double cos_max, int height, int width,
+                                  int levels, int l) {
+    PyramidSource<GATE> src = {fx, fy, cx, cy, cos_max, 0, {}};
+    const int level = levels - 1 - l;
+    for (int c = 0; c < level; ++c) {
+        src.offset += (long long)(height >> c) * (width >> c);
+        src.fx = src.fx / 2.0;
+        src.fy = src.fy / 2.0;
+        src.cx = (src.cx - 0.5) / 2.0;
+        src.cy = (src.cy - 0.5) / 2.0;
+    }
+    src.grid = grid_of(width >> level, height >> level);
+    return src;
+}
+
+// the pixels of a pyramid's buffer
+size_t pyramid_pixels(int height, int width, int pyramid_levels) {
+    size_t n = 0;
+    for (int l = 0; l < pyramid_levels; ++l) n += (size_t)(height >> l) * (width >> l);
+    return n;
+}
+
+// the pixels of the last iteration's pyramid level: the extents of the residual images
+size_t last_level_pixels(int height, int width, int levels, const int32_t* iterations) {
+    int last = 0;
+    for (int l = 0; l < levels; ++l)
+        if (iterations[l] > 0) last = levels - 1 - l;
+    return (size_t)(height >> last) * (width >> last);
+}
+
+// the optional loss of a run: loss 0 is none, and then the rest is not read
+struct Loss {
+    int loss;  // 0 or LSF_ICP_LOSS_*
+    double scale, intensity_scale;
+    float* weights_out;
+};
+
+// the run over level(l) with the optional colour term (coloured(base): the file's colour source over a level) and the
+// optional loss: one of four sources goes to launch(source_of), the file's launch_run over its own run
+template <typename Launch, typename LevelOf, typename Coloured>
+int launch_selected(bool term, const Loss& w, Launch launch, LevelOf level, Coloured coloured) {
+    auto robust = [&](auto base) {
+        return RobustSource<decltype(base)>{base, w.loss, w.scale, w.intensity_scale, w.weights_out};
+    };
+    if (!term && !w.loss) return launch(level);
+    if (!term) return launch([&](int l) { return robust(level(l)); });
+    if (!w.loss) return launch([&](int l) { return coloured(level(l)); });
+    return launch([&](int l) { return robust(coloured(level(l))); });
 }
 
 // sum(iterations), or -1 when an entry is negative, the records would not fit an int index, or there are none to

@@ -23,6 +23,8 @@
 //   RobustSource<S>             any of the four with every pair's rows scaled by the Huber or Tukey weight of its own
 //                               residual; three more sums (sum w, sum w_I, the outliers), at most 35, and the weight
 //                               image of the last iteration
+// On the host lsf_point_sdf_run and lsf_point_sdf_run_photometric share run_strided; the levels, the rows of a term
+// (add_rows) and the select over (colour term, loss) are lsf_icp_shared.h's.
 #include "lsf_icp_shared.h"
 #include "lsf_tsdf_sample.h"
 
@@ -93,30 +95,6 @@ struct SdfDev {
     double voxel, mu;  // metres: the voxel size and the truncation distance
     double off[3];     // array offset, voxels
 };
-
-// the rows of one term, J and r with the weight w (1 without a loss), into A's upper triangle, b
-template <bool ROBUST, int K>
-__device__ __forceinline__ void add_rows(const double (&J)[6], double r, double w, double (&acc)[K]) {
-    int n = 0;
-    if constexpr (ROBUST) {
-        double wJ[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) wJ[a] = w * J[a];
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[n++] += wJ[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] -= wJ[a] * r;
-    } else {
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[n++] += J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] -= J[a] * r;
-    }
-}
 
 // the colour term of a pixel that has a geometric pair (g: its world point, cell: where its SDF sample was taken): r_I,
 // its scaled terms added to acc; NaN and nothing added when one of the 8 colour weights is not > 0 or |r_I| exceeds the
@@ -330,41 +308,59 @@ int launch_run(const SdfRun& r, int levels, const int32_t* iterations, SourceOf 
     });
 }
 
-// the run over level(l) with the optional colour term (live_of(level): its LIVE) and the optional loss
+static_assert(LSF_POINT_SDF_LOSS_NONE == 0, "a Loss without a loss (lsf_icp_shared.h)");
+
+// the optional colour term of a run: the model's colour volume, the frame's colour image or intensity pyramid, the
+// image r_I goes to, and the term's three settings.  Without the term: colour NULL, lambda 0, both others inf
+struct ColourTerm {
+    const float* colour;
+    const void* live;
+    float* intensity_residuals_out;
+    double photometric_weight, max_intensity_difference, intensity_scale;
+};
+
+// the launches of a checked run over level(l) with the optional colour term (live_of(level): its LIVE) and loss
 template <typename Q, typename LevelOf, typename LiveOf>
-int launch_configured(const SdfRun& r, const Q* q, bool term, const float* colour, float* intensity_residuals_out,
-                      float* weights_out, LevelOf level, LiveOf live_of) {
+int launch_configured(const SdfRun& r, const Q* q, const ColourTerm& c, float* weights_out, LevelOf level,
+                      LiveOf live_of) {
     using BASE = decltype(level(0));
     using LIVE = decltype(live_of(level(0)));
-    auto coloured = [&](int l) {
-        const BASE base = level(l);
-        return SdfColourSource<BASE, LIVE>{base, live_of(base), reinterpret_cast<const float4*>(colour),
-                                           intensity_residuals_out, q->photometric_weight,
-                                           q->max_intensity_difference};
-    };
-    auto robust = [&](auto base) {
-        return RobustSource<decltype(base)>{base, q->loss, q->scale, q->intensity_scale, weights_out};
-    };
-    const bool loss = q->loss != LSF_POINT_SDF_LOSS_NONE;
-    if (!term && !loss) return launch_run(r, q->levels, q->iterations, level);
-    if (!term) return launch_run(r, q->levels, q->iterations, [&](int l) { return robust(level(l)); });
-    if (!loss) return launch_run(r, q->levels, q->iterations, coloured);
-    return launch_run(r, q->levels, q->iterations, [&](int l) { return robust(coloured(l)); });
+    return launch_selected(
+        c.colour != nullptr, {q->loss, q->scale, c.intensity_scale, weights_out},
+        [&](auto source_of) { return launch_run(r, q->levels, q->iterations, source_of); }, level,
+        [&](const BASE& base) {
+            return SdfColourSource<BASE, LIVE>{base, live_of(base), reinterpret_cast<const float4*>(c.colour),
+                                               c.intensity_residuals_out, c.photometric_weight,
+                                               c.max_intensity_difference};
+        });
 }
 
-// the source of iterations entry l of a pyramid run: lsf_depth_pyramid's layout and level intrinsics
-PyramidSource<false> pyramid_level(const lsf_point_sdf_pyramid_params* q, int l) {
-    PyramidSource<false> src = {q->fx, q->fy, q->cx, q->cy, -1.0, 0, {}};
-    const int level = q->levels - 1 - l;
-    for (int c = 0; c < level; ++c) {
-        src.offset += (long long)(q->image_height >> c) * (q->image_width >> c);
-        src.fx = src.fx / 2.0;
-        src.fy = src.fy / 2.0;
-        src.cx = (src.cx - 0.5) / 2.0;
-        src.cy = (src.cy - 0.5) / 2.0;
-    }
-    src.grid = grid_of(q->image_width >> level, q->image_height >> level);
-    return src;
+// the strided run of lsf_point_sdf_run and lsf_point_sdf_run_photometric (scratch_bytes: the caller's
+// LSF_*_SCRATCH_BYTES), after the caller's checks of the pointers and the colour term
+template <typename Q>
+int run_strided(const Q* q, const float* tsdf, const float* weight, const void* live_depth, double* twist_inout,
+                double* records, void* scratch, size_t scratch_bytes, float* residuals_out, float* weights_out,
+                const ColourTerm& c, void* stream) {
+    if (!params_ok<true>(q) || (q->loss == LSF_POINT_SDF_LOSS_NONE && weights_out)) return LSF_ERR_BAD_ARGUMENT;
+    const long long total = iteration_total(q->iterations, q->levels, records);
+    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
+    const size_t pixels = (size_t)q->image_height * q->image_width;
+    const size_t voxels = (size_t)q->depth * q->height * q->width * 4;
+    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, scratch_bytes},
+                 {residuals_out, pixels * 4}, {c.intensity_residuals_out, pixels * 4}, {weights_out, pixels * 4}},
+                {{tsdf, voxels}, {weight, voxels}, {c.colour, voxels * 4},
+                 {live_depth, pixels * kDepthBytes[q->depth_dtype]}, {c.live, pixels * 3}}))
+        return LSF_ERR_BAD_ARGUMENT;
+    if (total == 0) return 0;
+    const SdfRun r = run_of(q, tsdf, weight, live_depth, q->depth_unit_ratio, twist_inout, records, scratch,
+                            residuals_out, total, stream);
+    return dispatch_depth(q->depth_dtype, [&](auto dt) {
+        using DT = decltype(dt);
+        return launch_configured(
+            r, q, c, weights_out,
+            [&](int l) { return SdfSource<DT>{strided_level<DT>(q->image_height, q->image_width, q->strides[l])}; },
+            [&](const SdfSource<DT>&) { return ColourImage{reinterpret_cast<const uint8_t*>(c.live)}; });
+    });
 }
 
 }  // namespace
@@ -375,31 +371,9 @@ extern "C" int lsf_point_sdf_run(const float* tsdf, const float* weight, const v
     (void)hipGetLastError();
     if (!tsdf || !weight || tsdf == weight || !live_depth || !twist_inout || !scratch || !params)
         return LSF_ERR_BAD_ARGUMENT;
-    const lsf_point_sdf_params* q = params;
-    if (!params_ok<true>(q) || (q->loss == LSF_POINT_SDF_LOSS_NONE && weights_out)) return LSF_ERR_BAD_ARGUMENT;
-    const long long total = iteration_total(q->iterations, q->levels, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)q->image_height * q->image_width;
-    const size_t voxels = (size_t)q->depth * q->height * q->width * 4;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8}, {scratch, LSF_POINT_SDF_SCRATCH_BYTES},
-                 {residuals_out, pixels * 4}, {weights_out, pixels * 4}},
-                {{tsdf, voxels}, {weight, voxels}, {live_depth, pixels * kDepthBytes[q->depth_dtype]}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const SdfRun r = run_of(q, tsdf, weight, live_depth, q->depth_unit_ratio, twist_inout, records, scratch,
-                            residuals_out, total, stream);
-    return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        using DT = decltype(dt);
-        auto level = [&](int l) {
-            const int stride = q->strides[l];
-            return SdfSource<DT>{{grid_of((q->image_width + stride - 1) / stride,
-                                          (q->image_height + stride - 1) / stride), stride}};
-        };
-        if (q->loss == LSF_POINT_SDF_LOSS_NONE) return launch_run(r, q->levels, q->iterations, level);
-        return launch_run(r, q->levels, q->iterations, [&](int l) {
-            return RobustSource<SdfSource<DT>>{level(l), q->loss, q->scale, INFINITY, weights_out};
-        });
-    });
+    // the struct has no colour members: no term, and the loss weighs the geometric residual alone
+    return run_strided(params, tsdf, weight, live_depth, twist_inout, records, scratch, LSF_POINT_SDF_SCRATCH_BYTES,
+                       residuals_out, weights_out, {nullptr, nullptr, nullptr, 0.0, INFINITY, INFINITY}, stream);
 }
 
 extern "C" int lsf_point_sdf_run_photometric(const float* tsdf, const float* weight, const float* colour,
@@ -411,32 +385,12 @@ extern "C" int lsf_point_sdf_run_photometric(const float* tsdf, const float* wei
     if (!tsdf || !weight || tsdf == weight || !live_depth || !twist_inout || !scratch || !params)
         return LSF_ERR_BAD_ARGUMENT;
     const lsf_point_sdf_photometric_params* q = params;
-    if (!params_ok<true>(q) || (q->loss == LSF_POINT_SDF_LOSS_NONE && weights_out)) return LSF_ERR_BAD_ARGUMENT;
-    const int term = colour_term_of(q, colour, live_colour, intensity_residuals_out);
-    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
-    const long long total = iteration_total(q->iterations, q->levels, records);
-    if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    const size_t pixels = (size_t)q->image_height * q->image_width;
-    const size_t voxels = (size_t)q->depth * q->height * q->width * 4;
-    if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
-                 {scratch, LSF_POINT_SDF_COLOUR_SCRATCH_BYTES}, {residuals_out, pixels * 4},
-                 {intensity_residuals_out, pixels * 4}, {weights_out, pixels * 4}},
-                {{tsdf, voxels}, {weight, voxels}, {colour, voxels * 4},
-                 {live_depth, pixels * kDepthBytes[q->depth_dtype]}, {live_colour, pixels * 3}}))
-        return LSF_ERR_BAD_ARGUMENT;
-    if (total == 0) return 0;
-    const SdfRun r = run_of(q, tsdf, weight, live_depth, q->depth_unit_ratio, twist_inout, records, scratch,
-                            residuals_out, total, stream);
-    return dispatch_depth(q->depth_dtype, [&](auto dt) {
-        using DT = decltype(dt);
-        auto level = [&](int l) {
-            const int stride = q->strides[l];
-            return SdfSource<DT>{{grid_of((q->image_width + stride - 1) / stride,
-                                          (q->image_height + stride - 1) / stride), stride}};
-        };
-        return launch_configured(r, q, term == 1, colour, intensity_residuals_out, weights_out, level,
-                                 [&](const SdfSource<DT>&) { return ColourImage{live_colour}; });
-    });
+    if (colour_term_of(q, colour, live_colour, intensity_residuals_out) < 0) return LSF_ERR_BAD_ARGUMENT;
+    return run_strided(q, tsdf, weight, live_depth, twist_inout, records, scratch, LSF_POINT_SDF_COLOUR_SCRATCH_BYTES,
+                       residuals_out, weights_out,
+                       {colour, live_colour, intensity_residuals_out, q->photometric_weight,
+                        q->max_intensity_difference, q->intensity_scale},
+                       stream);
 }
 
 extern "C" int lsf_point_sdf_run_pyramid(const float* tsdf, const float* weight, const float* colour,
@@ -452,16 +406,11 @@ extern "C" int lsf_point_sdf_run_pyramid(const float* tsdf, const float* weight,
     if (q->pyramid_levels < 1 || q->pyramid_levels > LSF_ICP_MAX_LEVELS || q->levels > q->pyramid_levels ||
         (q->image_height >> (q->pyramid_levels - 1)) < 1 || (q->image_width >> (q->pyramid_levels - 1)) < 1)
         return LSF_ERR_BAD_ARGUMENT;
-    const int term = colour_term_of(q, colour, pyramid_intensity, intensity_residuals_out);
-    if (term < 0) return LSF_ERR_BAD_ARGUMENT;
+    if (colour_term_of(q, colour, pyramid_intensity, intensity_residuals_out) < 0) return LSF_ERR_BAD_ARGUMENT;
     const long long total = iteration_total(q->iterations, q->levels, records);
     if (total < 0) return LSF_ERR_BAD_ARGUMENT;
-    size_t levels_pixels = 0;
-    for (int l = 0; l < q->pyramid_levels; ++l) levels_pixels += (size_t)(q->image_height >> l) * (q->image_width >> l);
-    int last = 0;  // the level of the last iteration: the extents of the three images
-    for (int l = 0; l < q->levels; ++l)
-        if (q->iterations[l] > 0) last = q->levels - 1 - l;
-    const size_t last_bytes = (size_t)(q->image_height >> last) * (q->image_width >> last) * 4;
+    const size_t levels_pixels = pyramid_pixels(q->image_height, q->image_width, q->pyramid_levels);
+    const size_t last_bytes = last_level_pixels(q->image_height, q->image_width, q->levels, q->iterations) * 4;
     const size_t voxels = (size_t)q->depth * q->height * q->width * 4;
     if (aliased({{twist_inout, 6 * 8}, {records, (size_t)total * kRecord * 8},
                  {scratch, LSF_POINT_SDF_COLOUR_SCRATCH_BYTES}, {residuals_out, last_bytes},
@@ -472,8 +421,12 @@ extern "C" int lsf_point_sdf_run_pyramid(const float* tsdf, const float* weight,
     if (total == 0) return 0;
     const SdfRun r = run_of(q, tsdf, weight, pyramid_depth, 1.0, twist_inout, records, scratch, residuals_out, total,
                             stream);
-    return launch_configured(r, q, term == 1, colour, intensity_residuals_out, weights_out,
-                             [&](int l) { return pyramid_level(q, l); }, [&](const PyramidSource<false>& level) {
-                                 return IntensityLevel{pyramid_intensity ? pyramid_intensity + level.offset : nullptr};
-                             });
+    return launch_configured(
+        r, q, {colour, pyramid_intensity, intensity_residuals_out, q->photometric_weight, q->max_intensity_difference,
+               q->intensity_scale},
+        weights_out,
+        [&](int l) {
+            return pyramid_level<false>(q->fx, q->fy, q->cx, q->cy, -1.0, q->image_height, q->image_width, q->levels, l);
+        },
+        [&](const PyramidSource<false>& level) { return IntensityLevel{pyramid_intensity + level.offset}; });
 }

@@ -15,9 +15,9 @@ from . import _lib
 from ._lib import PointSdfParams, PointSdfPhotometricParams, PointSdfPyramidParams, lib
 from .device_core import require_gpu
 from .device_fusion import check_colour_image, check_colour_volume, check_model
-from .device_icp import (ITERATIONS, MAX_DISTANCE, RECORD, STRIDES, last_level, levels,  # noqa: F401
+from .device_icp import (ITERATIONS, MAX_DISTANCE, RECORD, STRIDES, last_level, levels, output_images,  # noqa: F401
                          photometric_settings, pyramid_iterations, robust_settings, unpack_record)
-from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, image_extents
+from .device_raycast import checked_depth_unit_ratio, checked_intrinsics, checked_live_depth, image_extents
 from .device_rigid import enqueue_run, twist6
 from .tsdf.generation import offsets_of
 
@@ -57,44 +57,6 @@ def params(shape, camera, image_shape, depth_code, array_offset, voxel_size=0.00
     return p
 
 
-_DEPTH_DTYPES = {_lib.DEPTH_U16: torch.uint16, _lib.DEPTH_F32: torch.float32, _lib.DEPTH_F64: torch.float64}
-
-
-def point_sdf_run(tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
-                  narrow_band_width_voxels=20, iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE,
-                  robust=None, residuals=False):
-    """the whole run enqueued: sum(iterations) + 1 launches and one copy back.  tsdf, weight: the model's float32
-    (Z, Y, X) device tensors; live_depth: device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*, scaled
-    by camera.depth_unit_ratio); twist: the starting 6-vector; robust: None or a rigid_opt.RobustLoss (its scale weighs
-    the residual in metres).  Returns (final twist float64 (6,), records float64 (sum(iterations), ICP_RECORD_DOUBLES),
-    and with residuals=True the last iteration's residual image (H, W) as a float32 device tensor -- NaN where a pixel
-    has no pair -- and, with a loss, its weight image, else two Nones)."""
-    require_gpu()
-    check_model(tsdf, weight)
-    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
-        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
-    if live_depth.dim() != 2:
-        raise ValueError("live_depth must be an (H, W) image, got shape %s" % (tuple(live_depth.shape),))
-    if live_depth.device != tsdf.device:
-        raise ValueError("live_depth is on %s, tsdf on %s" % (live_depth.device, tsdf.device))
-    h, w = (int(v) for v in live_depth.shape)
-    p = params(tuple(tsdf.shape), camera, (h, w), depth_code, array_offset, voxel_size, narrow_band_width_voxels,
-               iterations, strides, max_distance, robust)
-    if live_depth.dtype != _DEPTH_DTYPES[p.depth_dtype]:
-        raise ValueError("live_depth is %s, its depth_code says %s" % (live_depth.dtype, _DEPTH_DTYPES[p.depth_dtype]))
-    start = twist6(twist)
-    if not np.all(np.isfinite(start)):
-        raise ValueError("twist must be finite")
-    res = weights = None
-    if residuals:
-        res = torch.empty((h, w), dtype=torch.float32, device=tsdf.device)
-        if robust is not None:
-            weights = torch.empty((h, w), dtype=torch.float32, device=tsdf.device)
-    out, records = enqueue_run(lib.lsf_point_sdf_run, "lsf_point_sdf_run", (tsdf, weight, live_depth), p, start, 6, 8,
-                               RECORD, _lib.POINT_SDF_SCRATCH_BYTES, sum(p.iterations[:p.levels]), (res, weights))
-    return out, records, res, weights
-
-
 def _colour_into(p, robust, photometric_weight, max_intensity_difference):
     """the members the two colour structs have beyond lsf_point_sdf_params: lambda and its gate (0 and the gate alone
     without a photometric_weight) and the loss's intensity scale"""
@@ -130,14 +92,15 @@ def pyramid_params(shape, camera, image_shape, pyramid_levels, array_offset, vox
     return _colour_into(p, robust, photometric_weight, max_intensity_difference)
 
 
-def _check_colour_inputs(tsdf, weight, colour, live, photometric_weight, live_name):
-    """the colour volume and the live colour input go with a photometric_weight, and only with one"""
-    photometric = photometric_weight is not None
-    if (colour is None) == photometric or (live is None) == photometric:
-        raise ValueError("colour, %s and photometric_weight go together" % live_name)
-    if photometric:
-        check_colour_volume(colour, tsdf, weight)
-    return photometric
+# the entry point of a run by (pyramid, colour): its name in the library, its struct and its scratch bytes.  The loss is
+# a member of all three structs, so it is no part of the key
+_PYRAMID = ("lsf_point_sdf_run_pyramid", PointSdfPyramidParams, _lib.POINT_SDF_COLOUR_SCRATCH_BYTES)
+ENTRIES = {
+    (False, False): ("lsf_point_sdf_run", PointSdfParams, _lib.POINT_SDF_SCRATCH_BYTES),
+    (False, True): ("lsf_point_sdf_run_photometric", PointSdfPhotometricParams, _lib.POINT_SDF_COLOUR_SCRATCH_BYTES),
+    (True, False): _PYRAMID,  # the pyramid entry point takes the colour term as an option
+    (True, True): _PYRAMID,
+}
 
 
 def _level_buffer(x, name, pixels, device):
@@ -151,65 +114,92 @@ def _level_buffer(x, name, pixels, device):
     return x
 
 
-def _run_colour(entry, name, inputs, p, twist, residual_shape, photometric, robust):
-    """a run of one of the two colour entry points enqueued (device_rigid.enqueue_run): (twist, records, residual
-    image, intensity residual image, weight image); the images are None without residual_shape, the intensity one also
-    without the colour term, the weight image without a loss"""
+def _colour_given(tsdf, weight, colour, live, photometric_weight, live_name):
+    """whether a run has the colour term: the colour volume and the live colour input go with a photometric_weight, and
+    only with one"""
+    photometric = photometric_weight is not None
+    if (colour is None) == photometric or (live is None) == photometric:
+        raise ValueError("colour, %s and photometric_weight go together" % live_name)
+    if photometric:
+        check_colour_volume(colour, tsdf, weight)
+    return photometric
+
+
+def _enqueue(key, p, tsdf, weight, colour, live, twist, residual_shape, photometric, robust):
+    """the run of the filled struct p enqueued on key's entry point (device_rigid.enqueue_run).  live: the checked live
+    inputs, (depth,) or (depth, the colour term's); an entry point without the term takes neither colour nor the
+    intensity residual image.  Returns (twist, records, residual image, intensity residual image, weight image); the
+    images are None without residual_shape, the intensity one also without the colour term, the weight image without a
+    loss"""
+    name, _, scratch_bytes = ENTRIES[key]
     start = twist6(twist)
     if not np.all(np.isfinite(start)):
         raise ValueError("twist must be finite")
-    device = inputs[0].device
-    res = intensity = weights = None
-    if residual_shape is not None:
-        res = torch.empty(residual_shape, dtype=torch.float32, device=device)
-        if photometric:
-            intensity = torch.empty(residual_shape, dtype=torch.float32, device=device)
-        if robust is not None:
-            weights = torch.empty(residual_shape, dtype=torch.float32, device=device)
-    out, records = enqueue_run(entry, name, inputs, p, start, 6, 8, RECORD, _lib.POINT_SDF_COLOUR_SCRATCH_BYTES,
-                               sum(p.iterations[:p.levels]), (res, intensity, weights))
-    return out, records, res, intensity, weights
+    images = output_images(residual_shape, tsdf.device, photometric, robust is not None)
+    plain = len(live) == 1
+    out, records = enqueue_run(getattr(lib, name), name, (tsdf, weight) + (() if plain else (colour,)) + live, p, start,
+                               6, 8, RECORD, scratch_bytes, sum(p.iterations[:p.levels]),
+                               images[::2] if plain else images)
+    return (out, records) + images
+
+
+def run_strided(key, tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size,
+                narrow_band_width_voxels, iterations, strides, max_distance, robust, residuals, colour=None,
+                live_colour=None, photometric_weight=None, max_intensity_difference=math.inf):
+    """the strided run of the entry point of key (an ENTRIES key with pyramid False), checked and enqueued:
+    point_sdf_run_photometric's five values.  point_sdf_run and point_sdf_run_photometric are this at a fixed key"""
+    require_gpu()
+    check_model(tsdf, weight)
+    h, w = checked_live_depth(live_depth, depth_code, tsdf.device)
+    p = params(tuple(tsdf.shape), camera, (h, w), depth_code, array_offset, voxel_size, narrow_band_width_voxels,
+               iterations, strides, max_distance, robust, ENTRIES[key][1]())
+    photometric = False
+    if key[1]:
+        _colour_into(p, robust, photometric_weight, max_intensity_difference)
+        photometric = _colour_given(tsdf, weight, colour, live_colour, photometric_weight, "live_colour")
+    if photometric:
+        check_colour_image(live_colour, live_depth, (("tsdf", tsdf), ("weight", weight), ("colour", colour)))
+    return _enqueue(key, p, tsdf, weight, colour, (live_depth, live_colour) if key[1] else (live_depth,), twist,
+                    (h, w) if residuals else None, photometric, robust)
+
+
+def point_sdf_run(tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
+                  narrow_band_width_voxels=20, iterations=ITERATIONS, strides=STRIDES, max_distance=MAX_DISTANCE,
+                  robust=None, residuals=False):
+    """the whole run enqueued: sum(iterations) + 1 launches and one copy back.  tsdf, weight: the model's float32
+    (Z, Y, X) device tensors; live_depth: device depth image (uint16 / float32 / float64, depth_code LSF_DEPTH_*, scaled
+    by camera.depth_unit_ratio); twist: the starting 6-vector; robust: None or a rigid_opt.RobustLoss (its scale weighs
+    the residual in metres).  Returns (final twist float64 (6,), records float64 (sum(iterations), ICP_RECORD_DOUBLES),
+    and with residuals=True the last iteration's residual image (H, W) as a float32 device tensor -- NaN where a pixel
+    has no pair -- and, with a loss, its weight image, else two Nones)."""
+    out, records, res, _, weights = run_strided((False, False), tsdf, weight, live_depth, depth_code, camera,
+                                                array_offset, twist, voxel_size, narrow_band_width_voxels, iterations,
+                                                strides, max_distance, robust, residuals)
+    return out, records, res, weights
 
 
 def point_sdf_run_photometric(tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size=0.004,
                               narrow_band_width_voxels=20, iterations=ITERATIONS, strides=STRIDES,
                               max_distance=MAX_DISTANCE, robust=None, colour=None, live_colour=None,
                               photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
-    """point_sdf_run with the colour term (lsf_point_sdf_run_photometric): the same launches and one copy back.
-    colour: the model's float32 (Z, Y, X, 4) device colour volume; live_colour: the frame's uint8 (H, W, 3) device
-    image, registered to live_depth; photometric_weight: lambda, finite and > 0; the three go together, and without
-    them the call is point_sdf_run's.  max_intensity_difference: the gate on |r_I| in units of Y.  Returns (final
-    twist, records, and with residuals=True the last iteration's residual image, intensity residual image (None
-    without the colour term) and weight image (None without a loss), else three Nones); the records carry
-    photometric_count and photometric_energy, with a loss also photometric_weight_sum (unpack_record)."""
-    require_gpu()
-    check_model(tsdf, weight)
-    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
-        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
-    if live_depth.dim() != 2:
-        raise ValueError("live_depth must be an (H, W) image, got shape %s" % (tuple(live_depth.shape),))
-    if live_depth.device != tsdf.device:
-        raise ValueError("live_depth is on %s, tsdf on %s" % (live_depth.device, tsdf.device))
-    h, w = (int(v) for v in live_depth.shape)
-    p = photometric_params(tuple(tsdf.shape), camera, (h, w), depth_code, array_offset, voxel_size,
-                           narrow_band_width_voxels, iterations, strides, max_distance, robust, photometric_weight,
-                           max_intensity_difference)
-    if live_depth.dtype != _DEPTH_DTYPES[p.depth_dtype]:
-        raise ValueError("live_depth is %s, its depth_code says %s" % (live_depth.dtype, _DEPTH_DTYPES[p.depth_dtype]))
-    photometric = _check_colour_inputs(tsdf, weight, colour, live_colour, photometric_weight, "live_colour")
-    if photometric:
-        check_colour_image(live_colour, live_depth, (("tsdf", tsdf), ("weight", weight), ("colour", colour)))
-    return _run_colour(lib.lsf_point_sdf_run_photometric, "lsf_point_sdf_run_photometric",
-                       (tsdf, weight, colour, live_depth, live_colour), p, twist, (h, w) if residuals else None,
-                       photometric, robust)
+    """point_sdf_run with the colour term: the same launches and one copy back.  colour: the model's float32
+    (Z, Y, X, 4) device colour volume; live_colour: the frame's uint8 (H, W, 3) device image, registered to
+    live_depth; photometric_weight: lambda, finite and > 0; the three go together, and without them the call is
+    point_sdf_run's.  max_intensity_difference: the gate on |r_I| in units of Y.  Returns (final twist, records, and
+    with residuals=True the last iteration's residual image, intensity residual image (None without the colour term)
+    and weight image (None without a loss), else three Nones); the records carry photometric_count and
+    photometric_energy, with a loss also photometric_weight_sum (unpack_record)."""
+    return run_strided((False, True), tsdf, weight, live_depth, depth_code, camera, array_offset, twist, voxel_size,
+                       narrow_band_width_voxels, iterations, strides, max_distance, robust, residuals, colour,
+                       live_colour, photometric_weight, max_intensity_difference)
 
 
 def point_sdf_run_pyramid(tsdf, weight, pyramid_depth, pyramid_levels, image_shape, camera, array_offset, twist,
                           voxel_size=0.004, narrow_band_width_voxels=20, iterations=ITERATIONS,
                           max_distance=MAX_DISTANCE, robust=None, colour=None, pyramid_intensity=None,
                           photometric_weight=None, max_intensity_difference=math.inf, residuals=False):
-    """point-to-SDF tracking over a live depth pyramid (lsf_point_sdf_run_pyramid), enqueued: sum(iterations) + 1
-    launches and one copy back.  pyramid_depth: device_depth_pyramid.depth_pyramid's depth buffer of pyramid_levels
+    """point-to-SDF tracking over a live depth pyramid, enqueued: sum(iterations) + 1 launches and one copy back.
+    pyramid_depth: device_depth_pyramid.depth_pyramid's depth buffer of pyramid_levels
     levels for a frame of image_shape (H, W); iterations: one entry per tracked level, coarse first, entry k on level
     len(iterations) - 1 - k.  colour, pyramid_intensity (device_intensity_pyramid.intensity_pyramid's buffer of the
     frame's colour image, "colour") and photometric_weight go together: the colour term at every pixel's own level.
@@ -223,11 +213,9 @@ def point_sdf_run_pyramid(tsdf, weight, pyramid_depth, pyramid_levels, image_sha
                        max_intensity_difference)
     pixels = sum((h >> l) * (w >> l) for l in range(p.pyramid_levels))
     _level_buffer(pyramid_depth, "pyramid_depth", pixels, tsdf.device)
-    photometric = _check_colour_inputs(tsdf, weight, colour, pyramid_intensity, photometric_weight,
-                                       "pyramid_intensity")
+    photometric = _colour_given(tsdf, weight, colour, pyramid_intensity, photometric_weight, "pyramid_intensity")
     if photometric:
         _level_buffer(pyramid_intensity, "pyramid_intensity", pixels, tsdf.device)
     last = last_level(p.iterations[:p.levels])
-    return _run_colour(lib.lsf_point_sdf_run_pyramid, "lsf_point_sdf_run_pyramid",
-                       (tsdf, weight, colour, pyramid_depth, pyramid_intensity), p, twist,
-                       (h >> last, w >> last) if residuals else None, photometric, robust)
+    return _enqueue((True, photometric), p, tsdf, weight, colour, (pyramid_depth, pyramid_intensity), twist,
+                    (h >> last, w >> last) if residuals else None, photometric, robust)

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import RaycastParams, check, lib
 from .device_core import require_gpu, stream_ptr
 from .device_fusion import check_colour_volume, check_model
@@ -37,6 +38,25 @@ def checked_depth_unit_ratio(camera):
     if not np.isfinite(ratio):
         raise ValueError("the camera's depth_unit_ratio must be finite")
     return ratio
+
+
+DEPTH_DTYPES = {_lib.DEPTH_U16: torch.uint16, _lib.DEPTH_F32: torch.float32, _lib.DEPTH_F64: torch.float64}
+
+
+def checked_live_depth(live_depth, depth_code, device=None):
+    """(H, W) of a tracker's live depth image after its checks: a contiguous 2-D device tensor of the dtype its
+    LSF_DEPTH_* depth_code names -- a kernel reads it at that width --, on `device` (the model's) where one is given"""
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.is_cuda and live_depth.is_contiguous()):
+        raise ValueError("live_depth must be a contiguous device tensor (tsdf.generation.device_depth)")
+    if live_depth.dim() != 2:
+        raise ValueError("live_depth must be an (H, W) image, got shape %s" % (tuple(live_depth.shape),))
+    if device is not None and live_depth.device != device:
+        raise ValueError("live_depth is on %s, tsdf on %s" % (live_depth.device, device))
+    if depth_code not in DEPTH_DTYPES:
+        raise ValueError("depth_code must be an LSF_DEPTH_* code, got %r" % (depth_code,))
+    if live_depth.dtype != DEPTH_DTYPES[depth_code]:
+        raise ValueError("live_depth is %s, its depth_code says %s" % (live_depth.dtype, DEPTH_DTYPES[depth_code]))
+    return int(live_depth.shape[0]), int(live_depth.shape[1])
 
 
 def params(shape, camera, twist, array_offset, voxel_size, image_shape, fallback_code=None):

@@ -168,6 +168,7 @@ from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_
 from ..nonrigid_opt.hierarchical.hierarchical_optimizer3d import HierarchicalOptimizer3d
 from ..nonrigid_opt.slavcheva.slavcheva_optimizer3d import SlavchevaOptimizer3d
 from ..rigid_opt.depth_pyramid import DepthPyramid
+from ..rigid_opt.frame_tracker import device_colour_image
 from ..rigid_opt.point_to_sdf3d import PointToSdf3d
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
@@ -250,10 +251,6 @@ def _on_device(x, name, dtype, move=True):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
-def _colour_image(colour_image):
-    return _on_device(colour_image, "colour_image", np.uint8)
-
-
 class CanonicalVolume:
     """the weighted canonical TSDF: `tsdf` and `weight`, float32 device tensors of `shape` ((Z, Y, X), (H, W) or an
     int for a cube).  Depth mode needs a 3-D volume.  With colour=True (3-D only) also `colour`, a float32 device
@@ -299,7 +296,7 @@ class CanonicalVolume:
         if pixel_weight is not None:
             pixel_weight = _on_device(pixel_weight, "pixel_weight", np.float32, move=False)
         if colour_image is not None:
-            colour_image = _colour_image(colour_image)
+            colour_image = device_colour_image(colour_image)
         if warp is not None:
             warp = _on_device(warp, "warp", np.float32)
         return device_fusion.integrate_depth_by_arguments(
@@ -475,17 +472,15 @@ class SequenceFusion3d:
         new twist, the unpacked ICP records and the prediction's device hit count.  With photometric_weight the
         prediction carries the model's colour and the solve is the joint one, on the frame's colour_image"""
         model = self.canonical
-        if self.photometric_weight is not None:
-            self.prediction, normals, hits, self.prediction_colour = device_raycast.raycast(
-                model.tsdf, model.weight, self.camera, twist, self.array_offset, self.voxel_size, tuple(depth.shape),
-                normals=True, colour=model.colour)
-            twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist,
-                                               colour_image=colour_image, prediction_colour=self.prediction_colour)
-            return twist, records, hits
-        self.prediction, normals, hits = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist,
-                                                                self.array_offset, self.voxel_size, tuple(depth.shape),
-                                                                normals=True)
-        twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist)
+        joint = self.photometric_weight is not None
+        cast = device_raycast.raycast(model.tsdf, model.weight, self.camera, twist, self.array_offset, self.voxel_size,
+                                      tuple(depth.shape), normals=True, colour=model.colour if joint else None)
+        self.prediction, normals, hits = cast[:3]
+        colours = {}
+        if joint:
+            self.prediction_colour = cast[3]
+            colours = dict(colour_image=colour_image, prediction_colour=self.prediction_colour)
+        twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist, **colours)
         return twist, records, hits
 
     def _frame_weight(self, depth, code, tracked):
@@ -511,7 +506,7 @@ class SequenceFusion3d:
         depth, code = device_depth(depth_image)
         sdf_joint = self.sdf_tracker is not None and self.sdf_tracker.photometric_weight is not None
         if self.photometric_weight is not None or sdf_joint:
-            colour_image = _colour_image(colour_image)  # on the device once: the tracker and the fusion both read it
+            colour_image = device_colour_image(colour_image)  # once: the tracker and the fusion both read it
         model = self.canonical
         rigid_records, nonrigid, hits, tracked = [], None, None, False
         gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
@@ -560,7 +555,7 @@ class SequenceFusion3d:
             record, unpack = device_fusion.integrate_depth_by_arguments(
                 model.tsdf, model.weight, depth, code, self.camera, self.array_offset, twist, w=1.0,
                 max_weight=model.max_weight, pixel_weight=self._frame_weight(depth, code, tracked), carve=self.carve,
-                colour=model.colour, colour_image=_colour_image(colour_image) if self.colour else None,
+                colour=model.colour, colour_image=device_colour_image(colour_image) if self.colour else None,
                 colour_band=self.colour_band, warp=self.warp if through else None, **gen)
         frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
                  "rigid_records": rigid_records, "nonrigid": nonrigid,

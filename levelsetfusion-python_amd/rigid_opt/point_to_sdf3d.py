@@ -44,9 +44,7 @@ import torch
 from .. import device_icp, device_point_sdf
 from ..device_core import require_gpu
 from ..device_rigid import twist6
-from .depth_pyramid import DepthPyramid
-from .intensity_pyramid import IntensityPyramid
-from .robust_loss import RobustLoss
+from .frame_tracker import FrameTracker, device_colour_image
 from ..tsdf.generation import device_depth
 
 __all__ = ["PointToSdf3d"]
@@ -58,7 +56,7 @@ def _volume(x):
     return t.to("cuda").to(torch.float32).contiguous()
 
 
-class PointToSdf3d:
+class PointToSdf3d(FrameTracker):
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
                  max_distance=device_icp.MAX_DISTANCE, robust=None, pyramid=None, photometric_weight=None,
                  max_intensity_difference=math.inf, intensity_pyramid=None):
@@ -68,42 +66,8 @@ class PointToSdf3d:
         photometric_weight: None (geometry only) or lambda, finite and > 0 (with a pyramid it needs an
         intensity_pyramid); max_intensity_difference: the gate on |r_I|, > 0; intensity_pyramid: None or an
         IntensityPyramid of pyramid.levels levels, which needs both a pyramid and a photometric_weight"""
-        self.camera = camera
-        if pyramid is not None and not isinstance(pyramid, DepthPyramid):
-            raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
-        self.pyramid = pyramid
-        if pyramid is None:
-            self.iterations, self.strides = device_icp.levels(iterations, strides)
-        else:
-            self.iterations = device_icp.pyramid_iterations(iterations, pyramid.levels)
-            self.strides = None
-        if not float(max_distance) > 0:
-            raise ValueError("max_distance must be positive")
-        self.max_distance = float(max_distance)
-        if robust is not None and not isinstance(robust, RobustLoss):
-            raise ValueError("robust must be a rigid_opt.RobustLoss or None, got %r" % (robust,))
-        self.robust = robust
-        self.photometric_weight = None
-        _, self.max_intensity_difference = device_icp.photometric_settings(1.0, max_intensity_difference)
-        if intensity_pyramid is not None:
-            if not isinstance(intensity_pyramid, IntensityPyramid):
-                raise ValueError("intensity_pyramid must be a rigid_opt.IntensityPyramid or None, got %r"
-                                 % (intensity_pyramid,))
-            if pyramid is None or photometric_weight is None:
-                raise ValueError("intensity_pyramid needs both a pyramid and a photometric_weight")
-            if intensity_pyramid.levels != pyramid.levels:
-                raise ValueError("intensity_pyramid has %d levels, the pyramid %d: they must be equal"
-                                 % (intensity_pyramid.levels, pyramid.levels))
-        self.intensity_pyramid = intensity_pyramid
-        if photometric_weight is not None:
-            if pyramid is not None and intensity_pyramid is None:
-                raise ValueError("photometric_weight needs the strided path: there is no intensity pyramid")
-            self.photometric_weight, _ = device_icp.photometric_settings(photometric_weight)
-        self.last_records = []
-        self.last_residuals = None
-        self.last_weights = None  # the weight image of the last robust call with residuals=True
-        self.last_intensity_residuals = None  # r_I of the last call with a photometric_weight and residuals=True
-        self.last_pyramid = None  # the PyramidLevels of the last call with a pyramid
+        super().__init__(camera, iterations, strides, max_distance, pyramid, photometric_weight,
+                         max_intensity_difference, intensity_pyramid, robust)
         self.last_intensity_pyramid = None  # the frame's IntensityLevels of the last joint pyramid call
 
     def track(self, depth, code, tsdf, weight, array_offset, twist, voxel_size=0.004, narrow_band_width_voxels=20,
@@ -116,28 +80,20 @@ class PointToSdf3d:
         if (self.photometric_weight is None) != (colour is None) or (colour is None) != (colour_image is None):
             raise ValueError("colour and colour_image go with a tracker made with photometric_weight, and only with "
                              "one")
-        if self.pyramid is None and self.photometric_weight is None:
-            out, records, res, self.last_weights = device_point_sdf.point_sdf_run(
-                tsdf, weight, depth, code, self.camera, array_offset, twist, voxel_size, narrow_band_width_voxels,
-                self.iterations, self.strides, self.max_distance, self.robust, residuals)
-        elif self.pyramid is None:
-            out, records, res, self.last_intensity_residuals, self.last_weights = \
-                device_point_sdf.point_sdf_run_photometric(
-                    tsdf, weight, depth, code, self.camera, array_offset, twist, voxel_size, narrow_band_width_voxels,
-                    self.iterations, self.strides, self.max_distance, self.robust, colour, colour_image,
-                    self.photometric_weight, self.max_intensity_difference, residuals)
-        else:
-            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
-            live = None
-            if self.intensity_pyramid is not None:
-                self.last_intensity_pyramid = self.intensity_pyramid.build_device(colour_image)
-                live = self.last_intensity_pyramid.buffer
-            out, records, res, self.last_intensity_residuals, self.last_weights = \
-                device_point_sdf.point_sdf_run_pyramid(
-                    tsdf, weight, self.last_pyramid.buffers[0], self.pyramid.levels, tuple(depth.shape), self.camera,
-                    array_offset, twist, voxel_size, narrow_band_width_voxels, self.iterations, self.max_distance,
-                    self.robust, colour, live, self.photometric_weight, self.max_intensity_difference, residuals)
-        return out, [device_icp.unpack_record(r) for r in records], res
+        if self.pyramid is None:  # the entry point with the colour members only for a tracker with the term
+            return self._keep(device_point_sdf.run_strided(
+                (False, self.photometric_weight is not None), tsdf, weight, depth, code, self.camera, array_offset,
+                twist, voxel_size, narrow_band_width_voxels, self.iterations, self.strides, self.max_distance,
+                self.robust, residuals, colour, colour_image, self.photometric_weight, self.max_intensity_difference))
+        self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
+        live = None
+        if self.intensity_pyramid is not None:
+            self.last_intensity_pyramid = self.intensity_pyramid.build_device(colour_image)
+            live = self.last_intensity_pyramid.buffer
+        return self._keep(device_point_sdf.point_sdf_run_pyramid(
+            tsdf, weight, self.last_pyramid.buffers[0], self.pyramid.levels, tuple(depth.shape), self.camera,
+            array_offset, twist, voxel_size, narrow_band_width_voxels, self.iterations, self.max_distance, self.robust,
+            colour, live, self.photometric_weight, self.max_intensity_difference, residuals))
 
     def optimize(self, depth_image, tsdf, weight, array_offset, twist=None, voxel_size=0.004,
                  narrow_band_width_voxels=20, residuals=False, colour=None, colour_image=None):
@@ -149,15 +105,8 @@ class PointToSdf3d:
         device) and colour_image (uint8 (H, W, 3), numpy or device)."""
         require_gpu()
         depth, code = device_depth(depth_image)
-        if colour_image is not None and not isinstance(colour_image, torch.Tensor):
-            a = np.asarray(colour_image)
-            if a.dtype != np.uint8:
-                raise ValueError("colour_image must be uint8, got %s" % a.dtype)
-            colour_image = torch.from_numpy(np.ascontiguousarray(a))
-        if colour_image is not None:
-            colour_image = colour_image.to("cuda")
         out, self.last_records, self.last_residuals = self.track(
             depth, code, _volume(tsdf), _volume(weight), array_offset,
             np.zeros(6) if twist is None else twist6(twist), voxel_size, narrow_band_width_voxels, residuals,
-            None if colour is None else _volume(colour), colour_image)
+            None if colour is None else _volume(colour), device_colour_image(colour_image))
         return out

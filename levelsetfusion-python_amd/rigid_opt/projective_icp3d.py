@@ -48,9 +48,7 @@ import torch
 from .. import device_icp
 from ..device_core import require_gpu
 from ..device_rigid import twist6
-from .depth_pyramid import DepthPyramid
-from .intensity_pyramid import IntensityPyramid
-from .robust_loss import RobustLoss
+from .frame_tracker import FrameTracker, device_colour_image
 from ..tsdf.generation import device_depth
 
 __all__ = ["ProjectiveIcp3d"]
@@ -65,7 +63,7 @@ def _prediction(x, trailing):
     return t
 
 
-class ProjectiveIcp3d:
+class ProjectiveIcp3d(FrameTracker):
     def __init__(self, camera, iterations=device_icp.ITERATIONS, strides=device_icp.STRIDES,
                  max_distance=device_icp.MAX_DISTANCE, pyramid=None, max_normal_angle=None, photometric_weight=None,
                  max_intensity_difference=math.inf, intensity_pyramid=None, robust=None):
@@ -75,47 +73,14 @@ class ProjectiveIcp3d:
         intensity_pyramid); max_intensity_difference: the gate on |r_I|, > 0; intensity_pyramid: None or an
         IntensityPyramid of pyramid.levels levels, which needs both a pyramid and a photometric_weight; robust: None
         (least squares) or a RobustLoss, with any of the above"""
-        self.camera = camera
-        if pyramid is not None and not isinstance(pyramid, DepthPyramid):
-            raise ValueError("pyramid must be a rigid_opt.DepthPyramid or None, got %r" % (pyramid,))
-        self.pyramid, self.max_normal_angle = pyramid, None
+        super().__init__(camera, iterations, strides, max_distance, pyramid, photometric_weight,
+                         max_intensity_difference, intensity_pyramid, robust)
+        self.max_normal_angle = None
         if max_normal_angle is not None:
             if pyramid is None:
                 raise ValueError("max_normal_angle needs a pyramid: the strided path has no live normals")
             device_icp.cos_max_angle(max_normal_angle)
             self.max_normal_angle = float(max_normal_angle)
-        if pyramid is None:
-            self.iterations, self.strides = device_icp.levels(iterations, strides)
-        else:
-            self.iterations = device_icp.pyramid_iterations(iterations, pyramid.levels)
-            self.strides = None
-        if not float(max_distance) > 0:
-            raise ValueError("max_distance must be positive")
-        self.max_distance = float(max_distance)
-        self.photometric_weight = None
-        _, self.max_intensity_difference = device_icp.photometric_settings(1.0, max_intensity_difference)
-        if intensity_pyramid is not None:
-            if not isinstance(intensity_pyramid, IntensityPyramid):
-                raise ValueError("intensity_pyramid must be a rigid_opt.IntensityPyramid or None, got %r"
-                                 % (intensity_pyramid,))
-            if pyramid is None or photometric_weight is None:
-                raise ValueError("intensity_pyramid needs both a pyramid and a photometric_weight")
-            if intensity_pyramid.levels != pyramid.levels:
-                raise ValueError("intensity_pyramid has %d levels, the pyramid %d: they must be equal"
-                                 % (intensity_pyramid.levels, pyramid.levels))
-        self.intensity_pyramid = intensity_pyramid
-        if photometric_weight is not None:
-            if pyramid is not None and intensity_pyramid is None:
-                raise ValueError("photometric_weight needs the strided path: there is no intensity pyramid")
-            self.photometric_weight, _ = device_icp.photometric_settings(photometric_weight)
-        if robust is not None and not isinstance(robust, RobustLoss):
-            raise ValueError("robust must be a rigid_opt.RobustLoss or None, got %r" % (robust,))
-        self.robust = robust
-        self.last_records = []
-        self.last_residuals = None
-        self.last_weights = None  # the geometric weight image of the last robust call with residuals=True
-        self.last_intensity_residuals = None
-        self.last_pyramid = None
         self.last_intensity_pyramids = None  # (live, prediction) IntensityLevels of the last joint pyramid call
 
     def track(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals=False,
@@ -123,58 +88,28 @@ class ProjectiveIcp3d:
         """optimize() on device inputs (tsdf.generation.device_depth's depth and LSF_DEPTH_* code, the prediction's
         float32 device depth and normals at twist_p): (final twist, the unpacked records, the residual image or None).
         With a photometric_weight also the frame's uint8 (H, W, 3) device colour image and the prediction's float32
-        (H, W, 4) one; the intensity residual image is kept as `last_intensity_residuals`"""
+        (H, W, 4) one; the intensity residual image is kept as `last_intensity_residuals`, a loss's weight image as
+        `last_weights`"""
         if (self.photometric_weight is None) != (colour_image is None) or \
                 (colour_image is None) != (prediction_colour is None):
             raise ValueError("colour_image and prediction_colour go with a tracker made with photometric_weight, and "
                              "only with one")
-        if self.robust is not None:
-            return self._track_robust(depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals,
-                                      colour_image, prediction_colour)
-        if self.intensity_pyramid is not None:
-            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
-            live, pred = self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
-                                                         self.intensity_pyramid.build_prediction(prediction_colour))
-            out, records, res, self.last_intensity_residuals = device_icp.icp_run_pyramid_photometric(
-                *self.last_pyramid.buffers, live.buffer, self.pyramid.levels, prediction_depth, prediction_normals,
-                pred.buffer, self.camera, twist_p, self.photometric_weight, twist, self.iterations, self.max_distance,
-                self.max_normal_angle, self.max_intensity_difference, residuals)
-        elif self.photometric_weight is not None:
-            out, records, res, self.last_intensity_residuals = device_icp.icp_run_photometric(
-                depth, code, colour_image, prediction_depth, prediction_normals, prediction_colour, self.camera,
-                twist_p, self.photometric_weight, twist, self.iterations, self.strides, self.max_distance,
-                self.max_intensity_difference, residuals)
-        elif self.pyramid is None:
-            out, records, res = device_icp.icp_run(depth, code, prediction_depth, prediction_normals, self.camera,
-                                                   twist_p, twist, self.iterations, self.strides, self.max_distance,
-                                                   residuals)
-        else:
-            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
-            out, records, res = device_icp.icp_run_pyramid(
-                *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
-                twist_p, twist, self.iterations, self.max_distance, self.max_normal_angle, residuals)
-        return out, [device_icp.unpack_record(r) for r in records], res
-
-    def _track_robust(self, depth, code, prediction_depth, prediction_normals, twist_p, twist, residuals,
-                      colour_image, prediction_colour):
-        """track() through the robust entry points: the same four configurations"""
+        # the entry point is the configuration's (device_icp.ENTRIES): a tracker without a loss never runs a robust one
+        key = (self.pyramid is not None, self.photometric_weight is not None, self.robust is not None)
+        term = (self.photometric_weight, self.max_intensity_difference, self.robust)
         if self.pyramid is None:
-            out, records, res, self.last_intensity_residuals, self.last_weights = device_icp.icp_run_robust(
-                depth, code, prediction_depth, prediction_normals, self.camera, twist_p, self.robust, twist,
-                self.iterations, self.strides, self.max_distance, colour_image, prediction_colour,
-                self.photometric_weight, self.max_intensity_difference, residuals)
-        else:
-            self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
-            live = pred = None
-            if self.intensity_pyramid is not None:
-                live, pred = self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
-                                                             self.intensity_pyramid.build_prediction(prediction_colour))
-                live, pred = live.buffer, pred.buffer
-            out, records, res, self.last_intensity_residuals, self.last_weights = device_icp.icp_run_pyramid_robust(
-                *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
-                twist_p, self.robust, twist, self.iterations, self.max_distance, self.max_normal_angle, live, pred,
-                self.photometric_weight, self.max_intensity_difference, residuals)
-        return out, [device_icp.unpack_record(r) for r in records], res
+            return self._keep(device_icp.run_strided(
+                key, depth, code, prediction_depth, prediction_normals, self.camera, twist_p, twist, self.iterations,
+                self.strides, self.max_distance, residuals, colour_image, prediction_colour, *term))
+        self.last_pyramid = self.pyramid.build_device(depth, code, self.camera)
+        live = pred = None
+        if self.intensity_pyramid is not None:
+            self.last_intensity_pyramids = (self.intensity_pyramid.build_device(colour_image),
+                                            self.intensity_pyramid.build_prediction(prediction_colour))
+            live, pred = (levels.buffer for levels in self.last_intensity_pyramids)
+        return self._keep(device_icp.run_pyramid(
+            key, *self.last_pyramid.buffers, self.pyramid.levels, prediction_depth, prediction_normals, self.camera,
+            twist_p, twist, self.iterations, self.max_distance, self.max_normal_angle, residuals, live, pred, *term))
 
     def optimize(self, live_depth, prediction_depth, prediction_normals, prediction_twist, twist=None,
                  residuals=False, colour_image=None, prediction_colour=None):
@@ -186,16 +121,9 @@ class ProjectiveIcp3d:
         require_gpu()
         depth, code = device_depth(live_depth)
         twist_p = twist6(prediction_twist)
-        if colour_image is not None and not isinstance(colour_image, torch.Tensor):
-            a = np.asarray(colour_image)
-            if a.dtype != np.uint8:
-                raise ValueError("colour_image must be uint8, got %s" % a.dtype)
-            colour_image = torch.from_numpy(np.ascontiguousarray(a))
-        if colour_image is not None:
-            colour_image = colour_image.to("cuda")
         if prediction_colour is not None:
             prediction_colour = _prediction(prediction_colour, (4,))
         out, self.last_records, self.last_residuals = self.track(
             depth, code, _prediction(prediction_depth, ()), _prediction(prediction_normals, (3,)), twist_p,
-            twist_p if twist is None else twist, residuals, colour_image, prediction_colour)
+            twist_p if twist is None else twist, residuals, device_colour_image(colour_image), prediction_colour)
         return out

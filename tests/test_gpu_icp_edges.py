@@ -104,3 +104,34 @@ def test_reruns_are_bit_identical(lsf):
     b = _run("float32", *IS.PYRAMID, residuals=True)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     assert _bits_equal(a[2].cpu().numpy(), b[2].cpu().numpy())
+
+
+@pytest.mark.parametrize("entry", ["icp_run", "icp_run_photometric", "icp_run_robust"])
+def test_a_live_depth_that_is_not_what_its_code_says_is_refused(lsf, monkeypatch, entry):
+    """an 8 x 8 float32 image given as float64 would be read past its end, given as uint16 misread; a 3-D tensor has no
+    (H, W): each is a ValueError before any launch"""
+    from levelsetfusion_python_amd import _lib, device_icp
+    from levelsetfusion_python_amd.rigid_opt import RobustLoss
+
+    def launched(*args):
+        raise AssertionError("the library was called")
+    for name in ("lsf_icp_run", "lsf_icp_run_photometric", "lsf_icp_run_robust"):
+        monkeypatch.setattr(_lib.lib, name, launched)
+    live = torch.ones((8, 8), dtype=torch.float32, device="cuda")
+    pd, pn = torch.ones((8, 8), device="cuda"), torch.zeros((8, 8, 3), device="cuda")
+    colour = dict(live_colour=torch.zeros((8, 8, 3), dtype=torch.uint8, device="cuda"),
+                  pred_colour=torch.zeros((8, 8, 4), device="cuda"), photometric_weight=0.1)
+    zero = np.zeros(6)
+
+    def run(depth, code):
+        if entry == "icp_run":
+            return device_icp.icp_run(depth, code, pd, pn, _camera(1.0), zero)
+        if entry == "icp_run_photometric":
+            return device_icp.icp_run_photometric(depth, code, colour["live_colour"], pd, pn, colour["pred_colour"],
+                                                  _camera(1.0), zero, colour["photometric_weight"])
+        return device_icp.icp_run_robust(depth, code, pd, pn, _camera(1.0), zero, RobustLoss("tukey", 0.01))
+    for code in (_lib.DEPTH_F64, _lib.DEPTH_U16):
+        with pytest.raises(ValueError, match="its depth_code says"):
+            run(live, code)
+    with pytest.raises(ValueError, match=r"\(H, W\) image"):
+        run(torch.ones((2, 8, 8), dtype=torch.float32, device="cuda"), _lib.DEPTH_F32)
