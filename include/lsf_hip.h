@@ -1679,6 +1679,31 @@ int lsf_mesh_vertex_colours(const float *tsdf, const float *colour, const uint8_
                             const int32_t *vertex_base, uint8_t *colours, int64_t vertex_count, int32_t default_red,
                             int32_t default_green, int32_t default_blue, const lsf_mesh_params *params, void *stream);
 
+/* ---- the moving volume: the canonical model shifted by whole voxels ----------------------------------------------------
+ * The reference has no moving volume; the contract is this project's ("Moving volume";
+ * tests/volume_shift_restatement.py restates it).  With s = (shift_x, shift_y, shift_z), any sign,
+ *     dst(v) = src(v + s)                                   where v + s lies inside the volume
+ *     dst(v) = (tsdf 1, weight 0, colour record 0 0 0 0)    elsewhere
+ * for tsdf, weight and, when given, the 16-byte colour record.  |s_j| >= n_j on any axis gives an all-empty
+ * destination.  Values move as bits: NaNs, their payloads and -0.0 survive.  Out of place, one launch, no host wait:
+ * every destination voxel is written exactly once and a source voxel that leaves is never read.  The unit of work is
+ * one row (z, y) per wave, LSF_VOLUME_SHIFT_BLOCK_ROWS rows per workgroup, on at most LSF_VOLUME_SHIFT_MAX_BLOCKS
+ * workgroups with a stride loop behind them. */
+typedef struct lsf_volume_shift_params {
+    int32_t depth, height, width;        /* volume extents z, y, x, >= 1 each; at most 2^31 - 1 voxels */
+    int32_t shift_x, shift_y, shift_z;   /* whole voxels, any sign and size */
+} lsf_volume_shift_params;
+#define LSF_VOLUME_SHIFT_MAX_BLOCKS 2048
+#define LSF_VOLUME_SHIFT_BLOCK_ROWS 4
+
+/* tsdf, weight, out_tsdf, out_weight: DEVICE float32 [depth][height][width], 4-byte aligned.  colour, out_colour: both
+ * NULL (no colour volume), or both DEVICE float32 [depth][height][width][4], 16-byte aligned.  Refused with
+ * LSF_ERR_BAD_ARGUMENT: a NULL among the first four, one colour pointer NULL and the other not, a colour pointer off a
+ * 16-byte boundary, extents < 1, and any source array overlapping any destination array or two destination arrays
+ * overlapping; more than 2^31 - 1 voxels is LSF_ERR_BAD_DIMS. */
+int lsf_volume_shift(const float *tsdf, const float *weight, const float *colour, float *out_tsdf, float *out_weight,
+                     float *out_colour, const lsf_volume_shift_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "d72dd95c04440bad"
+HEADER_ABI_HASH = "88f9a6300475259d"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -255,6 +255,14 @@ class MeshParams(ctypes.Structure):
                                                "min_weight")] + \
                [(n, ctypes.c_int32) for n in ("depth", "height", "width")]
 
+
+class VolumeShiftParams(ctypes.Structure):
+    """lsf_volume_shift_params: the model shifted by whole voxels (lsf_volume_shift)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("depth", "height", "width", "shift_x", "shift_y", "shift_z")]
+
+
+VOLUME_SHIFT_MAX_BLOCKS = 2048
+VOLUME_SHIFT_BLOCK_ROWS = 4
 
 ICP_MAX_LEVELS = 4
 ICP_RECORD_DOUBLES = 64
@@ -499,6 +507,7 @@ PROTOTYPES = {
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
     "lsf_mesh_vertex_colours": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int32, _P(MeshParams), _vp]),
+    "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),

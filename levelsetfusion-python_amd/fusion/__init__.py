@@ -135,11 +135,30 @@ warped into the model by `nonrigid_optimizer.optimize(live, model.tsdf)`, and fu
 uncarved, uncoloured -- `carve`, `confidence` and `colour` raise with it, since the observation mask, the weights and
 the colour would have to be warped with the live field.
 
+Moving volume ("Moving volume"; tests/volume_shift_restatement.py restates it): all of the above
+happens in one box, fixed in the world by field_shape and array_offset.  SequenceFusion3d(..., moving_volume=
+MovingVolume(threshold_voxels, anchor)) makes it a window that follows the camera in whole-voxel steps.  After a frame
+is fused the policy takes `anchor`, a point in camera coordinates some way in front of the lens, to world coordinates
+with the frame's twist; when it lies more than threshold_voxels from the window's centre on any axis, the window moves
+by trunc of that distance on every axis.  CanonicalVolume.shift(s, array_offset) then copies the model shifted by s into
+its spare buffers (one launch of csrc/lsf_volume_shift.hip: dst(v) = src(v + s), empty where v + s leaves the volume)
+and swaps them in, and `array_offset` becomes array_offset + s (`initial_array_offset` keeps the first).  A voxel's
+world point is float32((float64(v) + array_offset) * voxel_size), so a retained voxel keeps it bit for bit and every
+later fusion is the one a fixed volume would have made there.  With the policy's stream_mesh the cells that leave are
+meshed first -- at most three boxes, each through extract_mesh's kernels with their host read -- and appended to
+`streamed_meshes` as host tuples; extract_mesh(include_streamed=True) is merge_meshes of the window's mesh and those
+chunks.  Every cell is drawn exactly once; the vertices on a seam appear on both sides, and since the window goes on
+fusing the layer a chunk was cut along, later frames can open hairline cracks there (Kintinuous has the same property).
+The frame record gains "shift" and "streamed_faces", only with a moving_volume.  The shift sits between frames, so it
+combines with every tracking mode and every non-rigid setting; `warp` and `prediction` remain the last frame's, in the
+window that frame had.  Cost: profiles/moving_volume_cost.md.
+
 Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
-vertex and face totals.
+vertex and face totals.  A moving volume's policy adds none (the twist is on the host already); a shift that streams
+costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host.
 
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SobolevFusion
 (sobolev_smoothing_enabled) or out of a z-slab / multi-GPU run (`comm`), a carve-distance
@@ -155,13 +174,16 @@ pyramid or filtered depth as the point source and a colour term against the colo
 a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casting step, a confidence
 image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
-colours, welding vertices by position, decimation, and a mesh extracted without the host read of its totals."""
+colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, and for the
+moving volume streaming TSDF values out or back in (space the window re-enters starts empty), welding across seams,
+and a shift enqueued without the mesh totals' host read."""
 import math
 
 import numpy as np
 import torch
 
-from .. import device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid
+from .. import (device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid,
+                device_volume_shift)
 from ..device_core import require_gpu
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
                              unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
@@ -173,9 +195,11 @@ from ..rigid_opt.point_to_sdf3d import PointToSdf3d
 from ..rigid_opt.projective_icp3d import ProjectiveIcp3d
 from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_record
 from .._lib import DEPTH_F32
-from ..tsdf.generation import DepthCamera, device_depth
+from ..math_utils.transformation import twist_vector_to_matrix3d
+from ..tsdf.generation import DepthCamera, device_depth, offsets_of
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "unpack_record", "unpack_weighted_record",
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "merge_meshes",
+           "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
            "TRACKING_REFERENCES", "TRACKING_MODES", "DIRECT_TRACKING_MODES"]
@@ -251,6 +275,84 @@ def _on_device(x, name, dtype, move=True):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
+class MovingVolume:
+    """the policy of a window that follows the camera in whole-voxel steps (module docstring, "Moving volume").  Host
+    only.  threshold_voxels: positive; the window stays while the anchor is within that many voxels of its centre on
+    every axis.  anchor: the point in CAMERA coordinates (metres) the window keeps near its centre, (0, 0, depth) some
+    way in front of the lens -- the model is where the camera looks; it has no default, since no depth is right
+    across scenes.  stream_mesh, min_weight, normals: whether and how SequenceFusion3d meshes the cells that leave."""
+
+    def __init__(self, threshold_voxels, anchor, stream_mesh=True, min_weight=0.0, normals=False):
+        self.threshold_voxels = float(threshold_voxels)
+        if not (np.isfinite(self.threshold_voxels) and self.threshold_voxels > 0):
+            raise ValueError("threshold_voxels must be finite and positive, got %r" % (threshold_voxels,))
+        a = np.asarray(anchor, dtype=np.float64).reshape(-1)
+        if a.size != 3 or not np.all(np.isfinite(a)):
+            raise ValueError("anchor must be three finite camera coordinates in metres, got %r" % (anchor,))
+        self.anchor = a.copy()
+        self.min_weight = float(min_weight)
+        if np.isnan(self.min_weight):
+            raise ValueError("min_weight must not be NaN")
+        self.stream_mesh, self.normals = bool(stream_mesh), bool(normals)
+
+    def shift_for(self, twist, array_offset, shape, voxel_size):
+        """(sx, sy, sz), Python ints, all zero for "stay".  The anchor goes to world coordinates by the inverse of
+        twist_vector_to_matrix3d of the float32-rounded twist (the generator's convention, raycast's); d is its
+        position in voxels minus the window's centre array_offset + (n - 1) / 2 per axis, in float64.  While no |d_j|
+        exceeds the threshold the window stays; otherwise the shift is trunc(d_j) on EVERY axis, so one shift
+        re-centres all three and shifts stay rare.  shape is the model's (Z, Y, X)."""
+        if len(shape) != 3:
+            raise ValueError("a moving volume needs a 3-D (Z, Y, X) model, got shape %s" % (tuple(shape),))
+        if not (np.isfinite(voxel_size) and voxel_size > 0):
+            raise ValueError("voxel_size must be finite and positive")
+        t32 = np.asarray(twist, dtype=np.float64).reshape(6).astype(np.float32)
+        m = twist_vector_to_matrix3d(t32)  # world -> camera
+        rot, t = m[:3, :3].astype(np.float64), m[:3, 3].astype(np.float64)
+        world = rot.T @ (self.anchor - t)
+        n = np.array([shape[2], shape[1], shape[0]], dtype=np.float64)  # x, y, z
+        d = world / float(voxel_size) - (offsets_of(array_offset) + (n - 1.0) / 2.0)
+        if not np.all(np.isfinite(d)):
+            raise ValueError("the anchor's world position is not finite under twist %r" % (twist,))
+        if not np.any(np.abs(d) > self.threshold_voxels):
+            return (0, 0, 0)
+        return tuple(int(v) for v in np.trunc(d))
+
+
+def _mesh_layout(mesh):
+    """(with normals, with colours) of a host mesh tuple in extract_mesh's layout: (V, F), (V, F, N), (V, F, C) or
+    (V, F, N, C), C being uint8"""
+    if not isinstance(mesh, (tuple, list)) or not 2 <= len(mesh) <= 4:
+        raise ValueError("a mesh is a tuple (vertices, faces[, normals][, colours])")
+    extras = [np.asarray(a) for a in mesh[2:]]
+    coloured = bool(extras) and extras[-1].dtype == np.uint8
+    with_normals = len(extras) - int(coloured) == 1
+    if len(extras) - int(coloured) not in (0, 1):
+        raise ValueError("a mesh is a tuple (vertices, faces[, normals][, colours])")
+    return with_normals, coloured
+
+
+def merge_meshes(meshes):
+    """the concatenation of host meshes in extract_mesh's layout (numpy tuples (vertices, faces[, normals][, colours])):
+    vertices, normals and colours stacked in order, every mesh's face indices offset by the vertices before it.
+    Nothing is welded.  Meshes of different layouts are refused, and so is an empty list: it has no layout."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("merge_meshes needs at least one mesh")
+    layout = _mesh_layout(meshes[0])
+    for m in meshes[1:]:
+        if _mesh_layout(m) != layout:
+            raise ValueError("merge_meshes needs meshes of one layout (normals and colours in all or in none)")
+    counts = [len(m[0]) for m in meshes]
+    if sum(counts) > 0x7fffffff:
+        raise ValueError("the merged mesh has more vertices than int32 face indices reach")
+    bases = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int32)
+    out = [np.concatenate([np.asarray(m[0], dtype=np.float32).reshape(-1, 3) for m in meshes]),
+           np.concatenate([np.asarray(m[1], dtype=np.int32).reshape(-1, 3) + b for m, b in zip(meshes, bases)])]
+    for j in range(2, len(meshes[0])):
+        out.append(np.concatenate([np.asarray(m[j]).reshape(-1, 3) for m in meshes]))
+    return tuple(out)
+
+
 class CanonicalVolume:
     """the weighted canonical TSDF: `tsdf` and `weight`, float32 device tensors of `shape` ((Z, Y, X), (H, W) or an
     int for a cube).  Depth mode needs a 3-D volume.  With colour=True (3-D only) also `colour`, a float32 device
@@ -266,6 +368,7 @@ class CanonicalVolume:
         self.tsdf = torch.ones(self.shape, dtype=torch.float32, device="cuda")
         self.weight = torch.zeros(self.shape, dtype=torch.float32, device="cuda")
         self.colour = torch.zeros(self.shape + (4,), dtype=torch.float32, device="cuda") if colour else None
+        self._spare = None  # shift: the buffers the next shifted copy is written to
 
     def reset(self):
         """back to the empty model: tsdf 1, weight 0 everywhere (and a colour volume 0)"""
@@ -350,6 +453,56 @@ class CanonicalVolume:
             out = tuple(t.cpu().numpy() for t in out)
         return out
 
+    def _leaving_mesh(self, box, array_offset, voxel_size, min_weight, normals, colours):
+        """the host mesh of one box of leaving cells ((x0, x1), (y0, y1), (z0, z1)): extract_mesh of a contiguous copy
+        of its voxels -- the cells' range plus one layer on the high side -- with array_offset moved by its origin"""
+        (x0, x1), (y0, y1), (z0, z1) = box
+        part = (slice(z0, z1 + 1), slice(y0, y1 + 1), slice(x0, x1 + 1))
+        colour = self.colour[part].contiguous() if colours else None
+        out = device_mesh.extract_mesh(self.tsdf[part].contiguous(), self.weight[part].contiguous(),
+                                       offsets_of(array_offset) + np.array([x0, y0, z0], dtype=np.float64),
+                                       voxel_size, 0.0, min_weight, normals, colour)
+        keep = [out[0], out[1]] + ([out[2]] if normals else []) + ([out[3]] if colours else [])
+        return tuple(t.cpu().numpy() for t in keep)
+
+    def shift(self, shift_voxels, array_offset, voxel_size=0.004, stream_mesh=False, min_weight=0.0, normals=False,
+              colours=False):
+        """move the window by shift_voxels = (sx, sy, sz) whole voxels: afterwards voxel v holds what voxel v + s held,
+        and the voxels that entered are empty (tsdf 1, weight 0, colour 0); one launch of csrc/lsf_volume_shift.hip.
+        Returns (new_array_offset, chunks) with new_array_offset = array_offset + s (float64 (3,)), under which every
+        retained voxel keeps its world point bit for bit.  3-D volumes only.  The copy is out of place into a spare
+        set of buffers, allocated at the first non-zero shift, and `tsdf`, `weight` and `colour` are swapped with
+        them: no later call allocates, and a tensor taken from these attributes BEFORE a shift is the spare
+        afterwards (the next shift overwrites it).  A zero shift returns (array_offset, []) at once, without a launch.
+        With stream_mesh the cells that leave -- a cell, the cube between voxel c and c + 1, leaves when any of its 8
+        corners does -- are meshed first, at iso 0 with extract_mesh's kernels: device_volume_shift.leaving_boxes cuts
+        them into at most three disjoint boxes, each meshed from a contiguous copy of its voxels, and `chunks` lists
+        their host tuples in extract_mesh's layout (with normals / colours as asked; boxes without a face are left
+        out).  Every cell of the old volume is thus drawn exactly once across the chunks and the new window; the
+        seam's vertices appear in both, nothing is welded.  Each box costs extract_mesh's host read."""
+        if len(self.shape) != 3:
+            raise ValueError("a volume shift needs a 3-D model, this one has shape %s" % (self.shape,))
+        s = device_volume_shift.shift_of(shift_voxels)
+        offset = offsets_of(array_offset).copy()
+        if colours and self.colour is None:
+            raise ValueError("colours=True needs a volume made with colour=True")
+        if s == (0, 0, 0):
+            return offset, []
+        chunks = []
+        if stream_mesh:
+            for box in device_volume_shift.leaving_boxes(self.shape, s):
+                mesh = self._leaving_mesh(box, offset, voxel_size, min_weight, normals, colours)
+                if len(mesh[1]):
+                    chunks.append(mesh)
+        if self._spare is None:
+            self._spare = (torch.empty_like(self.tsdf), torch.empty_like(self.weight),
+                           None if self.colour is None else torch.empty_like(self.colour))
+        out_tsdf, out_weight, out_colour = self._spare
+        device_volume_shift.shift(self.tsdf, self.weight, self.colour, out_tsdf, out_weight, out_colour, s)
+        self._spare = (self.tsdf, self.weight, self.colour)
+        self.tsdf, self.weight, self.colour = out_tsdf, out_weight, out_colour
+        return offset + np.array(s, dtype=np.float64), chunks
+
 
 class SequenceFusion3d:
     """track each depth frame against the model (tracking_reference "model"), the live volume of its ray-cast
@@ -365,7 +518,10 @@ class SequenceFusion3d:
     and `prediction_colour` is the last prediction's float32 (H, W, 4) colour image; with icp_intensity_pyramid the
     joint solve runs on the icp_pyramid (`icp.last_intensity_pyramids` keeps the two intensity pyramids); with
     icp_robust the solve is reweighted by that RobustLoss and the records carry weight_sum, photometric_weight_sum
-    and outliers.  In "sdf" mode rigid_records holds `sdf_tracker`'s records, in the same layout."""
+    and outliers.  In "sdf" mode rigid_records holds `sdf_tracker`'s records, in the same layout.  With moving_volume
+    (a MovingVolume) the model is a window that follows the camera: `array_offset` moves in whole voxels
+    (`initial_array_offset` keeps the construction value), the frame records carry shift and streamed_faces, and
+    `streamed_meshes` lists the host meshes of what left (module docstring, "Moving volume")."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
@@ -373,7 +529,10 @@ class SequenceFusion3d:
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
                  photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None,
-                 icp_robust=None, sdf_tracker=None):
+                 icp_robust=None, sdf_tracker=None, moving_volume=None):
+        if moving_volume is not None and not isinstance(moving_volume, MovingVolume):
+            raise ValueError("moving_volume must be a fusion.MovingVolume or None, got %r" % (moving_volume,))
+        self.moving_volume = moving_volume
         if confidence is not None and not isinstance(confidence, DepthConfidence):
             raise ValueError("confidence must be a fusion.DepthConfidence or None, got %r" % (confidence,))
         self.carve, self.confidence = bool(carve), confidence
@@ -394,6 +553,8 @@ class SequenceFusion3d:
         self.array_offset = np.asarray(array_offset, dtype=np.float64).reshape(-1)
         if self.array_offset.size != 3:
             raise ValueError("array_offset must have 3 entries, got %d" % self.array_offset.size)
+        self.initial_array_offset = self.array_offset.copy()  # a moving_volume moves array_offset; this one stays
+        self.streamed_meshes = []  # a moving_volume with stream_mesh: the host meshes of the cells that left
         if not voxel_size > 0 or not narrow_band_width_voxels > 0:
             raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
         if int(rigid_iterations) < 0:
@@ -561,6 +722,14 @@ class SequenceFusion3d:
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
                  "fusion": unpack(record.cpu().numpy()),
                  "prediction_hits": None if hits is None else int(hits.item())}
+        if self.moving_volume is not None:  # between frames: the policy reads the frame's twist, already on the host
+            mv = self.moving_volume
+            s = mv.shift_for(frame["twist"], self.array_offset, self.field_shape, self.voxel_size)
+            self.array_offset, chunks = model.shift(s, self.array_offset, self.voxel_size, mv.stream_mesh,
+                                                    mv.min_weight, mv.normals, colours=mv.stream_mesh and self.colour)
+            self.streamed_meshes.extend(chunks)
+            frame["shift"] = s
+            frame["streamed_faces"] = int(sum(len(c[1]) for c in chunks))
         if self.tracking_reference == "raycast":
             self._previous = (depth, code)
         self.twists.append(frame["twist"].copy())
@@ -568,7 +737,25 @@ class SequenceFusion3d:
         return frame
 
     def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False, colours=False,
-                     default_colour=device_mesh.DEFAULT_COLOUR):
-        """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size"""
-        return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
-                                           colours, default_colour)
+                     default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False):
+        """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size.  With
+        include_streamed (a sequence made with a moving_volume that streams) the window's mesh is followed by the
+        streamed chunks, merge_meshes of them all: host arrays only, and only as the chunks were made -- iso 0, the
+        policy's min_weight and normals, colours exactly when the sequence has colour, the default default_colour;
+        anything else raises, since the chunks cannot be drawn again"""
+        if not include_streamed:
+            return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
+                                               colours, default_colour)
+        mv = self.moving_volume
+        if mv is None or not mv.stream_mesh:
+            raise ValueError("include_streamed needs a sequence made with a moving_volume that has stream_mesh=True")
+        same = (not as_tensor and iso == 0.0 and float(min_weight) == mv.min_weight and bool(normals) == mv.normals
+                and bool(colours) == self.colour
+                and device_mesh.default_colour_of(default_colour) == device_mesh.DEFAULT_COLOUR)
+        if not same:
+            raise ValueError("include_streamed gives host meshes with the attributes the chunks were streamed with: "
+                             "iso=0, min_weight=%r, normals=%r, colours=%r, the default default_colour, as_tensor=False"
+                             % (mv.min_weight, mv.normals, self.colour))
+        window = self.canonical.extract_mesh(self.array_offset, self.voxel_size, 0.0, mv.min_weight, mv.normals, False,
+                                             self.colour)
+        return merge_meshes([window] + self.streamed_meshes)
