@@ -546,6 +546,26 @@ int lsf_state_run_finish(const lsf_state_run *run, const lsf_slavcheva_params *p
                          float *live_out,
                          float lower_threshold, double *statistics16, double *finalize_scratch, int64_t *words_device,
                          int64_t *words_host, lsf_state_run_result *result, void *stream);
+/* lsf_state_run_finish with RECORD ROWS.  No launch of a fixed-count call (loop NULL, or min_iterations >= iterations) reads
+ * a record, so with a rows buffer its iteration launches end without the workgroup-wide reduction and the atomics: every
+ * wave stores one row {max_packed, three energy sums} of 4 int64, and ONE launch behind the last iteration (one workgroup
+ * per iteration, a fixed association: the same bits on every run) combines each iteration's rows into slot 0 of its record
+ * and zeroes the other slots' used words -- the finalize pass's guard, words_host and `result` are what
+ * lsf_state_run_finish gives, the energies to the rounding of another order of float64 adds.  record_rows: DEVICE memory,
+ * 32-byte aligned, contents undefined on entry, record_rows_elements >= lsf_state_run_rows_elements(&run->grid, iterations,
+ * launches per iteration) int64 or the call is refused before it launches anything; NULL: lsf_state_run_finish.  A call
+ * whose stop test can fire keeps the atomics (the next launch's gate and the host read its records between launches) and
+ * leaves the buffer alone.  *rows_taken (may be NULL): 1 when the launches ended in rows, else 0. */
+int lsf_state_run_finish_rows(const lsf_state_run *run, const lsf_slavcheva_params *params, int32_t *list_interior,
+                              int32_t *list_boundary, lsf_band_box *boxes, float *box_canonical,
+                              lsf_iteration_record *records, int32_t iterations, const lsf_run_loop *loop, float *live_out,
+                              float lower_threshold, double *statistics16, double *finalize_scratch, int64_t *words_device,
+                              int64_t *words_host, lsf_state_run_result *result, int64_t *record_rows,
+                              int64_t record_rows_elements, int32_t *rows_taken, void *stream);
+/* int64 elements of record_rows for `iterations` iterations of n_lists launches each (1, or 2 when totals_host[0] and [1] are
+ * both non-zero) on this grid, whatever the lists' lengths: the launchers' own largest grids, one row per wave; 0 for
+ * arguments that make no call. */
+int64_t lsf_state_run_rows_elements(const lsf_grid *grid, int32_t iterations, int32_t n_lists);
 
 /* The SobolevFusion counterpart of lsf_state_run_finish (round 6): the loop of slavcheva_optimizer2d.py:354-388 WITH a Sobolev
  * filter, for whole 3-D volumes of whole boxes (the conditions of lsf_sobolev_state_update_boxes), behind a

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "88f9a6300475259d"
+HEADER_ABI_HASH = "e7f8790ad697fe6d"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -441,6 +441,10 @@ PROTOTYPES = {
     "lsf_slavcheva_state_iteration_boxes": (ctypes.c_int, [_vp, _vp, _vp, _P(Grid), _P(SlavchevaParams), _P(Gate), _vp, _vp,
                                                            _i64, _vp]),
     "lsf_state_run_begin": (ctypes.c_int, [_P(StateRun), _vp]),
+    "lsf_state_run_finish_rows": (ctypes.c_int, [_P(StateRun), _P(SlavchevaParams), _vp, _vp, _vp, _vp, _vp, _i32, _P(RunLoop),
+                                                 _vp, _f32, _vp, _vp, _vp, _vp, _P(StateRunResult), _vp, ctypes.c_int64,
+                                                 _P(ctypes.c_int32), _vp]),
+    "lsf_state_run_rows_elements": (ctypes.c_int64, [_P(Grid), _i32, _i32]),
     "lsf_state_run_finish": (ctypes.c_int, [_P(StateRun), _P(SlavchevaParams), _vp, _vp, _vp, _vp, _vp, _i32, _P(RunLoop), _vp,
                                             _f32, _vp, _vp, _vp, _vp, _P(StateRunResult), _vp]),
     "lsf_sobolev_run_finish": (ctypes.c_int, [_P(StateRun), _P(SlavchevaParams), _P(ctypes.c_double), _i32, _vp, _vp, _vp, _vp,

@@ -368,6 +368,15 @@ __host__ inline unsigned band_list_blocks(unsigned count, unsigned default_per_x
     return kXcds * ((per_xcd + rounds - 1) / rounds);
 }
 
+// the largest grid band_list_blocks gives for any list of at most `count` entries (its result is not monotonic: one
+// unit per XCD beyond the cap halves it)
+__host__ inline unsigned band_list_blocks_max(unsigned count, unsigned default_per_xcd = 256u) {
+    const unsigned units = (count + kBlock - 1) / kBlock;
+    if (units <= kXcds) return units < 1 ? 1 : units;
+    const unsigned per_xcd = (units + kXcds - 1) / kXcds;
+    return kXcds * (per_xcd < default_per_xcd ? per_xcd : default_per_xcd);
+}
+
 // (A dynamic variant -- per-XCD work queues with atomic heads and stealing -- was measured and rejected: device-scope
 // returning atomics on a contended address serialise at ~140 ns here, 16 K grabs per 256^3 launch cost 0.29 ms.)
 
@@ -589,6 +598,28 @@ __device__ inline void block_reduce_commit(unsigned long long packed, const doub
     }
 }
 
+// The other way for a workgroup of an iteration kernel to end (fixed-count library calls, lsf_state_run_finish): nothing
+// reads a record before the call's end there, so every WAVE leaves its packed maximum and its three sums in a row of its
+// own -- rows[block * waves + wave], one 32-byte store of lane 0 -- and records_from_rows_kernel combines the rows of all
+// the call's launches once, behind the last iteration.  No barrier, no LDS, no second stage, no atomic; a wave that
+// processed nothing stores zeros, so a launch defines every row of its block.  Must be called by every thread of the block.
+struct alignas(32) RecordRow {
+    unsigned long long max_packed;
+    double data, smoothing, level_set;
+};
+
+__device__ inline void wave_reduce_store_row(unsigned long long packed, const double (&sums)[3], RecordRow* __restrict__ rows) {
+    RecordRow r;
+    r.max_packed = wave_max_u64(packed);
+    r.data = wave_sum_f64(sums[0]);
+    r.smoothing = wave_sum_f64(sums[1]);
+    r.level_set = wave_sum_f64(sums[2]);
+    if ((threadIdx.x & (kWave - 1)) == 0) rows[blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave] = r;
+}
+
+// the rows one launch of `blocks` workgroups of `threads` threads writes
+__host__ inline unsigned launch_rows(unsigned blocks, unsigned threads) { return blocks * (threads / kWave); }
+
 // taps of one separable-filter pass, by value in the kernel arguments
 template <int NT>
 struct TapsN {
@@ -664,5 +695,33 @@ inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int launch_status() { return (int)hipGetLastError(); }
+
+// What lsf_slavcheva_state_iteration and lsf_slavcheva_state_iteration_boxes forward to (lsf_slavcheva_state.hip,
+// lsf_slavcheva_box.hip), with the row ending on top: rows != NULL -> the launch (a list or box walk, no gate) leaves its
+// waves' results in rows[0 .. *rows_written) and touches no record; refused before anything is launched when that is more
+// than rows_capacity.  *_rows_max: the most rows one such launch can write on this grid.
+int state_iteration_launch(const float* state_in, const float* canonical, float* state_out, const lsf_grid* grid,
+                           const lsf_slavcheva_params* params, const lsf_gate* gate, lsf_iteration_record* record,
+                           const int32_t* band_list, int64_t band_count, int32_t band_subset, RecordRow* rows,
+                           unsigned rows_capacity, unsigned* rows_written, void* stream);
+int state_iteration_boxes_launch(const float* state_in, const float* canonical_boxed, float* state_out, const lsf_grid* grid,
+                                 const lsf_slavcheva_params* params, const lsf_gate* gate, lsf_iteration_record* record,
+                                 const lsf_band_box* boxes, int64_t box_count, RecordRow* rows, unsigned rows_capacity,
+                                 unsigned* rows_written, void* stream);
+// lsf_state_prepare (lsf_slavcheva.hip); zero_fifth: its scan also writes counts_out[4] = 0 (the number of boxes of a
+// library-enqueued call that counts none: no memset launch for one word)
+int state_prepare_launch(const float* live, const float* canonical, float* state_a, float* state_b, const lsf_grid* grid,
+                         int32_t* scratch, int64_t* counts_out, bool zero_fifth, void* stream);
+unsigned state_iteration_rows_max(const lsf_grid* grid);
+unsigned state_iteration_boxes_rows_max(const lsf_grid* grid);
+// lsf_state_finalize_listed (lsf_slavcheva_state.hip) whose one-block combine kernel also gathers the four used words of
+// the n_word_slots slots of word_records, and the 16 statistics behind them, into words_out (statistics16 required)
+int state_finalize_listed_launch(const float* state, const float* canonical, float* live_out, float* warp_interleaved_out,
+                                 const lsf_grid* grid, const int32_t* const* band_lists, const int64_t* band_counts,
+                                 int32_t n_lists, int64_t opposite_count, int64_t first_opposite, float lower_threshold,
+                                 double* statistics16, double* scratch, const int32_t* skip_flag,
+                                 const lsf_iteration_record* guard_records, int32_t guard_count, float guard_limit,
+                                 const lsf_iteration_record* word_records, int32_t n_word_slots, int64_t* words_out,
+                                 void* stream);
 
 }  // namespace lsf

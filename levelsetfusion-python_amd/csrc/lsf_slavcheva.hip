@@ -447,10 +447,11 @@ __global__ __launch_bounds__(1024) void band_tile_totals_kernel(const int* __res
 
 __global__ __launch_bounds__(1024) void band_scan_tiles_kernel(int* __restrict__ sums_base, unsigned n, unsigned stride,
                                                                const int* __restrict__ tile_out, unsigned tiles,
-                                                               long long* __restrict__ totals) {
+                                                               long long* __restrict__ totals, int zero_fifth) {
     const unsigned tile = blockIdx.x, a = blockIdx.y, t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
     if (a == 2u) {  // the unlisted voxels with live = -canonical: their number and the first of them (one thread: <= 256 tiles)
         if (tile == 0u && t == 0u) {
+            if (zero_fifth) totals[4] = 0;  // (library-enqueued calls that count no boxes: the fifth total, without a memset)
             long long sum = 0;
             int first = 0x7fffffff;
             for (unsigned k = 0; k < tiles; ++k) {
@@ -668,13 +669,11 @@ __global__ __launch_bounds__(kBlock) void state_prepare4_kernel(const vf4* __res
 // from the chunks' non-empty flags (written by lsf_state_prepare), then the needed chunks written as (live, 0) to both
 // states; needed[c] keeps the verdict for whoever has to complete a state later (invert != 0: write exactly the chunks
 // NOT needed, from the kept verdicts).
-// step 1: the verdicts.  One WAVE per chunk, the (dz, dy) offsets dealt to its lanes (25 of them at reach 2: one round; a
-// thread per chunk walked them one after the other, 12 us at 256^3 for a few dozen dependent flag loads each)
-__global__ __launch_bounds__(kBlock) void chunk_needed_kernel(unsigned chunks, long long row, long long slice, int dims,
-                                                              int reach, const int* __restrict__ nonempty,
-                                                              int* __restrict__ needed) {
-    const unsigned c = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    if (c >= chunks) return;
+// step 1: the verdict of chunk c < chunks.  One WAVE per chunk, the (dz, dy) offsets dealt to its lanes (25 of them at reach
+// 2: one round; a thread per chunk walked them one after the other, 12 us at 256^3 for a few dozen dependent flag loads
+// each).  Called by a whole wave; the same answer in every lane.
+__device__ inline bool chunk_is_needed(unsigned c, unsigned chunks, long long row, long long slice, int dims, int reach,
+                                       const int* __restrict__ nonempty) {
     const int lane = threadIdx.x % kWave;
     const long long c0 = (long long)c * kBandChunk;
     const int span = 2 * reach + 1, zs = dims == 3 ? span : 1;
@@ -689,23 +688,41 @@ __global__ __launch_bounds__(kBlock) void chunk_needed_kernel(unsigned chunks, l
         last = last >= (long long)chunks ? (long long)chunks - 1 : last;
         for (long long cand = first; cand <= last; ++cand) hit |= nonempty[cand] != 0;
     }
-    const bool any = __any(hit);
-    if (lane == 0) needed[c] = any ? 1 : 0;
+    return __any(hit);
 }
 
 // step 2: (live, 0) into both states for the chunks whose verdict equals `want`: one chunk per block (four per block
 // measured slower, 58 against 46 us at 256^3: the needed chunks come in runs, and a block that draws four of them keeps
-// its CU's other slots waiting), two chunks in three leave after one load on a narrow band
+// its CU's other slots waiting), two chunks in three leave after one load on a narrow band.  reach > 0: step 1 happens
+// here -- wave k of the block forms the verdict of the block's k-th chunk and keeps it in needed[], the block goes on behind
+// one barrier (a launch of its own for the verdicts was 5 us at 256^3, the floor of any launch); reach == 0: the kept
+// verdicts are read.
 constexpr int kPackChunks = 1;
+static_assert(kPackChunks <= kBlock / kWave, "a wave per chunk of the block forms the verdicts");
 __global__ __launch_bounds__(kBlock) void state_pack_needed_kernel(const float* __restrict__ live, vf4* __restrict__ a,
                                                                    vf4* __restrict__ b, unsigned n, unsigned chunks,
-                                                                   const int* __restrict__ needed, int want) {
+                                                                   int* __restrict__ needed, int want, int reach,
+                                                                   long long row, long long slice, int dims,
+                                                                   const int* __restrict__ nonempty) {
     const int t = threadIdx.x;
+    __shared__ int s_verdict[kPackChunks];
+    if (reach > 0) {  // (uniform over the launch)
+        const int k = t / kWave;
+        const unsigned c = blockIdx.x * kPackChunks + k;
+        if (k < kPackChunks && c < chunks) {
+            const int any = chunk_is_needed(c, chunks, row, slice, dims, reach, nonempty) ? 1 : 0;
+            if (t % kWave == 0) {
+                needed[c] = any;
+                s_verdict[k] = any;
+            }
+        }
+        __syncthreads();
+    }
     int verdict[kPackChunks];
 #pragma unroll
     for (int k = 0; k < kPackChunks; ++k) {
         const unsigned c = blockIdx.x * kPackChunks + k;
-        verdict[k] = c < chunks ? needed[c] : -1;
+        verdict[k] = c < chunks ? (reach > 0 ? s_verdict[k] : needed[c]) : -1;
     }
 #pragma unroll
     for (int k = 0; k < kPackChunks; ++k) {
@@ -1023,6 +1040,11 @@ extern "C" int lsf_band_boxes_fill(const lsf_grid* grid, int32_t subset, const i
 
 extern "C" int lsf_state_prepare(const float* live, const float* canonical, float* state_a, float* state_b,
                                  const lsf_grid* grid, int32_t* scratch, int64_t* counts_out, void* stream) {
+    return state_prepare_launch(live, canonical, state_a, state_b, grid, scratch, counts_out, false, stream);
+}
+
+int lsf::state_prepare_launch(const float* live, const float* canonical, float* state_a, float* state_b, const lsf_grid* grid,
+                              int32_t* scratch, int64_t* counts_out, bool zero_fifth, void* stream) {
     if (int e = check_grid(grid, true)) return e;
     // state_b: optional; state_a AND state_b NULL: the states are written by lsf_state_pack_needed
     if (!live || !canonical || (!state_a && state_b) || !scratch || !counts_out) return LSF_ERR_BAD_ARGUMENT;
@@ -1045,11 +1067,12 @@ extern "C" int lsf_state_prepare(const float* live, const float* canonical, floa
                            sums_interior, sums_boundary, prepare_masks(scratch, chunks), prepare_opposite(scratch, chunks),
                            prepare_nonempty(scratch, chunks));
     // the scan of the two count arrays and the reduction of the unlisted voxels' counts: a block per tile of 4096 chunks
+    // (zero_fifth: the second launch also writes the fifth total)
     const unsigned tiles = prepare_scan_tiles(chunks) > 0u ? prepare_scan_tiles(chunks) : 1u;
     hipLaunchKernelGGL(band_tile_totals_kernel, dim3(tiles, 3), dim3(1024), 0, s, scratch, chunks, chunks + 1,
                        (const int*)prepare_opposite(scratch, chunks), prepare_tile_totals(scratch, chunks), tiles);
     hipLaunchKernelGGL(band_scan_tiles_kernel, dim3(tiles, 3), dim3(1024), 0, s, scratch, chunks, chunks + 1,
-                       (const int*)prepare_tile_totals(scratch, chunks), tiles, (long long*)counts_out);
+                       (const int*)prepare_tile_totals(scratch, chunks), tiles, (long long*)counts_out, zero_fifth ? 1 : 0);
     return launch_status();
 }
 
@@ -1060,13 +1083,11 @@ extern "C" int lsf_state_pack_needed(const float* live, float* state_a, float* s
     if (grid->z_begin != 0 || grid->z_end != grid->nz) return LSF_ERR_BAD_ARGUMENT;  // whole arrays only
     unsigned first, n, chunks;
     band_range(grid, first, n, chunks);
-    if (!invert)
-        hipLaunchKernelGGL(chunk_needed_kernel, dim3((chunks + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, as_stream(stream),
-                           chunks, (long long)grid->nx, (long long)grid->nx * grid->ny, grid->dims, reach,
-                           prepare_nonempty(scratch, chunks), prepare_needed(scratch, chunks));
+    // invert == 0: the kernel forms the verdicts itself and keeps them; invert != 0: it reads the kept ones
     hipLaunchKernelGGL(state_pack_needed_kernel, dim3((chunks + kPackChunks - 1) / kPackChunks), dim3(kBlock), 0,
                        as_stream(stream), live, reinterpret_cast<vf4*>(state_a), reinterpret_cast<vf4*>(state_b), n, chunks,
-                       prepare_needed(scratch, chunks), invert ? 0 : 1);
+                       prepare_needed(scratch, chunks), invert ? 0 : 1, invert ? 0 : (int)reach, (long long)grid->nx,
+                       (long long)grid->nx * grid->ny, grid->dims, (const int*)prepare_nonempty(scratch, chunks));
     return launch_status();
 }
 

@@ -84,7 +84,7 @@ template <int SMOOTH, bool LEVELSET, int DATA, int ENERGY>
 __global__ __launch_bounds__(kBoxThreads) __attribute__((amdgpu_waves_per_eu(kBoxWaves / 4, kBoxWaves / 4)))
 void slavcheva_state_box_kernel(const vf4* __restrict__ state_in, const float* __restrict__ canonical_boxed,
                                 vf4* __restrict__ state_out, Grid g, Params p, lsf_gate gate, lsf_iteration_record* record,
-                                const lsf_band_box* __restrict__ boxes, unsigned box_count) {
+                                const lsf_band_box* __restrict__ boxes, unsigned box_count, RecordRow* __restrict__ rows) {
     g.y_global_offset = 0;  // whole volumes and z-slabs: every row is a row of the volume, every row's energies count
     g.ny_global = g.ny;
     g.y_cut = 0;
@@ -239,7 +239,9 @@ void slavcheva_state_box_kernel(const vf4* __restrict__ state_in, const float* _
     double* dst[3] = {ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->data_energy : nullptr,
                       ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->smoothing_energy : nullptr,
                       ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->level_set_energy : nullptr};
-    block_reduce_commit<3>(best, en, record_max(record), dst);
+    // rows (wave-uniform, a kernel argument): the launch's own row block of a fixed-count library call -- no record is touched
+    if (rows) wave_reduce_store_row(best, en, rows);
+    else block_reduce_commit<3>(best, en, record_max(record), dst);
 }
 
 struct BoxLaunch {
@@ -254,6 +256,7 @@ struct BoxLaunch {
     lsf_iteration_record* record;
     const lsf_band_box* boxes;
     unsigned box_count;
+    RecordRow* rows;
 };
 
 constexpr size_t kBoxLdsBytes = (size_t)kBoxWaves * 2 * kImage * sizeof(vf4);  // 136 KiB with 16 waves
@@ -271,7 +274,7 @@ int launch_box(const BoxLaunch& a) {
         configured[dev] = true;
     }
     hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(kBoxThreads), kBoxLdsBytes, a.s, a.state_in, a.canonical, a.state_out, a.g,
-                       a.p, a.gate, a.record, a.boxes, a.box_count);
+                       a.p, a.gate, a.record, a.boxes, a.box_count, a.rows);
     return 0;
 }
 
@@ -338,6 +341,22 @@ extern "C" int lsf_slavcheva_state_iteration_boxes(const float* state_in, const 
                                                    const lsf_grid* grid, const lsf_slavcheva_params* params,
                                                    const lsf_gate* gate, lsf_iteration_record* record,
                                                    const lsf_band_box* boxes, int64_t box_count, void* stream) {
+    return state_iteration_boxes_launch(state_in, canonical_boxed, state_out, grid, params, gate, record, boxes, box_count,
+                                        nullptr, 0u, nullptr, stream);
+}
+
+// the most rows a box launch on this grid can write: one workgroup of kBoxWaves waves per CU
+unsigned lsf::state_iteration_boxes_rows_max(const lsf_grid* grid) {
+    const long long n = (long long)grid->nz * grid->ny * grid->nx;
+    const unsigned count = (unsigned)(n < 0x0fffffffll ? n : 0x0fffffffll);
+    return launch_rows(cu_list_blocks(count, box_compute_units()), kBoxThreads);
+}
+
+int lsf::state_iteration_boxes_launch(const float* state_in, const float* canonical_boxed, float* state_out,
+                                      const lsf_grid* grid, const lsf_slavcheva_params* params, const lsf_gate* gate,
+                                      lsf_iteration_record* record, const lsf_band_box* boxes, int64_t box_count,
+                                      RecordRow* rows, unsigned rows_capacity, unsigned* rows_written, void* stream) {
+    if (rows_written) *rows_written = 0u;
     if (int e = check_grid(grid)) return e;
     if (!state_in || !canonical_boxed || !state_out || state_out == state_in || !params || !record || !boxes || box_count < 0 ||
         box_count > 0x3ffffffll)
@@ -349,9 +368,14 @@ extern "C" int lsf_slavcheva_state_iteration_boxes(const float* state_in, const 
     if (box_count == 0) return 0;
     Grid g = make_grid(grid, 4);
     g.list_store_nt = box_count * 64ll * 32ll > 200ll * 1000 * 1000 * 5 / 4;  // as the list walk: lists too long for the Infinity Cache
-    BoxLaunch a{cu_list_blocks((unsigned)box_count * kWave, box_compute_units()), as_stream(stream),
-                reinterpret_cast<const vf4*>(state_in), canonical_boxed, reinterpret_cast<vf4*>(state_out), g, box_params(params),
-                gate_or_open(gate), record, boxes, (unsigned)box_count};
+    const unsigned blocks = cu_list_blocks((unsigned)box_count * kWave, box_compute_units());
+    if (rows) {  // as the list walk's launcher: no gate, and only into a block of rows that holds the whole launch
+        if (gate || launch_rows(blocks, kBoxThreads) > rows_capacity) return LSF_ERR_BAD_ARGUMENT;
+        if (rows_written) *rows_written = launch_rows(blocks, kBoxThreads);
+    }
+    BoxLaunch a{blocks, as_stream(stream), reinterpret_cast<const vf4*>(state_in), canonical_boxed,
+                reinterpret_cast<vf4*>(state_out), g, box_params(params), gate_or_open(gate), record, boxes,
+                (unsigned)box_count, rows};
     const bool killing = params->smoothing_method == LSF_SMOOTHING_KILLING;
     const bool ls = params->level_set_enabled != 0;
     const bool fdm = params->data_method == LSF_DATA_THRESHOLDED_FDM;

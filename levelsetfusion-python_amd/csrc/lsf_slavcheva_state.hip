@@ -50,7 +50,7 @@ void slavcheva_state_kernel(const vf4* __restrict__ state_in,
                                                                  vf4* __restrict__ state_out, Grid g, Params p,
                                                                  lsf_gate gate, lsf_iteration_record* record,
                                                                  const int* __restrict__ band_list,
-                                                                 unsigned band_count) {
+                                                                 unsigned band_count, RecordRow* __restrict__ rows) {
     constexpr int WALK = walk_of(WALK_CODE);
     if (WALK_CODE == WALK) {  // not cut along y: every row is a row of the volume, every row's energies count
         g.y_global_offset = 0;
@@ -302,7 +302,9 @@ void slavcheva_state_kernel(const vf4* __restrict__ state_in,
     double* dst[3] = {ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->data_energy : nullptr,
                       ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->smoothing_energy : nullptr,
                       ENERGY != LSF_ENERGY_NONE ? &record_slot(record)->level_set_energy : nullptr};
-    block_reduce_commit<3>(best, en, record_max(record), dst);
+    // rows (wave-uniform, a kernel argument): the launch's own row block of a fixed-count library call -- no record is touched
+    if (rows) wave_reduce_store_row(best, en, rows);
+    else block_reduce_commit<3>(best, en, record_max(record), dst);
 #ifdef LSF_STATE_TRACE
     if (wave_row && (threadIdx.x & 63) == 0) wave_row[3] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -500,7 +502,14 @@ __global__ __launch_bounds__(kBlock) void state_finalize_combine_kernel(const do
                                                                         unsigned rows, double voxels,
                                                                         double* __restrict__ out16, double unlisted,
                                                                         double opposite, long long first_opposite,
-                                                                        long long first_voxel) {
+                                                                        long long first_voxel,
+                                                                        const long long* __restrict__ word_records,
+                                                                        int n_word_slots, long long* __restrict__ words_out) {
+    // (library-enqueued calls) the four used words of every slot of the call's records -- a slot is 4 KiB -- and, below,
+    // the 16 statistics behind them: what goes to the host in ONE copy, without a launch of its own
+    if (words_out)
+        for (int k = threadIdx.x; k < n_word_slots * 4; k += kBlock)
+            words_out[k] = word_records[(long long)(k >> 2) * (sizeof(lsf_record_slot) / 8) + (k & 3)];
     unsigned long long best_w = 0ull, best_d = 0ull;
     double sums[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double mn = __longlong_as_double(0x7ff0000000000000ll);
@@ -560,6 +569,8 @@ __global__ __launch_bounds__(kBlock) void state_finalize_combine_kernel(const do
     out16[11] = t[4]; out16[12] = t[5];
     out16[13] = d ? (double)(~(unsigned)d) : -1.0;
     out16[14] = 0.0; out16[15] = 0.0;
+    if (words_out)
+        for (int j = 0; j < 16; ++j) words_out[n_word_slots * 4 + j] = __double_as_longlong(out16[j]);
 }
 
 struct LaunchArgs {
@@ -574,6 +585,7 @@ struct LaunchArgs {
     lsf_iteration_record* record;
     const int* band_list;
     unsigned band_count;
+    RecordRow* rows;
 };
 
 template <int D, int SMOOTH, bool LEVELSET, int DATA, int ENERGY, int WALK>
@@ -583,13 +595,13 @@ void launch_one(const LaunchArgs& a) {
             hipLaunchKernelGGL((slavcheva_state_kernel<D, SMOOTH, LEVELSET, DATA, ENERGY,
                                                        WALK == kWalkList ? kWalkListYCut : kWalkListInteriorYCut>),
                                dim3(a.blocks), dim3(a.threads), 0, a.s, a.state_in, a.canonical, a.state_out, a.g, a.p, a.gate,
-                               a.record, a.band_list, a.band_count);
+                               a.record, a.band_list, a.band_count, a.rows);
             return;
         }
     }
     hipLaunchKernelGGL((slavcheva_state_kernel<D, SMOOTH, LEVELSET, DATA, ENERGY, WALK>), dim3(a.blocks),
                        dim3(a.threads), 0, a.s, a.state_in, a.canonical, a.state_out, a.g, a.p, a.gate,
-                       a.record, a.band_list, a.band_count);
+                       a.record, a.band_list, a.band_count, a.rows);
 }
 
 template <int D, int SMOOTH, bool LEVELSET, int DATA, int WALK>
@@ -715,7 +727,7 @@ extern "C" int lsf_state_finalize(const float* state, const float* canonical, fl
                        slice * grid->z_global_offset, lower_threshold, statistics16 ? scratch : (double*)nullptr);
     if (statistics16)
         hipLaunchKernelGGL(state_finalize_combine_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), scratch, blocks,
-                           (double)n, statistics16, 0.0, 0.0, 0ll, 0ll);
+                           (double)n, statistics16, 0.0, 0.0, 0ll, 0ll, (const long long*)nullptr, 0, (long long*)nullptr);
     return launch_status();
 }
 
@@ -735,7 +747,7 @@ extern "C" int lsf_planar_finalize(const float* live, const float* warp_planar, 
                        statistics16 ? scratch : (double*)nullptr);
     if (statistics16)
         hipLaunchKernelGGL(state_finalize_combine_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), scratch, blocks,
-                           (double)n, statistics16, 0.0, 0.0, 0ll, 0ll);
+                           (double)n, statistics16, 0.0, 0.0, 0ll, 0ll, (const long long*)nullptr, 0, (long long*)nullptr);
     return launch_status();
 }
 
@@ -746,7 +758,20 @@ extern "C" int lsf_state_finalize_listed(const float* state, const float* canoni
                                          double* statistics16, double* scratch, const int32_t* skip_flag,
                                          const lsf_iteration_record* guard_records, int32_t guard_count, float guard_limit,
                                          void* stream) {
+    return state_finalize_listed_launch(state, canonical, live_out, warp_interleaved_out, grid, band_lists, band_counts, n_lists,
+                                        opposite_count, first_opposite, lower_threshold, statistics16, scratch, skip_flag,
+                                        guard_records, guard_count, guard_limit, nullptr, 0, nullptr, stream);
+}
+
+int lsf::state_finalize_listed_launch(const float* state, const float* canonical, float* live_out, float* warp_interleaved_out,
+                                      const lsf_grid* grid, const int32_t* const* band_lists, const int64_t* band_counts,
+                                      int32_t n_lists, int64_t opposite_count, int64_t first_opposite, float lower_threshold,
+                                      double* statistics16, double* scratch, const int32_t* skip_flag,
+                                      const lsf_iteration_record* guard_records, int32_t guard_count, float guard_limit,
+                                      const lsf_iteration_record* word_records, int32_t n_word_slots, int64_t* words_out,
+                                      void* stream) {
     if (int e = check_grid(grid, true)) return e;
+    if (words_out && (!statistics16 || !word_records || n_word_slots < 0)) return LSF_ERR_BAD_ARGUMENT;
     if (statistics16 && grid_is_y_cut(grid)) return LSF_ERR_BAD_ARGUMENT;  // the statistics report z-cut indices only
     if (!state || n_lists < 0 || n_lists > 2 || (n_lists && (!band_lists || !band_counts)) ||
         (statistics16 && (!canonical || !scratch)) || grid->z_begin != 0 || grid->z_end != grid->nz)
@@ -772,7 +797,9 @@ extern "C" int lsf_state_finalize_listed(const float* state, const float* canoni
         const long long first_voxel = (long long)grid->ny * grid->nx * grid->z_global_offset;
         hipLaunchKernelGGL(state_finalize_combine_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), scratch, rows,
                            (double)n, statistics16, (double)(n - listed), (double)opposite_count,
-                           (long long)first_opposite + first_voxel, first_voxel);
+                           (long long)first_opposite + first_voxel, first_voxel,
+                           reinterpret_cast<const long long*>(word_records), (int)n_word_slots,
+                           reinterpret_cast<long long*>(words_out));
     }
     return launch_status();
 }
@@ -782,6 +809,25 @@ extern "C" int lsf_slavcheva_state_iteration(const float* state_in, const float*
                                              const lsf_gate* gate, lsf_iteration_record* record,
                                              const int32_t* band_list, int64_t band_count, int32_t band_subset,
                                              void* stream) {
+    return state_iteration_launch(state_in, canonical, state_out, grid, params, gate, record, band_list, band_count,
+                                  band_subset, nullptr, 0u, nullptr, stream);
+}
+
+// the most rows a list launch on this grid can write, whatever the list's length: the INTERIOR walk's one CU-sized
+// workgroup per CU, or the general list walk's largest grid
+unsigned lsf::state_iteration_rows_max(const lsf_grid* grid) {
+    const long long n = (long long)grid->nz * grid->ny * grid->nx;
+    const unsigned count = (unsigned)(n < 0x7fffffffll ? n : 0x7fffffffll);
+    const unsigned interior = launch_rows(cu_list_blocks(count, compute_units()), kCuBlock);
+    const unsigned general = launch_rows(band_list_blocks_max(count, 128u), kBlock);
+    return interior > general ? interior : general;
+}
+
+int lsf::state_iteration_launch(const float* state_in, const float* canonical, float* state_out, const lsf_grid* grid,
+                                const lsf_slavcheva_params* params, const lsf_gate* gate, lsf_iteration_record* record,
+                                const int32_t* band_list, int64_t band_count, int32_t band_subset, RecordRow* rows,
+                                unsigned rows_capacity, unsigned* rows_written, void* stream) {
+    if (rows_written) *rows_written = 0u;
     if (int e = check_grid(grid, /*allow_y_cut=*/true)) return e;
     if (!state_in || !canonical || !state_out || state_out == state_in || !params || !record)
         return LSF_ERR_BAD_ARGUMENT;
@@ -819,9 +865,16 @@ extern "C" int lsf_slavcheva_state_iteration(const float* state_in, const float*
     g.list_group = LSF_LIST_GROUP;
 #endif
     g.list_store_nt = listed && band_count * 32ll > 200ll * 1000 * 1000;
-    LaunchArgs a{blocks, all_interior ? list_threads : (unsigned)(kTileX * tile_y), as_stream(stream), reinterpret_cast<const vf4*>(state_in), canonical,
+    const unsigned threads = all_interior ? list_threads : (unsigned)(kTileX * tile_y);
+    if (rows) {
+        // the row ending: list walks without a gate (a launch its gate closed would leave its rows undefined), and only
+        // into a block of rows that holds the whole launch
+        if (!listed || gate || launch_rows(blocks, threads) > rows_capacity) return LSF_ERR_BAD_ARGUMENT;
+        if (rows_written) *rows_written = launch_rows(blocks, threads);
+    }
+    LaunchArgs a{blocks, threads, as_stream(stream), reinterpret_cast<const vf4*>(state_in), canonical,
                  reinterpret_cast<vf4*>(state_out), g, make_params(params), gate_or_open(gate), record, band_list,
-                 (unsigned)band_count};
+                 (unsigned)band_count, rows};
     if (grid->dims == 2) {
         if (all_interior) pick_terms<2, kWalkListInterior>(params, a);
         else if (listed) pick_terms<2, kWalkList>(params, a);

@@ -10,6 +10,8 @@ SLAVCHEVA_DEFAULTS = dict(
     use_band_list=True,    # False: the fused kernel walks every voxel (measurements, tests)
     library_run=True,      # whole calls enqueued by the library (lsf_state_run_* / lsf_slab_run_*); False: one foreign call
                            # per launch (tests hold the two against each other)
+    record_rows=True,      # fixed-count library calls: the iteration launches end in one stored row per wave, combined once
+                           # per call (lsf_state_run::record_rows); False: every launch reduces into its record by atomics
     box_walk=None,         # None: by band size (box_walk_min_band_bytes); True / False: always / never
     sobolev_boxes=True,    # SobolevFusion on whole 3-D volumes: y pass, z pass and update box by box (False: lists)
     # The ping-pong states are initialised only where an iteration can read them while every update stays below this many
@@ -62,4 +64,4 @@ def apply(engine, defaults, options):
 def new_call_report():
     """what the last optimize() call took: tests and measurements read it instead of private attributes"""
     return types.SimpleNamespace(sparse_states=False, box_walk=False, sobolev_boxes=False, library_run=False,
-                                 blocked_levels=0)
+                                 blocked_levels=0, record_rows=False)

@@ -91,6 +91,12 @@ class RunMixin:
             boxes = torch.empty((n_boxes, 2), dtype=torch.int64, device=device)
             box_canonical = torch.empty(n_boxes * dev.BOX_EDGE ** 3, dtype=torch.float32, device=device)
         self.last_call.box_walk = boxes is not None and not sobolev
+        record_rows = None
+        if loop is None and not sobolev and self.record_rows:
+            # a fixed count reads no record before its end: one row per wave of every launch, combined once per call
+            n_launches = int(n_interior > 0) + int(n_boundary > 0 or n_interior == 0)
+            record_rows = torch.empty(int(_lib.lib.lsf_state_run_rows_elements(ctypes.byref(whole), iterations, n_launches)),
+                                      dtype=torch.int64, device=device)
         records = dev.new_records(iterations, device)
         n_words = iterations * _lib.RECORD_SLOTS * dev.USED_SLOT_WORDS
         words = torch.empty(n_words + 16, dtype=torch.int64, device=device)  # the records' used words, then the statistics
@@ -130,7 +136,7 @@ class RunMixin:
                 ctypes.c_void_p(words_host.data_ptr()), ctypes.byref(result), stream), "lsf_sobolev_run_finish")
         else:
             self._run_finish(run, p_lists, n_interior, boxes, box_canonical, records, iterations, loop, target, n,
-                             lower_threshold, stats, stats_scratch, statistics, words, words_host, result, stream)
+                             lower_threshold, stats, stats_scratch, statistics, words, words_host, result, stream, record_rows)
         return self._after_run(result, executed, iterations, f, max_value, argmax, energies, weights, states, canonical, grid,
                                bands, outcome, statistics, words_host, n_words, g4[1] if sobolev else None)
 
@@ -155,9 +161,10 @@ class RunMixin:
         return g4
 
     def _run_finish(self, run, p_lists, n_interior, boxes, box_canonical, records, iterations, loop, target, n,
-                    lower_threshold, stats, stats_scratch, statistics, words, words_host, result, stream):
+                    lower_threshold, stats, stats_scratch, statistics, words, words_host, result, stream, record_rows=None):
         none = ctypes.c_void_p(0)
-        _lib.check(_lib.lib.lsf_state_run_finish(
+        rows_taken = ctypes.c_int32(0)
+        _lib.check(_lib.lib.lsf_state_run_finish_rows(
             ctypes.byref(run), ctypes.byref(self.params), ctypes.c_void_p(p_lists),
             ctypes.c_void_p(p_lists + 4 * n_interior), ctypes.c_void_p(boxes.data_ptr() if boxes is not None else 0),
             ctypes.c_void_p(box_canonical.data_ptr() if boxes is not None else 0),
@@ -165,7 +172,11 @@ class RunMixin:
             dev._ptr(target, n, "live_out"), float(lower_threshold),
             ctypes.c_void_p(stats.data_ptr()) if statistics else none,
             ctypes.c_void_p(stats_scratch.data_ptr()) if statistics else none, ctypes.c_void_p(words.data_ptr()),
-            ctypes.c_void_p(words_host.data_ptr()), ctypes.byref(result), stream), "lsf_state_run_finish")
+            ctypes.c_void_p(words_host.data_ptr()), ctypes.byref(result),
+            ctypes.c_void_p(record_rows.data_ptr()) if record_rows is not None else none,
+            record_rows.numel() if record_rows is not None else 0, ctypes.byref(rows_taken), stream),
+            "lsf_state_run_finish_rows")
+        self.last_call.record_rows = bool(rows_taken.value)
 
     def _after_run(self, result, executed, iterations, f, max_value, argmax, energies, weights, states, canonical, grid, bands,
                    outcome, statistics, words_host, n_words, sobolev_gradient):
