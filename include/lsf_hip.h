@@ -368,14 +368,16 @@ int lsf_band_list_fill(const float *live, const float *canonical, const lsf_grid
  * -- what lsf_state_finalize_listed needs to know about the voxels no list holds.  lsf_band_list_fill_prepared then writes one subset's list from the ballots the prepare pass kept
  * in scratch (16 bytes per 64 voxels) -- live and canonical are not read again.
  * state_a AND state_b NULL: the pass only counts; lsf_state_pack_needed then writes the two states (live, 0) ONLY where
- * an iteration can read them: the 1024-voxel chunks that have a voxel within `reach` voxels (per axis) of a chunk that
- * holds band voxels -- 3^D stencils reach 1, the re-warp gather of an update shorter than `reach` voxels reaches `reach`
+ * an iteration can read them: the groups of 32 consecutive voxels that have a voxel within `reach` voxels (per axis) of a
+ * band voxel -- 3^D stencils reach 1, the re-warp gather of an update shorter than `reach` voxels reaches `reach`
  * (1 <= reach <= 8).  Everything else of the two buffers stays UNINITIALISED: a run is valid only while every
  * iteration's maximum update stays below `reach` (lsf_state_finalize_listed's guard_records check that on the device,
  * the host on the records it reads), and whole-state readers (lsf_state_unpack, lsf_state_finalize) must first complete the state with
- * invert = 1 (writes exactly the chunks the first call left out, from the verdicts it kept in scratch).  On a narrow
- * band this replaces 2 x 16 B per VOXEL of initialisation by 2 x 16 B per voxel NEAR THE BAND (a quarter of a 256^3
- * sphere pair). */
+ * invert = 1 (writes exactly the groups the first call left out, from the verdicts it kept in scratch: a bit per group,
+ * an int32 per 1024 voxels).  On a narrow band this replaces 2 x 16 B per VOXEL of initialisation by 2 x 16 B per voxel
+ * NEAR THE BAND (a fifth of a 256^3 sphere pair).  Arrays of fewer than 2^21 voxels (LSF_SPARSE_MIN_VOXELS in the
+ * environment moves the limit) keep whole 1024-voxel chunks: a chunk near a chunk with band voxels is written whole and
+ * its kept word is 1. */
 int64_t lsf_state_prepare_scratch_elements(const lsf_grid *grid);
 int lsf_state_pack_needed(const float *live, float *state_a, float *state_b, const lsf_grid *grid, int32_t *scratch,
                           int32_t reach, int32_t invert, void *stream);

@@ -661,17 +661,20 @@ __global__ __launch_bounds__(kBlock) void state_prepare4_kernel(const vf4* __res
     }
 }
 
-// The ping-pong states only where an iteration can READ them (lsf_state_pack_needed): chunk c (1024 consecutive voxels) is
-// needed when some chunk that holds band voxels has a voxel within `reach` voxels of it along every axis -- the 3^D
-// stencils reach 1, the re-warp gather of an update shorter than `reach` voxels floor(|w|) + 1 <= reach.  In linear
-// indices: the voxels of chunk c shifted by dz * slice + dy * row, |dz|, |dy| <= reach, and widened by `reach` along x,
-// fall into at most three consecutive chunks per (dz, dy) -- row ends only ever add candidates.  Two steps: the verdicts
-// from the chunks' non-empty flags (written by lsf_state_prepare), then the needed chunks written as (live, 0) to both
-// states; needed[c] keeps the verdict for whoever has to complete a state later (invert != 0: write exactly the chunks
-// NOT needed, from the kept verdicts).
-// step 1: the verdict of chunk c < chunks.  One WAVE per chunk, the (dz, dy) offsets dealt to its lanes (25 of them at reach
-// 2: one round; a thread per chunk walked them one after the other, 12 us at 256^3 for a few dozen dependent flag loads
-// each).  Called by a whole wave; the same answer in every lane.
+// The ping-pong states only where an iteration can READ them (lsf_state_pack_needed): a GROUP of kPackGroup = 32
+// consecutive voxels (an aligned 512-byte run of float4 per state) is needed when a band voxel lies within `reach` voxels
+// of one of its voxels along every axis -- the 3^D stencils reach 1, the re-warp gather of an update shorter than `reach`
+// voxels floor(|w|) + 1 <= reach.  In linear indices: the voxels of the group shifted by dz * slice + dy * row, |dz|,
+// |dy| <= reach, and widened by `reach` along x, are a run of at most 32 + 2 * reach bits of the band ballots
+// lsf_state_prepare kept, in one or two of their 64-bit words -- row ends only ever add candidates, so ragged rows and
+// non-cubic volumes are no special case.  The same test per 1024-voxel CHUNK on the chunks' non-empty flags (at most three
+// consecutive chunks per (dz, dy)) comes first: a chunk it rules out holds no needed group, and two chunks in three of a
+// narrow band leave there.  The needed groups are written as (live, 0) to both states; needed[c] keeps chunk c's 32
+// verdicts, bit g = voxels 32 g ... of the chunk, for whoever has to complete a state later (invert != 0: write exactly
+// the groups NOT written, from the kept masks).
+// step 1a: is any group of chunk c < chunks needed at all.  One WAVE, the (dz, dy) offsets dealt to its lanes (25 of them
+// at reach 2: one round; a thread per chunk walked them one after the other, 12 us at 256^3 for a few dozen dependent flag
+// loads each).  Called by a whole wave; the same answer in every lane.
 __device__ inline bool chunk_is_needed(unsigned c, unsigned chunks, long long row, long long slice, int dims, int reach,
                                        const int* __restrict__ nonempty) {
     const int lane = threadIdx.x % kWave;
@@ -686,62 +689,119 @@ __device__ inline bool chunk_is_needed(unsigned c, unsigned chunks, long long ro
         long long last = hi >= 0 ? hi / kBandChunk : -((-hi + kBandChunk - 1) / kBandChunk);
         first = first < 0 ? 0 : first;
         last = last >= (long long)chunks ? (long long)chunks - 1 : last;
-        for (long long cand = first; cand <= last; ++cand) hit |= nonempty[cand] != 0;
+        // the (at most three) flags in one round of loads, not one behind the other
+        int flag[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) flag[j] = first + j <= last ? nonempty[first + j] : 0;
+        hit |= (flag[0] | flag[1] | flag[2]) != 0;
     }
     return __any(hit);
 }
 
-// step 2: (live, 0) into both states for the chunks whose verdict equals `want`: one chunk per block (four per block
+// step 1b: the verdicts of the 32 groups of a chunk that step 1a kept, formed by the whole block.  Thread t takes group
+// t % 32 and the (dz, dy) offsets t / 32, t / 32 + 8, ... (25 at reach 2: three or four per thread); the run of bits is cut
+// to the array -- the ballots cover whole chunks and are zero behind the last voxel.  Lanes l and l + 32 of a wave hold the
+// same group: the wave's ballot folds into 32 bits.  Returns the share of the calling WAVE, the same in every lane; the
+// chunk's mask is the OR of the four.  (Measured at 256^3, profiles/sparse_init_granularity_cost.md: the loads of a thread
+// one behind the other 46 us for the kernel, four offsets' loads in flight together 36 us; eighteen lanes loading the words
+// of one offset for the whole wave and the lanes picking theirs by lane exchange: three loads per lane, and 43-50 us.)
+constexpr int kPackGroup = 32;  // voxels per verdict
+constexpr int kPackGroups = (int)kBandChunk / kPackGroup;
+static_assert(kPackGroups == 32 && kWave == 2 * kPackGroups && kBlock % kPackGroups == 0,
+              "a chunk's verdicts fill the int kept per chunk; two half waves per ballot");
+__device__ inline unsigned group_verdicts_of_wave(unsigned c, unsigned chunks, long long row, long long slice, int dims,
+                                                  int reach, const unsigned long long* __restrict__ masks) {
+    const int span = 2 * reach + 1, offsets = span * (dims == 3 ? span : 1);
+    const long long bits = (long long)chunks * kBandChunk;
+    const long long g0 = (long long)c * kBandChunk + (threadIdx.x % kPackGroups) * kPackGroup;
+    constexpr int kStep = kBlock / kPackGroups, kBatch = 4;  // offsets per round of the block; rounds loaded together
+    bool hit = false;
+    for (int k0 = threadIdx.x / kPackGroups; k0 < offsets; k0 += kBatch * kStep) {
+        // [2 W + 0]: the INTERIOR ballot of voxels 64 W ..., [2 W + 1]: the BOUNDARY ballot; hi - lo < 64: the run lies in
+        // word lo / 64 and word hi / 64, the same or neighbours.  No branch around the loads: the sixteen of a batch are in
+        // flight together; an offset past the last one or a run outside the array reads word 0 and counts nothing.
+        unsigned long long first[kBatch], second[kBatch], upto[kBatch];
+        bool one[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const int k = k0 + u * kStep;
+            const int dy = k % span - reach, dz = dims == 3 ? k / span - reach : 0;
+            long long lo = g0 + dz * slice + dy * row - reach, hi = g0 + kPackGroup - 1 + dz * slice + dy * row + reach;
+            lo = lo < 0 ? 0 : lo;
+            hi = hi >= bits ? bits - 1 : hi;
+            const bool inside = k < offsets && lo <= hi;
+            const long long w0 = inside ? lo >> 6 : 0, w1 = inside ? hi >> 6 : 0;
+            first[u] = (masks[2 * w0] | masks[2 * w0 + 1]) & (inside ? ~0ull << (lo & 63) : 0ull);
+            second[u] = masks[2 * w1] | masks[2 * w1 + 1];
+            upto[u] = ~0ull >> (63 - (hi & 63));
+            one[u] = w0 == w1;
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u)
+            hit |= (one[u] ? first[u] & upto[u] : first[u] | (second[u] & upto[u])) != 0ull;
+    }
+    const unsigned long long both = __ballot(hit);
+    return (unsigned)both | (unsigned)(both >> 32);
+}
+
+// step 2: (live, 0) into both states for the groups whose verdict equals `want`: one chunk per block (four per block
 // measured slower, 58 against 46 us at 256^3: the needed chunks come in runs, and a block that draws four of them keeps
-// its CU's other slots waiting), two chunks in three leave after one load on a narrow band.  reach > 0: step 1 happens
-// here -- wave k of the block forms the verdict of the block's k-th chunk and keeps it in needed[], the block goes on behind
-// one barrier (a launch of its own for the verdicts was 5 us at 256^3, the floor of any launch); reach == 0: the kept
-// verdicts are read.
-constexpr int kPackChunks = 1;
-static_assert(kPackChunks <= kBlock / kWave, "a wave per chunk of the block forms the verdicts");
+// its CU's other slots waiting).  reach > 0: step 1 happens here (a launch of its own for the verdicts was 5 us at 256^3,
+// the floor of any launch) -- every wave asks step 1a for itself: the same flags, the same answer, and two chunks in
+// three of a narrow band leave after that one round of loads, without a barrier; in the others each wave forms its share
+// of the group verdicts, the block goes on behind one barrier and keeps the mask in needed[].  reach == 0: the kept masks
+// are read.  A thread loads live and stores only where its voxel's group bit says so: half a wave per group, 512 bytes
+// per store instruction and state.  groups == 0 (small volumes, see lsf_state_pack_needed): step 1b is left out, a chunk
+// that step 1a keeps is written whole and needed[c] is 1, as before there were groups.
 __global__ __launch_bounds__(kBlock) void state_pack_needed_kernel(const float* __restrict__ live, vf4* __restrict__ a,
                                                                    vf4* __restrict__ b, unsigned n, unsigned chunks,
                                                                    int* __restrict__ needed, int want, int reach,
                                                                    long long row, long long slice, int dims,
-                                                                   const int* __restrict__ nonempty) {
+                                                                   const int* __restrict__ nonempty,
+                                                                   const unsigned long long* __restrict__ masks,
+                                                                   int groups) {
     const int t = threadIdx.x;
-    __shared__ int s_verdict[kPackChunks];
+    const unsigned c = blockIdx.x;  // one block per chunk: c < chunks
+    __shared__ unsigned s_share[kBlock / kWave];
+    unsigned mask;
     if (reach > 0) {  // (uniform over the launch)
-        const int k = t / kWave;
-        const unsigned c = blockIdx.x * kPackChunks + k;
-        if (k < kPackChunks && c < chunks) {
-            const int any = chunk_is_needed(c, chunks, row, slice, dims, reach, nonempty) ? 1 : 0;
-            if (t % kWave == 0) {
-                needed[c] = any;
-                s_verdict[k] = any;
-            }
+        if (!chunk_is_needed(c, chunks, row, slice, dims, reach, nonempty)) {  // (uniform over the block)
+            if (t == 0) needed[c] = 0;
+            return;
         }
-        __syncthreads();
+        if (!groups) {  // (uniform over the launch)
+            if (t == 0) needed[c] = 1;
+            mask = ~0u;
+        } else {
+            const unsigned share = group_verdicts_of_wave(c, chunks, row, slice, dims, reach, masks);
+            if (t % kWave == 0) s_share[t / kWave] = share;
+            __syncthreads();
+            mask = 0u;
+#pragma unroll
+            for (int w = 0; w < kBlock / kWave; ++w) mask |= s_share[w];
+            if (t == 0) needed[c] = (int)mask;
+        }
+    } else {
+        mask = groups ? (unsigned)needed[c] : needed[c] != 0 ? ~0u : 0u;
     }
-    int verdict[kPackChunks];
+    if (want == 0) mask = ~mask;
+    float l[4];
 #pragma unroll
-    for (int k = 0; k < kPackChunks; ++k) {
-        const unsigned c = blockIdx.x * kPackChunks + k;
-        verdict[k] = c < chunks ? (reach > 0 ? s_verdict[k] : needed[c]) : -1;
+    for (int j = 0; j < 4; ++j) {  // the (up to) four loads of a thread first, together
+        const unsigned at = j * kBlock + t, v = c * kBandChunk + at;
+        l[j] = ((mask >> (at / kPackGroup)) & 1u) != 0u && v < n ? live[v] : 0.0f;
     }
 #pragma unroll
-    for (int k = 0; k < kPackChunks; ++k) {
-        if (verdict[k] != want) continue;
-        const unsigned c = blockIdx.x * kPackChunks + k;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned v = c * kBandChunk + j * kBlock + t;
-            if (v < n) {
-                vf4 o;
-                o.x = live[v]; o.y = 0.0f; o.z = 0.0f; o.w = 0.0f;
-                if (a) a[v] = o;
-                if (b) b[v] = o;
-            }
+    for (int j = 0; j < 4; ++j) {
+        const unsigned at = j * kBlock + t, v = c * kBandChunk + at;
+        if (((mask >> (at / kPackGroup)) & 1u) != 0u && v < n) {
+            vf4 o;
+            o.x = l[j]; o.y = 0.0f; o.z = 0.0f; o.w = 0.0f;
+            if (a) a[v] = o;
+            if (b) b[v] = o;
         }
     }
 }
-
-
 
 // ordered fill of one subset's list from the ballots lsf_state_prepare kept (which = 0 INTERIOR, 1 BOUNDARY).  One WAVE
 // per 1024-voxel chunk: its sixteen ballots arrive in one load (lane w holds word w), a chunk without entries -- nine
@@ -907,7 +967,8 @@ static inline int* prepare_opposite(int32_t* scratch, unsigned chunks) {
     return reinterpret_cast<int*>(prepare_masks(scratch, chunks) + (size_t)chunks * 32);
 }
 
-// ... then one int per chunk: does the chunk hold band voxels; then one per chunk: lsf_state_pack_needed's verdict
+// ... then one int per chunk: does the chunk hold band voxels; then one per chunk: lsf_state_pack_needed's verdicts, a bit
+// per group of 32 voxels
 static inline int* prepare_nonempty(int32_t* scratch, unsigned chunks) { return prepare_opposite(scratch, chunks) + 2 * (size_t)chunks; }
 static inline int* prepare_needed(int32_t* scratch, unsigned chunks) { return prepare_nonempty(scratch, chunks) + chunks; }
 // ... then the scan's per-tile totals (band_tile_totals_kernel): 4 ints per tile of 4096 chunks
@@ -1076,6 +1137,20 @@ int lsf::state_prepare_launch(const float* live, const float* canonical, float* 
     return launch_status();
 }
 
+// Group verdicts from this many voxels up, whole chunks and a 0 / 1 word per chunk below: 2^21, the size from which the
+// engine initialises sparsely by default (engine_options sparse_min_voxels), or what LSF_SPARSE_MIN_VOXELS sets in its
+// place -- the same variable and default as the engine's, so that one number says from where the sparse initialisation is
+// the product path (0: at every size; read at every call, the same for the invert call of a scratch).  Below it a call is
+// launch-bound, the sparse initialisation runs only where somebody forces it, and what it writes there -- whole needed
+// chunks, the words 0 / 1 -- is what tests/test_gpu_record_rows.py holds the prologue to at 32^3, 64^3 and 23 ragged chunks.
+static long long pack_group_min_voxels() {
+    const char* text = std::getenv("LSF_SPARSE_MIN_VOXELS");
+    if (!text || !*text) return 1ll << 21;
+    char* end = nullptr;
+    const long long value = std::strtoll(text, &end, 10);
+    return end && *end == 0 && value >= 0 ? value : 1ll << 21;
+}
+
 extern "C" int lsf_state_pack_needed(const float* live, float* state_a, float* state_b, const lsf_grid* grid,
                                      int32_t* scratch, int32_t reach, int32_t invert, void* stream) {
     if (int e = check_grid(grid, true)) return e;  // whole local arrays, also of slabs cut along y (as lsf_state_prepare)
@@ -1083,11 +1158,13 @@ extern "C" int lsf_state_pack_needed(const float* live, float* state_a, float* s
     if (grid->z_begin != 0 || grid->z_end != grid->nz) return LSF_ERR_BAD_ARGUMENT;  // whole arrays only
     unsigned first, n, chunks;
     band_range(grid, first, n, chunks);
-    // invert == 0: the kernel forms the verdicts itself and keeps them; invert != 0: it reads the kept ones
-    hipLaunchKernelGGL(state_pack_needed_kernel, dim3((chunks + kPackChunks - 1) / kPackChunks), dim3(kBlock), 0,
-                       as_stream(stream), live, reinterpret_cast<vf4*>(state_a), reinterpret_cast<vf4*>(state_b), n, chunks,
+    // invert == 0: the kernel forms the group verdicts itself and keeps them; invert != 0: it reads the kept ones
+    hipLaunchKernelGGL(state_pack_needed_kernel, dim3(chunks), dim3(kBlock), 0, as_stream(stream), live,
+                       reinterpret_cast<vf4*>(state_a), reinterpret_cast<vf4*>(state_b), n, chunks,
                        prepare_needed(scratch, chunks), invert ? 0 : 1, invert ? 0 : (int)reach, (long long)grid->nx,
-                       (long long)grid->nx * grid->ny, grid->dims, (const int*)prepare_nonempty(scratch, chunks));
+                       (long long)grid->nx * grid->ny, grid->dims, (const int*)prepare_nonempty(scratch, chunks),
+                       (const unsigned long long*)prepare_masks(scratch, chunks),
+                       (long long)n >= pack_group_min_voxels() ? 1 : 0);
     return launch_status();
 }
 

@@ -7,6 +7,7 @@ The common helpers live in device_core.py, the field operations (warps, pyramids
 term on its own in device_terms.py; this module re-exports them and holds the optimizers' kernels.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -130,23 +131,27 @@ class StatePrepare:
     is where the host waits for the list sizes."""
 
     CHUNK = 1024  # voxels per count of lsf_state_prepare's scratch (kBandChunk)
+    GROUP = 32  # voxels per verdict of lsf_state_pack_needed (kPackGroup): a bit per group in one int32 per chunk
     SPLIT_MAX_VOXELS = 1 << 24  # up to here the second state's fill fits into the host's wait for the list sizes
 
-    def __init__(self, live, canonical, grid=None, cut_chunks=None, sparse_reach=0):
+    def __init__(self, live, canonical, grid=None, cut_chunks=None, sparse_reach=0, states=None):
         """cut_chunks (optional): int64 device tensor of chunk indices <= the number of chunks -- the number of INTERIOR /
         BOUNDARY list entries in front of voxel 1024 * chunk comes back with the list sizes (collect), e.g. the positions
         of z cuts in the lists of a slab whose slices are a multiple of 1024 voxels, without a search and a second host
         read.  (The entry AT the number of chunks is not a count: use cut_totals for a cut at the end of the array.)
-        sparse_reach > 0: the states are written ONLY in the 1024-voxel chunks an iteration can read while every update
-        stays below `sparse_reach` voxels (lsf_state_pack_needed) -- the rest of both buffers stays uninitialised;
-        complete(state, live) fills it in for whole-state readers."""
+        sparse_reach > 0: the states are written ONLY in the groups of 32 consecutive voxels an iteration can read while
+        every update stays below `sparse_reach` voxels (lsf_state_pack_needed) -- the rest of both buffers stays
+        uninitialised; complete(state, live) fills it in for whole-state readers.
+        states (optional): the two float4 tensors to write instead of fresh ones."""
         self.grid = grid = grid or make_grid(live.shape)
         n = n_voxels(grid)
-        self.states = [torch.empty(tuple(live.shape) + (4,), dtype=torch.float32, device=live.device) for _ in range(2)]
+        self.states = list(states) if states is not None else [
+            torch.empty(tuple(live.shape) + (4,), dtype=torch.float32, device=live.device) for _ in range(2)]
         n_scratch = int(lib.lsf_state_prepare_scratch_elements(ctypes.byref(grid)))
         self._scratch = torch.empty(n_scratch, dtype=torch.int32, device=live.device)
         totals = torch.empty(4, dtype=torch.int64, device=live.device)
         self.sparse_reach = int(sparse_reach)
+        self._groups = n >= self.group_min_voxels()
         split = n <= self.SPLIT_MAX_VOXELS
         none = ctypes.c_void_p(0)
         check(lib.lsf_state_prepare(_ptr(live, n, "live"), _ptr(canonical, n, "canonical"),
@@ -167,8 +172,8 @@ class StatePrepare:
         self._copied = torch.cuda.Event()
         self._copied.record()
         # the states are written BEHIND the copy of the list sizes: the card fills them while the host wakes up on
-        # the sizes and enqueues the list fills, instead of idling there.  Sparse: both states, in the chunks near the
-        # band only (a quarter of a 256^3 sphere pair: 2 x 64 MB instead of 2 x 256 MB); else the second state (two states
+        # the sizes and enqueues the list fills, instead of idling there.  Sparse: both states, in the groups near the
+        # band only (a fifth of a 256^3 sphere pair: 2 x 52 MB instead of 2 x 268 MB); else the second state (two states
         # in the counting pass: 125 us in front of the sizes; one: 80 us, and these 65 us overlap the host's round trip)
         if self.sparse_reach:
             check(lib.lsf_state_pack_needed(_ptr(live, n, "live"), _ptr(self.states[0], 4 * n, "state"),
@@ -180,7 +185,7 @@ class StatePrepare:
                                      ctypes.c_void_p(0), ctypes.byref(full_range(grid)), stream_ptr()), "lsf_state_pack")
 
     def complete(self, state, live):
-        """sparse states only: write (live, 0) into the chunks of `state` the prepare step left uninitialised (live = the
+        """sparse states only: write (live, 0) into the groups of `state` the prepare step left uninitialised (live = the
         input live field, or any array that still holds it at the voxels outside the band lists)"""
         if not self.sparse_reach:
             return state
@@ -190,12 +195,34 @@ class StatePrepare:
                                         self.sparse_reach, 1, stream_ptr()), "lsf_state_pack_needed")
         return state
 
-    def needed_fraction(self):
-        """share of the 1024-voxel chunks the sparse prepare step initialised (a host read: measurements, tests)"""
+    @staticmethod
+    def group_min_voxels():
+        """arrays of at least this many voxels get a verdict per 32-voxel group, smaller ones per 1024-voxel chunk
+        (lsf_slavcheva.hip::pack_group_min_voxels, the same reading of LSF_SPARSE_MIN_VOXELS)"""
+        text = os.environ.get("LSF_SPARSE_MIN_VOXELS", "")
+        return int(text) if text.isdigit() else 1 << 21
+
+    def _needed_words(self):
         n = n_voxels(self.grid)
         chunks = (n + self.CHUNK - 1) // self.CHUNK
         at = 2 * (chunks + 1) + 64 * chunks + 2 * chunks + chunks  # lsf_slavcheva.hip::prepare_needed
-        return float(self._scratch[at:at + chunks].ne(0).float().mean().item())
+        return self._scratch[at:at + chunks]
+
+    def needed_masks(self):
+        """int32 per 1024-voxel chunk: bit g set = the sparse prepare step initialised voxels 32 g .. 32 g + 31 of the chunk
+        (below group_min_voxels() the kept word is 0 / 1 for the whole chunk: no bit or all of them)"""
+        words = self._needed_words()
+        return words if self._groups else -words.ne(0).to(torch.int32)
+
+    def needed_fraction(self):
+        """share of the 1024-voxel chunks in which the sparse prepare step initialised anything (a host read:
+        measurements, tests)"""
+        return float(self._needed_words().ne(0).float().mean().item())
+
+    def written_fraction(self):
+        """share of the 32-voxel groups the sparse prepare step initialised (a host read: measurements, tests)"""
+        masks = self.needed_masks().cpu().numpy().view(np.uint32)
+        return float(np.unpackbits(masks.view(np.uint8)).mean())
 
     def collect(self):
         """(band lists -- empty lists dropped, but never both --, (number of voxels outside the band with
