@@ -1726,6 +1726,65 @@ typedef struct lsf_volume_shift_params {
 int lsf_volume_shift(const float *tsdf, const float *weight, const float *colour, float *out_tsdf, float *out_weight,
                      float *out_colour, const lsf_volume_shift_params *params, void *stream);
 
+/* ---- the moving volume's brick store: what leaves the window is kept, what re-enters is written back -------------------
+ * The contract is this project's ("Brick store"; tests/volume_bricks_restatement.py restates
+ * it).  The world is cut into bricks of LSF_VOLUME_BRICK voxels per axis on an integer lattice.  The window's voxel
+ * v = (x, y, z) is the lattice voxel g + v, g = (origin_x, origin_y, origin_z), any sign; its brick is
+ * floor((g + v) / 8) per axis and its place in the brick (g + v) mod 8 >= 0.  The brick grid of a window is the box of
+ * bricks it touches, floor(g_j / 8) .. floor((g_j + n_j - 1) / 8) per axis, numbered z-major (x fastest).  A brick is
+ * 512 records [8][8][8] (z, y, x) of each of tsdf, weight and, when given, the 16-byte colour record, and 64 validity
+ * bytes: byte r = zl * 8 + yl, bit xl.
+ * With s = (shift_x, shift_y, shift_z) clamped to [-n, n] per axis, lsf_volume_shift by s makes dst(v) = src(v + s).  A
+ * voxel u of the OLD window therefore LEAVES when u - s lies outside the volume (no destination voxel takes it), and a
+ * voxel v of the NEW window ENTERED when v + s lies outside the volume (nothing was copied into it): the voxels that
+ * entered under s are the ones that leave under -s.  A voxel HOLDS DATA when the bits of its weight
+ * have any of the low 31 set: any non-zero weight, a NaN included.  Values move as 32-bit words, so NaN payloads and
+ * -0.0 survive.  One wave owns one brick and lane r its x-row (zl, yl) = (r / 8, r % 8); whether a brick touches the
+ * leaving / entering region is decided from its coordinate before any load; LSF_VOLUME_BRICKS_BLOCK_BRICKS bricks per
+ * workgroup on at most LSF_VOLUME_BRICKS_MAX_BLOCKS workgroups with a stride loop behind them.  No atomics, no waits
+ * between workgroups. */
+typedef struct lsf_volume_bricks_params {
+    int32_t depth, height, width;           /* window extents z, y, x, >= 1 each; at most 2^31 - 1 voxels */
+    int32_t origin_x, origin_y, origin_z;   /* g: the window's voxel (0, 0, 0) on the lattice; |g_j| + n_j within int32 */
+    int32_t shift_x, shift_y, shift_z;      /* whole voxels, any sign and size */
+} lsf_volume_bricks_params;
+#define LSF_VOLUME_BRICK 8
+#define LSF_VOLUME_BRICKS_MAX_BLOCKS 2048
+#define LSF_VOLUME_BRICKS_BLOCK_BRICKS 4
+
+/* Per brick b of the grid: flags[b] = 1 when any voxel of it that lies inside the window leaves and holds data, else 0;
+ * offsets[b] = the exclusive prefix sum of the flags in grid order; *total = their sum.  weight: DEVICE float32
+ * [depth][height][width]; flags, offsets: DEVICE int32, one per brick of the grid; total: DEVICE int64.  Two launches
+ * (the flags, then a one-workgroup scan), no host wait; the order is the grid's whatever the schedule.  Refused with
+ * LSF_ERR_BAD_ARGUMENT: a NULL, extents < 1, |g_j| + n_j beyond int32, a misaligned pointer, an output overlapping the
+ * weights or another output; more than 2^31 - 1 voxels or bricks is LSF_ERR_BAD_DIMS. */
+int lsf_volume_bricks_count(const float *weight, int32_t *flags, int32_t *offsets, int64_t *total,
+                            const lsf_volume_bricks_params *params, void *stream);
+
+/* After lsf_volume_bricks_count with the same weight and params, and after the host has read *total into brick_count:
+ * every flagged brick b writes row offsets[b] of the outputs -- out_coords [brick_count][3]: its lattice brick
+ * coordinate (x, y, z); out_tsdf, out_weight [brick_count][8][8][8] and out_colour [brick_count][8][8][8][4]: for a
+ * voxel that is inside the window, leaves and holds data the window's words, for every other voxel the empty voxel
+ * (tsdf 1, weight 0, colour record 0 0 0 0); out_valid [brick_count][64]: a bit set exactly for the voxels of the first
+ * kind.  Every word of every row is written; rows come in grid order, which is ascending (z, y, x).  A row index not
+ * below brick_count is never written.  One launch, none when brick_count is 0.  colour, out_colour: both NULL or both
+ * set, 16-byte aligned.  Refused as lsf_volume_bricks_count refuses, and a brick_count < 0 or above the number of bricks
+ * of the grid, and any output overlapping an input or another output. */
+int lsf_volume_bricks_gather(const float *tsdf, const float *weight, const float *colour, const int32_t *flags,
+                             const int32_t *offsets, int64_t brick_count, int32_t *out_coords, float *out_tsdf,
+                             float *out_weight, float *out_colour, uint8_t *out_valid,
+                             const lsf_volume_bricks_params *params, void *stream);
+
+/* The way back, IN PLACE: for each of the brick_count given bricks (coords [brick_count][3] and the rows in
+ * lsf_volume_bricks_gather's layout) and each of its voxels that lies inside the window, is entering under
+ * params->shift and has its validity bit set, the brick's words are written into tsdf, weight and colour.  Nothing else
+ * is touched.  |shift_j| >= n_j on some axis makes every voxel entering: a dense volume assembled from bricks.  The
+ * caller guarantees distinct coordinates; bricks outside the window's grid are skipped.  One launch, none when
+ * brick_count is 0.  brick_colour, colour: both NULL or both set, 16-byte aligned.  Refused as above. */
+int lsf_volume_bricks_scatter(const int32_t *coords, const float *brick_tsdf, const float *brick_weight,
+                              const float *brick_colour, const uint8_t *brick_valid, int64_t brick_count, float *tsdf,
+                              float *weight, float *colour, const lsf_volume_bricks_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

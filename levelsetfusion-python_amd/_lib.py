@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "e7f8790ad697fe6d"
+HEADER_ABI_HASH = "281d797ac3088c72"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -263,6 +263,17 @@ class VolumeShiftParams(ctypes.Structure):
 
 VOLUME_SHIFT_MAX_BLOCKS = 2048
 VOLUME_SHIFT_BLOCK_ROWS = 4
+
+
+class VolumeBricksParams(ctypes.Structure):
+    """lsf_volume_bricks_params: the window on the brick lattice (lsf_volume_bricks_count / _gather / _scatter)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("depth", "height", "width", "origin_x", "origin_y", "origin_z",
+                                              "shift_x", "shift_y", "shift_z")]
+
+
+VOLUME_BRICK = 8
+VOLUME_BRICKS_MAX_BLOCKS = 2048
+VOLUME_BRICKS_BLOCK_BRICKS = 4
 
 ICP_MAX_LEVELS = 4
 ICP_RECORD_DOUBLES = 64
@@ -512,6 +523,11 @@ PROTOTYPES = {
     "lsf_mesh_vertex_colours": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int32, _P(MeshParams), _vp]),
     "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
+    "lsf_volume_bricks_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(VolumeBricksParams), _vp]),
+    "lsf_volume_bricks_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                _P(VolumeBricksParams), _vp]),
+    "lsf_volume_bricks_scatter": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                                 _P(VolumeBricksParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),

@@ -153,12 +153,29 @@ The frame record gains "shift" and "streamed_faces", only with a moving_volume. 
 combines with every tracking mode and every non-rigid setting; `warp` and `prediction` remain the last frame's, in the
 window that frame had.  Cost: profiles/moving_volume_cost.md.
 
+Brick store ("Brick store"; tests/volume_bricks_restatement.py restates it): opt-in, the window
+made lossless.  The world is cut into bricks of 8 voxels per axis on an integer lattice that a BrickStore fixes at its
+first use (`origin`, the array_offset of the first shift that uses it; every later window must lie whole voxels from it).
+CanonicalVolume.shift(..., brick_store=store) compacts the bricks that hold a voxel which leaves with data
+(csrc/lsf_volume_bricks.hip: a count with one host read of the total, then a gather), copies them to the host and merges
+them into the store, shifts as above, and writes the store's bricks that touch what entered back into the new buffers
+(a scatter in place), clearing them in the store: a lattice voxel with data lives in exactly one place, the window or
+the store.  A voxel holds data when its weight is non-zero (a NaN counts); one that leaves without data is not kept
+and comes back as the empty voxel (tsdf 1, weight 0, colour 0).  CanonicalVolume.assemble(store, array_offset) builds
+window plus store as fresh dense device tensors over their bounding box.  MovingVolume(..., stream_mesh=False,
+keep_tsdf=True) makes SequenceFusion3d own `brick_store` and pass it to every shift -- the frame records gain bricks_out
+and bricks_in -- and extract_mesh(include_streamed=True) then meshes the assembled map: one mesh without seams, at the
+caller's iso, min_weight, normals and colours.  keep_tsdf does not combine with stream_mesh (a re-entered region would be
+meshed twice).  Cost: profiles/volume_bricks_cost.md.
+
 Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals.  A moving volume's policy adds none (the twist is on the host already); a shift that streams
-costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host.
+costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
+store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
+bricks to the card.
 
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SobolevFusion
 (sobolev_smoothing_enabled) or out of a z-slab / multi-GPU run (`comm`), a carve-distance
@@ -175,15 +192,15 @@ a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casti
 image in the prediction, a colour image of another
 resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, and for the
-moving volume streaming TSDF values out or back in (space the window re-enters starts empty), welding across seams,
-and a shift enqueued without the mesh totals' host read."""
+moving volume welding across seams, a shift enqueued without the mesh totals' host read, and for its brick store
+saving the store to disk, streaming without the host read of the brick total, and bricks in half precision."""
 import math
 
 import numpy as np
 import torch
 
 from .. import (device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid,
-                device_volume_shift)
+                device_volume_bricks, device_volume_shift)
 from ..device_core import require_gpu
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
                              unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
@@ -197,8 +214,9 @@ from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_reco
 from .._lib import DEPTH_F32
 from ..math_utils.transformation import twist_vector_to_matrix3d
 from ..tsdf.generation import DepthCamera, device_depth, offsets_of
+from .brick_store import BrickStore
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "merge_meshes",
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "merge_meshes",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
@@ -280,9 +298,17 @@ class MovingVolume:
     only.  threshold_voxels: positive; the window stays while the anchor is within that many voxels of its centre on
     every axis.  anchor: the point in CAMERA coordinates (metres) the window keeps near its centre, (0, 0, depth) some
     way in front of the lens -- the model is where the camera looks; it has no default, since no depth is right
-    across scenes.  stream_mesh, min_weight, normals: whether and how SequenceFusion3d meshes the cells that leave."""
+    across scenes.  stream_mesh, min_weight, normals: whether and how SequenceFusion3d meshes the cells that leave.
+    keep_tsdf: SequenceFusion3d keeps what leaves with data in it as bricks (its `brick_store`) and writes back what
+    the window re-enters; it does not combine with stream_mesh, which would mesh a re-entered region twice, and since
+    stream_mesh defaults to True, keep_tsdf=True needs stream_mesh=False said explicitly."""
 
-    def __init__(self, threshold_voxels, anchor, stream_mesh=True, min_weight=0.0, normals=False):
+    def __init__(self, threshold_voxels, anchor, stream_mesh=True, min_weight=0.0, normals=False, keep_tsdf=False):
+        if keep_tsdf and stream_mesh:
+            raise ValueError("keep_tsdf=True does not combine with stream_mesh=True (a region the window re-enters "
+                             "would be meshed twice); stream_mesh defaults to True, so pass stream_mesh=False "
+                             "explicitly with keep_tsdf=True")
+        self.keep_tsdf = bool(keep_tsdf)
         self.threshold_voxels = float(threshold_voxels)
         if not (np.isfinite(self.threshold_voxels) and self.threshold_voxels > 0):
             raise ValueError("threshold_voxels must be finite and positive, got %r" % (threshold_voxels,))
@@ -369,6 +395,7 @@ class CanonicalVolume:
         self.weight = torch.zeros(self.shape, dtype=torch.float32, device="cuda")
         self.colour = torch.zeros(self.shape + (4,), dtype=torch.float32, device="cuda") if colour else None
         self._spare = None  # shift: the buffers the next shifted copy is written to
+        self._bricks = None  # shift(brick_store=): the flags, offsets and total of the brick count, kept like _spare
 
     def reset(self):
         """back to the empty model: tsdf 1, weight 0 everywhere (and a colour volume 0)"""
@@ -465,8 +492,88 @@ class CanonicalVolume:
         keep = [out[0], out[1]] + ([out[2]] if normals else []) + ([out[3]] if colours else [])
         return tuple(t.cpu().numpy() for t in keep)
 
+    def _brick_lattice(self, brick_store, array_offset, fix=True):
+        """the window's lattice origin g in `brick_store` after the checks that need no device"""
+        if not isinstance(brick_store, BrickStore):
+            raise ValueError("brick_store must be a fusion.BrickStore or None, got %r" % (brick_store,))
+        if len(self.shape) != 3:
+            raise ValueError("a brick store needs a 3-D model, this one has shape %s" % (self.shape,))
+        if brick_store.colour != (self.colour is not None):
+            raise ValueError("the brick store was made with colour=%r, the volume with colour=%r: they must agree"
+                             % (brick_store.colour, self.colour is not None))
+        return brick_store.lattice_origin(array_offset, fix)
+
+    def _bricks_out(self, store, g, s):
+        """steps 2-4 of a shift with a store: count, the one host read, gather, the rows' copy to the host, the merge"""
+        B = device_volume_bricks
+        if self._bricks is None:  # the largest grid any alignment of this shape has
+            most = int(np.prod([(n + B.BRICK - 2) // B.BRICK + 1 for n in self.shape]))
+            self._bricks = (torch.empty(most, dtype=torch.int32, device=self.tsdf.device),
+                            torch.empty(most, dtype=torch.int32, device=self.tsdf.device),
+                            torch.empty(1, dtype=torch.int64, device=self.tsdf.device))
+        nbricks = int(np.prod(B.brick_grid(self.shape, g)[1]))
+        flags, offsets, total = self._bricks[0][:nbricks], self._bricks[1][:nbricks], self._bricks[2]
+        B.count(self.weight, flags, offsets, total, g, s)
+        k = int(total.item())  # the host wait of a shift with a store
+        if k == 0:
+            return 0, 0
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.tsdf.device)
+        cube = (k, B.BRICK, B.BRICK, B.BRICK)
+        rows = (new((k, 3), torch.int32), new(cube, torch.float32), new(cube, torch.float32),
+                None if self.colour is None else new(cube + (4,), torch.float32), new((k, B.VALID_BYTES), torch.uint8))
+        B.gather(self.tsdf, self.weight, self.colour, flags, offsets, k, *rows, g, s)
+        return k, store.merge(*(None if t is None else t.cpu().numpy() for t in rows))
+
+    def _bricks_in(self, store, g, s):
+        """steps 6-8: the stored bricks that touch what entered a window at lattice origin g under s go up, are
+        scattered into the window's buffers and lose the validity bits of what was written"""
+        B = device_volume_bricks
+        coords, tsdf, weight, colour, valid = store.lookup_entering(*B.entering_flags(self.shape, g, s))
+        taken = B.entering_mask(self.shape, g, s, coords) & B.unpack_valid(valid)
+        touched = taken.reshape(len(coords), B.BRICK_VOXELS).any(axis=1)
+        if not touched.any():
+            return 0, 0
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a[touched])).to(self.tsdf.device)
+        B.scatter(up(coords), up(tsdf), up(weight), up(colour), up(valid), self.tsdf, self.weight, self.colour, g, s)
+        store.clear_valid(coords[touched], taken[touched])
+        return int(touched.sum()), int(taken.sum())
+
+    def assemble(self, brick_store, array_offset, max_voxels=2 ** 28):
+        """the whole map, window and store, as fresh dense device tensors over the lattice bounding box of the two:
+        (tsdf, weight, colour or None, array_offset_of_box).  The box is filled with the empty voxel, the window is
+        copied in, and one lsf_volume_bricks_scatter with an all-entering shift writes the stored voxels; a stored
+        voxel inside the window is never valid, so the order does not matter.  array_offset is the window's.
+        ValueError when the box has more than max_voxels voxels, or more than 2^31 - 1."""
+        g = np.array(self._brick_lattice(brick_store, array_offset, fix=False), dtype=np.int64)
+        n = np.array(self.shape[::-1], dtype=np.int64)
+        lo, hi = g, g + n
+        bounds = brick_store.bounds()
+        if bounds is not None:
+            lo, hi = np.minimum(lo, bounds[0]), np.maximum(hi, bounds[1])
+        dims = hi - lo
+        voxels = int(dims[0]) * int(dims[1]) * int(dims[2])
+        if voxels > min(int(max_voxels), 0x7fffffff):
+            raise ValueError("the map's box has %d x %d x %d voxels (x, y, z), more than max_voxels = %d or than "
+                             "int32 indices reach" % (dims[0], dims[1], dims[2], max_voxels))
+        shape = tuple(int(v) for v in dims[::-1])
+        tsdf = torch.ones(shape, dtype=torch.float32, device=self.tsdf.device)
+        weight = torch.zeros(shape, dtype=torch.float32, device=self.tsdf.device)
+        colour = None if self.colour is None else torch.zeros(shape + (4,), dtype=torch.float32,
+                                                              device=self.tsdf.device)
+        x0, y0, z0 = (int(v) for v in g - lo)
+        part = (slice(z0, z0 + self.shape[0]), slice(y0, y0 + self.shape[1]), slice(x0, x0 + self.shape[2]))
+        tsdf[part], weight[part] = self.tsdf, self.weight
+        if colour is not None:
+            colour[part] = self.colour
+        if len(brick_store):
+            rows = brick_store.lookup(brick_store.coords())
+            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.tsdf.device)
+            device_volume_bricks.scatter(*(up(a) for a in rows), tsdf, weight, colour, tuple(int(v) for v in lo),
+                                         (shape[2], 0, 0))
+        return tsdf, weight, colour, offsets_of(array_offset) + (lo - g).astype(np.float64)
+
     def shift(self, shift_voxels, array_offset, voxel_size=0.004, stream_mesh=False, min_weight=0.0, normals=False,
-              colours=False):
+              colours=False, brick_store=None):
         """move the window by shift_voxels = (sx, sy, sz) whole voxels: afterwards voxel v holds what voxel v + s held,
         and the voxels that entered are empty (tsdf 1, weight 0, colour 0); one launch of csrc/lsf_volume_shift.hip.
         Returns (new_array_offset, chunks) with new_array_offset = array_offset + s (float64 (3,)), under which every
@@ -479,13 +586,25 @@ class CanonicalVolume:
         them into at most three disjoint boxes, each meshed from a contiguous copy of its voxels, and `chunks` lists
         their host tuples in extract_mesh's layout (with normals / colours as asked; boxes without a face are left
         out).  Every cell of the old volume is thus drawn exactly once across the chunks and the new window; the
-        seam's vertices appear in both, nothing is welded.  Each box costs extract_mesh's host read."""
+        seam's vertices appear in both, nothing is welded.  Each box costs extract_mesh's host read.
+        With brick_store (a BrickStore whose `colour` matches the volume's) the window is lossless: the first such
+        call fixes the store's lattice at array_offset, and every later array_offset must lie whole voxels from it.
+        In order: the bricks holding a voxel that leaves with data are counted (lsf_volume_bricks_count) and the total
+        is read on the host; those bricks are gathered and copied to the host; the store merges them (valid voxels
+        overwrite, validity bits are ORed); the shifted copy runs as above; the store's bricks that touch what entered
+        are uploaded and scattered into the new buffers; the store clears the validity bits of what was written and
+        drops the bricks left without one.  A voxel that leaves without data is not kept and comes back empty.
+        `brick_store.last` has the counts.  The return value is unchanged.  Cost: one host wait for the total and the
+        copies of the rows, both ways; the workspaces of the count are allocated once per volume."""
         if len(self.shape) != 3:
             raise ValueError("a volume shift needs a 3-D model, this one has shape %s" % (self.shape,))
         s = device_volume_shift.shift_of(shift_voxels)
         offset = offsets_of(array_offset).copy()
         if colours and self.colour is None:
             raise ValueError("colours=True needs a volume made with colour=True")
+        g = None if brick_store is None else self._brick_lattice(brick_store, offset)
+        if brick_store is not None:
+            brick_store.last = {"bricks_out": 0, "voxels_out": 0, "bricks_in": 0, "voxels_in": 0}
         if s == (0, 0, 0):
             return offset, []
         chunks = []
@@ -498,9 +617,16 @@ class CanonicalVolume:
             self._spare = (torch.empty_like(self.tsdf), torch.empty_like(self.weight),
                            None if self.colour is None else torch.empty_like(self.colour))
         out_tsdf, out_weight, out_colour = self._spare
+        if brick_store is not None:
+            device_volume_bricks.params(self.shape, tuple(a + b for a, b in zip(g, s)), s)  # the new origin fits too
+            bricks_out, voxels_out = self._bricks_out(brick_store, g, s)
         device_volume_shift.shift(self.tsdf, self.weight, self.colour, out_tsdf, out_weight, out_colour, s)
         self._spare = (self.tsdf, self.weight, self.colour)
         self.tsdf, self.weight, self.colour = out_tsdf, out_weight, out_colour
+        if brick_store is not None:
+            bricks_in, voxels_in = self._bricks_in(brick_store, tuple(a + b for a, b in zip(g, s)), s)
+            brick_store.last = {"bricks_out": bricks_out, "voxels_out": voxels_out, "bricks_in": bricks_in,
+                                "voxels_in": voxels_in}
         return offset + np.array(s, dtype=np.float64), chunks
 
 
@@ -555,6 +681,9 @@ class SequenceFusion3d:
             raise ValueError("array_offset must have 3 entries, got %d" % self.array_offset.size)
         self.initial_array_offset = self.array_offset.copy()  # a moving_volume moves array_offset; this one stays
         self.streamed_meshes = []  # a moving_volume with stream_mesh: the host meshes of the cells that left
+        # a moving_volume with keep_tsdf: the bricks that left, written back when the window re-enters them
+        self.brick_store = BrickStore(colour=bool(colour)) if moving_volume is not None and moving_volume.keep_tsdf \
+            else None
         if not voxel_size > 0 or not narrow_band_width_voxels > 0:
             raise ValueError("voxel_size and narrow_band_width_voxels must be positive")
         if int(rigid_iterations) < 0:
@@ -726,10 +855,14 @@ class SequenceFusion3d:
             mv = self.moving_volume
             s = mv.shift_for(frame["twist"], self.array_offset, self.field_shape, self.voxel_size)
             self.array_offset, chunks = model.shift(s, self.array_offset, self.voxel_size, mv.stream_mesh,
-                                                    mv.min_weight, mv.normals, colours=mv.stream_mesh and self.colour)
+                                                    mv.min_weight, mv.normals, colours=mv.stream_mesh and self.colour,
+                                                    brick_store=self.brick_store)
             self.streamed_meshes.extend(chunks)
             frame["shift"] = s
             frame["streamed_faces"] = int(sum(len(c[1]) for c in chunks))
+            if self.brick_store is not None:
+                frame["bricks_out"] = self.brick_store.last["bricks_out"]
+                frame["bricks_in"] = self.brick_store.last["bricks_in"]
         if self.tracking_reference == "raycast":
             self._previous = (depth, code)
         self.twists.append(frame["twist"].copy())
@@ -742,11 +875,21 @@ class SequenceFusion3d:
         include_streamed (a sequence made with a moving_volume that streams) the window's mesh is followed by the
         streamed chunks, merge_meshes of them all: host arrays only, and only as the chunks were made -- iso 0, the
         policy's min_weight and normals, colours exactly when the sequence has colour, the default default_colour;
-        anything else raises, since the chunks cannot be drawn again"""
+        anything else raises, since the chunks cannot be drawn again.  With a moving_volume that has keep_tsdf,
+        include_streamed meshes CanonicalVolume.assemble of the window and the brick store instead: one mesh of the
+        whole map without seams, at the caller's iso, min_weight, normals and colours, as tensors too"""
         if not include_streamed:
             return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
                                                colours, default_colour)
         mv = self.moving_volume
+        if mv is not None and mv.keep_tsdf:
+            if colours and not self.colour:
+                raise ValueError("colours=True needs a sequence made with colour=True")
+            tsdf, weight, colour, offset = self.canonical.assemble(self.brick_store, self.array_offset)
+            out = device_mesh.extract_mesh(tsdf, weight, offset, self.voxel_size, iso, min_weight, normals,
+                                           *((colour, default_colour) if colours else ()))
+            out = tuple(t for t, kept in zip(out, (True, True, normals, colours)) if kept)
+            return out if as_tensor else tuple(t.cpu().numpy() for t in out)
         if mv is None or not mv.stream_mesh:
             raise ValueError("include_streamed needs a sequence made with a moving_volume that has stream_mesh=True")
         same = (not as_tensor and iso == 0.0 and float(min_weight) == mv.min_weight and bool(normals) == mv.normals
