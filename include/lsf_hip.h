@@ -1785,6 +1785,88 @@ int lsf_volume_bricks_scatter(const int32_t *coords, const float *brick_tsdf, co
                               const float *brick_colour, const uint8_t *brick_valid, int64_t brick_count, float *tsdf,
                               float *weight, float *colour, const lsf_volume_bricks_params *params, void *stream);
 
+/* ---- the RGB-D sensor front end: lens rectification and depth-to-colour registration -----------------------------------
+ * The contract is this project's ("RGB-D sensor"; tests/rgbd_restatement.py restates it).  A
+ * raw depth image, taken through a lens with distortion, is registered into an IDEAL pinhole camera (the rectified colour
+ * camera, or the depth camera's own matrix): every depth pixel is lifted along its undistorted ray, moved by
+ * q = R p + t and splatted through a z-buffer; the raw colour image is resampled into the same ideal camera.  A pixel of
+ * the result without an answer has depth 0, which every kernel that reads depth treats as "no measurement".
+ * Every float step is float64, one IEEE operation each in the order written here (the library is built with
+ * -ffp-contract=off).  Pixel centres lie at integer coordinates.  Distortion is OpenCV's rational model with
+ * k = (k1, k2, p1, p2, k3, k4, k5, k6):
+ *     r2 = x*x + y*y,  num = 1 + r2*(k1 + r2*(k2 + r2*k3)),  den = 1 + r2*(k4 + r2*(k5 + r2*k6)),
+ *     dx = 2*p1*x*y + p2*(r2 + 2*x*x),  dy = p1*(r2 + 2*y*y) + 2*p2*x*y,   (products left to right)
+ *     xd = x*(num/den) + dx,  yd = y*(num/den) + dy.
+ * One lane per pixel on workgroups of 256 lanes along rows, at most LSF_RGBD_MAX_BLOCKS workgroups with a stride loop
+ * behind them; the only atomics are unsigned minima on the z-buffer and integer sums on the record, one per workgroup
+ * and non-zero count (four LDS words carry the waves' sums). */
+typedef struct lsf_rgbd_params {
+    double fx, fy, cx, cy;                  /* the SOURCE camera: the lens of the ray table, of the rectified image */
+    double k[8];                            /* its distortion (k1, k2, p1, p2, k3, k4, k5, k6); finite */
+    double out_fx, out_fy, out_cx, out_cy;  /* the ideal OUTPUT camera (register_depth, rectify_colour) */
+    double rotation[9];                     /* R, row-major: q = R p + t takes depth-camera to output-camera coordinates */
+    double translation[3];                  /* t, in metres */
+    double depth_unit_ratio;                /* register_depth: metres per depth unit, finite and > 0 */
+    int32_t height, width;                  /* the source image (the depth image; the raw colour image) */
+    int32_t out_height, out_width;          /* the output image */
+    int32_t max_footprint;                  /* register_depth: 1 .. LSF_RGBD_MAX_FOOTPRINT output pixels per axis */
+    int32_t reserved;                       /* 0 */
+} lsf_rgbd_params;
+#define LSF_RGBD_UNDISTORT_ITERATIONS 10
+#define LSF_RGBD_MAX_FOOTPRINT 16
+#define LSF_RGBD_DEFAULT_FOOTPRINT 8
+#define LSF_RGBD_MAX_BLOCKS 512
+#define LSF_RGBD_RECORD_WORDS 8
+#define LSF_RGBD_ZBUFFER_EMPTY 0x7f800000u
+
+/* Once per sensor: the undistorted normalised coordinates of the source camera's pixels.  corner_rays: DEVICE float64
+ * [height + 1][width + 1][2], at (u - 0.5, v - 0.5) for u in 0..width, v in 0..height; centre_rays: DEVICE float64
+ * [height][width][2], at (u, v).  From xd = (u - cx) / fx, yd = (v - cy) / fy: with all eight coefficients 0 the ray is
+ * (xd, yd) itself; otherwise LSF_RGBD_UNDISTORT_ITERATIONS fixed-point steps from (x, y) = (xd, yd), one step being
+ * x' = (xd - dx(x, y)) * den / num, y' = (yd - dy(x, y)) * den / num with r2, num, den of (x, y), no early exit.  One
+ * launch.  Reads params->fx .. k, height, width.  Refused with LSF_ERR_BAD_ARGUMENT: a NULL, extents < 1, fx or fy zero
+ * or not finite, cx, cy or a coefficient not finite, a table off 8-byte alignment, overlapping tables; more than
+ * 2^31 - 1 pixels (corners) is LSF_ERR_BAD_DIMS. */
+int lsf_rgbd_ray_table(double *corner_rays, double *centre_rays, const lsf_rgbd_params *params, void *stream);
+
+/* depth: DEVICE [height][width] of depth_dtype (LSF_DEPTH_*), scaled as the TSDF generators scale it (uint16 and float64
+ * times the ratio in float64, float32 times float32(ratio) in float32).  corner_rays, centre_rays: lsf_rgbd_ray_table's,
+ * of the depth image's extents.  zbuffer: DEVICE uint32 [out_height][out_width], workspace.  colour_valid: NULL or DEVICE
+ * uint8 [out_height][out_width] (lsf_rgbd_rectify_colour's).  out_depth: DEVICE float32 [out_height][out_width], metres,
+ * 0 where nothing landed.  record: DEVICE int64 [LSF_RGBD_RECORD_WORDS] = valid, behind, outside, empty, clipped,
+ * written, filled, masked; exact counts.  Three launches (clear, splat, finalise), no host wait.
+ * Per depth pixel: z = the scaled depth as float64; VALID when z is finite and > 0.  The centre point
+ * p = (xc*z, yc*z, z) moves to q_i = ((R[i][0]*p0 + R[i][1]*p1) + R[i][2]*p2) + t[i]; the pixel is BEHIND unless
+ * q_z > 0 and float32(q_z) is finite.  Each of its four corner rays, scaled by the pixel's own z, moves the same way; a
+ * corner with q_z <= 0 also makes the pixel BEHIND.  Each corner projects to U = out_fx*(q_x/q_z) + out_cx, V likewise.
+ * The footprint is the columns u0 <= i < u1, u0 = ceil(min U), u1 = ceil(max U), and the rows v0 <= j < v1 likewise: the
+ * output pixels whose centre lies in the bounding box of the projected quad; neighbours share corners, so a continuous
+ * surface leaves no gap.  A U or V that is not finite, or a bound beyond +-2147483000, makes the pixel OUTSIDE.  An
+ * extent above max_footprint keeps its first max_footprint columns (rows) from the low end and the pixel is counted
+ * CLIPPED.  A range that holds no pixel: EMPTY.  A range wholly off the image: OUTSIDE.  Otherwise WRITTEN: every
+ * in-image pixel of the range takes the unsigned minimum of itself and the bits of float32(q_z) (positive finite floats
+ * order as their bits; LSF_RGBD_ZBUFFER_EMPTY is +inf), so the result does not depend on the order and reruns are bit
+ * identical.  valid = behind + outside + empty + written.  Finalise: out_depth is the z-buffer's float, 0 where it is
+ * empty; FILLED counts the pixels that are not empty; where colour_valid is 0, out_depth is 0 and a filled pixel is
+ * counted MASKED.
+ * Refused with LSF_ERR_BAD_ARGUMENT: a NULL (but colour_valid), a bad depth_dtype, extents < 1, out_fx or out_fy zero or
+ * not finite, a non-finite out_cx, out_cy, R, t or ratio, a ratio <= 0, max_footprint out of range, a table off 8-byte
+ * alignment, zbuffer, out_depth or depth off their element's alignment, any overlap among the buffers; more than
+ * 2^31 - 1 pixels is LSF_ERR_BAD_DIMS. */
+int lsf_rgbd_register_depth(const void *depth, int32_t depth_dtype, const double *corner_rays, const double *centre_rays,
+                            uint32_t *zbuffer, const uint8_t *colour_valid, float *out_depth, int64_t *record,
+                            const lsf_rgbd_params *params, void *stream);
+
+/* src: DEVICE uint8 [height][width][3], the raw image of the source camera; dst: DEVICE uint8 [out_height][out_width][3];
+ * valid: DEVICE uint8 [out_height][out_width].  Output pixel (u, v) gives x = (u - out_cx)/out_fx, y likewise, (xd, yd)
+ * by the source's coefficients, us = fx*xd + cx, vs = fy*yd + cy.  VALID (1) when both are finite, 0 <= us <= width - 1
+ * and 0 <= vs <= height - 1; then, with u0 = floor(us), a = us - u0, u1 = min(u0 + 1, width - 1) and v0, b, v1 likewise,
+ * each channel is  top = s[v0][u0]*(1 - a) + s[v0][u1]*a,  bottom = s[v1][u0]*(1 - a) + s[v1][u1]*a,
+ * byte = floor((top*(1 - b) + bottom*b) + 0.5).  Otherwise the pixel is (0, 0, 0) and valid 0.  One launch.  Refused as
+ * above: a NULL, extents < 1, a focal length zero or not finite, a non-finite centre or coefficient, any overlap. */
+int lsf_rgbd_rectify_colour(const uint8_t *src, uint8_t *dst, uint8_t *valid, const lsf_rgbd_params *params,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "281d797ac3088c72"
+HEADER_ABI_HASH = "a67f633a97d3742a"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -274,6 +274,25 @@ class VolumeBricksParams(ctypes.Structure):
 VOLUME_BRICK = 8
 VOLUME_BRICKS_MAX_BLOCKS = 2048
 VOLUME_BRICKS_BLOCK_BRICKS = 4
+
+
+class RgbdParams(ctypes.Structure):
+    """lsf_rgbd_params: the source lens, the ideal output camera and the transform between them (lsf_rgbd_ray_table /
+    _register_depth / _rectify_colour)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy")] + [("k", ctypes.c_double * 8)] + \
+               [(n, ctypes.c_double) for n in ("out_fx", "out_fy", "out_cx", "out_cy")] + \
+               [("rotation", ctypes.c_double * 9), ("translation", ctypes.c_double * 3),
+                ("depth_unit_ratio", ctypes.c_double)] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "out_height", "out_width", "max_footprint",
+                                              "reserved")]
+
+
+RGBD_UNDISTORT_ITERATIONS = 10
+RGBD_MAX_FOOTPRINT = 16
+RGBD_DEFAULT_FOOTPRINT = 8
+RGBD_MAX_BLOCKS = 512
+RGBD_RECORD_WORDS = 8
+RGBD_ZBUFFER_EMPTY = 0x7f800000
 
 ICP_MAX_LEVELS = 4
 ICP_RECORD_DOUBLES = 64
@@ -528,6 +547,9 @@ PROTOTYPES = {
                                                 _P(VolumeBricksParams), _vp]),
     "lsf_volume_bricks_scatter": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                                  _P(VolumeBricksParams), _vp]),
+    "lsf_rgbd_ray_table": (ctypes.c_int, [_vp, _vp, _P(RgbdParams), _vp]),
+    "lsf_rgbd_register_depth": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _P(RgbdParams), _vp]),
+    "lsf_rgbd_rectify_colour": (ctypes.c_int, [_vp, _vp, _vp, _P(RgbdParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),

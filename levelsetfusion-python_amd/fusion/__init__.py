@@ -168,6 +168,18 @@ and bricks_in -- and extract_mesh(include_streamed=True) then meshes the assembl
 caller's iso, min_weight, normals and colours.  keep_tsdf does not combine with stream_mesh (a re-entered region would be
 meshed twice).  Cost: profiles/volume_bricks_cost.md.
 
+RGB-D sensor ("RGB-D sensor"; tests/rgbd_restatement.py restates it): everything above assumes
+that one ideal pinhole camera made both images.  RgbdSensor(depth_camera, colour_camera, depth_to_colour) stands in front
+of it for a real sensor -- two lenses with distortion, apart, of different resolutions.  sensor.register(depth_image,
+colour_image) registers the raw depth into the RECTIFIED colour camera (csrc/lsf_rgbd.hip: every depth pixel lifted along
+its undistorted ray, moved by q = R p + t, and its projected quad's bounding box splatted through an unsigned-minimum
+z-buffer) and resamples the raw colour into the same ideal camera; a pixel without an answer has depth 0, which every
+kernel here already reads as "no measurement".  SequenceFusion3d(None, ..., sensor=sensor) does that to every raw pair
+given to integrate and then runs the frame unchanged on sensor.camera: every tracking mode, carve, confidence, the
+pyramids, moving_volume and the non-rigid steps see the registered stream, and the frame record gains "registration", the
+call's eight counts.  With colour=False the sensor gets no colour image; the depth is still registered into the colour
+camera when the sensor has one.  Without the keyword nothing changes.  Cost: profiles/rgbd_sensor_cost.md.
+
 Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
@@ -175,7 +187,8 @@ the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_m
 vertex and face totals.  A moving volume's policy adds none (the twist is on the host already); a shift that streams
 costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
 store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
-bricks to the card.
+bricks to the card.  A sensor adds none per frame (its record is read with the fusion record's wait); its first frame
+waits once for the check of the ray tables.
 
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SobolevFusion
 (sobolev_smoothing_enabled) or out of a z-slab / multi-GPU run (`comm`), a carve-distance
@@ -189,8 +202,9 @@ with SDF-2-SDF, for the "sdf" tracker through the sequence's own `icp_*` and `ph
 pyramid or filtered depth as the point source and a colour term against the colour volume (both are settings of the
 `sdf_tracker`), a normal-angle gate from the SDF gradient,
 a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casting step, a confidence
-image in the prediction, a colour image of another
-resolution or camera than the depth image's, marching squares for 2-D models, vertex attributes beyond normals and
+image in the prediction, for the RGB-D sensor fisheye and thin-prism lens models, registering colour into the depth
+camera, hole filling, time synchronisation of the two streams, rolling shutter and the reference's XML calibration
+files, marching squares for 2-D models, vertex attributes beyond normals and
 colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, and for the
 moving volume welding across seams, a shift enqueued without the mesh totals' host read, and for its brick store
 saving the store to disk, streaming without the host read of the brick total, and bricks in half precision."""
@@ -200,7 +214,7 @@ import numpy as np
 import torch
 
 from .. import (device_depth_confidence, device_fusion, device_icp, device_mesh, device_raycast, device_rigid,
-                device_volume_bricks, device_volume_shift)
+                device_rgbd, device_volume_bricks, device_volume_shift)
 from ..device_core import require_gpu
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
                              unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
@@ -215,8 +229,10 @@ from .._lib import DEPTH_F32
 from ..math_utils.transformation import twist_vector_to_matrix3d
 from ..tsdf.generation import DepthCamera, device_depth, offsets_of
 from .brick_store import BrickStore
+from .rgbd_sensor import RgbdSensor
 
-__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "merge_meshes",
+__all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "RgbdSensor",
+           "merge_meshes",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
@@ -647,7 +663,10 @@ class SequenceFusion3d:
     and outliers.  In "sdf" mode rigid_records holds `sdf_tracker`'s records, in the same layout.  With moving_volume
     (a MovingVolume) the model is a window that follows the camera: `array_offset` moves in whole voxels
     (`initial_array_offset` keeps the construction value), the frame records carry shift and streamed_faces, and
-    `streamed_meshes` lists the host meshes of what left (module docstring, "Moving volume")."""
+    `streamed_meshes` lists the host meshes of what left (module docstring, "Moving volume").  With sensor (an
+    RgbdSensor) integrate takes the RAW frame pair, registers it first and runs the frame on the registered pair;
+    `camera` may then be None and is sensor.camera, and the frame records carry registration (module docstring,
+    "RGB-D sensor")."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
@@ -655,7 +674,17 @@ class SequenceFusion3d:
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
                  photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None,
-                 icp_robust=None, sdf_tracker=None, moving_volume=None):
+                 icp_robust=None, sdf_tracker=None, moving_volume=None, sensor=None):
+        if sensor is not None:
+            if not isinstance(sensor, RgbdSensor):
+                raise ValueError("sensor must be a fusion.RgbdSensor or None, got %r" % (sensor,))
+            if camera is not None and camera is not sensor.camera:
+                raise ValueError("a sequence with a sensor runs on sensor.camera, the camera of the registered stream: "
+                                 "pass camera=None (or sensor.camera)")
+            camera = sensor.camera
+        elif camera is None:
+            raise ValueError("camera may be None only with a sensor")
+        self.sensor = sensor
         if moving_volume is not None and not isinstance(moving_volume, MovingVolume):
             raise ValueError("moving_volume must be a fusion.MovingVolume or None, got %r" % (moving_volume,))
         self.moving_volume = moving_volume
@@ -793,6 +822,9 @@ class SequenceFusion3d:
         if not self.colour and colour_image is not None:
             raise ValueError("colour_image needs a sequence made with colour=True")
         k = len(self.twists)
+        registration = None
+        if self.sensor is not None:  # the raw pair becomes the registered pair; everything below sees that stream
+            depth_image, colour_image, registration = self.sensor.register_device(depth_image, colour_image)
         depth, code = device_depth(depth_image)
         sdf_joint = self.sdf_tracker is not None and self.sdf_tracker.photometric_weight is not None
         if self.photometric_weight is not None or sdf_joint:
@@ -851,6 +883,8 @@ class SequenceFusion3d:
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
                  "fusion": unpack(record.cpu().numpy()),
                  "prediction_hits": None if hits is None else int(hits.item())}
+        if registration is not None:
+            frame["registration"] = device_rgbd.unpack_record(registration.cpu().numpy())
         if self.moving_volume is not None:  # between frames: the policy reads the frame's twist, already on the host
             mv = self.moving_volume
             s = mv.shift_for(frame["twist"], self.array_offset, self.field_shape, self.voxel_size)

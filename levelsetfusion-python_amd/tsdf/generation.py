@@ -1,6 +1,7 @@
 """TSDF generation from depth images on the GPU -- the input stage of the optimizers
 (reference: tsdf/generation.py:130-235, 356-437; camera model calib/camera.py:69-311 reduced to what is consumed:
-a 3x3 intrinsic matrix and the depth unit ratio).  Nearest-pixel lookup (FilteringMethod.NONE) and the two bilinear 2-D
+a 3x3 intrinsic matrix and the depth unit ratio; distortion coefficients and the transform to a colour camera are
+fusion.RgbdSensor's, which hands the generators the images of an ideal camera).  Nearest-pixel lookup (FilteringMethod.NONE) and the two bilinear 2-D
 variants (tsdf/generation.py:18-128) here, the EWA filters in tsdf/ewa.py of this package."""
 import ctypes
 from enum import Enum
