@@ -44,6 +44,7 @@ struct Grid {
     int fast_ok;           // 32-bit buffer addressing is possible: 3 planes of a vector field stay below 4 GiB
     int wide_ok;           // float4 state kernels: a wave's neighbourhoods may be addressed relative to its first lane
     int e_begin, e_end;    // slices whose energies count (lsf_grid::energy_z_begin / _end; default: all)
+    int e_all;             // [e_begin, e_end) holds every slice of the array: no voxel needs the test (wave-uniform)
     unsigned list_group;   // wave-units per group of the fused kernel's list walk (wave_list_walk)
     int list_store_nt;     // list walk: non-temporal stores of the new state (lists too long for the Infinity Cache)
     int shift_x, shift_y;  // log2(nx), log2(ny) when both are powers of two (voxel index -> x, y, z by shifts), else -1
@@ -85,6 +86,7 @@ __host__ inline Grid make_grid(const lsf_grid* g, int tile_y = 4) {
     const bool limited = g->energy_z_end > g->energy_z_begin;
     r.e_begin = limited ? g->energy_z_begin : 0;
     r.e_end = limited ? g->energy_z_end : g->nz;
+    r.e_all = r.e_begin <= 0 && r.e_end >= g->nz;
     r.list_group = 4u;
     r.list_store_nt = 0;
     auto log2_of = [](int v) {
@@ -513,11 +515,19 @@ __device__ inline double shfl_down_f64(double v, int delta) {
 // source (row 0 of row_bcast:15, rows 0-1 of row_bcast:31) receive the identity.  ~85 VALU instructions for one packed
 // maximum + three float64 sums where six ds_bpermute steps each took ~1 us at the end of every wave of the fused kernel.
 // ALL 64 lanes must be active.
+// bound_ctrl with every row and bank enabled: a lane without a source reads 0 -- the bit pattern of both identities, the
+// packed maximum's 0 and the sum's +0.0 -- so the move has no `old` operand to be set up in front of it (one v_mov_b32
+// per DPP move otherwise: 48 of them in a row ending)
 template <int CTRL>
 __device__ inline unsigned long long dpp_u64(unsigned long long v) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, false);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, true);
     return ((unsigned long long)hi << 32) | lo;
+}
+
+template <int CTRL>
+__device__ inline double dpp_f64(double v) {
+    return __longlong_as_double((long long)dpp_u64<CTRL>((unsigned long long)__double_as_longlong(v)));
 }
 
 __device__ inline unsigned long long broadcast_lane63_u64(unsigned long long v) {
@@ -526,6 +536,15 @@ __device__ inline unsigned long long broadcast_lane63_u64(unsigned long long v) 
     return ((unsigned long long)hi << 32) | lo;
 }
 
+// the six steps of a wave reduction, in the order every reduction here takes them (the association of a sum is fixed by it)
+#define LSF_DPP_STEPS(STEP)                \
+    STEP(0xb1)  /* quad_perm:[1,0,3,2] */  \
+    STEP(0x4e)  /* quad_perm:[2,3,0,1] */  \
+    STEP(0x124) /* row_ror:4 */            \
+    STEP(0x128) /* row_ror:8 */            \
+    STEP(0x142) /* row_bcast:15 */         \
+    STEP(0x143) /* row_bcast:31 */
+
 // maximum over the wave, in EVERY lane
 __device__ inline unsigned long long wave_max_u64(unsigned long long v) {
 #define LSF_STEP(CTRL)                                   \
@@ -533,26 +552,15 @@ __device__ inline unsigned long long wave_max_u64(unsigned long long v) {
         const unsigned long long o = dpp_u64<CTRL>(v);   \
         v = o > v ? o : v;                               \
     }
-    LSF_STEP(0xb1)   // quad_perm:[1,0,3,2]
-    LSF_STEP(0x4e)   // quad_perm:[2,3,0,1]
-    LSF_STEP(0x124)  // row_ror:4
-    LSF_STEP(0x128)  // row_ror:8
-    LSF_STEP(0x142)  // row_bcast:15
-    LSF_STEP(0x143)  // row_bcast:31
+    LSF_DPP_STEPS(LSF_STEP)
 #undef LSF_STEP
     return broadcast_lane63_u64(v);
 }
 
 // sum over the wave, in EVERY lane (a fixed association, the same in every launch)
 __device__ inline double wave_sum_f64(double v) {
-#define LSF_STEP(CTRL)                                                                                               \
-    v += __longlong_as_double((long long)dpp_u64<CTRL>((unsigned long long)__double_as_longlong(v)));
-    LSF_STEP(0xb1)
-    LSF_STEP(0x4e)
-    LSF_STEP(0x124)
-    LSF_STEP(0x128)
-    LSF_STEP(0x142)
-    LSF_STEP(0x143)
+#define LSF_STEP(CTRL) v += dpp_f64<CTRL>(v);
+    LSF_DPP_STEPS(LSF_STEP)
 #undef LSF_STEP
     return __longlong_as_double((long long)broadcast_lane63_u64((unsigned long long)__double_as_longlong(v)));
 }
@@ -600,7 +608,7 @@ __device__ inline void block_reduce_commit(unsigned long long packed, const doub
 
 // The other way for a workgroup of an iteration kernel to end (fixed-count library calls, lsf_state_run_finish): nothing
 // reads a record before the call's end there, so every WAVE leaves its packed maximum and its three sums in a row of its
-// own -- rows[block * waves + wave], one 32-byte store of lane 0 -- and records_from_rows_kernel combines the rows of all
+// own -- rows[block * waves + wave], one 32-byte store of lane 63 -- and records_from_rows_kernel combines the rows of all
 // the call's launches once, behind the last iteration.  No barrier, no LDS, no second stage, no atomic; a wave that
 // processed nothing stores zeros, so a launch defines every row of its block.  Must be called by every thread of the block.
 struct alignas(32) RecordRow {
@@ -609,12 +617,27 @@ struct alignas(32) RecordRow {
 };
 
 __device__ inline void wave_reduce_store_row(unsigned long long packed, const double (&sums)[3], RecordRow* __restrict__ rows) {
+    // the four reductions step by step side by side: a DPP move must wait two issue slots for the VALU result it reads, and
+    // the other three chains' moves stand in those slots instead of s_nop.  Each chain takes the steps of wave_max_u64 /
+    // wave_sum_f64 in their order (the same sums, bit for bit); the result is complete in lane 63, which stores it
+    // itself -- no readlane broadcast and no copies back into lane 0.
     RecordRow r;
-    r.max_packed = wave_max_u64(packed);
-    r.data = wave_sum_f64(sums[0]);
-    r.smoothing = wave_sum_f64(sums[1]);
-    r.level_set = wave_sum_f64(sums[2]);
-    if ((threadIdx.x & (kWave - 1)) == 0) rows[blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave] = r;
+    r.max_packed = packed;
+    r.data = sums[0];
+    r.smoothing = sums[1];
+    r.level_set = sums[2];
+#define LSF_STEP(CTRL)                                                                                             \
+    {                                                                                                              \
+        const unsigned long long om = dpp_u64<CTRL>(r.max_packed);                                                 \
+        const double o0 = dpp_f64<CTRL>(r.data), o1 = dpp_f64<CTRL>(r.smoothing), o2 = dpp_f64<CTRL>(r.level_set); \
+        r.max_packed = om > r.max_packed ? om : r.max_packed;                                                      \
+        r.data += o0;                                                                                              \
+        r.smoothing += o1;                                                                                         \
+        r.level_set += o2;                                                                                         \
+    }
+    LSF_DPP_STEPS(LSF_STEP)
+#undef LSF_STEP
+    if ((threadIdx.x & (kWave - 1)) == kWave - 1) rows[blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave] = r;
 }
 
 // the rows one launch of `blocks` workgroups of `threads` threads writes

@@ -164,6 +164,16 @@ void slavcheva_state_kernel(const vf4* __restrict__ state_in,
 #endif
         int x, y, z;
         decode_voxel(g, i, x, y, z);
+        // whose energies count: a slab's recomputed halo slices / rows belong to the neighbour's sums.  A grid whose range
+        // holds every slice skips the slice test behind a scalar branch, next to the one decode_voxel takes (the empty asm
+        // keeps the compiler from computing the test for everybody and discarding it); a walk that is not cut along y has
+        // no row test at all.
+        bool in_range = true;
+        if (!g.e_all) {
+            asm volatile("");
+            in_range = (z >= g.e_begin) & (z < g.e_end);
+        }
+        if (WALK_CODE != WALK) in_range = in_range & (y >= g.ey_begin) & (y < g.ey_end);
         Deferred d;
         d.i = listed ? (int)i : -1;
         const float l = sc.x;
@@ -171,11 +181,18 @@ void slavcheva_state_kernel(const vf4* __restrict__ state_in,
         float gv[3] = {0.0f, 0.0f, 0.0f};
         double e[3] = {0.0, 0.0, 0.0};
         fast_voxel_gradient<D, SMOOTH, LEVELSET, DATA, ENERGY>(n, p, l, cn, gv, e);
-        const bool counted = in_band && z >= g.e_begin && z < g.e_end && y >= g.ey_begin && y < g.ey_end;
+        // whose energies count: a slab's recomputed halo slices / rows belong to the neighbour's sums.  A grid whose range
+        // holds every slice skips the slice test (wave-uniform), a walk that is not cut along y has no row test at all.
+        const bool counted = in_band & in_range;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             d.wv[c] = (c < D && in_band) ? (-gv[c]) * p.rate : 0.0f;
-            en[c] += counted ? e[c] : 0.0;
+            // every term's energy is a float32 value widened (lsf_slavcheva_terms.h): narrowing it back is exact, the
+            // select works on one register instead of two, and (double)0.0f is 0.0.  (The empty asm keeps the compiler
+            // from moving the conversion in front of the select again.)
+            float ec = counted ? (float)e[c] : 0.0f;
+            asm("" : "+v"(ec));
+            en[c] += (double)ec;
         }
         const float len = vec_length<D>(d.wv);
         const bool moved = !(d.wv[0] == 0.0f && d.wv[1] == 0.0f && d.wv[2] == 0.0f);
@@ -212,6 +229,9 @@ void slavcheva_state_kernel(const vf4* __restrict__ state_in,
         // neighbourhood loads and waits for memory once.  Lanes past the end of the list read its LAST entry (a valid,
         // listed voxel: their loads stay inside the array) and are not processed.
         const WaveWalk w = wave_list_walk(band_count, g.list_group);
+        // (measured and rejected: the wave's number through readfirstlane, which makes the loop test a scalar compare and
+        // saves five VALU instructions per unit -- the bench's iteration launch took 28.1-28.2 us with it against 27.4-27.6
+        // without, five alternations on one box: profiles/list_walk_issue_slots.md)
         const unsigned waves = blockDim.x / kWave, wave = threadIdx.x / kWave;
         auto entry = [&](unsigned unit, bool& listed) {
             const unsigned k = unit * kWave + (threadIdx.x & (kWave - 1));
