@@ -1867,6 +1867,70 @@ int lsf_rgbd_register_depth(const void *depth, int32_t depth_dtype, const double
 int lsf_rgbd_rectify_colour(const uint8_t *src, uint8_t *dst, uint8_t *valid, const lsf_rgbd_params *params,
                             void *stream);
 
+/* ---- keyframe ferns: a frame's code, its distance to the stored keyframes, the nearest, the append ------------------------
+ * The contract is this project's ("Tracking quality and relocalisation";
+ * tests/relocaliser_restatement.py restates it), after Glocker et al., "Real-time RGB-D camera relocalization via
+ * randomized ferns".  A frame is reduced to a COARSE image of block means; a fern is `decisions` threshold tests on that
+ * image and gives one byte; a frame's code is `ferns` bytes; the distance of two codes is the number of ferns whose bytes
+ * differ.  Every sum is an integer sum and every count an integer, so the results do not depend on any order and a rerun
+ * is bit identical; there are no atomics and no host wait. */
+typedef struct lsf_reloc_params {
+    double depth_unit_ratio;             /* encode: metres per depth unit, finite and > 0 */
+    double depth_near, depth_far;        /* encode: near and far; a pixel counts when near <= d <= far; 0 < near < far <= 64 */
+    int32_t height, width;               /* encode: the frame */
+    int32_t coarse_height, coarse_width; /* the coarse image; encode needs coarse_height <= height, likewise the width */
+    int32_t channels;                    /* of the coarse image: 1 (depth) or 4 (depth, R, G, B) */
+    int32_t ferns, decisions;            /* query: F in 1 .. LSF_RELOC_MAX_FERNS, D in 1 .. LSF_RELOC_MAX_DECISIONS */
+    int32_t capacity;                    /* query: the rows the database holds, >= 1 */
+    int32_t candidates;                  /* query: 1 .. LSF_RELOC_MAX_CANDIDATES nearest keyframes */
+    int32_t harvest;                     /* query: 1 appends the frame when it is far from every keyframe, 0 never */
+    int32_t harvest_differing;           /* query with harvest: the least distance that appends, >= 1 */
+    int32_t reserved;                    /* 0 */
+} lsf_reloc_params;
+#define LSF_RELOC_MAX_BLOCKS 1024
+#define LSF_RELOC_MAX_FERNS 4096
+#define LSF_RELOC_MAX_DECISIONS 8
+#define LSF_RELOC_MAX_CANDIDATES 4
+#define LSF_RELOC_MAX_DEPTH 64.0
+#define LSF_RELOC_ENCODE_RECORD_WORDS 2
+#define LSF_RELOC_QUERY_RECORD_WORDS 12
+
+/* depth: DEVICE [height][width] of depth_dtype (LSF_DEPTH_*), scaled as the TSDF generators scale it (uint16 and float64
+ * times the ratio in float64, float32 times float32(ratio) in float32); d is that value as float64.  colour: NULL
+ * (channels 1) or DEVICE uint8 [height][width][3] registered to the depth (channels 4).  coarse: DEVICE float32
+ * [coarse_height][coarse_width][channels].  block_counts: DEVICE int32 [coarse_height][coarse_width], the counting pixels
+ * of every block.  record: DEVICE int32 [LSF_RELOC_ENCODE_RECORD_WORDS] = counting pixels, valid blocks.
+ * Coarse row i covers the image rows [i*height/coarse_height, (i + 1)*height/coarse_height) in integer division, the
+ * columns likewise.  A pixel COUNTS when near <= d <= far (a NaN does not).  A block is VALID when at least half of its
+ * pixels count (2*count >= pixels).  A valid block's depth is float32((double(sum q) / double(count)) / 2^20) with
+ * q = (int64) rint(d * 2^20) summed as integers over its counting pixels, and with colour its channels 1..3 are
+ * float32(double(sum of the byte) / double(count)) over the same pixels; every channel of a block that is not valid is 0.
+ * Two launches (a wave per block; one workgroup for the record).  Refused with LSF_ERR_BAD_ARGUMENT: a NULL (but
+ * colour), a bad depth_dtype, extents < 1, a coarse extent above the image's, channels that is not 1 without and 4 with
+ * colour, a ratio, near or far that is not finite, ratio <= 0, near <= 0, near >= far, far > LSF_RELOC_MAX_DEPTH, a buffer
+ * off its element's alignment, any overlap; more than 2^31 - 1 pixels is LSF_ERR_BAD_DIMS. */
+int lsf_reloc_encode(const void *depth, int32_t depth_dtype, const uint8_t *colour, float *coarse, int32_t *block_counts,
+                     int32_t *record, const lsf_reloc_params *params, void *stream);
+
+/* coarse: lsf_reloc_encode's.  The fern table, DEVICE, [ferns][decisions] each: locations int32 (a coarse pixel index
+ * i*coarse_width + j), channels uint8 (< channels), thresholds float32.  codes: DEVICE uint8 [capacity][ferns], 16-byte
+ * aligned, the database; n_keyframes: DEVICE int32, its size, read as min(max(n, 0), capacity).  frame_code: DEVICE uint8
+ * [ferns], out.  distances: DEVICE int32 [capacity], out.  record: DEVICE int32 [LSF_RELOC_QUERY_RECORD_WORDS], out.
+ * Frame code: bit j of byte f is 1 when coarse[location][channel] > threshold AND coarse[location][0] > 0, for decision
+ * (f, j); a location or a channel outside the coarse image gives 0.  distances[k] for k < n: the ferns f with
+ * codes[k][f] != frame_code[f]; -1 for k >= n.  Nearest: the `candidates` keyframes in rising order of (distance, id).
+ * With harvest, the frame is WANTED when n == 0 or the smallest distance is >= harvest_differing; a wanted frame is
+ * appended when n < capacity: codes[n] = frame_code and *n_keyframes = n + 1 (distances keeps the values from before).
+ * record: [0] n before the call, [1, 5) the nearest ids, -1 where n is smaller, [5, 9) their distances, -1 likewise,
+ * [9] the appended id or -1, [10] 1 when a wanted frame met a full database, [11] 0.
+ * Three launches (the code; a wave per keyframe row, which reads aligned 16-byte words; one workgroup that selects and
+ * appends).  Refused with LSF_ERR_BAD_ARGUMENT: a NULL, coarse extents < 1, channels not 1 or 4, ferns, decisions or
+ * candidates out of range, capacity < 1, harvest not 0 or 1, harvest_differing < 1 with harvest, codes off 16-byte and
+ * an int32 or float32 buffer off 4-byte alignment, any overlap; capacity * ferns above 2^31 - 1 is LSF_ERR_BAD_DIMS. */
+int lsf_reloc_query(const float *coarse, const int32_t *locations, const uint8_t *channels, const float *thresholds,
+                    uint8_t *codes, int32_t *n_keyframes, uint8_t *frame_code, int32_t *distances, int32_t *record,
+                    const lsf_reloc_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

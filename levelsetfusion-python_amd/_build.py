@@ -13,7 +13,7 @@ SOURCES = ["lsf_fields.hip", "lsf_hierarchical.hip", "lsf_slavcheva.hip", "lsf_s
            "lsf_terms.hip", "lsf_rigid.hip", "lsf_rigid3d.hip", "lsf_fusion.hip",
            "lsf_raycast.hip", "lsf_mesh.hip", "lsf_icp.hip", "lsf_depth_pyramid.hip", "lsf_depth_confidence.hip",
            "lsf_intensity_pyramid.hip", "lsf_point_sdf.hip", "lsf_volume_shift.hip", "lsf_volume_bricks.hip",
-           "lsf_rgbd.hip"]
+           "lsf_rgbd.hip", "lsf_relocaliser.hip"]
 HEADERS = ["lsf_device.h", "lsf_slavcheva_terms.h", "lsf_slavcheva_state_taps.h", "lsf_tsdf_typed.h",
            "lsf_rigid_solve.h", "lsf_mesh_tables.h", "lsf_icp_shared.h", "lsf_tsdf_sample.h",
            os.path.join("..", "..", "include", "lsf_hip.h")]

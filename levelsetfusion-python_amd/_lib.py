@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "a67f633a97d3742a"
+HEADER_ABI_HASH = "7b9c31a7c45631ef"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -294,6 +294,23 @@ RGBD_MAX_BLOCKS = 512
 RGBD_RECORD_WORDS = 8
 RGBD_ZBUFFER_EMPTY = 0x7f800000
 
+class RelocParams(ctypes.Structure):
+    """lsf_reloc_params: the frame, the coarse image, the fern table's extents and the database (lsf_reloc_encode /
+    lsf_reloc_query)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("depth_unit_ratio", "depth_near", "depth_far")] + \
+               [(n, ctypes.c_int32) for n in ("height", "width", "coarse_height", "coarse_width", "channels", "ferns",
+                                              "decisions", "capacity", "candidates", "harvest", "harvest_differing",
+                                              "reserved")]
+
+
+RELOC_MAX_BLOCKS = 1024
+RELOC_MAX_FERNS = 4096
+RELOC_MAX_DECISIONS = 8
+RELOC_MAX_CANDIDATES = 4
+RELOC_MAX_DEPTH = 64.0
+RELOC_ENCODE_RECORD_WORDS = 2
+RELOC_QUERY_RECORD_WORDS = 12
+
 ICP_MAX_LEVELS = 4
 ICP_RECORD_DOUBLES = 64
 ICP_MAX_BLOCKS = 256
@@ -550,6 +567,8 @@ PROTOTYPES = {
     "lsf_rgbd_ray_table": (ctypes.c_int, [_vp, _vp, _P(RgbdParams), _vp]),
     "lsf_rgbd_register_depth": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _P(RgbdParams), _vp]),
     "lsf_rgbd_rectify_colour": (ctypes.c_int, [_vp, _vp, _vp, _P(RgbdParams), _vp]),
+    "lsf_reloc_encode": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _P(RelocParams), _vp]),
+    "lsf_reloc_query": (ctypes.c_int, [_vp] * 9 + [_P(RelocParams), _vp]),
     "lsf_icp_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpParams), _vp]),
     "lsf_depth_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _P(DepthPyramidParams), _vp]),
     "lsf_icp_run_pyramid": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(IcpPyramidParams), _vp]),

@@ -180,6 +180,23 @@ pyramids, moving_volume and the non-rigid steps see the registered stream, and t
 call's eight counts.  With colour=False the sensor gets no colour image; the depth is still registered into the colour
 camera when the sensor has one.  Without the keyword nothing changes.  Cost: profiles/rgbd_sensor_cost.md.
 
+Tracking quality and relocalisation (INTEGRATION.md section 3, "Tracking quality and relocalisation";
+tests/relocaliser_restatement.py restates it): without them every tracker result is trusted.  With
+SequenceFusion3d(tracking_quality=TrackingQuality(min_pair_fraction, max_rms)), in "icp" and "sdf" mode, a frame k >= 1 is
+judged by its last ICP record: good when the record is not skipped, count * s^2 / (H * W) >= min_pair_fraction (s the
+stride of the record's level) and sqrt(energy / count) <= max_rms.  A frame that is not good is not fused and takes no
+non-rigid step, its twist in `twists` is the last good twist, and the next frame starts from there; the frame record
+gains tracking_state ("tracking" or "lost") and tracking_quality (pair_fraction, rms, skipped), and its fusion is None
+when nothing was fused.  relocaliser=Relocaliser(...) (it implies TrackingQuality(); refused with a moving_volume, whose
+window a keyframe's view may have left) adds the way back: every frame is encoded into a coarse image of block means
+and, when fused, offered to a database of keyframes encoded by random ferns (csrc/lsf_relocaliser.hip: lsf_reloc_encode,
+lsf_reloc_query), which keeps the frames that are far from all it holds, with their twists.  A frame that is not good,
+or that follows a lost one, is tracked again from the nearest keyframes' twists in order and last from the last good
+twist (not again, when it has just failed from it); the first good result makes it "relocalised", none leaves it
+"lost".  From a relocalisation on, Relocaliser(resume_after=) good frames, the relocalised one included, are tracked
+but not fused ("recovering").  The record gains keyframe and relocalisation.  Without the keywords nothing changes, and
+no record has a new key.  Cost: profiles/relocaliser_cost.md.
+
 Host synchronisations per frame: the rigid run's or the ICP run's one copy back (frames >= 1 with rigid_iterations > 0,
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
@@ -188,7 +205,9 @@ vertex and face totals.  A moving volume's policy adds none (the twist is on the
 costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
 store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
 bricks to the card.  A sensor adds none per frame (its record is read with the fusion record's wait); its first frame
-waits once for the check of the ray tables.
+waits once for the check of the ray tables.  A tracking_quality adds none (the records are on the host); a relocaliser adds
+one 48-byte copy per query: one per fused frame, one more per frame that has to be relocalised, and a tracker run per
+start that is tried.
 
 Not covered: carving, weights or colour in volume mode, a cumulative warp out of SobolevFusion
 (sobolev_smoothing_enabled) or out of a z-slab / multi-GPU run (`comm`), a carve-distance
@@ -205,9 +224,11 @@ a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casti
 image in the prediction, for the RGB-D sensor fisheye and thin-prism lens models, registering colour into the depth
 camera, hole filling, time synchronisation of the two streams, rolling shutter and the reference's XML calibration
 files, marching squares for 2-D models, vertex attributes beyond normals and
-colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, and for the
-moving volume welding across seams, a shift enqueued without the mesh totals' host read, and for its brick store
-saving the store to disk, streaming without the host read of the brick total, and bricks in half precision."""
+colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, for the
+relocaliser relocalising inside a moving window, saving the keyframe database, loop closure and a learned quality
+test, and for the moving volume welding across seams, a shift enqueued without the mesh totals' host read, and for its
+brick store saving the store to disk, streaming without the host read of the brick total, and bricks in half
+precision."""
 import math
 
 import numpy as np
@@ -229,9 +250,11 @@ from .._lib import DEPTH_F32
 from ..math_utils.transformation import twist_vector_to_matrix3d
 from ..tsdf.generation import DepthCamera, device_depth, offsets_of
 from .brick_store import BrickStore
+from .relocaliser import Relocaliser, TrackingQuality, level_stride
 from .rgbd_sensor import RgbdSensor
 
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "RgbdSensor",
+           "Relocaliser", "TrackingQuality",
            "merge_meshes",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
@@ -666,7 +689,11 @@ class SequenceFusion3d:
     `streamed_meshes` lists the host meshes of what left (module docstring, "Moving volume").  With sensor (an
     RgbdSensor) integrate takes the RAW frame pair, registers it first and runs the frame on the registered pair;
     `camera` may then be None and is sensor.camera, and the frame records carry registration (module docstring,
-    "RGB-D sensor")."""
+    "RGB-D sensor").  With tracking_quality (a TrackingQuality; "icp" and "sdf" mode) a frame whose last ICP record
+    fails the gate is not fused and keeps the last good twist, `tracking_state` is the last frame's state and the
+    records carry tracking_state and tracking_quality; with relocaliser (a Relocaliser) fused frames become keyframes
+    and a lost frame is tracked again from the nearest keyframes' twists, the records carrying keyframe and
+    relocalisation (module docstring, "Tracking quality and relocalisation")."""
 
     def __init__(self, camera, field_shape, array_offset, voxel_size=0.004, narrow_band_width_voxels=20,
                  max_weight=math.inf, rigid_iterations=60, rigid_rate=0.5, eta=0.01, nonrigid_optimizer=None,
@@ -674,7 +701,8 @@ class SequenceFusion3d:
                  icp_strides=device_icp.STRIDES, icp_max_distance=device_icp.MAX_DISTANCE, icp_pyramid=None,
                  icp_max_normal_angle=None, carve=False, confidence=None, colour=False, colour_band=1.0,
                  photometric_weight=None, icp_max_intensity_difference=math.inf, icp_intensity_pyramid=None,
-                 icp_robust=None, sdf_tracker=None, moving_volume=None, sensor=None):
+                 icp_robust=None, sdf_tracker=None, moving_volume=None, sensor=None, tracking_quality=None,
+                 relocaliser=None):
         if sensor is not None:
             if not isinstance(sensor, RgbdSensor):
                 raise ValueError("sensor must be a fusion.RgbdSensor or None, got %r" % (sensor,))
@@ -755,6 +783,22 @@ class SequenceFusion3d:
             if self.sdf_tracker.photometric_weight is not None and not self.colour:
                 raise ValueError("an sdf_tracker with a photometric_weight needs colour=True: its colour term reads "
                                  "the model's colour volume")
+        if tracking_quality is not None and not isinstance(tracking_quality, TrackingQuality):
+            raise ValueError("tracking_quality must be a fusion.TrackingQuality or None, got %r" % (tracking_quality,))
+        if relocaliser is not None:
+            if not isinstance(relocaliser, Relocaliser):
+                raise ValueError("relocaliser must be a fusion.Relocaliser or None, got %r" % (relocaliser,))
+            if moving_volume is not None:
+                raise ValueError("a relocaliser does not combine with a moving_volume: a keyframe's view may have left "
+                                 "the window, and relocalising inside a moving window is out of scope")
+            if tracking_quality is None:
+                tracking_quality = TrackingQuality()
+        if tracking_quality is not None and tracking_reference not in ("icp", "sdf"):
+            raise ValueError("tracking_quality and relocaliser judge the ICP records of tracking_reference \"icp\" and "
+                             "\"sdf\"; %r writes none" % (tracking_reference,))
+        self.tracking_quality, self.relocaliser = tracking_quality, relocaliser
+        self.tracking_state = "tracking"  # with a tracking_quality: the last frame's state
+        self._recovering = 0  # with a relocaliser: the good frames still to pass unfused after a relocalisation
         self.voxel_size = voxel_size
         self.narrow_band_width_voxels = narrow_band_width_voxels
         self.rigid_iterations = int(rigid_iterations)
@@ -802,6 +846,69 @@ class SequenceFusion3d:
         twist, records, _ = self.icp.track(depth, code, self.prediction, normals, twist, twist, **colours)
         return twist, records, hits
 
+    def _track_direct(self, depth, code, twist, colour_image, gen):
+        """"icp" and "sdf" mode: the frame tracked from twist (the "icp" prediction is ray-cast at twist).  Returns the
+        new twist, the unpacked records, the prediction's device hit count (None in "sdf" mode) and whether a tracker
+        ran at all"""
+        model = self.canonical
+        if self.tracking_reference == "icp":
+            if sum(self.icp_iterations) > 0:
+                return self._track_icp(depth, code, twist,
+                                       None if self.photometric_weight is None else colour_image) + (True,)
+        elif sum(self.sdf_tracker.iterations) > 0:
+            joint = {}
+            if self.sdf_tracker.photometric_weight is not None:
+                joint = dict(colour=model.colour, colour_image=colour_image)
+            new, records, _ = self.sdf_tracker.track(depth, code, model.tsdf, model.weight, self.array_offset, twist,
+                                                     **gen, **joint)
+            return new, records, None, True
+        return twist, [], None, False
+
+    def _track_judged(self, depth, code, last_good, colour_image, gen, coarse, verdict):
+        """a frame k >= 1 under a tracking_quality (module docstring, "Tracking quality and relocalisation"): tracked from
+        the last good twist unless the state is lost, judged, and with a relocaliser tried again from the nearest
+        keyframes' twists and last from the last good twist.  Returns _track_direct's tuple of the attempt that was
+        good -- of the last attempt, with the last good twist, when none was -- and whether the frame is fused; fills
+        verdict with state, quality and relocalisation"""
+        tracker = self.icp if self.tracking_reference == "icp" else self.sdf_tracker
+        shape = tuple(depth.shape)
+
+        def attempt(start):
+            out = self._track_direct(depth, code, start.copy(), colour_image, gen)
+            last = out[1][-1] if out[1] else None
+            stride = 1 if last is None else level_stride(tracker, last["level"])
+            return out, self.tracking_quality.judge(last, shape, stride)
+
+        reloc = self.relocaliser
+        was_lost = reloc is not None and self.tracking_state == "lost"
+        out, quality, state = None, None, "lost"
+        if not was_lost:
+            out, quality = attempt(last_good)
+            if quality["good"]:
+                state = "tracking"
+        if state == "lost" and reloc is not None:
+            found = reloc.query(coarse)
+            verdict["relocalisation"] = {"candidates": found["nearest"], "distances": found["distances"],
+                                         "chosen": None}
+            starts = [(i, reloc.twists[i]) for i in found["nearest"]] + ([(-1, last_good)] if was_lost else [])
+            for chosen, start in starts:  # the last good twist last; a frame that just failed from it is not tried again
+                out, quality = attempt(start)
+                if quality["good"]:
+                    state = "relocalised"
+                    verdict["relocalisation"]["chosen"] = chosen
+                    self._recovering = reloc.resume_after
+                    break
+        good = state != "lost"
+        fuse = good
+        if good and self._recovering > 0:  # tracked, not fused: the model waits until the track has settled
+            self._recovering -= 1
+            fuse = False
+            state = state if state == "relocalised" else "recovering"
+        verdict["state"], verdict["quality"] = state, {k: quality[k] for k in ("pair_fraction", "rms", "skipped")}
+        if not good:
+            return last_good, out[1], out[2], out[3], False
+        return out + (fuse,)
+
     def _frame_weight(self, depth, code, tracked):
         """the frame's confidence image (None without `confidence`): from the tracker's pyramid of this frame when it
         built one (tracked) with the confidence's filter settings, else from a one-level pyramid of its own"""
@@ -832,21 +939,19 @@ class SequenceFusion3d:
         model = self.canonical
         rigid_records, nonrigid, hits, tracked = [], None, None, False
         gen = dict(voxel_size=self.voxel_size, narrow_band_width_voxels=self.narrow_band_width_voxels)
+        # with a tracking_quality: whether the frame is fused, and what the frame record gains
+        fuse, verdict, coarse = True, {}, None
+        if self.relocaliser is not None:
+            coarse = self.relocaliser.encode(depth, self.camera, colour_image if self.colour else None)
         if k == 0:
             twist = self.initial_twist.copy()
         else:
             twist = self.twists[-1].copy()
-            if self.tracking_reference == "icp":
-                if sum(self.icp_iterations) > 0:
-                    twist, rigid_records, hits = self._track_icp(
-                        depth, code, twist, None if self.photometric_weight is None else colour_image)
-                    tracked = True
-            elif self.tracking_reference == "sdf":
-                if sum(self.sdf_tracker.iterations) > 0:
-                    joint = dict(colour=model.colour, colour_image=colour_image) if sdf_joint else {}
-                    twist, rigid_records, _ = self.sdf_tracker.track(
-                        depth, code, model.tsdf, model.weight, self.array_offset, twist, **gen, **joint)
-                    tracked = True
+            if self.tracking_quality is not None:
+                twist, rigid_records, hits, tracked, fuse = self._track_judged(depth, code, twist, colour_image, gen,
+                                                                               coarse, verdict)
+            elif self.tracking_reference in ("icp", "sdf"):
+                twist, rigid_records, hits, tracked = self._track_direct(depth, code, twist, colour_image, gen)
             elif self.rigid_iterations > 0:
                 reference = model.tsdf
                 if self.tracking_reference == "raycast":
@@ -856,7 +961,7 @@ class SequenceFusion3d:
                     self.eta, self.voxel_size, self.voxel_size, self.narrow_band_width_voxels, twist=twist)
                 rigid_records = [unpack_rigid_record(r) for r in records]
                 del reference
-        through = self.nonrigid_optimizer is not None and k > 0  # the frame takes the non-rigid step
+        through = self.nonrigid_optimizer is not None and k > 0 and fuse  # the frame takes the non-rigid step
         if through:
             live = device_rigid.live_volume_3d(depth, code, self.camera, self.field_shape, self.array_offset, twist,
                                                **gen)
@@ -870,7 +975,9 @@ class SequenceFusion3d:
             else:
                 self.nonrigid_optimizer.optimize(live, model.tsdf)
             nonrigid = self.nonrigid_optimizer.engine.last_call
-        if through and not self.warped:  # the live volume, warped into the model, is fused in volume mode
+        if not fuse:  # a frame that is not good leaves the model alone
+            record, unpack = None, None
+        elif through and not self.warped:  # the live volume, warped into the model, is fused in volume mode
             record, unpack = device_fusion.integrate_volume(model.tsdf, model.weight, live, 1.0,
                                                             model.max_weight), unpack_record
         else:  # depth mode, through the frame's warp field when it has one
@@ -881,8 +988,16 @@ class SequenceFusion3d:
                 colour_band=self.colour_band, warp=self.warp if through else None, **gen)
         frame = {"frame": k, "twist": np.asarray(twist, dtype=np.float64).reshape(6).copy(),
                  "rigid_records": rigid_records, "nonrigid": nonrigid,
-                 "fusion": unpack(record.cpu().numpy()),
+                 "fusion": None if record is None else unpack(record.cpu().numpy()),
                  "prediction_hits": None if hits is None else int(hits.item())}
+        if self.tracking_quality is not None:
+            frame["tracking_state"] = self.tracking_state = verdict.get("state", "tracking")
+            frame["tracking_quality"] = verdict.get("quality")
+        if self.relocaliser is not None:
+            frame["relocalisation"] = verdict.get("relocalisation")
+            frame["keyframe"] = None
+            if fuse:  # every fused frame may become a keyframe
+                frame["keyframe"] = self.relocaliser.query(coarse, harvest=True, twist=frame["twist"])["appended"]
         if registration is not None:
             frame["registration"] = device_rgbd.unpack_record(registration.cpu().numpy())
         if self.moving_volume is not None:  # between frames: the policy reads the frame's twist, already on the host
