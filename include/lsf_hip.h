@@ -1921,6 +1921,9 @@ int lsf_reloc_encode(const void *depth, int32_t depth_dtype, const uint8_t *colo
  * codes[k][f] != frame_code[f]; -1 for k >= n.  Nearest: the `candidates` keyframes in rising order of (distance, id).
  * With harvest, the frame is WANTED when n == 0 or the smallest distance is >= harvest_differing; a wanted frame is
  * appended when n < capacity: codes[n] = frame_code and *n_keyframes = n + 1 (distances keeps the values from before).
+ * *n_keyframes is written only by an append, n being the value as read: a word below 0 becomes 1 when the frame is
+ * appended (an empty database wants every frame) and stays as it was otherwise; a word above capacity is never written,
+ * and a wanted frame sets record[10].
  * record: [0] n before the call, [1, 5) the nearest ids, -1 where n is smaller, [5, 9) their distances, -1 likewise,
  * [9] the appended id or -1, [10] 1 when a wanted frame met a full database, [11] 0.
  * Three launches (the code; a wave per keyframe row, which reads aligned 16-byte words; one workgroup that selects and

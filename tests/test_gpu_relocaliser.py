@@ -4,11 +4,13 @@ distances, nearest, records, the database after an append, and a second run of e
 SequenceFusion3d(tracking_quality=, relocaliser=) over tests/moving_volume_scene.py in the fixed window: a kidnapped
 camera (scene A), leaving the window and coming back (scene B), the gate alone, and the gate that nothing violates.
 The encode kernel gives a wave to every coarse block and four to a workgroup: 5 x 7 blocks is nine workgroups with a
-ragged last one, 37 x 53 over 5 x 7 makes blocks of 7 or 8 rows by 7 or 8 columns (fewer pixels than lanes, and more),
-120 x 160 over 15 x 20 blocks of exactly one wave.  The distance kernel gives a wave to every keyframe row and reads
-aligned 16-byte words: F = 70 and 500 put most rows off that alignment, and the last row's last word reaches past the
-array unless capacity * F is a multiple of 16."""
-import functools
+ragged last one, 37 x 53 over 5 x 7 makes blocks of 7 or 8 rows by 7 or 8 columns (49 to 64 pixels: fewer than a
+wave's lanes, and exactly as many), 120 x 160 over 15 x 20 blocks of exactly one wave.  The distance kernel gives a wave
+to every keyframe row and reads aligned 16-byte words: F = 70 and 500 put most rows off that alignment, and the last
+row's last word reaches past the array unless capacity * F is a multiple of 16.  Every loop here stays in its first
+trip; blocks of more pixels than lanes, more blocks or rows than the capped grid has waves, rows of more than 64 words
+and more keys than the select kernel has lanes are in tests/test_gpu_second_trip.py, on the inputs of
+tests/test_relocaliser_host.py."""
 import math
 
 import numpy as np
@@ -19,6 +21,8 @@ import moving_volume_scene as MS
 import relocaliser_restatement as R
 from test_relocaliser_host import (COARSE, DECISIONS, DEPTH_RANGE, FERNS, HARVEST, MAX_RMS, MIN_PAIR_FRACTION, SCENE_A,
                                    SCENE_B, check_recovery, frame, pose_errors)
+from test_relocaliser_host import depth_image as _depth_image
+from test_relocaliser_host import query_case as _query_case
 
 pytestmark = pytest.mark.gpu
 
@@ -42,28 +46,6 @@ def _bits(t):
 
 # ---- encode ---------------------------------------------------------------------------------------------------------------
 
-def _depth_image(shape, coarse_shape, dtype, rng):
-    """metres in [0.3, 3.9] with zeros, values outside [0.5, 3.5], a NaN and an inf (float types), and two blocks set by
-    hand: block (0, 1) with exactly half of its pixels counting (the next whole number when they are odd), block (0, 0)
-    with one fewer"""
-    h, w = shape
-    d = rng.uniform(0.3, 3.9, shape)
-    d[rng.random(shape) < 0.15] = 0.0
-    d[rng.random(shape) < 0.05] = 7.5
-    ch, cw = coarse_shape
-    for j, fewer in ((0, 1), (1, 0)):
-        rows, cols = slice(0, h // ch), slice(j * w // cw, (j + 1) * w // cw)
-        block = np.zeros(((h // ch), cols.stop - cols.start))
-        n = block.size // 2 - fewer if block.size % 2 == 0 else (block.size + 1) // 2 - fewer
-        block.reshape(-1)[:n] = rng.uniform(0.6, 3.0, n)
-        d[rows, cols] = block
-    if dtype == np.uint16:
-        return np.round(d * 1000.0).astype(np.uint16), 0.001
-    d = d.astype(dtype)
-    d[h // 2, w // 2], d[h // 2, w // 2 + 1] = np.nan, np.inf
-    return d, 1.0
-
-
 @pytest.mark.parametrize("with_colour", [False, True])
 @pytest.mark.parametrize("dtype", [np.float32, np.uint16, np.float64])
 @pytest.mark.parametrize("shape, coarse_shape", [((37, 53), (5, 7)), ((120, 160), (15, 20))])
@@ -79,6 +61,11 @@ def test_encode_against_restatement(lsf, shape, coarse_shape, dtype, with_colour
     assert (want_counts[0, 0] + 1) * 2 in (pixels[0], pixels[0] + 1) and want[0, 0, 0] == 0
     assert want_counts[0, 1] * 2 == pixels[1] and want[0, 1, 0] > 0
     assert 0 < want_record["valid_blocks"] < want_counts.size
+    encode_twice_against(D, depth, ratio, coarse_shape, colour, want, want_counts, want_record)
+
+
+def encode_twice_against(D, depth, ratio, coarse_shape, colour, want, want_counts, want_record):
+    """two runs of lsf_reloc_encode over host inputs, each against the restated coarse bits, block counts and record"""
     from levelsetfusion_python_amd.tsdf.generation import device_depth
     d_depth = device_depth(depth)[0]
     d_colour = None if colour is None else _cuda(colour)
@@ -87,7 +74,7 @@ def test_encode_against_restatement(lsf, shape, coarse_shape, dtype, with_colour
         assert np.array_equal(_bits(coarse), want.view(np.uint32))
         assert np.array_equal(counts.cpu().numpy(), want_counts)
         assert D.unpack_encode_record(record.cpu().numpy()) == want_record
-    assert coarse.shape == coarse_shape + ((4,) if with_colour else (1,))
+    assert coarse.shape == tuple(coarse_shape) + ((1,) if colour is None else (4,))
 
 
 def test_encode_refusals_on_the_device(lsf):
@@ -110,28 +97,6 @@ def test_encode_refusals_on_the_device(lsf):
 
 # ---- query ----------------------------------------------------------------------------------------------------------------
 
-@functools.lru_cache(maxsize=None)
-def _query_case(ferns, decisions, colour):
-    """a coarse image with empty blocks, a table that also points outside it, and 131 keyframe codes around the frame's"""
-    rng = np.random.default_rng(ferns * 10 + decisions)
-    ch, cw, c = 6, 9, 4 if colour else 1
-    coarse = rng.uniform(0.5, 3.5, (ch, cw, c)).astype(np.float32)
-    if colour:
-        coarse[..., 1:] = rng.uniform(0, 255, (ch, cw, 3)).astype(np.float32)
-    coarse[rng.random((ch, cw)) < 0.2] = 0
-    table = list(R.fern_table(ferns, decisions, (ch, cw), (0.5, 3.5), colour, 3))
-    table[0][0, 0], table[0][1, 0] = ch * cw, -1  # outside: bit 0
-    if not colour:
-        table[1][2, 0] = 1                        # a channel the image does not have: bit 0
-    code = R.frame_code(coarse, *table)
-    rows = np.repeat(code[None, :], 131, axis=0)
-    for k in range(131):  # keyframe k differs in (k * 7) % (ferns + 1) ferns: distances in no order
-        flip = rng.permutation(ferns)[:(k * 7) % (ferns + 1)]
-        rows[k, flip] ^= rng.integers(1, 1 << decisions, len(flip)).astype(np.uint8)
-    rows[57] = rows[23]  # two keyframes with equal codes
-    return coarse, tuple(table), rows
-
-
 def _run_query(D, coarse, table, rows, n, capacity, **kw):
     codes = np.zeros((capacity, rows.shape[1]), np.uint8)
     codes[:n] = rows[:n]
@@ -152,10 +117,14 @@ def _run_query(D, coarse, table, rows, n, capacity, **kw):
 def test_query_against_restatement(lsf, ferns, decisions):
     from levelsetfusion_python_amd import device_relocaliser as D
     colour = decisions == 4
-    coarse, table, rows = _query_case(ferns, decisions, colour)
+    assert (ferns * 131) % 16 != 0 and (ferns * 1) % 16 != 0  # rows off the 16-byte alignment, a ragged last word
+    query_comparison(D, ferns, decisions, *_query_case(ferns, decisions, colour))
+
+
+def query_comparison(D, ferns, decisions, coarse, table, rows):
+    """lsf_reloc_query against the restatement over the 131 keyframes of a query_case"""
     code = R.frame_code(coarse, *table)
     assert code.max() < (1 << decisions) and code.any()
-    assert (ferns * 131) % 16 != 0 and (ferns * 1) % 16 != 0  # rows off the 16-byte alignment, a ragged last word
     # a database of 0, 1, 130 and `capacity` keyframes
     rec = _run_query(D, coarse, table, rows, 0, 131, candidates=4, harvest=True, harvest_differing=3)[2]
     assert rec.tolist() == [0] + [-1] * 8 + [0, 0, 0]  # an empty database takes the frame

@@ -5,7 +5,9 @@ one-workgroup pass loops over more partials than it has lanes.  Every test here 
 kernel's work split, that its shape crosses the cap -- a later change of a cap fails that line instead of silently
 emptying the test -- and that work with an effect lies past it, then compares as the first-trip tests do: bit for bit
 per voxel, counts and maxima exactly, float64 sums to the existing relative bounds.  The shapes are the smallest that
-cross."""
+cross.  Sections 7 to 15 (the relocaliser, the brick store) compare bits, codes, counts, ids and records exactly; their
+inputs and crossing assertions live in tests/test_relocaliser_host.py and tests/test_volume_bricks_host.py, which check
+them without a card."""
 import functools
 
 import numpy as np
@@ -15,7 +17,11 @@ import torch
 import fusion_restatement as F
 import fusion_weighted_restatement as FW
 import mesh_restatement as M
+import relocaliser_restatement as R
 import rigid3d_restatement as R3
+import test_relocaliser_host as RH
+import test_volume_bricks_host as BH
+import volume_bricks_restatement as B
 from test_gpu_fusion import SUM_RTOL
 from test_gpu_fusion import _assert_record as _assert_fusion_record
 from test_gpu_fusion import _host_record, _random_live, _random_model
@@ -23,8 +29,11 @@ from test_gpu_fusion_weighted import SUM_RTOL as WEIGHTED_SUM_RTOL
 from test_gpu_fusion_weighted import _assert_record as _assert_weighted_record
 from test_gpu_fusion_weighted import _random_weights, _unpack
 from test_gpu_mesh import _check as _check_mesh
+from test_gpu_relocaliser import _bits as _relocaliser_bits
+from test_gpu_relocaliser import _cuda, _run_query, encode_twice_against, query_comparison
 from test_gpu_rigid3d import A_RTOL, TWIST_ATOL, TWISTS, _bits_equal, _camera, _depth, _run, _teacher_forced
 from test_gpu_term_leaves import TERM_CAP, assert_terms_match_the_oracle, maxdiff, rel, term_fields
+from test_gpu_volume_bricks import count_and_gather_against_restatement, round_trip, scatter_against_restatement
 from test_rigid3d_host import K_SYN, XI0
 
 pytestmark = pytest.mark.gpu
@@ -388,3 +397,175 @@ def test_halo_copy_past_its_grid(lsf):
     assert torch.equal(live2[:h], hi[0]) and torch.equal(warp2[:, :h], hi[1:])
     assert torch.equal(live2[nz - h:], lo[0]) and torch.equal(warp2[:, nz - h:], lo[1:])
     assert torch.equal(live2[h:nz - h], live[h:nz - h]) and torch.equal(warp2[:, h:nz - h], warp[:, h:nz - h])
+
+
+# ------------------------------------------------------------------------------------- 7. relocaliser: the pixel loop
+# The inputs of sections 7 to 12, the constants that mirror csrc/lsf_relocaliser.hip and the assertions that a shape
+# crosses its cap with a visible effect past it are tests/test_relocaliser_host.py's, where they run without a card.
+
+def _colour_image(shape, with_colour, seed):
+    return np.random.default_rng(seed).integers(0, 256, shape + (3,)).astype(np.uint8) if with_colour else None
+
+
+@pytest.mark.parametrize("with_colour", [False, True])
+@pytest.mark.parametrize("dtype", [np.float32, np.uint16, np.float64])
+@pytest.mark.parametrize("shape, coarse_shape", RH.PIXEL_LOOP_IMAGES)
+def test_reloc_encode_pixel_loop(lsf, shape, coarse_shape, dtype, with_colour):
+    """`for (p = lane; p < pixels; p += kWave)` of reloc_encode_kernel: blocks of 306 to 342 pixels (five or six trips,
+    the last one ragged; two workgroups, the second with two idle waves) and the header's 640 x 480 over 30 x 40 (four
+    whole trips), with one block whose counting pixels all lie at p >= 64 and one that counts in its last trip only"""
+    from levelsetfusion_python_amd import device_relocaliser as D
+    depth, ratio = RH.pixel_loop_image(shape, coarse_shape, dtype)
+    colour = _colour_image(shape, with_colour, 5)
+    want, want_counts, want_record = R.encode(depth, ratio, coarse_shape, (0.5, 3.5), colour)
+    RH.check_pixel_loop_image(shape, coarse_shape, depth, ratio, want, want_counts)
+    if with_colour:
+        assert want[-1, -1, 1:].all()  # the colour sums of the block that counts past the first trip only
+    assert 0 < want_record["valid_blocks"] < want_counts.size
+    encode_twice_against(D, depth, ratio, coarse_shape, colour, want, want_counts, want_record)
+
+
+# ------------------------------------------------------------------------------------- 8. relocaliser: the block loop
+@pytest.mark.parametrize("shape, dtype, with_colour", [(RH.BLOCK_LOOP_IMAGES[0], np.float32, True),
+                                                       (RH.BLOCK_LOOP_IMAGES[1], np.uint16, False),
+                                                       (RH.BLOCK_LOOP_IMAGES[1], np.float64, True)])
+def test_reloc_encode_block_loop(lsf, shape, dtype, with_colour):
+    """`b += waves` of reloc_encode_kernel, and the record kernel's sums over the blocks past it: 4160 coarse blocks on
+    4096 waves, of one pixel each (`2 * count >= pixels` decided by a single pixel) and of 2 or 3 rows by 2 or 3 columns"""
+    from levelsetfusion_python_amd import device_relocaliser as D
+    depth, ratio = RH.depth_image(shape, RH.BLOCK_LOOP_COARSE, dtype, np.random.default_rng(shape[0]))
+    colour = _colour_image(shape, with_colour, 6)
+    want, want_counts, want_record = R.encode(depth, ratio, RH.BLOCK_LOOP_COARSE, (0.5, 3.5), colour)
+    RH.check_block_loop_image(shape, want, want_counts, want_record)
+    encode_twice_against(D, depth, ratio, RH.BLOCK_LOOP_COARSE, colour, want, want_counts, want_record)
+
+
+# ---------------------------------------------------------------- 9. relocaliser: the distance word loop, the maximum F
+@pytest.mark.parametrize("ferns, decisions", [(1030, 8), (RH.RELOC_MAX_FERNS, 1)])
+def test_reloc_distance_word_loop(lsf, ferns, decisions):
+    """`w += kWave` of reloc_distance_kernel under test_gpu_relocaliser's query comparison: F = 1030 (rows of 64.4 words
+    off the alignment, a last word past the array) and F = 4096 (aligned rows of four whole trips, the LDS copy of the
+    code full, 16 workgroups of the code kernel), with keyframes that differ from the frame only past the first trip"""
+    from levelsetfusion_python_amd import device_relocaliser as D
+    coarse, table, rows = RH.query_case(ferns, decisions, False, True)
+    RH.check_word_loop_case(ferns, coarse, table, rows)
+    query_comparison(D, ferns, decisions, coarse, table, rows)
+
+
+# -------------------------------------------------------------- 10. relocaliser: the distance row loop, the select loop
+@pytest.mark.parametrize("name", list(RH.ROW_LOOP_CASES))
+def test_reloc_row_loop_and_selection(lsf, name):
+    """`k += waves` of reloc_distance_kernel and `k += kBlock` of reloc_select_kernel over 4101 keyframes of 70 ferns:
+    the four nearest spread over the first 256 keys, the later trips of the selection and the rows past 4096, a tie of
+    equal codes across 4096 that goes to the lower id, the nearest of all in the last row; a database of `capacity`
+    keyframes and of one fewer, harvest at the threshold (an append into row 4100), one below it, and into a full one"""
+    from levelsetfusion_python_amd import device_relocaliser as D
+    coarse, table, rows = RH.row_loop_case(name)
+    capacity = len(rows)
+    nearest = RH.check_row_loop_case(name, coarse, table, rows)
+    code = R.frame_code(coarse, *table)
+    want = _run_query(D, coarse, table, rows, capacity, capacity, candidates=4)
+    assert want[2][5] == nearest and (want[1] >= 0).all() and want[2][9] == -1
+    n = capacity - 1
+    want = _run_query(D, coarse, table, rows, n, capacity, candidates=4)
+    fewer = int(want[2][5])  # the nearest of the smaller database
+    assert want[1][n] == -1 and (want[1][:n] >= 0).all() and fewer == (2 if name == "far-first" else nearest)
+    at = _run_query(D, coarse, table, rows, n, capacity, candidates=4, harvest=True, harvest_differing=fewer)
+    assert at[2][9] == n >= RH.RELOC_WAVES and at[4] == capacity and np.array_equal(at[3][n], code)
+    below = _run_query(D, coarse, table, rows, n, capacity, candidates=4, harvest=True, harvest_differing=fewer + 1)
+    assert below[2][9] == -1 and below[2][10] == 0 and below[4] == n
+    full = _run_query(D, coarse, table, rows, capacity, capacity, candidates=4, harvest=True, harvest_differing=nearest)
+    assert full[2][9] == -1 and full[2][10] == 1 and full[4] == capacity
+
+
+# --------------------------------------------------------------------- 11. relocaliser: n_keyframes outside [0, capacity]
+@pytest.mark.parametrize("harvest", [False, True])
+@pytest.mark.parametrize("outside", [-5, 7])
+def test_reloc_size_word_outside_the_database(lsf, outside, harvest):
+    """*n_keyframes = -5 and capacity + 7: the kernels read min(max(n, 0), capacity), as R.query does, and write the
+    word only when they append (include/lsf_hip.h, lsf_reloc_query) -- -5 with harvest becomes 1, -5 without stays -5,
+    capacity + 7 stays and `full` is set for a wanted frame"""
+    from levelsetfusion_python_amd import device_relocaliser as D
+    coarse, table, rows = RH.query_case(70, 4, True)
+    codes = rows[[k for k in range(131) if (k * 7) % 71 >= (23 * 7) % 71]]  # no keyframe equals the frame
+    capacity = len(codes)
+    n = outside if outside < 0 else capacity + outside
+    kw = dict(candidates=4, harvest=harvest, harvest_differing=1)
+    want = R.query(coarse, table, codes, n, 4, harvest, 1)
+    assert want[2][0] == (0 if n < 0 else capacity) and (want[1] >= 0).all() == (n > 0) and want[1].min() != 0
+    for _ in range(2):
+        d_codes, d_n = _cuda(codes), torch.tensor([n], dtype=torch.int32, device="cuda")
+        got = D.query(_cuda(coarse), *(_cuda(a) for a in table), d_codes, d_n, **kw)
+        for a, b in zip(got, want[:3]):
+            assert np.array_equal(a.cpu().numpy(), b)
+        assert np.array_equal(d_codes.cpu().numpy(), want[3])
+        appended = int(want[2][9]) >= 0
+        assert appended == (harvest and n < 0) and int(want[2][10]) == (1 if harvest and n > 0 else 0)
+        if appended:
+            assert int(d_n.item()) == want[4] == 1 and np.array_equal(want[3][0], want[0])
+        else:
+            assert int(d_n.item()) == n  # not written
+
+
+# ------------------------------------------------------------------ 12. fusion.Relocaliser with more than 256 keyframes
+def test_relocaliser_object_with_many_keyframes(lsf):
+    """test_gpu_relocaliser.test_relocaliser_object's comparison with R.Database over 280 synthetic frames that are all
+    harvested, and four of them shown again: the select kernel's lanes take a second key, and nearest keyframes lie on
+    both sides of key 256.  280 frames of 24 x 32 pixels take about a second, the restated database included."""
+    coarse_want, found_want, db = RH.many_keyframes_restated()
+    assert db.n == RH.MANY_FRAMES > RH.RELOC_BLOCK
+    reloc = lsf.fusion.Relocaliser(**RH.MANY_KEYFRAMES)
+    frames = RH.many_frames()
+    queries = [(k, True) for k in range(RH.MANY_FRAMES)] + [(k, False) for k in RH.MANY_AGAIN]
+    for (k, harvest), want in zip(queries, found_want):
+        coarse = reloc.encode(frames[k])
+        assert np.array_equal(_relocaliser_bits(coarse), coarse_want[k].view(np.uint32))
+        got = reloc.query(coarse, harvest=harvest, twist=np.full(6, k, np.float64) if harvest else None)
+        assert {name: got[name] for name in want} == want and not got["full"], k
+    assert any(f["nearest"][0] >= RH.RELOC_BLOCK for f in found_want[RH.MANY_FRAMES:])
+    codes, twists = reloc.keyframes()
+    assert len(codes) == db.n > RH.RELOC_BLOCK and np.array_equal(codes, db.codes[:db.n])
+    assert np.array_equal(twists, db.twists) and int(reloc.size.item()) == db.n
+    assert all(np.array_equal(a, b) for a, b in zip(reloc.table, db.table))
+
+
+# --------------------------------------------------------------------------- 13 to 15. the brick store past 8192 bricks
+# The window, its shifts, the constants that mirror csrc/lsf_volume_bricks.hip and the assertions of the crossing are
+# tests/test_volume_bricks_host.py's.
+
+@pytest.mark.parametrize("with_colour", [False, True])
+def test_bricks_count_and_gather_past_the_cap(lsf, with_colour):
+    """`b += stride` of bricks_flag_kernel and bricks_gather_kernel and the second trip of bricks_scan_kernel (the carry;
+    whole threads, a partial one and idle ones after a whole trip) on a 65 x 65 x 2 grid of 8450 bricks: flagged and
+    touched-but-unflagged bricks past index 8192, and under the shift that makes everything leave more than 8192 rows"""
+    want = BH.big_window_counts()
+    assert want[BH.BIG_ALL_SHIFT][2] > BH.BRICKS_WAVES and want[BH.BIG_Y_SHIFT][0][BH.BRICKS_WAVES:].sum() >= 100
+    rows, touched_unflagged = count_and_gather_against_restatement(BH.BIG_SHAPE, (BH.BIG_ORIGIN,), BH.BIG_SHIFTS,
+                                                                   with_colour)
+    assert rows == sum(v[2] for v in want.values()) and touched_unflagged > 0
+
+
+@pytest.mark.parametrize("with_colour", [False, True])
+def test_bricks_scatter_past_the_cap(lsf, with_colour):
+    """`k += stride` of bricks_scatter_kernel over 8452 rows: every brick of the big window's grid and two outside it,
+    shuffled, random validity bytes; tests/test_volume_bricks_host.py asserts that the rows from 8192 on change more
+    than 1000 words under the last two shifts"""
+    bricks = BH.big_window_bricks(with_colour)
+    assert len(bricks[0]) > BH.BRICKS_WAVES
+    dev_bricks = tuple(None if a is None else torch.from_numpy(np.array(a)).cuda() for a in bricks)
+    scatter_against_restatement(bricks, dev_bricks, BH.BIG_SHAPE, BH.BIG_ORIGIN, BH.BIG_SHIFTS, with_colour)
+    for dev, host in zip(dev_bricks[1:3], bricks[1:3]):
+        assert np.array_equal(dev.cpu().numpy().view(np.uint32), host.view(np.uint32))  # read only
+
+
+@pytest.mark.parametrize("shift", [BH.BIG_SHIFTS[2], (0, BH.BIG_SHAPE[1] + 5, 0)])
+def test_bricks_round_trip_past_the_cap(lsf, shift):
+    """test_gpu_volume_bricks.test_round_trip's body on the big window at its lattice origin: a partial shift that takes
+    the whole first z layer out, and one that empties the window (more than 8192 rows out, and scattered back)"""
+    want = BH.big_window_counts()
+    leaving = B.count(BH.inputs(BH.BIG_SHAPE)[1], BH.BIG_ORIGIN, shift)
+    assert leaving[0].size > BH.BRICKS_WAVES and leaving[0][BH.BRICKS_WAVES:].sum() > 0
+    if shift[1] > BH.BIG_SHAPE[1]:
+        assert leaving[2] == want[BH.BIG_ALL_SHIFT][2] > BH.BRICKS_WAVES  # everything leaves either way
+    vol, store, _ = round_trip(lsf, BH.BIG_SHAPE, shift, BH.BIG_ORIGIN)
+    assert len(store) == 0 and store.last["bricks_in"] == leaving[2]

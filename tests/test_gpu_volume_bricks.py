@@ -13,8 +13,10 @@ import torch
 
 import moving_volume_scene as MS
 import volume_bricks_restatement as B
-from test_volume_bricks_host import (RETURN_K, blobby_weights, frames_since_overlap_began, return_twists,
-                                     shared_voxels, window_trail)
+from test_volume_bricks_host import RETURN_K, frames_since_overlap_began, return_twists, shared_voxels, window_trail
+from test_volume_bricks_host import inputs as _inputs
+from test_volume_bricks_host import random_bricks as _random_bricks
+from test_volume_bricks_host import shifts as _shifts
 from test_volume_shift_host import _special_volume
 
 pytestmark = pytest.mark.gpu
@@ -28,11 +30,6 @@ GARBAGE = 0x5a5a5a5a  # what the outputs hold before a call: every word must be 
 def lsf():
     import levelsetfusion_python_amd as m
     return m
-
-
-def _shifts(shape):
-    """(sx, sy, sz): one per sign and axis, a diagonal, and one that makes everything leave"""
-    return [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (2, -3, 1), (0, -(shape[1] + 5), 1)]
 
 
 def _u32(t):
@@ -54,18 +51,6 @@ def _garbage(shape, dtype=torch.float32):
     return t.view(torch.float32)
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(shape):
-    """tsdf, weight, colour with NaN payloads, +-inf and -0.0; about half of the weights zero in blobs"""
-    rng = np.random.default_rng(sum(shape) + 1)
-    arrays = (_special_volume(shape, rng),
-              blobby_weights(shape, rng, _special_volume(shape, rng), largest=max(6, min(shape) // 2 + 1)),
-              _special_volume(shape, rng, (4,)))
-    for a in arrays:
-        a.setflags(write=False)
-    return arrays
-
-
 def _count(D, dw, shape, g, s):
     nb = int(np.prod(D.brick_grid(shape, g)[1]))
     flags, offsets = _garbage((nb,), torch.int32), _garbage((nb,), torch.int32)
@@ -77,14 +62,23 @@ def _count(D, dw, shape, g, s):
 @pytest.mark.parametrize("with_colour", [False, True])
 @pytest.mark.parametrize("shape", VOLUMES)
 def test_count_and_gather_against_restatement(lsf, shape, with_colour):
+    rows, touched_unflagged = count_and_gather_against_restatement(shape, ORIGINS, _shifts(shape), with_colour)
+    assert rows > 0
+    if shape == VOLUMES[-1]:
+        assert touched_unflagged > 0  # the blobs: bricks that a shift touches and that hold no data there
+
+
+def count_and_gather_against_restatement(shape, origins, shifts, with_colour):
+    """lsf_volume_bricks_count and _gather over _inputs(shape) at every origin and shift, outputs that start as
+    garbage, against B.count and B.gather; returns (the rows gathered, the touched bricks left unflagged) over all"""
     from levelsetfusion_python_amd import device_volume_bricks as D
     t, w, c = _inputs(shape)
     c = c if with_colour else None
     dt, dw, dc = _dev(t), _dev(w), _dev(c)
     rows = touched_unflagged = 0
-    for g in ORIGINS:
+    for g in origins:
         coords_all = B.grid_coords(shape, g)
-        for s in _shifts(shape):
+        for s in shifts:
             flags, offsets, total = _count(D, dw, shape, g, s)
             want_flags, want_offsets, want_total = B.count(w, g, s)
             assert np.array_equal(flags.cpu().numpy(), want_flags), (g, s)
@@ -104,46 +98,37 @@ def test_count_and_gather_against_restatement(lsf, shape, with_colour):
             rows += k
             touched = D.leaving_mask(shape, g, s, coords_all).reshape(len(coords_all), -1).any(axis=1)
             touched_unflagged += int(np.sum(touched & (want_flags == 0)))
-    assert rows > 0
-    if shape == VOLUMES[-1]:
-        assert touched_unflagged > 0  # the blobs: bricks that a shift touches and that hold no data there
     for dev, host in ((dt, t), (dw, w)) + (((dc, c),) if with_colour else ()):
         assert np.array_equal(_u32(dev), host.view(np.uint32))  # read only
+    return rows, touched_unflagged
 
 
-def _random_bricks(shape, g, rng, with_colour):
-    """a brick for every brick of the window's grid and two outside it, in a shuffled order: special values, random
-    validity bytes, some rows wholly valid"""
-    coords = B.grid_coords(shape, g)
-    outside = np.array([coords.min(axis=0) - 1, coords.max(axis=0) + [1, 0, 0]], np.int32)
-    coords = rng.permutation(np.concatenate([coords, outside]))
-    k = len(coords)
-    valid = rng.integers(0, 256, (k, 64)).astype(np.uint8)
-    valid[rng.random((k, 64)) < 0.4] = 255
-    valid[rng.random((k, 64)) < 0.1] = 0
-    return (coords, _special_volume((k, 8, 8, 8), rng), _special_volume((k, 8, 8, 8), rng),
-            _special_volume((k, 8, 8, 8), rng, (4,)) if with_colour else None, valid)
+def scatter_against_restatement(bricks, dev_bricks, shape, g, shifts, with_colour):
+    """lsf_volume_bricks_scatter of the host rows `bricks` (dev_bricks: their device copies) into fresh copies of
+    _inputs(shape) under every shift, against B.scatter"""
+    from levelsetfusion_python_amd import device_volume_bricks as D
+    t, w, c = _inputs(shape)
+    c = c if with_colour else None
+    for s in shifts:
+        dt, dw, dc = _dev(t), _dev(w), _dev(c)  # what the contract does not name keeps these bits
+        D.scatter(*dev_bricks, dt, dw, dc, g, s)
+        want = B.scatter(*bricks, t, w, c, g, s)
+        assert np.array_equal(_u32(dt), want[0]) and np.array_equal(_u32(dw), want[1]), (g, s)
+        if with_colour:
+            assert np.array_equal(_u32(dc), want[2]), (g, s)
+        changed = _u32(dt) != t.view(np.uint32)
+        assert not np.any(changed & ~B.entering(shape, s))
 
 
 @pytest.mark.parametrize("with_colour", [False, True])
 @pytest.mark.parametrize("shape", VOLUMES)
 def test_scatter_against_restatement(lsf, shape, with_colour):
     from levelsetfusion_python_amd import device_volume_bricks as D
-    t, w, c = _inputs(shape)
-    c = c if with_colour else None
     rng = np.random.default_rng(17)
     for g in ORIGINS:
         bricks = _random_bricks(shape, g, rng, with_colour)
         dev_bricks = tuple(_dev(a) for a in bricks)
-        for s in _shifts(shape):
-            dt, dw, dc = _dev(t), _dev(w), _dev(c)  # what the contract does not name keeps these bits
-            D.scatter(*dev_bricks, dt, dw, dc, g, s)
-            want = B.scatter(*bricks, t, w, c, g, s)
-            assert np.array_equal(_u32(dt), want[0]) and np.array_equal(_u32(dw), want[1]), (g, s)
-            if with_colour:
-                assert np.array_equal(_u32(dc), want[2]), (g, s)
-            changed = _u32(dt) != t.view(np.uint32)
-            assert not np.any(changed & ~B.entering(shape, s))
+        scatter_against_restatement(bricks, dev_bricks, shape, g, _shifts(shape), with_colour)
         # all entering: a dense volume assembled from bricks equals the store's to_volume of the box
         store = lsf.fusion.BrickStore(colour=with_colour)
         store.merge(*bricks)
@@ -211,14 +196,29 @@ def _filled_volume(lsf, shape, colour=True):
 
 @pytest.mark.parametrize("shift", [(2, -3, 1), (0, 40, 0)])
 def test_round_trip(lsf, shift):
-    shape = VOLUMES[-1]
+    vol, store, off = round_trip(lsf, VOLUMES[-1], shift)
+    # refusals with a device
+    with pytest.raises(ValueError):
+        vol.shift((1, 0, 0), off + [0.5, 0, 0], brick_store=store)
+    with pytest.raises(ValueError):
+        vol.shift((1, 0, 0), off, brick_store=lsf.fusion.BrickStore())
+    with pytest.raises(ValueError):
+        lsf.fusion.CanonicalVolume((8, 8)).shift((1, 0), [0, 0, 0], brick_store=store)
+
+
+def round_trip(lsf, shape, shift, g=(0, 0, 0)):
+    """_inputs(shape) out of a window at lattice origin g by `shift` and back through CanonicalVolume.shift(brick_store=):
+    the store's counts, every data voxel back bit for bit, every other voxel that left empty; and the same pair of
+    shifts without a store, which loses what left.  Returns (the volume, the store, the window's array_offset)"""
     t, w, c = _inputs(shape)
     data = B.holds_data(w)
     off = np.array([1.5, -2.0, 3.25])
     back = tuple(-v for v in shift)
     vol, store = _filled_volume(lsf, shape), lsf.fusion.BrickStore(colour=True)
+    if g != (0, 0, 0):  # a lattice fixed earlier, elsewhere: the window lies at g in it
+        assert store.lattice_origin(off - g) == (0, 0, 0) and store.lattice_origin(off) == tuple(g)
     off1, chunks = vol.shift(shift, off, brick_store=store)
-    assert chunks == [] and np.array_equal(off1, off + shift) and np.array_equal(store.origin, off)
+    assert chunks == [] and np.array_equal(off1, off + shift) and np.array_equal(store.origin, off - g)
     leaving = B.leaving(shape, shift)
     assert store.last == {"bricks_out": len(store), "voxels_out": int((leaving & data).sum()), "bricks_in": 0,
                           "voxels_in": 0}
@@ -241,13 +241,7 @@ def test_round_trip(lsf, shift):
         assert np.all(got[leaving] == empty) and np.array_equal(got[~leaving], a[~leaving])
         lost |= bool(np.any(got[leaving & data] != a[leaving & data]))
     assert lost
-    # refusals with a device
-    with pytest.raises(ValueError):
-        vol.shift((1, 0, 0), off + [0.5, 0, 0], brick_store=store)
-    with pytest.raises(ValueError):
-        vol.shift((1, 0, 0), off, brick_store=lsf.fusion.BrickStore())
-    with pytest.raises(ValueError):
-        lsf.fusion.CanonicalVolume((8, 8)).shift((1, 0), [0, 0, 0], brick_store=store)
+    return vol, store, off
 
 
 def test_a_wandering_window_against_a_dense_world(lsf):

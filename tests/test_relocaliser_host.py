@@ -3,7 +3,9 @@
 a blank frame is far from everything, harvesting keeps a strict subset, and the restated sequence recovers from a
 kidnapped camera (scene A) and from leaving the fixed window and coming back (scene B) where the sequence without the
 keywords does not --, the refusals of lsf_reloc_encode and lsf_reloc_query that run before any launch, the host rules of
-fusion.TrackingQuality and fusion.Relocaliser, and SequenceFusion3d's constructor refusals."""
+fusion.TrackingQuality and fusion.Relocaliser, and SequenceFusion3d's constructor refusals.  Also the inputs of the GPU
+tests, and for those of tests/test_gpu_second_trip.py the assertions that they cross the kernels' caps with a visible
+effect past them, from constants and the restatement."""
 import ctypes
 import functools
 import inspect
@@ -362,6 +364,275 @@ def test_header_binding_exports_and_documents_agree(lsf):
 def _camera(lsf):
     from levelsetfusion_python_amd.tsdf.generation import DepthCamera
     return DepthCamera(intrinsics=DepthCamera.Intrinsics(intrinsic_matrix=MS.K), depth_unit_ratio=1.0)
+
+
+# ---- the inputs of the GPU tests, and what their shapes cross ---------------------------------------------------------------
+# tests/test_gpu_relocaliser.py and the relocaliser sections of tests/test_gpu_second_trip.py draw their inputs here, so
+# that what is assumed about them -- which cap a shape crosses, and that work with a visible effect lies past it -- is
+# checked without a card.  The constants mirror csrc/lsf_relocaliser.hip.
+
+RELOC_MAX_BLOCKS = 1024  # LSF_RELOC_MAX_BLOCKS (include/lsf_hip.h): workgroups of the encode and the distance kernel
+RELOC_BLOCK = 256        # kBlock (csrc/lsf_device.h): the lanes of the one-workgroup record and select kernels
+RELOC_WAVE = 64          # kWave: the lanes that walk a block's pixels, and a row's 16-byte words
+RELOC_BLOCK_WAVES = RELOC_BLOCK // RELOC_WAVE  # kBlockWaves: coarse blocks, or keyframe rows, per workgroup
+RELOC_WAVES = RELOC_MAX_BLOCKS * RELOC_BLOCK_WAVES  # the waves of a capped grid: blocks or rows of the first trip
+RELOC_WORD = 16          # the bytes of a word of the distance kernel: a row's first trip ends before its byte 64 * 16
+RELOC_MAX_FERNS = 4096   # LSF_RELOC_MAX_FERNS: the LDS copy of the frame's code
+
+
+def depth_image(shape, coarse_shape, dtype, rng):
+    """metres in [0.3, 3.9] with zeros, values outside [0.5, 3.5], a NaN and an inf (float types), and two blocks set by
+    hand: block (0, 1) with exactly half of its pixels counting (the next whole number when they are odd), block (0, 0)
+    with one fewer"""
+    h, w = shape
+    d = rng.uniform(0.3, 3.9, shape)
+    d[rng.random(shape) < 0.15] = 0.0
+    d[rng.random(shape) < 0.05] = 7.5
+    ch, cw = coarse_shape
+    for j, fewer in ((0, 1), (1, 0)):
+        rows, cols = slice(0, h // ch), slice(j * w // cw, (j + 1) * w // cw)
+        block = np.zeros(((h // ch), cols.stop - cols.start))
+        n = block.size // 2 - fewer if block.size % 2 == 0 else (block.size + 1) // 2 - fewer
+        block.reshape(-1)[:n] = rng.uniform(0.6, 3.0, n)
+        d[rows, cols] = block
+    if dtype == np.uint16:
+        return np.round(d * 1000.0).astype(np.uint16), 0.001
+    d = d.astype(dtype)
+    d[h // 2, w // 2], d[h // 2, w // 2 + 1] = np.nan, np.inf
+    return d, 1.0
+
+
+def block_slices(shape, coarse_shape, i, j):
+    (h, w), (ch, cw) = shape, coarse_shape
+    return slice(i * h // ch, (i + 1) * h // ch), slice(j * w // cw, (j + 1) * w // cw)
+
+
+def block_pixels(shape, coarse_shape):
+    """int (ch, cw): the pixels of every coarse block, from the slices the restatement cuts"""
+    ch, cw = coarse_shape
+    size = lambda s: s.stop - s.start
+    return np.array([[size(block_slices(shape, coarse_shape, i, j)[0]) * size(block_slices(shape, coarse_shape, i, j)[1])
+                      for j in range(cw)] for i in range(ch)])
+
+
+PIXEL_LOOP_IMAGES = (((37, 53), (2, 3)), ((480, 640), (30, 40)))  # (frame, coarse image): blocks of several waves
+LATE_BLOCKS = ((-1, -1), (-1, 0))  # the last block of the coarse image and the first of its last row
+
+
+def pixel_loop_image(shape, coarse_shape, dtype):
+    """depth_image with two more blocks set by hand, pixels counted row-major inside a block as the kernel's lanes walk
+    them: the last block has zeros in its first RELOC_WAVE pixels and counting depths in all the others, so everything
+    that counts there lies in a later trip, and the first block of the last row keeps only pixels of its last trip.
+    Returns (depth, ratio)."""
+    rng = np.random.default_rng(shape[0] + np.dtype(dtype).itemsize)
+    depth, ratio = depth_image(shape, coarse_shape, dtype, rng)
+    for (i, j), keep_from in zip(LATE_BLOCKS, (RELOC_WAVE, None)):
+        at = block_slices(shape, coarse_shape, i % coarse_shape[0], j % coarse_shape[1])
+        flat = depth[at].reshape(-1)  # a copy: the block is not contiguous
+        first = (len(flat) - 1) // RELOC_WAVE * RELOC_WAVE if keep_from is None else keep_from
+        flat[:first] = 0
+        if keep_from is not None:
+            flat[first:] = (rng.uniform(0.6, 3.0, len(flat) - first) / ratio).astype(flat.dtype)
+        depth[at] = flat.reshape(depth[at].shape)
+    return depth, ratio
+
+
+def check_pixel_loop_image(shape, coarse_shape, depth, ratio, want, want_counts):
+    """the crossing of `for (p = lane; p < pixels; p += kWave)` and its effect, from the restatement's outputs"""
+    pixels = block_pixels(shape, coarse_shape)
+    assert pixels.min() > RELOC_WAVE  # every block takes a second trip
+    trips = -(-pixels // RELOC_WAVE)
+    if shape == (37, 53):
+        assert sorted(set(trips.reshape(-1))) == [5, 6] and np.all(pixels % RELOC_WAVE != 0)  # a ragged last trip
+        # two workgroups, the second with two of its four waves idle
+        assert pixels.size == RELOC_BLOCK_WAVES + 2
+    else:
+        assert np.all(pixels == 4 * RELOC_WAVE) and pixels.size <= RELOC_WAVES  # the header's case: four whole trips
+    with np.errstate(invalid="ignore"):
+        d = R.scaled_depth(depth, ratio)
+        counting = (d >= 0.5) & (d <= 3.5)
+    (i, j), (k, l) = LATE_BLOCKS
+    late = counting[block_slices(shape, coarse_shape, i % coarse_shape[0], j % coarse_shape[1])].reshape(-1)
+    # a kernel that stops after one trip counts nothing here and writes 0; the block is valid
+    assert not late[:RELOC_WAVE].any() and want_counts[i, j] == late.sum() and want[i, j, 0] > 0
+    last = counting[block_slices(shape, coarse_shape, k % coarse_shape[0], l % coarse_shape[1])].reshape(-1)
+    start = (len(last) - 1) // RELOC_WAVE * RELOC_WAVE
+    assert start >= RELOC_WAVE and not last[:start].any() and want_counts[k, l] == last[start:].sum() > 0
+    assert want[k, l, 0] == 0  # fewer than half: the count alone shows the last trip
+
+
+BLOCK_LOOP_COARSE = (65, 64)
+BLOCK_LOOP_IMAGES = ((65, 64), (131, 129))  # one pixel per block; blocks of 2 or 3 rows by 2 or 3 columns
+
+
+def check_block_loop_image(shape, want, want_counts, want_record):
+    """the crossing of the encode kernel's `b += waves` and its effect, from the restatement's outputs"""
+    pixels = block_pixels(shape, BLOCK_LOOP_COARSE)
+    assert RELOC_WAVES < pixels.size <= RELOC_WAVES + RELOC_WAVE  # the first 64 waves take a second block
+    assert (pixels.min(), pixels.max()) == ((1, 1) if shape == BLOCK_LOOP_IMAGES[0] else (4, 9))
+    valid, counts = (want[..., 0] > 0).reshape(-1), want_counts.reshape(-1)
+    for side in (slice(0, RELOC_WAVES), slice(RELOC_WAVES, None)):  # valid and invalid blocks on both sides
+        assert valid[side].any() and not valid[side].all()
+    # the record's sums include the blocks past the cap
+    assert want_record["counting"] == counts.sum() > counts[:RELOC_WAVES].sum()
+    assert want_record["valid_blocks"] == valid.sum() > valid[:RELOC_WAVES].sum()
+
+
+LATE_ROWS = (5, 11)  # keyframes of query_case(late=True) that differ from the frame only past a row's first trip
+
+
+@functools.lru_cache(maxsize=None)
+def query_case(ferns, decisions, colour, late=False):
+    """a coarse image with empty blocks, a table that also points outside it, and 131 keyframe codes around the frame's.
+    With late, the keyframes LATE_ROWS differ from the frame only at byte >= 64 * 16 of their row (in every later trip
+    where the row has one)"""
+    rng = np.random.default_rng(ferns * 10 + decisions)
+    ch, cw, c = 6, 9, 4 if colour else 1
+    coarse = rng.uniform(0.5, 3.5, (ch, cw, c)).astype(np.float32)
+    if colour:
+        coarse[..., 1:] = rng.uniform(0, 255, (ch, cw, 3)).astype(np.float32)
+    coarse[rng.random((ch, cw)) < 0.2] = 0
+    table = list(R.fern_table(ferns, decisions, (ch, cw), (0.5, 3.5), colour, 3))
+    table[0][0, 0], table[0][1, 0] = ch * cw, -1  # outside: bit 0
+    if not colour:
+        table[1][2, 0] = 1                        # a channel the image does not have: bit 0
+    code = R.frame_code(coarse, *table)
+    rows = np.repeat(code[None, :], 131, axis=0)
+    for k in range(131):  # keyframe k differs in (k * 7) % (ferns + 1) ferns: distances in no order
+        flip = rng.permutation(ferns)[:(k * 7) % (ferns + 1)]
+        rows[k, flip] ^= rng.integers(1, 1 << decisions, len(flip)).astype(np.uint8)
+    rows[57] = rows[23]  # two keyframes with equal codes
+    if late:
+        first = RELOC_WAVE * RELOC_WORD
+        for k, flip in zip(LATE_ROWS, (np.arange(first, ferns, max(1, (ferns - first) // 40)), np.arange(first, ferns)[:3])):
+            rows[k] = code
+            rows[k, flip] ^= 1
+    return coarse, tuple(table), rows
+
+
+def check_word_loop_case(ferns, coarse, table, rows):
+    """the crossing of the distance kernel's `w += kWave` and its effect.  Row k is read as the 16-byte words from byte
+    k F - (k F) % 16 on, 64 of them in a trip: the first trip ends at or before byte 1024 of the row"""
+    first = RELOC_WAVE * RELOC_WORD
+    assert first < ferns <= RELOC_MAX_FERNS
+    code = R.frame_code(coarse, *table)
+    want = R.query(coarse, table, rows, len(rows))[1]
+    for k in LATE_ROWS:  # a kernel that stops after the first trip reports 0 for them
+        assert np.array_equal(rows[k, :first], code[:first]) and want[k] > 0
+        assert want[k] < (23 * 7) % (ferns + 1)  # nearer than the twins the comparison's tie rests on
+    if ferns == RELOC_MAX_FERNS:  # rows aligned, four whole trips, each of the later three with a differing fern
+        assert ferns % RELOC_WORD == 0 and ferns == 4 * first
+        assert all((rows[LATE_ROWS[0], t * first:(t + 1) * first] != code[t * first:(t + 1) * first]).any()
+                   for t in (1, 2, 3))
+    else:  # rows off the alignment, a ragged last word, a last word that reaches past the array
+        assert ferns % RELOC_WORD and (len(rows) * ferns) % RELOC_WORD
+
+
+ROW_LOOP_CAPACITY, ROW_LOOP_FERNS = 4101, 70
+# per case: keyframe -> its distance.  "spread": the four nearest lie in the select kernel's first trip (k < 256), in a
+# later one, and in the distance kernel's second trip (k >= 4096), and the tie of 4000 and 4097 straddles that cap;
+# "far-first": the overall nearest is the last row (outside the database when n is one below the capacity), the tie of
+# 150 and 4096 has one twin in each kernel's first trip and one past both caps
+ROW_LOOP_CASES = {"spread": {3000: 2, 4098: 3, 100: 4, 4000: 5, 4097: 5},
+                  "far-first": {4100: 1, 150: 2, 4096: 2, 2000: 3}}
+ROW_LOOP_TWINS = {"spread": (4000, 4097), "far-first": (150, 4096)}
+
+
+@functools.lru_cache(maxsize=None)
+def row_loop_case(name):
+    """(coarse, table, rows uint8 (ROW_LOOP_CAPACITY, 70)): every keyframe 10 to 70 ferns from the frame, except the
+    near ones of ROW_LOOP_CASES[name]; the twins have equal codes"""
+    coarse, table, _ = query_case(ROW_LOOP_FERNS, 4, True)
+    code = R.frame_code(coarse, *table)
+    rng = np.random.default_rng(len(name))
+    rows = np.repeat(code[None, :], ROW_LOOP_CAPACITY, axis=0)
+    near = ROW_LOOP_CASES[name]
+    for k in range(ROW_LOOP_CAPACITY):
+        flip = rng.permutation(ROW_LOOP_FERNS)[:near.get(k, int(rng.integers(10, ROW_LOOP_FERNS + 1)))]
+        rows[k, flip] ^= rng.integers(1, 16, len(flip)).astype(np.uint8)
+    a, b = ROW_LOOP_TWINS[name]
+    rows[b] = rows[a]
+    rows.setflags(write=False)
+    return coarse, table, rows
+
+
+def check_row_loop_case(name, coarse, table, rows):
+    """the crossing of the distance kernel's `k += waves` and the select kernel's `k += kBlock`, and their effect"""
+    capacity, ferns = rows.shape
+    assert capacity > RELOC_WAVES + RELOC_BLOCK_WAVES and capacity > RELOC_BLOCK and (capacity * ferns) % RELOC_WORD
+    near = ROW_LOOP_CASES[name]
+    _, distances, record, _, _ = R.query(coarse, table, rows, capacity, candidates=4)
+    assert {k: int(distances[k]) for k in near} == near and int(np.sort(distances)[len(near)]) >= 10
+    ids = record[1:5].tolist()
+    a, b = ROW_LOOP_TWINS[name]
+    assert a < RELOC_WAVES <= b and distances[a] == distances[b] and np.array_equal(rows[a], rows[b])
+    if name == "spread":
+        assert ids == [3000, 4098, 100, 4000]  # the tie goes to the lower id, 4097 stays out
+    else:
+        assert ids == [4100, 150, 4096, 2000]
+        assert R.query(coarse, table, rows, capacity - 1, candidates=4)[2][1:5].tolist()[:3] == [150, 4096, 2000]
+    # a select kernel that looked at its first 256 keys only, or distances that stopped at row 4096, give other ids
+    assert any(k < RELOC_BLOCK for k in ids) and any(RELOC_BLOCK <= k < RELOC_WAVES for k in ids)
+    assert any(k >= RELOC_WAVES for k in ids)
+    return int(record[5])
+
+
+MANY_KEYFRAMES = dict(ferns=128, decisions=4, coarse_shape=(6, 8), depth_range=(0.5, 3.5), harvest_threshold=0.2,
+                      max_keyframes=300, candidates=4, seed=9)
+MANY_FRAMES, MANY_FRAME_SHAPE = 280, (24, 32)
+MANY_AGAIN = (3, 150, 260, 279)  # frames shown a second time, without harvest
+
+
+@functools.lru_cache(maxsize=None)
+def many_frames():
+    """MANY_FRAMES depth frames of one random depth per coarse block (blocks of 4 x 4 pixels) with some blocks empty: two of
+    them agree in about a fifth of their ferns, so every one is harvested"""
+    rng = np.random.default_rng(31)
+    ch, cw = MANY_KEYFRAMES["coarse_shape"]
+    out = []
+    for _ in range(MANY_FRAMES):
+        blocks = rng.uniform(0.5, 3.5, (ch, cw))
+        blocks[rng.random((ch, cw)) < 0.1] = 0.0
+        frame = np.kron(blocks, np.ones((MANY_FRAME_SHAPE[0] // ch, MANY_FRAME_SHAPE[1] // cw))).astype(np.float32)
+        frame.setflags(write=False)
+        out.append(frame)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def many_keyframes_restated():
+    """the restated database over many_frames() with harvest, then MANY_AGAIN without: (per frame the restated coarse
+    image, per query the restated dict, the database)"""
+    db = R.Database(**MANY_KEYFRAMES)
+    coarse = [db.encode(f, 1.0) for f in many_frames()]
+    twists = [np.full(6, k, np.float64) for k in range(MANY_FRAMES)]
+    found = [db.query(c, True, t) for c, t in zip(coarse, twists)]
+    found += [db.query(coarse[k]) for k in MANY_AGAIN]
+    return coarse, found, db
+
+
+def test_the_second_trip_inputs_cross_their_caps(lsf):
+    """what tests/test_gpu_second_trip.py assumes about its relocaliser inputs, from constants and the restatement"""
+    L = lsf._lib
+    assert (RELOC_MAX_BLOCKS, RELOC_MAX_FERNS) == (L.RELOC_MAX_BLOCKS, L.RELOC_MAX_FERNS)
+    assert RELOC_WAVES == 4096 and RELOC_BLOCK_WAVES == 4
+    for shape, coarse_shape in PIXEL_LOOP_IMAGES:
+        for dtype in (np.float32, np.uint16):
+            depth, ratio = pixel_loop_image(shape, coarse_shape, dtype)
+            want, want_counts, _ = R.encode(depth, ratio, coarse_shape, (0.5, 3.5))
+            check_pixel_loop_image(shape, coarse_shape, depth, ratio, want, want_counts)
+    for shape in BLOCK_LOOP_IMAGES:
+        depth, ratio = depth_image(shape, BLOCK_LOOP_COARSE, np.float32, np.random.default_rng(shape[0]))
+        check_block_loop_image(shape, *R.encode(depth, ratio, BLOCK_LOOP_COARSE, (0.5, 3.5)))
+    for ferns, decisions in ((1030, 8), (RELOC_MAX_FERNS, 1)):
+        check_word_loop_case(ferns, *query_case(ferns, decisions, False, True))
+    for name in ROW_LOOP_CASES:
+        assert check_row_loop_case(name, *row_loop_case(name)) == min(ROW_LOOP_CASES[name].values())
+    _, found, db = many_keyframes_restated()
+    assert db.n == MANY_FRAMES > RELOC_BLOCK and [f["appended"] for f in found[:MANY_FRAMES]] == list(range(MANY_FRAMES))
+    again = found[MANY_FRAMES:]
+    assert [f["nearest"][0] for f in again] == list(MANY_AGAIN) and all(f["distances"][0] == 0 for f in again)
+    assert max(MANY_AGAIN) >= RELOC_BLOCK > min(MANY_AGAIN)  # nearest keyframes in the select kernel's second trip too
 
 
 def test_sequence_constructor_refusals(lsf):

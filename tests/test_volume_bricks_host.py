@@ -2,8 +2,12 @@
 gather and scatter as inverses of each other, fusion.BrickStore's merge / clear / to_volume rules against the restated
 store (with the restated kernels in place of the card), the refusals that need no device, the header's macros, and the
 out-and-back trajectory tests/test_gpu_volume_bricks.py fuses: the window leaves its first position completely and
-returns onto most of it."""
+returns onto most of it.  Also the inputs the GPU tests share, and the window of 8450 bricks that
+tests/test_gpu_second_trip.py takes past the kernels' capped grids: that it crosses them, with flagged bricks and changed
+words past the cap, is asserted here from constants and the restatement."""
+import functools
 import itertools
+import os
 
 import numpy as np
 import pytest
@@ -25,12 +29,131 @@ def blobby_weights(shape, rng, a, largest=6):
     a shift touches hold no data; returns a copy"""
     a = a.copy()
     zero = np.zeros(shape, bool)
-    while zero.mean() < 0.5:
+    zeroed = 0  # zero.sum(), kept along: the mean of a large volume is not taken once per blob
+    while zeroed / zero.size < 0.5:
         lo = [int(rng.integers(0, n)) for n in shape]
         hi = [min(n, l + int(rng.integers(1, largest + 1))) for n, l in zip(shape, lo)]
-        zero[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = True
+        box = zero[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+        zeroed += box.size - int(box.sum())
+        box[...] = True
     a[zero] = 0.0
     return a
+
+
+def shifts(shape):
+    """(sx, sy, sz): one per sign and axis, a diagonal, and one that makes everything leave"""
+    return [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (2, -3, 1), (0, -(shape[1] + 5), 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(shape):
+    """tsdf, weight, colour with NaN payloads, +-inf and -0.0; about half of the weights zero in blobs"""
+    rng = np.random.default_rng(sum(shape) + 1)
+    arrays = (_special_volume(shape, rng),
+              blobby_weights(shape, rng, _special_volume(shape, rng), largest=max(6, min(shape) // 2 + 1)),
+              _special_volume(shape, rng, (4,)))
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+def random_bricks(shape, g, rng, with_colour):
+    """a brick for every brick of the window's grid and two outside it, in a shuffled order: special values, random
+    validity bytes, some rows wholly valid"""
+    coords = B.grid_coords(shape, g)
+    outside = np.array([coords.min(axis=0) - 1, coords.max(axis=0) + [1, 0, 0]], np.int32)
+    coords = rng.permutation(np.concatenate([coords, outside]))
+    k = len(coords)
+    valid = rng.integers(0, 256, (k, 64)).astype(np.uint8)
+    valid[rng.random((k, 64)) < 0.4] = 255
+    valid[rng.random((k, 64)) < 0.1] = 0
+    return (coords, _special_volume((k, 8, 8, 8), rng), _special_volume((k, 8, 8, 8), rng),
+            _special_volume((k, 8, 8, 8), rng, (4,)) if with_colour else None, valid)
+
+
+# ---- a window of more bricks than the capped grids have waves --------------------------------------------------------------
+# tests/test_gpu_second_trip.py runs the brick kernels on this window; what it assumes -- which cap the grid crosses, and
+# that work with a visible effect lies past it -- is checked here without a card.  The constants mirror
+# csrc/lsf_volume_bricks.hip.
+
+BRICKS_MAX_BLOCKS = 2048    # LSF_VOLUME_BRICKS_MAX_BLOCKS (include/lsf_hip.h)
+BRICKS_BLOCK_BRICKS = 4     # LSF_VOLUME_BRICKS_BLOCK_BRICKS: a wave per brick, or per row of a scatter
+BRICKS_WAVES = BRICKS_MAX_BLOCKS * BRICKS_BLOCK_BRICKS  # bricks, or rows, of a capped grid's first trip
+SCAN_BLOCK, SCAN_ITEMS = 1024, 8  # kScanBlock, kScanItems: the one-workgroup scan takes 8192 flags per trip
+SCAN_TRIP = SCAN_BLOCK * SCAN_ITEMS
+BIG_SHAPE, BIG_ORIGIN = (2, 515, 515), (-3, 5, 7)  # (Z, Y, X), g: a 65 x 65 x 2 grid
+# an x-shift; a y-shift whose leaving rows end in the bricks of the grid's last y rows, the topmost of them with a single
+# leaving row; a diagonal that makes the whole first z layer leave; the shift that makes everything leave
+BIG_SHIFTS = ((1, 0, 0), (0, -25, 0), (2, -3, 1), (0, -(BIG_SHAPE[1] + 5), 1))
+BIG_Y_SHIFT, BIG_ALL_SHIFT = BIG_SHIFTS[1], BIG_SHIFTS[3]
+
+
+def touched_bricks(shape, g, s):
+    """bool [nbricks]: the bricks that hold a voxel inside the window that leaves under s, data or not"""
+    return B._cut(B._pad(B.leaving(shape, s), shape, g, False)).reshape(-1, B.BRICK ** 3).any(axis=1)
+
+
+@functools.lru_cache(maxsize=None)
+def big_window_counts():
+    """per shift of BIG_SHIFTS the restated (flags, offsets, total) of inputs(BIG_SHAPE), after the assertions of the
+    crossing: the grid against the capped launch and the scan's trip, and flagged bricks past both"""
+    first, counts = B.brick_grid(BIG_SHAPE, BIG_ORIGIN)
+    nbricks = int(np.prod(counts))
+    assert counts == (65, 65, 2) and nbricks == 8450 and int(np.prod(BIG_SHAPE)) == 530450
+    assert BRICKS_WAVES == SCAN_TRIP == 8192 < nbricks  # the flag and gather kernels' stride, the scan's second trip
+    # every brick is cut by a face of the window or is one of its two one-voxel z layers: none is whole
+    assert BIG_SHAPE[0] == 2 and BIG_ORIGIN[2] % B.BRICK == B.BRICK - 1 and counts[2] == 2
+    # the scan's second trip: whole threads, one partial thread, idle ones
+    rest = nbricks - SCAN_TRIP
+    assert rest // SCAN_ITEMS == 32 and rest % SCAN_ITEMS == 2 and -(-rest // SCAN_ITEMS) < SCAN_BLOCK
+    w = inputs(BIG_SHAPE)[1]
+    out = {}
+    for s in BIG_SHIFTS:
+        flags, offsets, total = B.count(w, BIG_ORIGIN, s)
+        touched = touched_bricks(BIG_SHAPE, BIG_ORIGIN, s)
+        assert np.all(touched[flags == 1])
+        out[s] = (flags, offsets, total)
+    flags, offsets, total = out[BIG_Y_SHIFT]
+    touched = touched_bricks(BIG_SHAPE, BIG_ORIGIN, BIG_Y_SHIFT)
+    # flagged bricks past the cap, and, the blobs, touched bricks without data there
+    assert flags[BRICKS_WAVES:].sum() >= 100 and np.any(touched[BRICKS_WAVES:] & (flags[BRICKS_WAVES:] == 0))
+    assert offsets[BRICKS_WAVES] == flags[:BRICKS_WAVES].sum() > 0  # what the scan carries into its second trip
+    flags, offsets, total = out[BIG_ALL_SHIFT]
+    assert np.all(touched_bricks(BIG_SHAPE, BIG_ORIGIN, BIG_ALL_SHIFT))
+    assert BRICKS_WAVES < total < nbricks  # gather writes slots >= 8192; the blobs leave some bricks without data
+    assert flags[SCAN_TRIP:].sum() > 200 and offsets[SCAN_TRIP] > 8000  # a dropped carry restarts these from 0
+    for s in (BIG_SHIFTS[0], BIG_SHIFTS[2]):
+        assert out[s][0][BRICKS_WAVES:].sum() > 0 and 0 < out[s][0][:BRICKS_WAVES].sum() < BRICKS_WAVES
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def big_window_bricks(with_colour):
+    """random_bricks for the big window's grid: more rows than the scatter kernel's capped grid has waves"""
+    bricks = random_bricks(BIG_SHAPE, BIG_ORIGIN, np.random.default_rng(29), with_colour)
+    assert len(bricks[0]) == 8452 > BRICKS_WAVES
+    for a in bricks:
+        if a is not None:
+            a.setflags(write=False)
+    return bricks
+
+
+def test_the_big_window_crosses_the_caps(lsf):
+    """what tests/test_gpu_second_trip.py assumes about the big window, from constants and the restatement"""
+    L = lsf._lib
+    assert (BRICKS_MAX_BLOCKS, BRICKS_BLOCK_BRICKS) == (L.VOLUME_BRICKS_MAX_BLOCKS, L.VOLUME_BRICKS_BLOCK_BRICKS)
+    source = open(os.path.join(os.path.dirname(lsf._build.ABI_HEADER), "..", "levelsetfusion-python_amd", "csrc",
+                               "lsf_volume_bricks.hip")).read()
+    assert "constexpr int kScanBlock = %d;" % SCAN_BLOCK in source and "constexpr int kScanItems = %d;" % SCAN_ITEMS in source
+    big_window_counts()
+    # the scatter's rows past the cap: under the shifts that make a z layer or everything enter they change more than
+    # 1000 words, so a stride that stops short of them fails
+    t, w, _ = inputs(BIG_SHAPE)
+    bricks = big_window_bricks(False)
+    first_trip = tuple(a if a is None else a[:BRICKS_WAVES] for a in bricks)
+    for s in BIG_SHIFTS[2:]:
+        whole, part = B.scatter(*bricks, t, w, None, BIG_ORIGIN, s), B.scatter(*first_trip, t, w, None, BIG_ORIGIN, s)
+        assert int((whole[0] != part[0]).sum() + (whole[1] != part[1]).sum()) > 1000, s
 
 
 def test_lattice_arithmetic_for_negative_origins(lsf):
