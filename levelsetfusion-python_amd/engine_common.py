@@ -57,6 +57,31 @@ def _retire_graphs(graphs):
     _RETIRED_GRAPHS.extend(graphs.values())  # list.extend is atomic under the GIL
     graphs.clear()
 
+class _Fast(dev.IterationLauncher):
+    """what a call leaves in engine._fast: ONE shape on every route.  Tests, tools and the benchmark read `bands`,
+    `records`, `boxes`, `grid`, `count`, `compact_faces`, `faces_ref` and `exchange_interval`; a route that has none of one
+    leaves None, (None, None) or 0 there.  Launch by launch it is also the call's dev.IterationLauncher (gate: its gate
+    arguments); a library call (gate None) has no per-iteration launch arguments to materialise."""
+
+    def __init__(self, grid, records, gate=None, bands=None):
+        if gate is None:
+            self.grid, self.records = grid, records
+        else:
+            super().__init__(grid, records, *gate)
+        self.bands = bands
+        self.boxes = (None, None)      # the library call's box walk: (boxes, boxed canonical values)
+        self.native = None             # slabs: the library's RCCL transport, or None (torch.distributed)
+        self.exchange_interval = 0     # slabs: iterations per halo exchange
+        self.faces_ref = None          # slabs, launch by launch: the compact faces' descriptor once they are agreed
+        self.compact_faces = None      # slabs, library call: did compact faces travel (1 / 0)
+        self.keep = None               # buffers the call's launches name by address
+
+    @property
+    def count(self):
+        """the number of listed voxels"""
+        return sum(b.count for b in self.bands)
+
+
 class _Counted:
     """stands for a band list where only the number of listed voxels matters"""
 
@@ -71,9 +96,8 @@ class _Lazy:
         self._make, self._value = make, None
 
     def get(self):
-        if self._value is None:
-            self._value = self._make()
-            self._make = None
+        if self._make is not None:
+            self._value, self._make = self._make(), None
         return self._value
 
 

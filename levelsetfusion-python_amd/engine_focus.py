@@ -8,9 +8,9 @@ never store -- the update BEFORE the snap of warp_field_advanced zeroes it."""
 import numpy as np
 import torch
 
-from . import _lib
 from . import device as dev
 from .engine_common import _conv_axis_order
+from .engine_outcome import without_energies
 
 
 class FocusMixin:
@@ -25,19 +25,14 @@ class FocusMixin:
         self._focus_flat = torch.as_tensor(np.atleast_1d(flat), dtype=torch.int64, device=live.device)
         self.focus_trace = dict(canonical=canonical.reshape(-1)[self._focus_flat].cpu().numpy(), sdf=[], warp=[])
 
-    def _probe_focus(self, i, lives, warps, states, canonical, grid):
+    def _probe_focus(self, i, iteration):
         """iteration i has run: the live value it started from and the length of its update BEFORE the snap, at the traced
         voxels.  The inputs of the iteration are still in the ping-pong buffers; the (filtered) gradient is recomputed
         from them by the unfused kernels on the whole array -- the same code path as gradient_field(), without the update
         kernel that zeroes it where the live field snapped."""
-        if states is not None:
-            live_in = torch.empty(tuple(states[0].shape[:-1]), dtype=torch.float32, device=states[0].device)
-            warp_in = torch.empty((grid.dims,) + tuple(live_in.shape), dtype=torch.float32, device=live_in.device)
-            dev.state_unpack(states[i % 2], dev.full_range(grid), live_in, warp_in, None)
-        else:
-            live_in, warp_in = lives[i % 2], warps[i % 2]
-        params = _lib.SlavchevaParams.from_buffer_copy(self.params)
-        params.energy_mode = _lib.ENERGY_NONE
+        canonical, grid = iteration.canonical, iteration.grid
+        live_in, warp_in = iteration.inputs(i)
+        params = without_energies(self.params)
         g0 = torch.empty_like(warp_in)
         dev.slavcheva_gradient(live_in, canonical, warp_in, g0, grid, params, None, dev.new_records(1, live_in.device), 0)
         g = g0

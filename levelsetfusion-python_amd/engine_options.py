@@ -62,6 +62,7 @@ def apply(engine, defaults, options):
 
 
 def new_call_report():
-    """what the last optimize() call took: tests and measurements read it instead of private attributes"""
+    """what the last optimize() call took: tests and measurements read it instead of private attributes.  route: how a
+    SlavchevaEngine call was enqueued (engine_slavcheva.ROUTES), None before a call and for the hierarchical engine"""
     return types.SimpleNamespace(sparse_states=False, box_walk=False, sobolev_boxes=False, library_run=False,
-                                 blocked_levels=0, record_rows=False)
+                                 blocked_levels=0, record_rows=False, route=None)

@@ -1,8 +1,50 @@
-"""What a SlavchevaEngine.optimize() call leaves behind: the final fields on the device (handed out on demand) and the
-per-iteration log."""
+"""What a SlavchevaEngine.optimize() call leaves behind: the final fields on the device (handed out on demand), the
+per-iteration log, how gradient_field() recomputes its field (the engine keeps it as an engine_common._Lazy: made when
+first read, then kept, and what it was made from let go of), and what the launch-by-launch iterations on
+the float4 ping-pong states share."""
 import torch
 
-from . import device as dev
+from . import _lib, device as dev
+
+
+def unpack_state(state, grid):
+    """a float4 state as fresh planar (live, warp) tensors"""
+    live = torch.empty(tuple(state.shape[:-1]), dtype=torch.float32, device=state.device)
+    warp = torch.empty((grid.dims,) + tuple(live.shape), dtype=torch.float32, device=state.device)
+    dev.state_unpack(state, grid, live, warp, None)
+    return live, warp
+
+
+def without_energies(params):
+    """a copy of the parameter block for launches whose records nobody reads"""
+    params = _lib.SlavchevaParams.from_buffer_copy(params)
+    params.energy_mode = _lib.ENERGY_NONE
+    return params
+
+
+def recompute_gradient(params, state_in, canonical, grid, bands=None, complete=None):
+    """The fused kernel does not store the gradient (12 B/voxel/iteration saved); it is recomputed here from the inputs
+    of the last iteration, which the ping-pong buffers still hold, by the unfused kernels -- same code path, same bits.
+    bands: the unfused kernels at the voxels of the call's band lists (the gradient is zero everywhere else): of the
+    input state only the listed voxels' neighbourhoods and re-warp cells are read, so a state that was initialised
+    near the band only (lsf_state_pack_needed) serves as it stands, and nothing of the caller's is touched.
+    complete = (dev.StatePrepare, live): the state was initialised near the band only and is read whole: complete it from
+    the call's live array, which still holds the input wherever no list entry points (the finalize pass writes listed
+    voxels only)."""
+    if complete is not None:
+        complete[0].complete(state_in, complete[1])
+    live_in, warp_in = unpack_state(state_in, grid)
+    g = torch.empty_like(warp_in) if bands is None else torch.zeros_like(warp_in)
+    scratch_records = dev.new_records(1, live_in.device)
+    params = without_energies(params)
+    warp_out, live_scratch = torch.empty_like(warp_in), torch.empty_like(live_in)
+    bands = [None] if bands is None else [band for band in bands if band.count]
+    for band in bands:
+        dev.slavcheva_gradient(live_in, canonical, warp_in, g, grid, params, None, scratch_records, 0, band)
+    for band in bands:
+        dev.slavcheva_update_rewarp(live_in, canonical, g, warp_out, live_scratch, grid, params, None, scratch_records, 0,
+                                    band)
+    return g
 
 
 class SlavchevaOutcome:
@@ -19,6 +61,7 @@ class SlavchevaOutcome:
         self._sparse = sparse
         self._guard = None
         self._warp_zeroed = warp_zeroed  # a zero-filled API-layout warp tensor made while the card was idle (or None)
+        self._early = None  # enqueue_finalize(): (its arguments, target, warp, raw statistics on their way to the host)
 
     def guard(self, records, count, limit):
         """a sparse run: the listed finalize pass leaves the caller's fields alone when one of records[0..count) holds a
@@ -56,7 +99,7 @@ class SlavchevaOutcome:
         device tensor, or None for a new one), builds the interleaved warp [z,]y,x,c and -- with `statistics` -- the raw
         convergence statistics (float64 [16] on the HOST: warp [0:8], |canonical - live| [8:16]).
         Returns (live, warp_interleaved, raw statistics or None)."""
-        early = getattr(self, "_early", None)
+        early = self._early
         if early is not None and early[0][0] is live_out and \
                 early[0][1:] == (float(lower_threshold), bool(statistics)):
             # already enqueued by optimize() behind the last iteration (fixed iteration counts): nothing left to launch
@@ -199,3 +242,39 @@ class _RunOutcome(SlavchevaOutcome):
         if live_out is not None and live_out is not self._live:
             live_out.copy_(self._live)
         return self._live, self.warp_interleaved, (self._raw if statistics else None)
+
+
+class _StateIteration:
+    """what the launch-by-launch iterations on the float4 ping-pong states share (the fused kernel: engine_slavcheva.py's
+    _FusedIteration, SobolevFusion on lists / boxes: engine_sobolev.py's _SobolevStatePlan): iteration i reads
+    states[i % 2] and writes the other.  listed, sparse, warp_zeroed: SlavchevaOutcome's; live_at_entry: a copy of what an
+    early finalize pass of a slab call overwrites."""
+
+    restore = None  # (the caller's tensor an early finalize pass has written, its contents before), slab calls
+
+    def hold(self, states, canonical, grid, records, listed=None, sparse=None, warp_zeroed=None, live_at_entry=None):
+        self.states, self.canonical, self.grid, self.records = states, canonical, grid, records
+        self._outcome_args = dict(listed=listed, sparse=sparse, warp_zeroed=warp_zeroed)
+        self._live_at_entry, self._early = live_at_entry, None
+
+    def inputs(self, i):
+        """planar (live, warp) iteration i started from"""
+        return unpack_state(self.states[i % 2], dev.full_range(self.grid))
+
+    def finalize_early(self, finalize, records, limit, sparse_reach):
+        """every launch runs ungated, so the final state is states[limit % 2]: finalize before looking.  A slab run
+        may still have to be discarded (see optimize()), and the pass writes the caller's tensor: optimize() puts
+        the copy taken at entry back before it runs the call again"""
+        early = self._early = SlavchevaOutcome(self.grid, self.canonical, state=self.states[limit % 2],
+                                               **self._outcome_args)
+        if self._outcome_args["sparse"] is not None:
+            # the pass must not touch the caller's fields when an update outran the initialised region
+            early.guard(records, limit, float(sparse_reach))
+        if self._live_at_entry is not None:
+            self.restore = (finalize[0], self._live_at_entry)
+        early.enqueue_finalize(*finalize)
+
+    def outcome(self, n_exec, limit):
+        if self._early is not None and n_exec == limit:
+            return self._early
+        return SlavchevaOutcome(self.grid, self.canonical, state=self.states[n_exec % 2], **self._outcome_args)

@@ -1,13 +1,14 @@
 """Whole optimize() calls enqueued by the LIBRARY (csrc/lsf_slavcheva_run.hip): the loop of
-slavcheva_optimizer2d.py:354-388 without a Python iteration -- two foreign calls that run without the interpreter lock."""
+slavcheva_optimizer2d.py:354-388 without a Python iteration -- two foreign calls that run without the interpreter lock.
+_RunCall is what the whole-volume call (here) and the z-slab call (engine_slab.py) set up and leave behind alike."""
 import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, device as dev
-from .engine_common import _Counted
-from .engine_outcome import _RunLog, _RunOutcome
+from .engine_common import _Fast, _Lazy
+from .engine_outcome import _RunLog, _RunOutcome, recompute_gradient
 
 
 class _SparseStateExceeded(Exception):
@@ -16,14 +17,81 @@ class _SparseStateExceeded(Exception):
     call on fully initialised states and keeps doing so for this optimizer)"""
 
 
-class _RunGradient:
-    """the SobolevFusion call's final gradient (float4 [z,]y,x,4), handed out planar like _SobolevStatePlan's"""
+class _RunCall:
+    """One library-enqueued call: what lsf_state_run_* (a whole volume) and lsf_slab_run_* (a z-slab rank) are handed and
+    leave behind alike, made in the order both need it -- the target, the states, the prepare scratch, the totals and the
+    lsf_state_run base block in front of the begin call; behind it the records, their used words and the result arrays;
+    and, BEFORE the blocking finish call, everything about the call's aftermath that does not depend on its results
+    (behind it the card idles until the next call's first launch: tools/host_tail.py)."""
 
-    def __init__(self, g4):
-        self._g4 = g4
+    def __init__(self, engine, live, canonical, grid, finalize, sparse, base, totals_name, n_totals, restore=False):
+        live_out = finalize[0]
+        self.engine, self.canonical, self.grid = engine, canonical, grid
+        device = self.device = live.device
+        n = self.n = dev.n_voxels(grid)
+        whole = self.whole = dev.full_range(grid)  # (a slab: the local array, owned slices + halos; z_global_offset stays)
+        engine.last_call.sparse_states = sparse
+        engine.last_call.library_run = True
+        usable = (live_out is not None and live_out.is_cuda and live_out.dtype == torch.float32
+                  and live_out.is_contiguous() and tuple(live_out.shape) == tuple(live.shape))
+        target = self.target = live_out if usable else torch.empty_like(live)
+        if target is not live:
+            target.copy_(live)  # the finalize pass writes listed voxels only
+        elif usable and restore:
+            # the pass writes the caller's tensor before every rank's records have said whether the call stands: what it
+            # overwrites is kept (optimize() puts it back before a wider re-run)
+            engine._slab_restore = (live_out, live_out.clone())
+        states = self.states = [torch.empty(tuple(live.shape) + (4,), dtype=torch.float32, device=device)
+                                for _ in range(2)]
+        self.scratch = torch.empty(int(_lib.lib.lsf_state_prepare_scratch_elements(ctypes.byref(whole))),
+                                   dtype=torch.int32, device=device)
+        self.totals = torch.empty(n_totals, dtype=torch.int64, device=device)
+        self.totals_host = dev.pinned_scratch(totals_name, n_totals, torch.int64)
+        base.live, base.canonical = dev._ptr(live, n, "live"), dev._ptr(canonical, n, "canonical")
+        base.state[0], base.state[1] = states[0].data_ptr(), states[1].data_ptr()
+        base.prepare_scratch, base.totals_device, base.totals_host = self.scratch.data_ptr(), self.totals.data_ptr(), \
+            self.totals_host.data_ptr()
+        base.grid = whole
+        base.sparse_reach = engine.sparse_reach if sparse else 0
+        base.second_state_late = int(not sparse and n <= dev.StatePrepare.SPLIT_MAX_VOXELS)
 
-    def final_gradient_planar(self, dims):
-        return self._g4[..., :dims].movedim(-1, 0).contiguous()
+    def results(self, lists, n_interior, n_boundary, iterations, device_words, host_name, host_words):
+        """the records, their used words on the device and on the host and the arrays the finish call decodes them into;
+        then what does not depend on the call's results: the two band lists cut from `lists` (sized from the totals the
+        begin call waited for), what the call leaves in engine._fast, its outcome"""
+        self.lists = lists
+        records = self.records = dev.new_records(iterations, self.device)
+        self.words = torch.empty(device_words, dtype=torch.int64, device=self.device)
+        self.words_host = dev.pinned_scratch(host_name, host_words, torch.int64)
+        self.max_value, self.argmax = np.empty(iterations, np.float32), np.empty(iterations, np.int64)
+        self.energies, self.executed = np.empty((iterations, 3), np.float64), np.empty(iterations, np.bool_)
+        self.result = _lib.StateRunResult(self.max_value.ctypes.data, self.argmax.ctypes.data, self.energies.ctypes.data,
+                                          self.executed.ctypes.data)
+        bands = self.bands = []
+        if n_interior:
+            bands.append(dev.BandList(lists[:n_interior], n_interior, _lib.BAND_INTERIOR))
+        if n_boundary or not bands:
+            bands.append(dev.BandList(lists[n_interior:] if n_boundary else lists[:1], n_boundary, _lib.BAND_BOUNDARY))
+        fast = self.fast = _Fast(self.grid, records, bands=bands)
+        self.outcome = _RunOutcome(self.grid, self.canonical, None, self.target, bands, None)
+        self.weights = tuple(self.engine.weights)
+        return fast
+
+    def leave(self, gradient_grid, gradient=None, n_exec=None):
+        """the call stands: the engine's count, log and gradient source, the outcome's final state"""
+        e = self.engine
+        if n_exec is None:
+            n_exec = len(self.executed) if self.executed.all() else int(self.executed.sum())
+        e._fast = self.fast
+        e.iteration_count = n_exec
+        e.log = _RunLog(self.max_value[:n_exec], self.argmax[:n_exec], self.energies[:n_exec], self.weights)
+        if gradient is None:
+            # gradient_field() recomputes the last iteration's gradient on demand from its INPUT state, at the listed voxels
+            params, state_in, canonical, bands = e.params, self.states[(n_exec - 1) % 2], self.canonical, self.bands
+            gradient = _Lazy(lambda: recompute_gradient(params, state_in, canonical, gradient_grid, bands))
+        e._gradient_state = gradient
+        self.outcome.state = self.states[n_exec % 2]
+        return self.outcome
 
 
 class RunMixin:
@@ -43,29 +111,9 @@ class RunMixin:
         loop = None
         if self.min_iterations < iterations:
             loop = _lib.RunLoop(self.min_iterations, self.max_iterations, self.lo, self.hi, self.check_interval, 0)
-        device = live.device
-        n = dev.n_voxels(grid)
-        whole = dev.full_range(grid)
-        sparse = (self.sparse_reach > 0 and n >= self.sparse_min_voxels and not self.sparse_disabled)
-        self.last_call.sparse_states = sparse
-        self.last_call.library_run = True
-        usable = (live_out is not None and live_out.is_cuda and live_out.dtype == torch.float32
-                  and live_out.is_contiguous() and tuple(live_out.shape) == tuple(live.shape))
-        target = live_out if usable else torch.empty_like(live)
-        if target is not live:
-            target.copy_(live)  # the finalize pass writes listed voxels only
-        states = [torch.empty(tuple(live.shape) + (4,), dtype=torch.float32, device=device) for _ in range(2)]
-        scratch = torch.empty(int(_lib.lib.lsf_state_prepare_scratch_elements(ctypes.byref(whole))), dtype=torch.int32,
-                              device=device)
-        totals = torch.empty(5, dtype=torch.int64, device=device)
-        totals_host = dev.pinned_scratch("run totals", 5, torch.int64)
         run = _lib.StateRun()
-        run.live, run.canonical = dev._ptr(live, n, "live"), dev._ptr(canonical, n, "canonical")
-        run.state[0], run.state[1] = states[0].data_ptr(), states[1].data_ptr()
-        run.prepare_scratch, run.totals_device, run.totals_host = scratch.data_ptr(), totals.data_ptr(), totals_host.data_ptr()
-        run.grid = whole
-        run.sparse_reach = self.sparse_reach if sparse else 0
-        run.second_state_late = int(not sparse and n <= dev.StatePrepare.SPLIT_MAX_VOXELS)
+        c = _RunCall(self, live, canonical, grid, finalize, self._sparse_states(grid), run, "run totals", 5)
+        device, n, whole = c.device, c.n, c.whole
         count_boxes = sobolev or (dev.boxes_ok(whole) and (self.box_walk is True or
                                                            (self.box_walk is None and n >= self.box_walk_min_voxels)))
         run.box_all = int(sobolev)
@@ -77,7 +125,7 @@ class RunMixin:
         stream = dev.stream_ptr()
         _lib.check(_lib.lib.lsf_state_run_begin(ctypes.byref(run), stream), "lsf_state_run_begin")
         # (the card is writing the states now; the lists are sized from the totals the call waited for)
-        n_interior, n_boundary, opposite, first_opposite, n_boxes = totals_host.tolist()
+        n_interior, n_boundary, opposite, first_opposite, n_boxes = c.totals_host.tolist()
         lists = torch.empty(max(n_interior + n_boundary, 1), dtype=torch.int32, device=device)
         boxes = box_canonical = None
         if sobolev:
@@ -97,31 +145,18 @@ class RunMixin:
             n_launches = int(n_interior > 0) + int(n_boundary > 0 or n_interior == 0)
             record_rows = torch.empty(int(_lib.lib.lsf_state_run_rows_elements(ctypes.byref(whole), iterations, n_launches)),
                                       dtype=torch.int64, device=device)
-        records = dev.new_records(iterations, device)
         n_words = iterations * _lib.RECORD_SLOTS * dev.USED_SLOT_WORDS
-        words = torch.empty(n_words + 16, dtype=torch.int64, device=device)  # the records' used words, then the statistics
-        words_host = dev.pinned_scratch("run records", words.numel(), torch.int64)
+        # (the records' used words, then the statistics)
+        f = c.results(lists, n_interior, n_boundary, iterations, n_words + 16, "run records", n_words + 16)
+        records, words, words_host, result = c.records, c.words, c.words_host, c.result
         stats = stats_scratch = None
         if statistics:
             stats = torch.empty(16, dtype=torch.float64, device=device)
             stats_scratch = torch.empty(2 * int(_lib.lib.lsf_state_finalize_scratch_elements(ctypes.byref(whole))),
                                         dtype=torch.float64, device=device)
-        max_value, argmax = np.empty(iterations, np.float32), np.empty(iterations, np.int64)
-        energies, executed = np.empty((iterations, 3), np.float64), np.empty(iterations, np.bool_)
-        result = _lib.StateRunResult(max_value.ctypes.data, argmax.ctypes.data, energies.ctypes.data, executed.ctypes.data)
         none = ctypes.c_void_p(0)
         p_lists = lists.data_ptr()
-        # everything about the call's aftermath that does not depend on its results is made BEFORE the blocking call below --
-        # behind it the card idles until the next call's first launch (tools/host_tail.py)
-        bands = []
-        if n_interior:
-            bands.append(dev.BandList(lists[:n_interior], n_interior, _lib.BAND_INTERIOR))
-        if n_boundary or not bands:
-            bands.append(dev.BandList(lists[n_interior:] if n_boundary else lists[:1], n_boundary, _lib.BAND_BOUNDARY))
-        f = _Counted(sum(b.count for b in bands))
-        f.bands, f.records, f.boxes = bands, records, (boxes, box_canonical)
-        outcome = _RunOutcome(grid, canonical, None, target, bands, None)
-        weights = tuple(self.weights)
+        f.boxes = (boxes, box_canonical)
         if sobolev:
             f.keep = (g4, list_all, taps)
             self._sobolev_band = f  # what bench.py prices this path over
@@ -130,15 +165,20 @@ class RunMixin:
                 int(taps.size), ctypes.c_void_p(p_lists), ctypes.c_void_p(p_lists + 4 * n_interior),
                 ctypes.c_void_p(list_all.data_ptr() if list_all is not None else 0), ctypes.c_void_p(boxes.data_ptr()),
                 ctypes.c_void_p(g4[0].data_ptr()), ctypes.c_void_p(g4[1].data_ptr()), ctypes.c_void_p(records.data_ptr()),
-                iterations, ctypes.byref(loop) if loop is not None else None, dev._ptr(target, n, "live_out"),
+                iterations, ctypes.byref(loop) if loop is not None else None, dev._ptr(c.target, n, "live_out"),
                 float(lower_threshold), ctypes.c_void_p(stats.data_ptr()) if statistics else none,
                 ctypes.c_void_p(stats_scratch.data_ptr()) if statistics else none, ctypes.c_void_p(words.data_ptr()),
                 ctypes.c_void_p(words_host.data_ptr()), ctypes.byref(result), stream), "lsf_sobolev_run_finish")
         else:
-            self._run_finish(run, p_lists, n_interior, boxes, box_canonical, records, iterations, loop, target, n,
+            self._run_finish(run, p_lists, n_interior, boxes, box_canonical, records, iterations, loop, c.target, n,
                              lower_threshold, stats, stats_scratch, statistics, words, words_host, result, stream, record_rows)
-        return self._after_run(result, executed, iterations, f, max_value, argmax, energies, weights, states, canonical, grid,
-                               bands, outcome, statistics, words_host, n_words, g4[1] if sobolev else None)
+        if result.reach_exceeded:
+            raise _SparseStateExceeded()  # the pass has left the caller's array alone (its guard); optimize() repeats
+        # SobolevFusion: the filtered gradient of the last executed iteration (float4, made planar when read)
+        outcome = c.leave(grid, _Lazy(lambda: g4[1][..., :grid.dims].movedim(-1, 0).contiguous()) if sobolev else None)
+        if statistics:
+            outcome._raw = words_host[n_words:].numpy().view(np.float64).copy()
+        return outcome
 
     def _sobolev_gradient_buffers(self, live, whole, lists, n_listed):
         """the two float4 gradient buffers of a library-enqueued SobolevFusion call, all zero: the previous call's buffers with
@@ -146,7 +186,7 @@ class RunMixin:
         for another shape, fresh zero fills (2 x 268 MB).  The optimizer keeps them between calls (the reference allocates its
         gradient per call, slavcheva_optimizer2d.py:343-346)."""
         key = (tuple(live.shape), live.device)
-        cache = getattr(self, "_g4_cache", None)
+        cache = self._g4_cache
         if cache is not None and cache[0] == key:
             _, g4, old_lists, old_n = cache
             for t, bricks in ((g4[0], 1), (g4[1], 0)):
@@ -178,21 +218,3 @@ class RunMixin:
             "lsf_state_run_finish_rows")
         self.last_call.record_rows = bool(rows_taken.value)
 
-    def _after_run(self, result, executed, iterations, f, max_value, argmax, energies, weights, states, canonical, grid, bands,
-                   outcome, statistics, words_host, n_words, sobolev_gradient):
-        if result.reach_exceeded:
-            raise _SparseStateExceeded()  # the pass has left the caller's array alone (its guard); optimize() repeats
-        n_exec = iterations if executed.all() else int(executed.sum())
-        self._fast = f
-        self.iteration_count = n_exec
-        self.log = _RunLog(max_value[:n_exec], argmax[:n_exec], energies[:n_exec], weights)
-        if sobolev_gradient is not None:
-            # the filtered gradient of the last executed iteration (float4, made planar when read)
-            self._gradient_state = ("float4", _RunGradient(sobolev_gradient), grid.dims)
-        else:
-            # gradient_field() recomputes the last iteration's gradient on demand from its INPUT state, at the listed voxels
-            self._gradient_state = ("recompute_listed", states[(n_exec - 1) % 2], canonical, grid, bands)
-        outcome.state = states[n_exec % 2]
-        if statistics:
-            outcome._raw = words_host[n_words:].numpy().view(np.float64).copy()
-        return outcome

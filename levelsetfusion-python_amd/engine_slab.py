@@ -6,12 +6,12 @@ run_hierarchical_optimizer3d_multipair.py:403-432."""
 import ctypes
 import os
 
-import numpy as np
 import torch
 
-from . import _lib, device as dev
-from .engine_common import _Counted, _Lazy
-from .engine_outcome import SlavchevaOutcome, _RunLog, _RunOutcome
+from . import _lib, device as dev, engine_options
+from .engine_common import _Lazy
+from .engine_outcome import SlavchevaOutcome
+from .engine_run import _RunCall
 
 
 class _HaloTooNarrow(Exception):
@@ -117,7 +117,7 @@ class SlabMixin:
         # Host work between two launches (the card waits for it: kernel trace of the loop-back): a face
         # is (device pointer, count) -- a run of a sorted list is pointer arithmetic, no tensor views -- and the faces
         # that have entries in both lists are merged in ONE launch into ONE buffer
-        if getattr(self, "_no_face", None) is None or self._no_face.device != live.device:
+        if self._no_face is None or self._no_face.device != live.device:
             self._no_face = torch.zeros(4, dtype=torch.int32, device=live.device)  # a valid address for an empty face
         none = (self._no_face.data_ptr(), 0)
         keep = [self._no_face]
@@ -180,7 +180,7 @@ class SlabMixin:
             torch.distributed.all_gather(rows, mine, group=self.comm.group)
             check = (torch.stack(rows), None)
         else:
-            if getattr(self, "_plan_stream", None) is None or self._plan_stream.device != live.device:
+            if self._plan_stream is None or self._plan_stream.device != live.device:
                 self._plan_stream = torch.cuda.Stream(device=live.device)
             with torch.cuda.stream(self._plan_stream):
                 staged = dev.pinned_scratch("face counts out", 4, torch.int64)
@@ -220,14 +220,13 @@ class SlabMixin:
             else:
                 for r in range(len(rows) - 1):
                     ok &= rows[r][1] == rows[r + 1][2] and rows[r + 1][0] == rows[r][3]
-            self._faces_verified = ok
         if not ok:
             import warnings
             if self.comm.layout.axis == 1:
                 warnings.warn("slab halos are not consistent with the neighbours' slabs (band voxel counts differ): the "
                               "rows travel whole through torch.distributed")
                 f.native = None
-                if not hasattr(self, "_comm_stream"):
+                if self._comm_stream is None:
                     self._comm_stream = torch.cuda.Stream(device=device)
                     self._events = [(torch.cuda.Event(), torch.cuda.Event()) for _ in range(2)]
             else:
@@ -278,7 +277,7 @@ class SlabMixin:
         if own < 2 * h:
             raise ValueError("a slab of %d slices is too thin for a %d-slice halo" % (own, h))
         fixed = self.min_iterations >= limit
-        f.exchange_interval = h if fixed and not getattr(self, "_exchange_every_iteration", False) else 1
+        f.exchange_interval = h if fixed and not self._exchange_every_iteration else 1
         slice_voxels = grid.ny * grid.nx
         listed = bands[0].indices is not None
         if listed and prepared is not None:  # the prepare pass brought the positions of the z cuts along
@@ -342,12 +341,12 @@ class SlabMixin:
         if f.native is not None:
             f.layout = _lib.SlabLayoutC(grid.nz, grid.ny, grid.nx, L.z_begin, L.z_end, h, lo_rank, hi_rank)
             f.layout_ref = ctypes.byref(f.layout)
-            # compact faces are planned when the first exchange is enqueued (_enqueue_state_iteration): the plan costs a
+            # compact faces are planned when the first exchange is enqueued (_enqueue_slab_state_iteration): the plan costs a
             # collective and a host read (~0.2 ms) that then wait behind the iterations already queued, not in front of them
             f.pending_face_plan = f.face_plan_args = None
             if listed and os.environ.get("LSF_SLAB_FACES", "compact") != "full":
                 f.face_plan_args = ((live, bands, cut, lo, hi, lo_rank, hi_rank), {})
-        elif not hasattr(self, "_comm_stream"):
+        elif self._comm_stream is None:
             self._comm_stream = torch.cuda.Stream(device=live.device)
             self._events = [(torch.cuda.Event(), torch.cuda.Event()) for _ in range(2)]
 
@@ -370,7 +369,7 @@ class SlabMixin:
         if bands[0].indices is None:
             raise ValueError("slabs cut along y run on band lists (use_band_list=True)")
         fixed = self.min_iterations >= limit
-        f.exchange_interval = h if fixed and not getattr(self, "_exchange_every_iteration", False) else 1
+        f.exchange_interval = h if fixed and not self._exchange_every_iteration else 1
         nx, ny = grid.nx, grid.ny
         rows = [((b.indices[:b.count] // nx) % ny) if b.count else None for b in bands]
 
@@ -430,7 +429,7 @@ class SlabMixin:
                                                       face(L.end - h, L.end) if hi else None],
                                                 recv=[face(L.begin - h, L.begin) if lo else None,
                                                       face(L.end, L.end + h) if hi else None])))
-        if f.native is None and not hasattr(self, "_comm_stream"):
+        if f.native is None and self._comm_stream is None:
             self._comm_stream = torch.cuda.Stream(device=live.device)
             self._events = [(torch.cuda.Event(), torch.cuda.Event()) for _ in range(2)]
 
@@ -449,98 +448,52 @@ class SlabMixin:
         rank's records.  The same launches as _enqueue_slab_state_iteration makes one by one from Python
         (tests/slab_loopback_worker.py holds the two against each other bit for bit), without ~50 Python -> C calls, the
         part descriptors and two torch.distributed collectives per call."""
-        live_out, lower_threshold, statistics = finalize
         L = self.comm.layout
         iterations = self.min_iterations
-        device = live.device
-        n = dev.n_voxels(grid)
-        whole = dev.full_range(grid)  # the local array: owned slices + halos (z_global_offset stays)
-        every = getattr(self, "_exchange_every_iteration", False)
-        # sparse states in exchange groups only, with a halo of at least the reach (see _optimize)
-        sparse = (not every and L.halo >= max(self.sparse_reach, 2) and self.sparse_reach > 0
-                  and n >= self.sparse_min_voxels and not self.sparse_disabled)
-        self.last_call.sparse_states = sparse
-        self.last_call.library_run = True
-        usable = (live_out is not None and live_out.is_cuda and live_out.dtype == torch.float32
-                  and live_out.is_contiguous() and tuple(live_out.shape) == tuple(live.shape))
-        target = live_out if usable else torch.empty_like(live)
-        if target is not live:
-            target.copy_(live)  # the finalize pass writes listed voxels only
-        elif usable:
-            # the pass writes the caller's tensor before every rank's records have said whether the call stands: what it
-            # overwrites is kept (optimize() puts it back before a wider re-run)
-            self._slab_restore = (live_out, live_out.clone())
-        states = [torch.empty(tuple(live.shape) + (4,), dtype=torch.float32, device=device) for _ in range(2)]
-        scratch = torch.empty(int(_lib.lib.lsf_state_prepare_scratch_elements(ctypes.byref(whole))), dtype=torch.int32,
-                              device=device)
-        n_totals = 5 + 2 * _lib.SLAB_MAX_CUTS
-        totals = torch.empty(n_totals, dtype=torch.int64, device=device)
-        totals_host = dev.pinned_scratch("slab run totals", n_totals, torch.int64)
-        _, world, lo_rank, hi_rank = self.comm.native_identity()
+        every = self._exchange_every_iteration
         run = _lib.SlabRun()
-        base = run.base
-        base.live, base.canonical = dev._ptr(live, n, "live"), dev._ptr(canonical, n, "canonical")
-        base.state[0], base.state[1] = states[0].data_ptr(), states[1].data_ptr()
-        base.prepare_scratch, base.totals_device, base.totals_host = scratch.data_ptr(), totals.data_ptr(), \
-            totals_host.data_ptr()
-        base.grid = whole
-        base.sparse_reach = self.sparse_reach if sparse else 0
-        base.second_state_late = int(not sparse and n <= dev.StatePrepare.SPLIT_MAX_VOXELS)
+        # sparse states in exchange groups only, with a halo of at least the reach (see _launch_plan)
+        c = _RunCall(self, live, canonical, grid, finalize, self._sparse_states(grid), run.base, "slab run totals",
+                     5 + 2 * _lib.SLAB_MAX_CUTS, restore=True)
+        device, n = c.device, c.n
+        _, world, lo_rank, hi_rank = self.comm.native_identity()
         run.layout = _lib.SlabLayoutC(grid.nz, grid.ny, grid.nx, L.z_begin, L.z_end, L.halo, lo_rank, hi_rank)
         run.exchange_interval = 1 if every else L.halo
         stream = dev.stream_ptr()
         native = self.comm.native()
         _lib.check(_lib.lib.lsf_slab_run_begin(ctypes.byref(run), stream), "lsf_slab_run_begin")
-        n_interior, n_boundary = totals_host[:2].tolist()
+        n_interior, n_boundary = c.totals_host[:2].tolist()
         lists = torch.empty(max(n_interior + n_boundary, 1), dtype=torch.int32, device=device)
         index_scratch = torch.empty(max(int(run.out_index_entries), 1), dtype=torch.int32, device=device)
         messages = None
         if os.environ.get("LSF_SLAB_FACES", "compact") != "full":
             messages = torch.empty(4 * int(run.out_face_entries) + 16, dtype=torch.float32, device=device)
-        records = dev.new_records(iterations, device)
         n_words = iterations * _lib.RECORD_SLOTS * dev.USED_SLOT_WORDS
-        words = torch.empty((1 + world) * n_words, dtype=torch.int64, device=device)
-        words_host = dev.pinned_scratch("slab run records", world * n_words, torch.int64)
-        max_value, argmax = np.empty(iterations, np.float32), np.empty(iterations, np.int64)
-        energies, executed = np.empty((iterations, 3), np.float64), np.empty(iterations, np.bool_)
-        result = _lib.StateRunResult(max_value.ctypes.data, argmax.ctypes.data, energies.ctypes.data, executed.ctypes.data)
+        f = c.results(lists, n_interior, n_boundary, iterations, (1 + world) * n_words, "slab run records", world * n_words)
         p_lists = lists.data_ptr()
-        bands = []
-        if n_interior:
-            bands.append(dev.BandList(lists[:n_interior], n_interior, _lib.BAND_INTERIOR))
-        if n_boundary or not bands:
-            bands.append(dev.BandList(lists[n_interior:] if n_boundary else lists[:1], n_boundary, _lib.BAND_BOUNDARY))
-        f = _Counted(sum(b.count for b in bands))
-        f.bands, f.records, f.exchange_interval, f.keep = bands, records, int(run.exchange_interval), (index_scratch, messages)
-        outcome = _RunOutcome(grid, canonical, None, target, bands, None)
-        weights = tuple(self.weights)
+        f.exchange_interval, f.keep = int(run.exchange_interval), (index_scratch, messages)
         _lib.check(_lib.lib.lsf_slab_run_finish(
             ctypes.byref(run), native, ctypes.byref(self.params), ctypes.c_void_p(p_lists),
             ctypes.c_void_p(p_lists + 4 * n_interior), ctypes.c_void_p(index_scratch.data_ptr()),
-            ctypes.c_void_p(messages.data_ptr() if messages is not None else 0), ctypes.c_void_p(records.data_ptr()),
-            iterations, dev._ptr(target, n, "live_out"), ctypes.c_void_p(words.data_ptr()),
-            ctypes.c_void_p(words_host.data_ptr()), ctypes.byref(result), stream), "lsf_slab_run_finish")
-        f.compact_faces = int(result.compact_faces)
-        if result.compact_faces == 0 and messages is not None:
+            ctypes.c_void_p(messages.data_ptr() if messages is not None else 0), ctypes.c_void_p(c.records.data_ptr()),
+            iterations, dev._ptr(c.target, n, "live_out"), ctypes.c_void_p(c.words.data_ptr()),
+            ctypes.c_void_p(c.words_host.data_ptr()), ctypes.byref(c.result), stream), "lsf_slab_run_finish")
+        f.compact_faces = int(c.result.compact_faces)
+        if c.result.compact_faces == 0 and messages is not None:
             import warnings
             warnings.warn("slab halos are not consistent with the neighbours' slabs (band voxel counts differ): whole "
                           "slices are exchanged")
         self._fast = f
-        n_exec = iterations if executed.all() else int(executed.sum())
+        n_exec = len(c.executed) if c.executed.all() else int(c.executed.sum())
         # every EXECUTED iteration must have stayed inside what the halo schedule keeps valid: one slice inside an exchange
         # group, the halo width with an exchange per iteration.  Every rank decoded the same gathered records, so the raise
         # is collective; optimize() restores the caller's tensor and runs the call again on a wider slab
         reach = 1 if run.exchange_interval > 1 else L.halo
-        if n_exec > 0 and not (max_value[:n_exec].max() < reach):
-            raise _HaloTooNarrow(float(max_value[:n_exec].max()), reach)
-        self.iteration_count = n_exec
-        self.log = _RunLog(max_value[:n_exec], argmax[:n_exec], energies[:n_exec], weights)
-        self._gradient_state = ("recompute_listed", states[(n_exec - 1) % 2], canonical, whole, bands)
-        outcome.state = states[n_exec % 2]
-        return outcome
+        if n_exec > 0 and not (c.max_value[:n_exec].max() < reach):
+            raise _HaloTooNarrow(float(c.max_value[:n_exec].max()), reach)
+        return c.leave(c.whole, n_exec=n_exec)
 
     def _optimize_widened(self, live, canonical, max_update):
-        import copy
         import math
         from .slab import SlabComm, SlabLayout
         L = self.comm.layout
@@ -565,11 +518,7 @@ class SlabMixin:
                 w.narrow(ax, L2.begin, L2.end - L2.begin).copy_(t.narrow(ax, L.begin, L.end - L.begin))
                 wide.append(w)
             comm2.exchange_halos(wide)
-            clone = copy.copy(self)
-            clone.comm = comm2
-            clone._exchange_every_iteration = True
-            for cached in ("_faces_verified", "_cut_chunk_cache", "_fast"):
-                clone.__dict__.pop(cached, None)
+            clone = self._widened_engine(comm2)
             try:
                 outcome = clone._optimize(wide[0], wide[1], None)
                 break
@@ -579,9 +528,31 @@ class SlabMixin:
         self.iteration_count, self.log, self.last_call = clone.iteration_count, clone.log, clone.last_call
         off = L2.halo_lo - L.halo_lo
         window = slice(off, off + L.nz_local)
-        self._gradient_state = ("wide", clone, window, ax)
+        # the call was re-run on a wider internal slab: its gradient, cut to this slab's slices
+        def cut():
+            g = clone.gradient_field()
+            return None if g is None else g.narrow(1 + ax, window.start, window.stop - window.start).contiguous()
+        self._gradient_state = _Lazy(cut)
         grid = self._grid(live)
         if outcome.state is not None:
             return SlavchevaOutcome(grid, canonical, state=outcome.state.narrow(ax, off, L.n_local).contiguous())
         return SlavchevaOutcome(grid, canonical, live=outcome.live().narrow(ax, off, L.n_local).contiguous(),
                                 warp_planar=outcome.warp_planar().narrow(1 + ax, off, L.n_local).contiguous())
+
+    # what a wider re-run shares with the engine it stands in for: the settings and parameters (the options among them)
+    # and the transport's device resources, which hold nothing of a call
+    _SHARED = ("direct", "sobolev", "sobolev_kernel", "cumulative_warp", "params", "weights", "lo", "hi", "max_iterations",
+               "min_iterations", "check_interval", "sparse_disabled", "iteration_hook", "focus_voxels",
+               "_comm_stream", "_events", "_plan_stream", "_no_face") + tuple(engine_options.SLAVCHEVA_DEFAULTS)
+
+    def _widened_engine(self, comm):
+        """the engine of a wider re-run on `comm`: _SHARED and every engine option are this engine's; everything a call
+        leaves or caches (_declare_call_state: _fast, the gradient sources, the cut-chunk and gradient-buffer caches)
+        starts fresh, and the faces travel every iteration"""
+        wide = object.__new__(type(self))
+        wide._declare_call_state()
+        for name in self._SHARED:
+            setattr(wide, name, getattr(self, name))
+        wide.comm = comm
+        wide._exchange_every_iteration = True
+        return wide

@@ -1,16 +1,18 @@
 """The SobolevFusion iteration (gradient, zero-preserving separable filter, update + re-warp:
-slavcheva_optimizer2d.py:163-236 with math_utils/convolution.py:114-132): the launch plan on the float4 layouts (band
-lists / boxes of a whole volume) and the planar-field iteration z-slabs and list-less runs keep."""
+slavcheva_optimizer2d.py:163-236 with math_utils/convolution.py:114-132) as the launch-by-launch call's iteration
+objects: the launch plan on the float4 layouts (band lists / boxes of a whole volume) and the planar-field iteration
+z-slabs and list-less runs keep."""
 import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, device as dev
-from .engine_common import _conv_axis_order
+from .engine_common import _Lazy, _conv_axis_order
+from .engine_outcome import SlavchevaOutcome, _StateIteration
 
 
-class _SobolevStatePlan:
+class _SobolevStatePlan(_StateIteration):
     """launch arguments of the SobolevFusion iteration on the float4 layouts (lsf_sobolev_state.hip), materialised once per
     optimize() call: iteration i reads states[i % 2] and writes the other; g4 = [raw gradient, filter buffer A, filter
     buffer B] (float4, zero-initialised: unlisted voxels are never written).  3-D: gradient -> raw, x pass raw -> A,
@@ -143,26 +145,63 @@ class _SobolevStatePlan:
         g4 = self.g4[self.final]
         return g4[..., :dims].movedim(-1, 0).contiguous()
 
+    def after(self, i):
+        """iteration i has run: the warp it left and its filtered gradient, planar"""
+        return self.inputs(i + 1)[1], self.final_gradient_planar(self.grid.dims)
+
+    def gradient_source(self, n_exec):
+        # the gradient buffers rotate identically every iteration, so the last executed iteration's filtered gradient is
+        # in the buffer the (gated, skipped) later launches would have used too
+        return _Lazy(lambda: self.final_gradient_planar(self.grid.dims))  # made planar on demand
 
 
-class PlanarSobolevMixin:
-    """SlavchevaEngine's iteration on PLANAR fields (z-slabs, filters of other lengths, list-less runs)"""
 
-    def _enqueue_iteration(self, i, live_in, live_out, warp_in, warp_out, canonical, grid, records, gbufs, limit):
+class _PlanarIteration:
+    """SlavchevaEngine's iteration on PLANAR fields (z-slabs, filters of other lengths, list-less runs): two (live, warp)
+    sets in ping-pong, iteration i reads set i % 2 and writes the other, and three gradient buffers"""
+
+    restore = None  # (no early finalize pass)
+
+    def __init__(self, engine, live, canonical, grid, records, limit):
+        self.engine, self.canonical, self.grid, self.records, self.limit = engine, canonical, grid, records, limit
+        self.lives = [live.clone(), live.clone()]
+        self.warps = [torch.zeros((grid.dims,) + tuple(live.shape), dtype=torch.float32, device=live.device)
+                      for _ in range(2)]
+        self.gbufs = [torch.zeros_like(self.warps[0]) for _ in range(3)]
+        self.last_g = None
+        # Band list: the gradient is zero outside the narrow band and the zero-preserving filter keeps it there
+        # (math_utils/convolution.py:118-127), so gradient, filter passes and update visit band voxels only; the
+        # zero-initialised g buffers and the two (live, 0) sets hold everything else.  z-slab runs list the whole
+        # local array (the x / y passes also run on the halo slices) and cut the owned part out of that list: it
+        # is sorted, so the owned slices are one contiguous run of it.
+        self.band = self.band_owned = None
+        if engine.use_band_list and len(engine.sobolev_kernel) in dev.LISTED_TAP_COUNTS:
+            b = self.band = dev.band_list(live, canonical, dev.full_range(grid), _lib.BAND_ALL)
+            if engine._slab():
+                slice_voxels = grid.ny * grid.nx
+                keys = torch.tensor([grid.z_begin * slice_voxels, grid.z_end * slice_voxels], dtype=torch.int32,
+                                    device=live.device)
+                lo, hi = torch.searchsorted(b.indices[:b.count], keys).tolist() if b.count else (0, 0)
+                self.band_owned = dev.BandList(b.indices[lo:hi] if hi > lo else b.indices[:1], hi - lo, b.subset)
+
+    def enqueue(self, i):
         """Sobolev path (planar fields): gradient kernel, zero-preserving separable filter, update + re-warp"""
-        gate = self._gate_for(records, i)
-        slab = self._slab()
-        g0, t1, t2 = gbufs
-        band = self._sobolev_band  # None: every voxel
+        e, grid, records, canonical = self.engine, self.grid, self.records, self.canonical
+        live_in, live_out, warp_in, warp_out = self.lives[i % 2], self.lives[(i + 1) % 2], self.warps[i % 2], \
+            self.warps[(i + 1) % 2]
+        gate = e._gate_for(records, i)
+        slab = e._slab()
+        g0, t1, t2 = self.gbufs
+        band = self.band  # None: every voxel
         # z-slab: the list of the WHOLE local array serves the x / y passes (they also run on the halo slices), its owned
         # part everything else
-        band_own = self._sobolev_band_owned if slab and band is not None else band
-        dev.slavcheva_gradient(live_in, canonical, warp_in, g0, grid, self.params, gate, records, i, band_own)
+        band_own = self.band_owned if slab and band is not None else band
+        dev.slavcheva_gradient(live_in, canonical, warp_in, g0, grid, e.params, gate, records, i, band_own)
         in_plane_grid = grid
         if slab:
             # the z pass of the filter reads len(kernel)//2 slices of the (x,y)-filtered field on either
             # side: exchange the raw gradient's halo once and run the x and y passes on the halo slices too
-            self.comm.exchange_halos([g0])
+            e.comm.exchange_halos([g0])
             in_plane_grid = dev.make_grid(live_in.shape, 0, grid.nz, grid.z_global_offset)
         src, dst = g0, t1
         axes = _conv_axis_order(grid.dims)
@@ -170,20 +209,39 @@ class PlanarSobolevMixin:
         # all its update needs): four launches per iteration instead of five
         fuse_last = band is not None
         for axis in axes[:-1] if fuse_last else axes:
-            dev.convolve_axis(src, dst, g0, grid if axis == 2 else in_plane_grid, axis, self.sobolev_kernel,
+            dev.convolve_axis(src, dst, g0, grid if axis == 2 else in_plane_grid, axis, e.sobolev_kernel,
                               gate, band_own if axis == 2 else band)
             src, dst = dst, (t2 if dst is t1 else t1)
         if fuse_last:
             axis = axes[-1]
             dev.slavcheva_filter_update_rewarp(src, g0, live_in, dst, warp_out, live_out,
-                                               grid if axis == 2 else in_plane_grid, self.params, axis,
-                                               self.sobolev_kernel, gate, records, i, band_own if axis == 2 else band)
+                                               grid if axis == 2 else in_plane_grid, e.params, axis,
+                                               e.sobolev_kernel, gate, records, i, band_own if axis == 2 else band)
             src = dst
         else:
-            dev.slavcheva_update_rewarp(live_in, canonical, src, warp_out, live_out, grid, self.params, gate,
+            dev.slavcheva_update_rewarp(live_in, canonical, src, warp_out, live_out, grid, e.params, gate,
                                         records, i, band_own)
-        self._last_g = src
+        self.last_g = src
         if slab:
-            self.comm.exchange_live_and_warp(live_out, warp_out)
-            if i + 1 < limit and i + 1 >= self.min_iterations:
-                self.comm.reduce_max(records, i)  # the next iteration's gate tests this record: make it global now
+            e.comm.exchange_live_and_warp(live_out, warp_out)
+            if i + 1 < self.limit and i + 1 >= e.min_iterations:
+                e.comm.reduce_max(records, i)  # the next iteration's gate tests this record: make it global now
+
+    def inputs(self, i):
+        """planar (live, warp) iteration i started from"""
+        return self.lives[i % 2], self.warps[i % 2]
+
+    def after(self, i):
+        """iteration i has run: the warp it left and its filtered gradient, planar"""
+        return self.warps[(i + 1) % 2], self.last_g
+
+    def finalize_early(self, finalize, records, limit, sparse_reach):
+        """(the planar finalize pass runs when the outcome is asked for it)"""
+
+    def outcome(self, n_exec, limit):
+        return SlavchevaOutcome(self.grid, self.canonical, live=self.lives[n_exec % 2],
+                                warp_planar=self.warps[n_exec % 2])
+
+    def gradient_source(self, n_exec):
+        g = self.last_g
+        return _Lazy(lambda: g)

@@ -43,14 +43,15 @@ print("pattern %s: band voxels in the %d boundary slices of the lower / upper fa
 print("transport:", "native RCCL (lsf_slab_state_iteration)" if comm.native() is not None else "torch.distributed",
       flush=True)
 from levelsetfusion_python_amd.engine import SlavchevaEngine
-_orig = SlavchevaEngine._enqueue_state_iteration
+from levelsetfusion_python_amd.engine_slavcheva import _FusedIteration
+_orig = _FusedIteration.enqueue
 _host = [0.0, 0]
 def _timed(self, *a, **k):
     t = time.perf_counter()
     _orig(self, *a, **k)
     _host[0] += time.perf_counter() - t
     _host[1] += 1
-SlavchevaEngine._enqueue_state_iteration = _timed
+_FusedIteration.enqueue = _timed
 _plan = {}
 def _wrap_plan(name):
     fn = getattr(SlavchevaEngine, name)
@@ -119,7 +120,7 @@ for rep in range(int(os.environ.get("REPS", "6"))):
             _f = opt.engine._fast
             print("    %s: library_run %s, exchange interval %d, compact faces %s" % (
                 name, opt.engine.last_call.library_run, _f.exchange_interval,
-                getattr(_f, "compact_faces", getattr(_f, "faces_ref", None) is not None)), flush=True)
+                _f.compact_faces if _f.compact_faces is not None else _f.faces_ref is not None), flush=True)
             if getattr(_f, "faces", None) is not None:
                 print("    compact faces: send %s / recv %s band voxels = %s / %s bytes per exchange (whole faces: 2 x %d bytes)"
                       % (list(_f.faces.send_count), list(_f.faces.recv_count), [16 * int(c) for c in _f.faces.send_count],
