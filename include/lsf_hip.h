@@ -1934,6 +1934,68 @@ int lsf_reloc_query(const float *coarse, const int32_t *locations, const uint8_t
                     uint8_t *codes, int32_t *n_keyframes, uint8_t *frame_code, int32_t *distances, int32_t *record,
                     const lsf_reloc_params *params, void *stream);
 
+/* ---- mesh simplification: welding and vertex-clustering decimation of a triangle mesh ----------------------------------
+ * The reference has no mesh at all; the contract is this project's ("Mesh simplification";
+ * tests/mesh_simplify_restatement.py restates it).  Vertices are grouped by a key -- the three bit patterns of the
+ * position with -0 read as +0 (weld), or the cell floor((p - origin) / cell_size) of a lattice (cluster) --, every group
+ * becomes one vertex, the faces are remapped, and faces that collapse, fold onto each other or repeat are dropped.
+ * Groups are found with an open-addressing hash table claimed by integer compare-and-swap; every sum is an integer
+ * atomic, so no output depends on which lane wins a slot or on the order lanes run in: a rerun, and a run with another
+ * table_slots, is bit-identical.  A call is lsf_mesh_simplify_count, one host read of the record, then
+ * lsf_mesh_simplify_emit into outputs of exactly the record's sizes.  Every probe loop ends after table_slots steps.
+ * Workspaces (DEVICE, the caller's, uninitialised; V = vertex_count, F = face_count, blocks(n) = ceil(n /
+ * LSF_MESH_SIMPLIFY_TILE), K = 3 * (cluster + has_normals + has_colours)):
+ *   table          int32 [table_slots]                          the hash table, used for the vertices, then the faces
+ *   vertex_work    int32 [LSF_MESH_SIMPLIFY_VERTEX_WORDS][V]    key (3 planes, [V][3]), slot, cluster id
+ *   cluster_work   int32 [LSF_MESH_SIMPLIFY_CLUSTER_WORDS][V]   members, used, first member, output index
+ *   sums           int64 [V][K]                                 per cluster: sum q (cluster), sum m (normals), sum c
+ *   face_work      int32 [LSF_MESH_SIMPLIFY_FACE_WORDS][F]      sorted ids (3 planes, [F][3]), state, net, first + / -
+ *   tile_offsets   int32 [3 * blocks(V) + 3 * blocks(F)]        the three scans' tile counts, then exclusive offsets,
+ *                                                               and the tiles' statistics words */
+typedef struct lsf_mesh_simplify_params {
+    double cell_size;                    /* cluster: the lattice edge, finite and > 0; weld: not read */
+    double origin_x, origin_y, origin_z; /* the lattice origin, finite; weld: not read */
+    int32_t vertex_count, face_count;    /* V and F, each 0 .. LSF_MESH_SIMPLIFY_MAX_ITEMS */
+    int32_t table_slots;                 /* a power of two, >= 2 * max(V, F, 1) */
+    int32_t cluster;                     /* 0: weld by bit pattern; 1: cluster by lattice cell */
+    int32_t has_normals, has_colours;    /* 0 or 1: whether normals / colours are given and produced */
+} lsf_mesh_simplify_params;
+#define LSF_MESH_SIMPLIFY_TILE 256
+#define LSF_MESH_SIMPLIFY_SCAN_THREADS 256
+#define LSF_MESH_SIMPLIFY_MAX_ITEMS (1 << 29)
+#define LSF_MESH_SIMPLIFY_VERTEX_WORDS 5
+#define LSF_MESH_SIMPLIFY_CLUSTER_WORDS 4
+#define LSF_MESH_SIMPLIFY_FACE_WORDS 7
+/* the record, DEVICE int64 [LSF_MESH_SIMPLIFY_RECORD_WORDS]: vertices_in, faces_in, invalid_vertices, invalid_faces,
+ * clusters, degenerate_faces, face_groups, cancelled_groups, multi_cover_groups, orphan_clusters, vertices_out,
+ * faces_out, table_overflow */
+#define LSF_MESH_SIMPLIFY_RECORD_WORDS 13
+
+/* vertices: DEVICE float32 [V][3]; faces: DEVICE int32 [F][3], any values (an index outside [0, V) makes the face
+ * invalid; it is checked before any gather); normals: DEVICE float32 [V][3] with has_normals, else NULL; colours: DEVICE
+ * uint8 [V][3] with has_colours, else NULL; all read only.  Writes the workspaces and the record.  Six fills and thirteen
+ * launches at most, no host wait.  Refused with LSF_ERR_BAD_ARGUMENT: a NULL where a size is not 0, a count outside its
+ * range, a table_slots that is not a power of two or is below 2 * max(V, F, 1), a flag that is not 0 or 1, normals or
+ * colours against their flag, in cluster mode a cell_size that is not finite and > 0 or an origin that is not finite,
+ * any overlap. */
+int lsf_mesh_simplify_count(const float *vertices, const int32_t *faces, const float *normals, const uint8_t *colours,
+                            int32_t *table, int32_t *vertex_work, int32_t *cluster_work, int64_t *sums,
+                            int32_t *face_work, int32_t *tile_offsets, int64_t *record,
+                            const lsf_mesh_simplify_params *params, void *stream);
+
+/* After lsf_mesh_simplify_count on the same inputs, workspaces and params, with clusters, vertices_out and faces_out the
+ * record's.  out_vertices: DEVICE float32 [vertices_out][3]; out_normals: DEVICE float32 [vertices_out][3] with
+ * has_normals, else NULL; out_colours: DEVICE uint8 [vertices_out][3] with has_colours, else NULL; out_faces: DEVICE int32
+ * [faces_out][3].  Two launches at most, none when vertices_out is 0.  Refused: what lsf_mesh_simplify_count refuses,
+ * clusters outside 0 .. V, vertices_out outside 0 .. clusters, faces_out outside 0 .. F, faces without vertices, a NULL
+ * output of a size that is not 0, any overlap. */
+int lsf_mesh_simplify_emit(const float *vertices, const int32_t *faces, const int32_t *vertex_work,
+                           int32_t *cluster_work,
+                           const int64_t *sums, const int32_t *face_work, const int32_t *tile_offsets,
+                           float *out_vertices, float *out_normals, uint8_t *out_colours, int32_t *out_faces,
+                           int64_t clusters, int64_t vertices_out, int64_t faces_out,
+                           const lsf_mesh_simplify_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

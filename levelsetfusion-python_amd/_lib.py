@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "7b9c31a7c45631ef"
+HEADER_ABI_HASH = "422afce346ce66e8"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -254,6 +254,25 @@ class MeshParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("voxel_size", "offset_x", "offset_y", "offset_z", "iso",
                                                "min_weight")] + \
                [(n, ctypes.c_int32) for n in ("depth", "height", "width")]
+
+
+MESH_SIMPLIFY_TILE = 256
+MESH_SIMPLIFY_SCAN_THREADS = 256
+MESH_SIMPLIFY_MAX_ITEMS = 1 << 29
+MESH_SIMPLIFY_VERTEX_WORDS = 5
+MESH_SIMPLIFY_CLUSTER_WORDS = 4
+MESH_SIMPLIFY_FACE_WORDS = 7
+MESH_SIMPLIFY_RECORD_FIELDS = ("vertices_in", "faces_in", "invalid_vertices", "invalid_faces", "clusters",
+                               "degenerate_faces", "face_groups", "cancelled_groups", "multi_cover_groups",
+                               "orphan_clusters", "vertices_out", "faces_out", "table_overflow")
+MESH_SIMPLIFY_RECORD_WORDS = len(MESH_SIMPLIFY_RECORD_FIELDS)
+
+
+class MeshSimplifyParams(ctypes.Structure):
+    """lsf_mesh_simplify_params: welding and vertex clustering of a mesh (lsf_mesh_simplify_count, _emit)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("cell_size", "origin_x", "origin_y", "origin_z")] + \
+               [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "table_slots", "cluster", "has_normals",
+                                              "has_colours")]
 
 
 class VolumeShiftParams(ctypes.Structure):
@@ -558,6 +577,8 @@ PROTOTYPES = {
     "lsf_mesh_emit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _P(MeshParams), _vp]),
     "lsf_mesh_vertex_colours": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int32, _P(MeshParams), _vp]),
+    "lsf_mesh_simplify_count": (ctypes.c_int, [_vp] * 11 + [_P(MeshSimplifyParams), _vp]),
+    "lsf_mesh_simplify_emit": (ctypes.c_int, [_vp] * 11 + [_i64, _i64, _i64, _P(MeshSimplifyParams), _vp]),
     "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
     "lsf_volume_bricks_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(VolumeBricksParams), _vp]),
     "lsf_volume_bricks_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,

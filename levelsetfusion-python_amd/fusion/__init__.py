@@ -40,6 +40,24 @@ corners have weight > min_weight, with a generated case table whose meshes are w
 ("Mesh extraction"; tests/mesh_restatement.py restates it).  It is five launches of
 csrc/lsf_mesh.hip with one host read of the vertex and face totals between the counting and the emitting launches;
 mesh_io.write_ply writes the result.  SequenceFusion3d.extract_mesh passes the sequence's array_offset and voxel_size.
+simplify_mesh(mesh, cell_size=None, origin=(0, 0, 0)) welds or decimates a mesh in that layout (INTEGRATION.md section 3,
+"Mesh simplification"; tests/mesh_simplify_restatement.py restates it; csrc/lsf_mesh_simplify.hip): vertices are grouped
+by a key -- the bit patterns of the position with -0 read as +0 (cell_size None: welding), or the cell
+floor((p - origin) / cell_size) of a lattice, at most 2^20 cells from the origin (vertex clustering) -- and the groups
+are numbered by their first member.  A group becomes one vertex: the first member's bits when welding, else the centre
+of the members' 2^-24-cell quantisation bins, float32(origin + cell_size (c + (sum q + n / 2) / (n 2^24))), within
+cell_size 2^-25 of their mean, so a cluster of one does not promise its member's bits back; its normal is the
+normalised integer sum of the members' normals scaled by 2^30, its colour the rounded integer mean.  Faces are remapped;
+one with two equal ids is dropped; the rest are grouped by their sorted ids, a face counting +1 when it is a rotation
+of the sorted triple and -1 otherwise: a group whose signs cancel is dropped whole (a flap), any other keeps its first
+face of the majority orientation.  Clusters no surviving face uses are removed.  Orders are the inputs' and every sum
+is an integer sum, so the result does not depend on how the lanes ran: groups are found with a hash table claimed by
+compare-and-swap, never by a sort.  A non-finite vertex or a face index outside the vertices raises ValueError after
+the one host read, that of the 13-word record (return_record=True returns it).  merge_meshes(..., weld=True),
+CanonicalVolume.extract_mesh(..., simplify_cell=) and SequenceFusion3d.extract_mesh(..., simplify_cell=, weld=) go
+through it -- simplify_cell in metres on the lattice through the world origin; weld, with include_streamed and a window
+that streams, makes one vertex of the seam vertices the merged chunks hold once each, before any clustering -- and
+every keyword defaults to the call as it was.  Cost: profiles/mesh_simplify_cost.md.
 
 SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
 first tracked, started from the previous frame's twist, as `tracking_reference` chooses: by the 6-DoF rigid tracker
@@ -147,7 +165,8 @@ world point is float32((float64(v) + array_offset) * voxel_size), so a retained 
 later fusion is the one a fixed volume would have made there.  With the policy's stream_mesh the cells that leave are
 meshed first -- at most three boxes, each through extract_mesh's kernels with their host read -- and appended to
 `streamed_meshes` as host tuples; extract_mesh(include_streamed=True) is merge_meshes of the window's mesh and those
-chunks.  Every cell is drawn exactly once; the vertices on a seam appear on both sides, and since the window goes on
+chunks.  Every cell is drawn exactly once; the vertices on a seam appear on both sides (weld=True makes one of
+those whose bits agree: simplify_mesh above), and since the window goes on
 fusing the layer a chunk was cut along, later frames can open hairline cracks there (Kintinuous has the same property).
 The frame record gains "shift" and "streamed_faces", only with a moving_volume.  The shift sits between frames, so it
 combines with every tracking mode and every non-rigid setting; `warp` and `prediction` remain the last frame's, in the
@@ -201,7 +220,8 @@ Host synchronisations per frame: the rigid run's or the ICP run's one copy back 
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
-vertex and face totals.  A moving volume's policy adds none (the twist is on the host already); a shift that streams
+vertex and face totals; simplify_cell= and weld= add one each, the read of the simplification's record.  A moving
+volume's policy adds none (the twist is on the host already); a shift that streams
 costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
 store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
 bricks to the card.  A sensor adds none per frame (its record is read with the fusion record's wait); its first frame
@@ -224,9 +244,11 @@ a minimum-weight gate and a per-voxel weight on the pairs, an adaptive ray-casti
 image in the prediction, for the RGB-D sensor fisheye and thin-prism lens models, registering colour into the depth
 camera, hole filling, time synchronisation of the two streams, rolling shutter and the reference's XML calibration
 files, marching squares for 2-D models, vertex attributes beyond normals and
-colours, welding vertices by position, decimation, a mesh extracted without the host read of its totals, for the
+colours, for mesh simplification quadric-error placement of the new vertices, a target face count, welding within a
+tolerance across seams that later frames have moved and per-face attributes, a mesh extracted without the host read of
+its totals, for the
 relocaliser relocalising inside a moving window, saving the keyframe database, loop closure and a learned quality
-test, and for the moving volume welding across seams, a shift enqueued without the mesh totals' host read, and for its
+test, and for the moving volume a shift enqueued without the mesh totals' host read, and for its
 brick store saving the store to disk, streaming without the host read of the brick total, and bricks in half
 precision."""
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
@@ -234,6 +256,7 @@ from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_
 from .brick_store import BrickStore
 from .canonical_volume import CanonicalVolume
 from .depth_confidence import DepthConfidence
+from .mesh_simplify import simplify_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality
 from .rgbd_sensor import RgbdSensor
@@ -241,7 +264,7 @@ from .sequence import DIRECT_TRACKING_MODES, TRACKING_MODES, TRACKING_REFERENCES
 
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "RgbdSensor",
            "Relocaliser", "TrackingQuality",
-           "merge_meshes",
+           "merge_meshes", "simplify_mesh",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",

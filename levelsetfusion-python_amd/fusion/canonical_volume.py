@@ -5,7 +5,8 @@ import math
 import numpy as np
 import torch
 
-from .. import device_fusion, device_mesh, device_raycast, device_volume_bricks, device_volume_shift
+from .. import (device_fusion, device_mesh, device_mesh_simplify, device_raycast, device_volume_bricks,
+                device_volume_shift)
 from ..device_core import require_gpu
 from ..rigid_opt.frame_tracker import device_colour_image
 from ..tsdf.generation import device_depth, offsets_of
@@ -39,6 +40,16 @@ def _on_device(x, name, dtype, move=True):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
+def simplified(out, normals, colours, simplify_cell):
+    """device_mesh.extract_mesh's tuple clustered by the lattice of edge simplify_cell through the origin (None: as it
+    is), with the normals and colours that were asked for, and the record or None"""
+    if simplify_cell is None:
+        return out, None
+    v, f, n, c, record = device_mesh_simplify.simplify(out[0], out[1], out[2] if normals else None,
+                                                       out[3] if colours else None, simplify_cell)
+    return ((v, f, n, c) if colours else (v, f, n)), record
+
+
 def mesh_outputs(out, normals, colours, as_tensor=False):
     """of device_mesh.extract_mesh's (vertices, faces, normals[, colours]) the ones asked for, in that order: the
     device tensors with as_tensor, numpy copies otherwise"""
@@ -63,6 +74,7 @@ class CanonicalVolume:
         self.colour = torch.zeros(self.shape + (4,), dtype=torch.float32, device="cuda") if colour else None
         self._spare = None  # shift: the buffers the next shifted copy is written to
         self._bricks = None  # shift(brick_store=): the flags, offsets and total of the brick count, kept like _spare
+        self.mesh_record = None  # extract_mesh(simplify_cell=): the last simplification's record
 
     def reset(self):
         """back to the empty model: tsdf 1, weight 0 everywhere (and a colour volume 0)"""
@@ -123,20 +135,24 @@ class CanonicalVolume:
         return out if normals or colours else out[0]
 
     def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False,
-                     colours=False, default_colour=device_mesh.DEFAULT_COLOUR):
+                     colours=False, default_colour=device_mesh.DEFAULT_COLOUR, simplify_cell=None):
         """the level set iso of the model as a triangle mesh, with raycast's conventions (voxel (i, j, k) at
         ((k, j, i) + array_offset) * voxel_size): float32 vertices (V, 3) in world metres, (x, y, z); int32 faces
         (F, 3), their right-hand normal towards larger tsdf; with normals=True also the float32 unit normals (V, 3).
         Only cells whose 8 corners have weight > min_weight draw.  Returns (vertices, faces) or (vertices, faces,
         normals): device tensors with as_tensor=True, numpy copies otherwise.  With colours=True (a volume made with
         colour=True) the uint8 vertex colours (V, 3) are appended, row i the colour of vertex i, default_colour where
-        neither end of the vertex's grid edge has a colour.  One host synchronisation: the read of the two totals."""
+        neither end of the vertex's grid edge has a colour.  One host synchronisation: the read of the two totals.
+        simplify_cell (metres) passes the mesh through vertex clustering on the lattice of that edge through the world
+        origin before it is returned -- simplify_mesh(extract_mesh(...), simplify_cell) without the copies -- for one
+        more host synchronisation, the read of its record, which `mesh_record` keeps."""
         if len(self.shape) != 3:
             raise ValueError("mesh extraction needs a 3-D model, this one has shape %s" % (self.shape,))
         if colours and self.colour is None:
             raise ValueError("colours=True needs a volume made with colour=True")
         out = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso, min_weight, normals,
                                        *((self.colour, default_colour) if colours else ()))
+        out, self.mesh_record = simplified(out, normals, colours, simplify_cell)
         return mesh_outputs(out, normals, colours, as_tensor)
 
     def _leaving_mesh(self, box, array_offset, voxel_size, min_weight, normals, colours):

@@ -58,22 +58,25 @@ class MovingVolume:
 
 
 def _mesh_layout(mesh):
-    """(with normals, with colours) of a host mesh tuple in extract_mesh's layout: (V, F), (V, F, N), (V, F, C) or
-    (V, F, N, C), C being uint8"""
+    """(with normals, with colours) of a mesh tuple in extract_mesh's layout, host arrays or tensors: (V, F), (V, F, N),
+    (V, F, C) or (V, F, N, C), C being uint8"""
     if not isinstance(mesh, (tuple, list)) or not 2 <= len(mesh) <= 4:
         raise ValueError("a mesh is a tuple (vertices, faces[, normals][, colours])")
-    extras = [np.asarray(a) for a in mesh[2:]]
-    coloured = bool(extras) and extras[-1].dtype == np.uint8
+    extras = [a if hasattr(a, "dtype") else np.asarray(a) for a in mesh[2:]]
+    coloured = bool(extras) and str(extras[-1].dtype).split(".")[-1] == "uint8"  # numpy's or torch's
     with_normals = len(extras) - int(coloured) == 1
     if len(extras) - int(coloured) not in (0, 1):
         raise ValueError("a mesh is a tuple (vertices, faces[, normals][, colours])")
     return with_normals, coloured
 
 
-def merge_meshes(meshes):
+def merge_meshes(meshes, weld=False):
     """the concatenation of host meshes in extract_mesh's layout (numpy tuples (vertices, faces[, normals][, colours])):
     vertices, normals and colours stacked in order, every mesh's face indices offset by the vertices before it.
-    Nothing is welded.  Meshes of different layouts are refused, and so is an empty list: it has no layout."""
+    Without weld nothing is welded: a seam's vertices appear once per mesh.  With weld the concatenation goes through
+    simplify_mesh on the device, which makes one vertex of the vertices whose positions are equal bit for bit (package
+    docstring, "Mesh simplification").  Meshes of different layouts are refused, and so is an empty list: it has no
+    layout."""
     meshes = list(meshes)
     if not meshes:
         raise ValueError("merge_meshes needs at least one mesh")
@@ -89,4 +92,7 @@ def merge_meshes(meshes):
            np.concatenate([np.asarray(m[1], dtype=np.int32).reshape(-1, 3) + b for m, b in zip(meshes, bases)])]
     for j in range(2, len(meshes[0])):
         out.append(np.concatenate([np.asarray(m[j]).reshape(-1, 3) for m in meshes]))
+    if weld:
+        from .mesh_simplify import simplify_mesh
+        return simplify_mesh(tuple(out))
     return tuple(out)

@@ -16,8 +16,9 @@ from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_reco
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 from .brick_store import BrickStore
-from .canonical_volume import CanonicalVolume, mesh_outputs
+from .canonical_volume import CanonicalVolume, mesh_outputs, simplified
 from .depth_confidence import DepthConfidence
+from .mesh_simplify import simplify_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality, level_stride
 from .rgbd_sensor import RgbdSensor
@@ -154,6 +155,7 @@ class SequenceFusion3d:
         self.field_shape, self.array_offset = field_shape, array_offset
         self.initial_array_offset = self.array_offset.copy()  # a moving_volume moves array_offset; this one stays
         self.streamed_meshes = []  # a moving_volume with stream_mesh: the host meshes of the cells that left
+        self.mesh_records = dict(weld=None, simplify=None)  # extract_mesh(weld=, simplify_cell=): the last call's
         # a moving_volume with keep_tsdf: the bricks that left, written back when the window re-enters them
         self.brick_store = BrickStore(colour=bool(colour)) if moving_volume is not None and moving_volume.keep_tsdf \
             else None
@@ -405,24 +407,35 @@ class SequenceFusion3d:
         return frame
 
     def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False, colours=False,
-                     default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False):
+                     default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False, simplify_cell=None, weld=False):
         """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size.  With
         include_streamed (a sequence made with a moving_volume that streams) the window's mesh is followed by the
         streamed chunks, merge_meshes of them all: host arrays only, and only as the chunks were made -- iso 0, the
         policy's min_weight and normals, colours exactly when the sequence has colour, the default default_colour;
         anything else raises, since the chunks cannot be drawn again.  With a moving_volume that has keep_tsdf,
         include_streamed meshes CanonicalVolume.assemble of the window and the brick store instead: one mesh of the
-        whole map without seams, at the caller's iso, min_weight, normals and colours, as tensors too"""
-        if not include_streamed:
-            return self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
-                                               colours, default_colour)
+        whole map without seams, at the caller's iso, min_weight, normals and colours, as tensors too.
+        simplify_cell (metres, lattice through the world origin) clusters the result's vertices, on every path.  weld
+        (only with include_streamed and a moving_volume that streams: nothing else has seams) first makes one vertex of
+        the seam vertices that the merged chunks hold once each; `mesh_records` keeps the records of the last call,
+        {"weld": ..., "simplify": ...}, None where a step did not run"""
+        self.mesh_records = dict(weld=None, simplify=None)
         mv = self.moving_volume
+        if weld and not (include_streamed and mv is not None and mv.stream_mesh):
+            raise ValueError("weld=True needs include_streamed=True and a moving_volume that has stream_mesh=True: no "
+                             "other mesh has seams")
+        if not include_streamed:
+            out = self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
+                                              colours, default_colour, simplify_cell)
+            self.mesh_records["simplify"] = self.canonical.mesh_record
+            return out
         if mv is not None and mv.keep_tsdf:
             if colours and not self.colour:
                 raise ValueError("colours=True needs a sequence made with colour=True")
             tsdf, weight, colour, offset = self.canonical.assemble(self.brick_store, self.array_offset)
             out = device_mesh.extract_mesh(tsdf, weight, offset, self.voxel_size, iso, min_weight, normals,
                                            *((colour, default_colour) if colours else ()))
+            out, self.mesh_records["simplify"] = simplified(out, normals, colours, simplify_cell)
             return mesh_outputs(out, normals, colours, as_tensor)
         if mv is None or not mv.stream_mesh:
             raise ValueError("include_streamed needs a sequence made with a moving_volume that has stream_mesh=True")
@@ -435,4 +448,9 @@ class SequenceFusion3d:
                              % (mv.min_weight, mv.normals, self.colour))
         window = self.canonical.extract_mesh(self.array_offset, self.voxel_size, 0.0, mv.min_weight, mv.normals, False,
                                              self.colour)
-        return merge_meshes([window] + self.streamed_meshes)
+        merged = merge_meshes([window] + self.streamed_meshes)
+        if weld:
+            *merged, self.mesh_records["weld"] = simplify_mesh(merged, return_record=True)
+        if simplify_cell is not None:
+            *merged, self.mesh_records["simplify"] = simplify_mesh(tuple(merged), simplify_cell, return_record=True)
+        return tuple(merged)
