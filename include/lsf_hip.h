@@ -1996,6 +1996,57 @@ int lsf_mesh_simplify_emit(const float *vertices, const int32_t *faces, const in
                            int64_t clusters, int64_t vertices_out, int64_t faces_out,
                            const lsf_mesh_simplify_params *params, void *stream);
 
+/* ---- Euclidean distance field: the exact, capped distance transform of the model's zero crossing ------------------------
+ * The reference has no distance transform; the contract is this project's ("Euclidean distance
+ * field"; tests/esdf_restatement.py restates it).  observed(v): weight(v) > min_weight.  inside(v): observed and
+ * tsdf(v) < iso.  site(v): observed, and some in-bounds 6-neighbour is observed with the other inside flag; with
+ * unknown = LSF_ESDF_UNKNOWN_OCCUPIED every voxel that is not observed is a site too.  key(v) = min over the sites s of
+ * (|v - s|^2, flat(s)), compared lexicographically, flat(s) = (z Y + y) X + x.  With R = max_distance_voxels:
+ *   distance2   the key's first part where it is <= R^2, else LSF_ESDF_FAR
+ *   nearest     the key's second part, -1 where distance2 is LSF_ESDF_FAR
+ *   esdf        sign * (sqrtf((float)distance2) * (float)voxel_size), (float)R in place of the root where distance2 is
+ *               LSF_ESDF_FAR; sign is -1 where inside(v), else +1
+ * The key is separable: a pass along x (which also finds the sites), one along y, one along z, each a partial minimum
+ * within R of the voxel, integers throughout.  No output depends on the launch shape: a rerun is bit-identical.
+ * Every launch walks a grid capped at LSF_ESDF_MAX_BLOCKS workgroups with a stride loop behind it: the x pass a row
+ * (z, y) per wave, LSF_ESDF_BLOCK_ROWS rows per workgroup, the y and z passes a voxel per lane, LSF_ESDF_BLOCK_VOXELS
+ * per workgroup.  Every loop is bounded by the volume's extents and by R. */
+typedef struct lsf_esdf_params {
+    double voxel_size;           /* metres, finite and > 0; rounded to float32 before the one multiply */
+    float iso, min_weight;       /* not NaN */
+    int32_t depth, height, width; /* Z, Y, X: each >= 1, Z Y X <= 2^31 - 1 */
+    int32_t max_distance_voxels; /* R: 1 .. LSF_ESDF_MAX_DISTANCE */
+    int32_t unknown;             /* LSF_ESDF_UNKNOWN_FREE or LSF_ESDF_UNKNOWN_OCCUPIED */
+    int32_t passes;              /* which launches the call enqueues, in order x, y, z: LSF_ESDF_PASSES_ALL, or for
+                                    measurement any non-empty subset, over the scratch a full call left */
+} lsf_esdf_params;
+#define LSF_ESDF_UNKNOWN_FREE 0
+#define LSF_ESDF_UNKNOWN_OCCUPIED 1
+#define LSF_ESDF_PASS_X 1
+#define LSF_ESDF_PASS_Y 2
+#define LSF_ESDF_PASS_Z 4
+#define LSF_ESDF_PASSES_ALL 7
+#define LSF_ESDF_MAX_DISTANCE 4096
+#define LSF_ESDF_FAR 0x7fffffff
+#define LSF_ESDF_MAX_BLOCKS 2048
+#define LSF_ESDF_BLOCK_ROWS 4
+#define LSF_ESDF_BLOCK_VOXELS 256
+/* the record, DEVICE int64 [LSF_ESDF_RECORD_WORDS]: sites, finite (voxels whose distance2 is not LSF_ESDF_FAR),
+ * max_distance2 (the largest such distance2; 0 when there is none).  Exact counts. */
+#define LSF_ESDF_RECORD_WORDS 3
+
+/* tsdf, weight: DEVICE float32 [Z][Y][X], read only.  scratch_a, scratch_b: DEVICE int32 [Z][Y][X], the caller's,
+ * uninitialised (the x pass leaves each voxel's signed offset to its row's nearest site in scratch_b, the y pass the
+ * packed offsets within the plane in scratch_a).  distance2, nearest: DEVICE int32 [Z][Y][X]; esdf: DEVICE float32
+ * [Z][Y][X]; record as above.  One fill (the record, zeroed by every call), then at most three launches;
+ * no host wait.  Refused with LSF_ERR_BAD_ARGUMENT before anything is launched: a NULL pointer, a dimension < 1, R outside
+ * 1 .. LSF_ESDF_MAX_DISTANCE, a voxel_size that is not finite and > 0, a NaN iso or min_weight, an unknown code other than
+ * the two, passes outside 1 .. LSF_ESDF_PASSES_ALL, a buffer off 4-byte (the record: 8-byte) alignment, any overlap
+ * between an output or scratch buffer and any other buffer; with LSF_ERR_BAD_DIMS: more than 2^31 - 1 voxels. */
+int lsf_esdf_compute(const float *tsdf, const float *weight, int32_t *scratch_a, int32_t *scratch_b,
+                     int32_t *distance2, int32_t *nearest, float *esdf, int64_t *record,
+                     const lsf_esdf_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

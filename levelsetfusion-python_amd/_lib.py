@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "422afce346ce66e8"
+HEADER_ABI_HASH = "52ab3f057a6bf65c"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -273,6 +273,23 @@ class MeshSimplifyParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("cell_size", "origin_x", "origin_y", "origin_z")] + \
                [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "table_slots", "cluster", "has_normals",
                                               "has_colours")]
+
+
+ESDF_UNKNOWN = {"free": 0, "occupied": 1}
+ESDF_PASS_X, ESDF_PASS_Y, ESDF_PASS_Z, ESDF_PASSES_ALL = 1, 2, 4, 7
+ESDF_MAX_DISTANCE = 4096
+ESDF_FAR = 0x7fffffff
+ESDF_MAX_BLOCKS = 2048
+ESDF_BLOCK_ROWS = 4
+ESDF_BLOCK_VOXELS = 256
+ESDF_RECORD_FIELDS = ("sites", "finite", "max_distance2")
+ESDF_RECORD_WORDS = len(ESDF_RECORD_FIELDS)
+
+
+class EsdfParams(ctypes.Structure):
+    """lsf_esdf_params: the Euclidean distance field of the model (lsf_esdf_compute)"""
+    _fields_ = [("voxel_size", ctypes.c_double), ("iso", ctypes.c_float), ("min_weight", ctypes.c_float)] + \
+               [(n, ctypes.c_int32) for n in ("depth", "height", "width", "max_distance_voxels", "unknown", "passes")]
 
 
 class VolumeShiftParams(ctypes.Structure):
@@ -579,6 +596,7 @@ PROTOTYPES = {
                                                ctypes.c_int32, _P(MeshParams), _vp]),
     "lsf_mesh_simplify_count": (ctypes.c_int, [_vp] * 11 + [_P(MeshSimplifyParams), _vp]),
     "lsf_mesh_simplify_emit": (ctypes.c_int, [_vp] * 11 + [_i64, _i64, _i64, _P(MeshSimplifyParams), _vp]),
+    "lsf_esdf_compute": (ctypes.c_int, [_vp] * 8 + [_P(EsdfParams), _vp]),
     "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
     "lsf_volume_bricks_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(VolumeBricksParams), _vp]),
     "lsf_volume_bricks_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,

@@ -58,6 +58,23 @@ CanonicalVolume.extract_mesh(..., simplify_cell=) and SequenceFusion3d.extract_m
 through it -- simplify_cell in metres on the lattice through the world origin; weld, with include_streamed and a window
 that streams, makes one vertex of the seam vertices the merged chunks hold once each, before any clustering -- and
 every keyword defaults to the call as it was.  Cost: profiles/mesh_simplify_cost.md.
+CanonicalVolume.esdf(voxel_size, max_distance_voxels=32, iso=0, min_weight=0, unknown="free", nearest=False) answers
+"how far is this voxel from the nearest surface?", which the model's own values do not: they are projective distances
+along the pixel's ray, truncated at +-1 (INTEGRATION.md section 3, "Euclidean distance field";
+tests/esdf_restatement.py restates it; csrc/lsf_esdf.hip).  A voxel is observed when weight > min_weight and inside when
+it is observed with tsdf < iso; a site is an observed voxel with an in-bounds observed 6-neighbour of the other inside
+flag, so both sides of every zero crossing between observed voxels are sites, and with unknown="occupied" every voxel
+that is not observed is a site too.  key(v) = min over the sites s of (|v - s|^2, flat(s)), lexicographic, with the
+integer squared lattice distance and flat(s) = (z Y + y) X + x: ties go to the smallest flat index, so the result is a
+function of the inputs alone.  distance2 is the key's first part where it is <= max_distance_voxels^2 (inclusive), else
+2^31 - 1; nearest its second part, else -1; esdf = sign * (sqrtf(float(distance2)) * float(voxel_size)) in metres, with
+float(max_distance_voxels) in place of the root beyond the cap, sign -1 where the voxel is inside and +1 elsewhere --
+also where it was never observed under unknown="free": `weight` masks those if the caller wants that.  The key is
+separable, so the kernels are a pass along x (which also finds the sites), one along y and one along z, integers
+throughout, and equal the restatement's brute force exactly.  A model without a site gives the cap everywhere and is
+no error.  `last_esdf_record` keeps {"sites", "finite", "max_distance2"}; brick_store= / array_offset= give the field
+of assemble()'s whole map, and SequenceFusion3d.esdf(include_streamed=True) passes its own.  One host synchronisation,
+the read of the record.  Cost: profiles/esdf_cost.md.
 
 SequenceFusion3d runs a depth sequence.  Frame 0 is fused under `initial_twist` (zero by default).  Every later frame is
 first tracked, started from the previous frame's twist, as `tracking_reference` chooses: by the 6-DoF rigid tracker
@@ -246,11 +263,14 @@ camera, hole filling, time synchronisation of the two streams, rolling shutter a
 files, marching squares for 2-D models, vertex attributes beyond normals and
 colours, for mesh simplification quadric-error placement of the new vertices, a target face count, welding within a
 tolerance across seams that later frames have moved and per-face attributes, a mesh extracted without the host read of
-its totals, for the
+its totals, for the Euclidean distance field an incremental update after a fusion or a shift, a 2-D slice call,
+sub-voxel site positions, z-slab and multi-GPU volumes and feeding the trackers or the level-set term from the field,
+for the
 relocaliser relocalising inside a moving window, saving the keyframe database, loop closure and a learned quality
 test, and for the moving volume a shift enqueued without the mesh totals' host read, and for its
 brick store saving the store to disk, streaming without the host read of the brick total, and bricks in half
 precision."""
+from ..device_esdf import RECORD_FIELDS as ESDF_RECORD_FIELDS, unpack_record as unpack_esdf_record
 from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_FIELDS, WEIGHTED_RECORD_FIELDS,
                              unpack_colour_record, unpack_record, unpack_warped_record, unpack_weighted_record)
 from .brick_store import BrickStore
@@ -267,5 +287,5 @@ __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolu
            "merge_meshes", "simplify_mesh",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
-           "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS",
+           "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS", "ESDF_RECORD_FIELDS", "unpack_esdf_record",
            "TRACKING_REFERENCES", "TRACKING_MODES", "DIRECT_TRACKING_MODES"]

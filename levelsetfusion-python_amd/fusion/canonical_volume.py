@@ -5,7 +5,7 @@ import math
 import numpy as np
 import torch
 
-from .. import (device_fusion, device_mesh, device_mesh_simplify, device_raycast, device_volume_bricks,
+from .. import (device_esdf, device_fusion, device_mesh, device_mesh_simplify, device_raycast, device_volume_bricks,
                 device_volume_shift)
 from ..device_core import require_gpu
 from ..rigid_opt.frame_tracker import device_colour_image
@@ -75,6 +75,9 @@ class CanonicalVolume:
         self._spare = None  # shift: the buffers the next shifted copy is written to
         self._bricks = None  # shift(brick_store=): the flags, offsets and total of the brick count, kept like _spare
         self.mesh_record = None  # extract_mesh(simplify_cell=): the last simplification's record
+        self._esdf = None  # esdf: the scratch volumes and the record's buffer, kept like _spare
+        self.last_esdf_record = None  # esdf: the last call's record
+        self.last_esdf_offset = None  # esdf(brick_store=): the array offset of the box the last field covers
 
     def reset(self):
         """back to the empty model: tsdf 1, weight 0 everywhere (and a colour volume 0)"""
@@ -154,6 +157,40 @@ class CanonicalVolume:
                                        *((self.colour, default_colour) if colours else ()))
         out, self.mesh_record = simplified(out, normals, colours, simplify_cell)
         return mesh_outputs(out, normals, colours, as_tensor)
+
+    def esdf(self, voxel_size=0.004, max_distance_voxels=32, iso=0.0, min_weight=0.0, unknown="free", nearest=False,
+             as_tensor=False, brick_store=None, array_offset=None, max_voxels=2 ** 28):
+        """the Euclidean signed distance field of the model (package docstring, "Euclidean distance field"): float32
+        (Z, Y, X) in metres, the distance from each voxel's centre to the centre of the nearest site -- an observed
+        voxel (weight > min_weight) with an observed 6-neighbour on the other side of iso -- negative where the voxel
+        itself is observed with tsdf < iso, and +-max_distance_voxels * voxel_size where no site lies within
+        max_distance_voxels (1 .. 4096; the cap is inclusive).  unknown="free" leaves voxels that were never observed
+        out of the sites: they carry a positive distance like free space, and `weight` masks them if the caller wants
+        that; unknown="occupied" makes every one of them a site.  With nearest=True returns (esdf, nearest), nearest the
+        int32 flat index (z Y + y) X + x of that site, the smallest among equally near ones, -1 beyond the cap.
+        Device tensors with as_tensor=True, numpy copies otherwise.  `last_esdf_record` keeps {"sites", "finite",
+        "max_distance2"}: the sites, the voxels within the cap and the largest squared lattice distance among them.
+        One host synchronisation: the read of that record.  With brick_store and the window's array_offset the field
+        is that of `assemble(brick_store, array_offset, max_voxels)`, window and store, over the lattice box of the
+        two, whose array offset `last_esdf_offset` keeps (None otherwise); assemble's refusals apply."""
+        if len(self.shape) != 3:
+            raise ValueError("a distance field needs a 3-D model, this one has shape %s" % (self.shape,))
+        if (brick_store is None) != (array_offset is None):
+            raise ValueError("brick_store and array_offset go together: the store's lattice is placed by the window's "
+                             "array_offset")
+        device_esdf.params(self.shape, voxel_size, max_distance_voxels, iso, min_weight, unknown)  # before any device work
+        tsdf, weight, worker, self.last_esdf_offset = self.tsdf, self.weight, self._esdf, None
+        if brick_store is not None:
+            tsdf, weight, _, self.last_esdf_offset = self.assemble(brick_store, array_offset, max_voxels)
+            worker = device_esdf.Esdf()  # the box is another shape: its scratch does not outlive the call
+        elif worker is None:
+            worker = self._esdf = device_esdf.Esdf()
+        field, _, site, self.last_esdf_record = worker.compute(tsdf, weight, voxel_size, max_distance_voxels, iso,
+                                                               min_weight, unknown)
+        out = (field, site) if nearest else (field,)
+        if not as_tensor:
+            out = tuple(t.cpu().numpy() for t in out)
+        return out if nearest else out[0]
 
     def _leaving_mesh(self, box, array_offset, voxel_size, min_weight, normals, colours):
         """the host mesh of one box of leaving cells ((x0, x1), (y0, y1), (z0, z1)): extract_mesh of a contiguous copy

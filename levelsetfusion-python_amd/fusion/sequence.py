@@ -156,6 +156,7 @@ class SequenceFusion3d:
         self.initial_array_offset = self.array_offset.copy()  # a moving_volume moves array_offset; this one stays
         self.streamed_meshes = []  # a moving_volume with stream_mesh: the host meshes of the cells that left
         self.mesh_records = dict(weld=None, simplify=None)  # extract_mesh(weld=, simplify_cell=): the last call's
+        self.last_esdf_record = self.last_esdf_offset = None  # esdf: the last call's record and its field's array offset
         # a moving_volume with keep_tsdf: the bricks that left, written back when the window re-enters them
         self.brick_store = BrickStore(colour=bool(colour)) if moving_volume is not None and moving_volume.keep_tsdf \
             else None
@@ -454,3 +455,21 @@ class SequenceFusion3d:
         if simplify_cell is not None:
             *merged, self.mesh_records["simplify"] = simplify_mesh(tuple(merged), simplify_cell, return_record=True)
         return tuple(merged)
+
+    def esdf(self, max_distance_voxels=32, iso=0.0, min_weight=0.0, unknown="free", nearest=False, as_tensor=False,
+             include_streamed=False):
+        """CanonicalVolume.esdf of the model with the sequence's voxel_size: the Euclidean signed distance field in
+        metres, or (esdf, nearest).  With include_streamed (a sequence made with a moving_volume that has keep_tsdf)
+        it is the field of CanonicalVolume.assemble of the window and the brick store, the whole map, and
+        `last_esdf_offset` is that box's array offset; without it `last_esdf_offset` is the window's array_offset.
+        `last_esdf_record` is the call's record"""
+        mv = self.moving_volume
+        if include_streamed and (mv is None or not mv.keep_tsdf):
+            raise ValueError("include_streamed needs a sequence made with a moving_volume that has keep_tsdf=True: only a "
+                             "brick store keeps the values that left the window")
+        store = dict(brick_store=self.brick_store, array_offset=self.array_offset) if include_streamed else {}
+        out = self.canonical.esdf(self.voxel_size, max_distance_voxels, iso, min_weight, unknown, nearest, as_tensor,
+                                  **store)
+        self.last_esdf_record = self.canonical.last_esdf_record
+        self.last_esdf_offset = self.canonical.last_esdf_offset if include_streamed else self.array_offset.copy()
+        return out
