@@ -1996,6 +1996,86 @@ int lsf_mesh_simplify_emit(const float *vertices, const int32_t *faces, const in
                            int64_t clusters, int64_t vertices_out, int64_t faces_out,
                            const lsf_mesh_simplify_params *params, void *stream);
 
+/* ---- mesh components: connected components of a triangle mesh, and the filter that removes components ------------------
+ * The reference has no mesh at all; the contract is this project's ("Mesh components";
+ * tests/mesh_components_restatement.py restates it).  Two vertices are connected when some face names both (a degenerate
+ * face still connects what it names); a component is a connected set of vertices, a vertex no face names is one of its
+ * own with 0 faces.  A component's label is the smallest vertex index in it, a face's label the label of its first
+ * vertex: the answer is a function of the mesh alone.  The table lists the C components in ascending label order with
+ * their vertex and face counts and bounds, the componentwise minimum and maximum of the members' positions (-0 read as
+ * +0).  The filter keeps the vertices and faces of the components whose row of keep[] is not 0, in input order, faces
+ * re-indexed, normals and colours carried bit for bit.
+ * Labels come from a lock-free union-find over parent[V] with integer atomics only: a root is linked under a smaller
+ * index of the other set by compare-and-swap, so a parent is always a strictly smaller index, every walk is strictly
+ * decreasing and the final root is the component's minimum, whichever lane wins.  Inside the linking launch every read
+ * of parent[] is a device-scope atomic load or the value a failed compare-and-swap returned.  Every walk and every retry
+ * loop ends after V + 1 steps at the latest (a walk takes at most V, and a compare-and-swap fails only because one of the
+ * at most V - 1 links succeeded); a lane that gets there adds to the record's step_cap and stops.  Counts and bounds are
+ * integer atomics (the bounds through an order-preserving image of the float bits), rows and kept items come from scans
+ * over index order: a rerun, and a run with another max_blocks, is bit-identical.
+ * A call is lsf_mesh_components_label, a host read of the record (components), then lsf_mesh_components_table into
+ * outputs of exactly that size; the filter goes on with lsf_mesh_components_select, a second host read of the record
+ * (vertices_out, faces_out) and lsf_mesh_components_emit into outputs of exactly those sizes.
+ * Every launch but the one-workgroup scans walks tiles of LSF_MESH_COMPONENTS_TILE items on a grid of at most max_blocks
+ * workgroups with a stride loop behind it; the scan workgroup of LSF_MESH_COMPONENTS_SCAN_THREADS lanes loops over the
+ * tile counts.
+ * Workspaces (DEVICE, the caller's, uninitialised; V = vertex_count, F = face_count, tiles(n) = ceil(n /
+ * LSF_MESH_COMPONENTS_TILE)):
+ *   vertex_work    int32 [LSF_MESH_COMPONENTS_VERTEX_WORDS][V]   parent, label, and indexed by label: vertex count, face
+ *                                                                count, bounds images (3 minima, 3 maxima), table row;
+ *                                                                then the output index of the vertex
+ *   tile_offsets   int32 [3 * tiles(V) + tiles(F)]               the scans' tile counts, then exclusive offsets */
+typedef struct lsf_mesh_components_params {
+    int32_t vertex_count, face_count; /* V and F, each 0 .. LSF_MESH_COMPONENTS_MAX_ITEMS */
+    int32_t has_normals, has_colours; /* 0 or 1: whether lsf_mesh_components_emit carries normals / colours */
+    int32_t max_blocks;               /* the cap of every grid, 1 .. LSF_MESH_COMPONENTS_MAX_BLOCKS; 0: that maximum.
+                                         No output depends on it */
+} lsf_mesh_components_params;
+#define LSF_MESH_COMPONENTS_TILE 256
+#define LSF_MESH_COMPONENTS_SCAN_THREADS 256
+#define LSF_MESH_COMPONENTS_MAX_BLOCKS 512
+#define LSF_MESH_COMPONENTS_MAX_ITEMS (1 << 29)
+#define LSF_MESH_COMPONENTS_VERTEX_WORDS 12
+/* the record, DEVICE int64 [LSF_MESH_COMPONENTS_RECORD_WORDS]: vertices_in, faces_in, invalid_vertices (a non-finite
+ * coordinate), invalid_faces (an index outside [0, V)), components, step_cap (lanes that met a step cap: never, by the
+ * argument above), and written by lsf_mesh_components_select: components_kept, vertices_out, faces_out */
+#define LSF_MESH_COMPONENTS_RECORD_WORDS 9
+
+/* vertices: DEVICE float32 [V][3]; faces: DEVICE int32 [F][3], any values (a face with an index outside [0, V) is counted
+ * before any gather and links nothing); both read only.  Writes the workspaces and the record (components_kept,
+ * vertices_out and faces_out as 0).  Seven launches at most, no fill, no host wait.  A caller refuses the mesh when the
+ * record counts an invalid vertex or face, and treats step_cap != 0 as an error.  Refused with LSF_ERR_BAD_ARGUMENT: a
+ * NULL where a size is not 0, a count outside its range, max_blocks outside its range, a flag that is not 0 or 1, a buffer
+ * off 4-byte (the record: 8-byte) alignment, any overlap. */
+int lsf_mesh_components_label(const float *vertices, const int32_t *faces, int32_t *vertex_work, int32_t *tile_offsets,
+                              int64_t *record, const lsf_mesh_components_params *params, void *stream);
+
+/* After lsf_mesh_components_label on the same faces, vertex_work and params, with components the record's.  labels,
+ * vertex_counts, face_counts: DEVICE int32 [components]; bounds: DEVICE float32 [components][2][3] (minimum, maximum);
+ * face_labels: DEVICE int32 [F].  The vertex labels are plane 1 of vertex_work.  Two launches at most.  Refused: what
+ * lsf_mesh_components_label refuses, components outside 0 .. V or 0 with V > 0. */
+int lsf_mesh_components_table(const int32_t *faces, const int32_t *vertex_work, int32_t *labels, int32_t *vertex_counts,
+                              int32_t *face_counts, float *bounds, int32_t *face_labels, int64_t components,
+                              const lsf_mesh_components_params *params, void *stream);
+
+/* After lsf_mesh_components_label likewise.  keep: DEVICE int32 [components], not 0 where the component of that row of
+ * the table stays; read only.  Counts the kept components, vertices and faces into the record and leaves the kept items'
+ * tile offsets in tile_offsets.  One fill and four launches at most, no host wait.  Refused: as above. */
+int lsf_mesh_components_select(const int32_t *faces, const int32_t *vertex_work, const int32_t *keep,
+                               int32_t *tile_offsets, int64_t *record, int64_t components,
+                               const lsf_mesh_components_params *params, void *stream);
+
+/* After lsf_mesh_components_select on the same inputs, workspaces, keep and params, with vertices_out and faces_out the
+ * record's.  normals: DEVICE float32 [V][3] with has_normals, else NULL; colours: DEVICE uint8 [V][3] with has_colours,
+ * else NULL.  out_vertices: DEVICE float32 [vertices_out][3]; out_normals, out_colours likewise with their flags, else
+ * NULL; out_faces: DEVICE int32 [faces_out][3].  Two launches at most, none when vertices_out is 0.  Refused: as above,
+ * vertices_out outside 0 .. V, faces_out outside 0 .. F, faces without vertices, normals or colours against their flag. */
+int lsf_mesh_components_emit(const float *vertices, const int32_t *faces, const float *normals, const uint8_t *colours,
+                             int32_t *vertex_work, const int32_t *keep, const int32_t *tile_offsets,
+                             float *out_vertices, float *out_normals, uint8_t *out_colours, int32_t *out_faces,
+                             int64_t components, int64_t vertices_out, int64_t faces_out,
+                             const lsf_mesh_components_params *params, void *stream);
+
 /* ---- Euclidean distance field: the exact, capped distance transform of the model's zero crossing ------------------------
  * The reference has no distance transform; the contract is this project's ("Euclidean distance
  * field"; tests/esdf_restatement.py restates it).  observed(v): weight(v) > min_weight.  inside(v): observed and

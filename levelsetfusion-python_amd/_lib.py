@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "52ab3f057a6bf65c"
+HEADER_ABI_HASH = "5acbbd3dbae5873f"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -273,6 +273,22 @@ class MeshSimplifyParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("cell_size", "origin_x", "origin_y", "origin_z")] + \
                [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "table_slots", "cluster", "has_normals",
                                               "has_colours")]
+
+
+MESH_COMPONENTS_TILE = 256
+MESH_COMPONENTS_SCAN_THREADS = 256
+MESH_COMPONENTS_MAX_BLOCKS = 512
+MESH_COMPONENTS_MAX_ITEMS = 1 << 29
+MESH_COMPONENTS_VERTEX_WORDS = 12
+MESH_COMPONENTS_RECORD_FIELDS = ("vertices_in", "faces_in", "invalid_vertices", "invalid_faces", "components",
+                                 "step_cap", "components_kept", "vertices_out", "faces_out")
+MESH_COMPONENTS_RECORD_WORDS = len(MESH_COMPONENTS_RECORD_FIELDS)
+
+
+class MeshComponentsParams(ctypes.Structure):
+    """lsf_mesh_components_params: connected components of a mesh (lsf_mesh_components_label, _table, _select, _emit)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "has_normals", "has_colours",
+                                              "max_blocks")]
 
 
 ESDF_UNKNOWN = {"free": 0, "occupied": 1}
@@ -596,6 +612,10 @@ PROTOTYPES = {
                                                ctypes.c_int32, _P(MeshParams), _vp]),
     "lsf_mesh_simplify_count": (ctypes.c_int, [_vp] * 11 + [_P(MeshSimplifyParams), _vp]),
     "lsf_mesh_simplify_emit": (ctypes.c_int, [_vp] * 11 + [_i64, _i64, _i64, _P(MeshSimplifyParams), _vp]),
+    "lsf_mesh_components_label": (ctypes.c_int, [_vp] * 5 + [_P(MeshComponentsParams), _vp]),
+    "lsf_mesh_components_table": (ctypes.c_int, [_vp] * 7 + [_i64, _P(MeshComponentsParams), _vp]),
+    "lsf_mesh_components_select": (ctypes.c_int, [_vp] * 5 + [_i64, _P(MeshComponentsParams), _vp]),
+    "lsf_mesh_components_emit": (ctypes.c_int, [_vp] * 11 + [_i64, _i64, _i64, _P(MeshComponentsParams), _vp]),
     "lsf_esdf_compute": (ctypes.c_int, [_vp] * 8 + [_P(EsdfParams), _vp]),
     "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
     "lsf_volume_bricks_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(VolumeBricksParams), _vp]),

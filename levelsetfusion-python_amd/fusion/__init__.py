@@ -58,6 +58,31 @@ CanonicalVolume.extract_mesh(..., simplify_cell=) and SequenceFusion3d.extract_m
 through it -- simplify_cell in metres on the lattice through the world origin; weld, with include_streamed and a window
 that streams, makes one vertex of the seam vertices the merged chunks hold once each, before any clustering -- and
 every keyword defaults to the call as it was.  Cost: profiles/mesh_simplify_cost.md.
+mesh_components(mesh) labels the connected components of a mesh in that layout and filter_mesh_components(mesh,
+min_faces=None, min_vertices=None, min_extent=None, keep_largest=None) removes the ones one does not want: the floaters
+that noise, flying pixels and half-carved surfaces leave around a model fused from real depth (INTEGRATION.md section 3,
+"Mesh components"; tests/mesh_components_restatement.py restates it; csrc/lsf_mesh_components.hip).  Two vertices are
+connected when some face names both, and a component is a connected set of vertices; a degenerate face still connects
+what it names, and a vertex that no face names is a component of its own with 0 faces.  A component's label is the
+smallest vertex index in it and a face's label the label of its first vertex, so the answer is a function of the mesh
+alone, not of the launch shape or of the order in which lanes ran.  mesh_components returns (vertex_labels int32 (V,),
+face_labels int32 (F,), table), the table a dict of labels, vertex_counts, face_counts int32 (C,) and bounds float32
+(C, 2, 3) for the C components in ascending label order; the bounds are the componentwise minimum and maximum of the
+members' positions, exact, with -0 read as +0 as the weld does.  A component passes the filter when it meets every
+threshold that is given -- face count >= min_faces, vertex count >= min_vertices, the longest edge of its bounds >=
+min_extent, compared in float64 of the float32 bounds and so exactly --, and with keep_largest = k only the first k
+passing components stay, in the order face count descending, label ascending.  Kept vertices and kept faces keep their
+input order, faces are re-indexed, normals and colours are carried bit for bit; no criterion at all is a ValueError.  The
+labels come from a lock-free union-find with integer atomics: a root is linked under a smaller index by
+compare-and-swap, so every walk is strictly decreasing and the final root is the component's minimum; every loop ends
+after V + 1 steps at the latest, and a lane that ever got there would raise RuntimeError through the record.  A face
+index outside [0, V) or a non-finite vertex is counted on the card before any gather through it and raises ValueError
+after the first host read; mesh_components reads the 9-word record once (the number of components), the filter twice
+(then the sizes of its outputs; return_record=True returns it).  CanonicalVolume.extract_mesh(...,
+min_component_faces=, keep_largest_components=) and the same keywords of SequenceFusion3d.extract_mesh apply the filter
+last, after include_streamed, weld and simplify_cell, and add the record to mesh_record / mesh_records under
+"components"; with both None the calls are as they were.  An unwelded seam of streamed meshes splits a component, so
+weld=True is what one wants with them.  Cost: profiles/mesh_components_cost.md.
 CanonicalVolume.esdf(voxel_size, max_distance_voxels=32, iso=0, min_weight=0, unknown="free", nearest=False) answers
 "how far is this voxel from the nearest surface?", which the model's own values do not: they are projective distances
 along the pixel's ray, truncated at +-1 (INTEGRATION.md section 3, "Euclidean distance field";
@@ -237,7 +262,8 @@ Host synchronisations per frame: the rigid run's or the ICP run's one copy back 
 or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode it also brings the prediction's hit
 count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
-vertex and face totals; simplify_cell= and weld= add one each, the read of the simplification's record.  A moving
+vertex and face totals; simplify_cell= and weld= add one each, the read of the simplification's record, min_component_faces= /
+keep_largest_components= two, the reads of the components' record.  A moving
 volume's policy adds none (the twist is on the host already); a shift that streams
 costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
 store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
@@ -262,7 +288,8 @@ image in the prediction, for the RGB-D sensor fisheye and thin-prism lens models
 camera, hole filling, time synchronisation of the two streams, rolling shutter and the reference's XML calibration
 files, marching squares for 2-D models, vertex attributes beyond normals and
 colours, for mesh simplification quadric-error placement of the new vertices, a target face count, welding within a
-tolerance across seams that later frames have moved and per-face attributes, a mesh extracted without the host read of
+tolerance across seams that later frames have moved and per-face attributes, for mesh components edge-adjacency
+instead of vertex-adjacency, per-component area or volume and components of the volume itself, a mesh extracted without the host read of
 its totals, for the Euclidean distance field an incremental update after a fusion or a shift, a 2-D slice call,
 sub-voxel site positions, z-slab and multi-GPU volumes and feeding the trackers or the level-set term from the field,
 for the
@@ -276,6 +303,7 @@ from ..device_fusion import (COLOUR_RECORD_FIELDS, RECORD_FIELDS, WARPED_RECORD_
 from .brick_store import BrickStore
 from .canonical_volume import CanonicalVolume
 from .depth_confidence import DepthConfidence
+from .mesh_components import filter_mesh_components, mesh_components
 from .mesh_simplify import simplify_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality
@@ -284,7 +312,7 @@ from .sequence import DIRECT_TRACKING_MODES, TRACKING_MODES, TRACKING_REFERENCES
 
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "RgbdSensor",
            "Relocaliser", "TrackingQuality",
-           "merge_meshes", "simplify_mesh",
+           "merge_meshes", "simplify_mesh", "mesh_components", "filter_mesh_components",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS", "ESDF_RECORD_FIELDS", "unpack_esdf_record",

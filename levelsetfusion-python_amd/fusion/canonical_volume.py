@@ -5,7 +5,7 @@ import math
 import numpy as np
 import torch
 
-from .. import (device_esdf, device_fusion, device_mesh, device_mesh_simplify, device_raycast, device_volume_bricks,
+from .. import (device_esdf, device_fusion, device_mesh, device_mesh_components, device_mesh_simplify, device_raycast, device_volume_bricks,
                 device_volume_shift)
 from ..device_core import require_gpu
 from ..rigid_opt.frame_tracker import device_colour_image
@@ -47,6 +47,18 @@ def simplified(out, normals, colours, simplify_cell):
         return out, None
     v, f, n, c, record = device_mesh_simplify.simplify(out[0], out[1], out[2] if normals else None,
                                                        out[3] if colours else None, simplify_cell)
+    return ((v, f, n, c) if colours else (v, f, n)), record
+
+
+def components_filtered(out, normals, colours, min_component_faces, keep_largest_components):
+    """device_mesh.extract_mesh's tuple without the components of fewer than min_component_faces faces, and of the rest
+    only the keep_largest_components largest (both None: as it is), with the normals and colours that were asked for,
+    and the record or None"""
+    if min_component_faces is None and keep_largest_components is None:
+        return out, None
+    v, f, n, c, record = device_mesh_components.filter(out[0], out[1], out[2] if normals else None,
+                                                       out[3] if colours else None, min_faces=min_component_faces,
+                                                       keep_largest=keep_largest_components)
     return ((v, f, n, c) if colours else (v, f, n)), record
 
 
@@ -138,7 +150,8 @@ class CanonicalVolume:
         return out if normals or colours else out[0]
 
     def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False,
-                     colours=False, default_colour=device_mesh.DEFAULT_COLOUR, simplify_cell=None):
+                     colours=False, default_colour=device_mesh.DEFAULT_COLOUR, simplify_cell=None,
+                     min_component_faces=None, keep_largest_components=None):
         """the level set iso of the model as a triangle mesh, with raycast's conventions (voxel (i, j, k) at
         ((k, j, i) + array_offset) * voxel_size): float32 vertices (V, 3) in world metres, (x, y, z); int32 faces
         (F, 3), their right-hand normal towards larger tsdf; with normals=True also the float32 unit normals (V, 3).
@@ -148,7 +161,12 @@ class CanonicalVolume:
         neither end of the vertex's grid edge has a colour.  One host synchronisation: the read of the two totals.
         simplify_cell (metres) passes the mesh through vertex clustering on the lattice of that edge through the world
         origin before it is returned -- simplify_mesh(extract_mesh(...), simplify_cell) without the copies -- for one
-        more host synchronisation, the read of its record, which `mesh_record` keeps."""
+        more host synchronisation, the read of its record, which `mesh_record` keeps.
+        min_component_faces and keep_largest_components remove floaters last, after simplify_cell:
+        filter_mesh_components(mesh, min_faces=min_component_faces, keep_largest=keep_largest_components) without the
+        copies, for two more host synchronisations; `mesh_record` then is a dict that holds the simplification's fields,
+        if that ran, and the components' record under "components".  With both None the call and `mesh_record` are as
+        they were."""
         if len(self.shape) != 3:
             raise ValueError("mesh extraction needs a 3-D model, this one has shape %s" % (self.shape,))
         if colours and self.colour is None:
@@ -156,6 +174,9 @@ class CanonicalVolume:
         out = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso, min_weight, normals,
                                        *((self.colour, default_colour) if colours else ()))
         out, self.mesh_record = simplified(out, normals, colours, simplify_cell)
+        out, record = components_filtered(out, normals, colours, min_component_faces, keep_largest_components)
+        if record is not None:
+            self.mesh_record = dict(self.mesh_record or {}, components=record)
         return mesh_outputs(out, normals, colours, as_tensor)
 
     def esdf(self, voxel_size=0.004, max_distance_voxels=32, iso=0.0, min_weight=0.0, unknown="free", nearest=False,

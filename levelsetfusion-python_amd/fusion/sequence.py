@@ -16,8 +16,9 @@ from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_reco
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 from .brick_store import BrickStore
-from .canonical_volume import CanonicalVolume, mesh_outputs, simplified
+from .canonical_volume import CanonicalVolume, components_filtered, mesh_outputs, simplified
 from .depth_confidence import DepthConfidence
+from .mesh_components import filter_mesh_components
 from .mesh_simplify import simplify_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality, level_stride
@@ -408,7 +409,8 @@ class SequenceFusion3d:
         return frame
 
     def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False, colours=False,
-                     default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False, simplify_cell=None, weld=False):
+                     default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False, simplify_cell=None, weld=False,
+                     min_component_faces=None, keep_largest_components=None):
         """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size.  With
         include_streamed (a sequence made with a moving_volume that streams) the window's mesh is followed by the
         streamed chunks, merge_meshes of them all: host arrays only, and only as the chunks were made -- iso 0, the
@@ -419,16 +421,28 @@ class SequenceFusion3d:
         simplify_cell (metres, lattice through the world origin) clusters the result's vertices, on every path.  weld
         (only with include_streamed and a moving_volume that streams: nothing else has seams) first makes one vertex of
         the seam vertices that the merged chunks hold once each; `mesh_records` keeps the records of the last call,
-        {"weld": ..., "simplify": ...}, None where a step did not run"""
+        {"weld": ..., "simplify": ...}, None where a step did not run.  min_component_faces and
+        keep_largest_components remove floaters last, after include_streamed, weld and simplify_cell, on every path
+        (filter_mesh_components with min_faces and keep_largest); `mesh_records` then also has "components", that
+        step's record.  An unwelded seam of streamed meshes splits a component in two, so with include_streamed on a
+        moving_volume that streams meshes weld=True is what one wants with them."""
         self.mesh_records = dict(weld=None, simplify=None)
+        floaters = dict(min_faces=min_component_faces, keep_largest=keep_largest_components)
+        filtering = min_component_faces is not None or keep_largest_components is not None
         mv = self.moving_volume
         if weld and not (include_streamed and mv is not None and mv.stream_mesh):
             raise ValueError("weld=True needs include_streamed=True and a moving_volume that has stream_mesh=True: no "
                              "other mesh has seams")
         if not include_streamed:
             out = self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
-                                              colours, default_colour, simplify_cell)
-            self.mesh_records["simplify"] = self.canonical.mesh_record
+                                              colours, default_colour, simplify_cell, min_component_faces,
+                                              keep_largest_components)
+            record = self.canonical.mesh_record
+            if filtering:
+                record = dict(record)  # the volume keeps its own
+                self.mesh_records["components"] = record.pop("components")
+                record = record or None
+            self.mesh_records["simplify"] = record
             return out
         if mv is not None and mv.keep_tsdf:
             if colours and not self.colour:
@@ -437,6 +451,9 @@ class SequenceFusion3d:
             out = device_mesh.extract_mesh(tsdf, weight, offset, self.voxel_size, iso, min_weight, normals,
                                            *((colour, default_colour) if colours else ()))
             out, self.mesh_records["simplify"] = simplified(out, normals, colours, simplify_cell)
+            out, record = components_filtered(out, normals, colours, min_component_faces, keep_largest_components)
+            if filtering:
+                self.mesh_records["components"] = record
             return mesh_outputs(out, normals, colours, as_tensor)
         if mv is None or not mv.stream_mesh:
             raise ValueError("include_streamed needs a sequence made with a moving_volume that has stream_mesh=True")
@@ -454,6 +471,9 @@ class SequenceFusion3d:
             *merged, self.mesh_records["weld"] = simplify_mesh(merged, return_record=True)
         if simplify_cell is not None:
             *merged, self.mesh_records["simplify"] = simplify_mesh(tuple(merged), simplify_cell, return_record=True)
+        if filtering:
+            *merged, self.mesh_records["components"] = filter_mesh_components(tuple(merged), return_record=True,
+                                                                              **floaters)
         return tuple(merged)
 
     def esdf(self, max_distance_voxels=32, iso=0.0, min_weight=0.0, unknown="free", nearest=False, as_tensor=False,
