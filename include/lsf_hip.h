@@ -2076,6 +2076,95 @@ int lsf_mesh_components_emit(const float *vertices, const int32_t *faces, const 
                              int64_t components, int64_t vertices_out, int64_t faces_out,
                              const lsf_mesh_components_params *params, void *stream);
 
+/* ---- mesh smoothing: Taubin passes over the edge neighbours, and vertex normals rebuilt from the faces -------------------
+ * The reference has no mesh at all; the contract is this project's ("Mesh smoothing";
+ * tests/mesh_smooth_restatement.py restates it and the kernels equal it bit for bit at any launch shape and table size).
+ * Edges: every face contributes its corner pairs (0,1), (1,2), (2,0); a pair with equal ends is skipped, every other pair
+ * adds 1 to the face count of the undirected edge {a, b} (a face naming a vertex twice adds 2 to its one edge).  Two
+ * vertices are neighbours when an edge joins them; N(i) is the set of distinct neighbours, d(i) its size.
+ * Pinned: with boundary_fixed a vertex is pinned when it is an end of an edge whose face count is not 2 (open borders and
+ * non-manifold edges); otherwise none is.  A pinned vertex and a vertex with d = 0 keep their position bit for bit.
+ * One pass with weight w (lambda or mu, float64): B is the largest |coordinate| of the pass's input, by an integer maximum
+ * on the float bits; with E the exponent field of B's bits, e = max(E, 1) - 126 (B < 2^e, and B >= 2^(e-1) for a normal
+ * B), q = 2^(e-32), and q = 1 when B = 0.  Q(x) = (int64) rint(double(x) / q), ties to even, 0 for a non-finite x (q and
+ * 1 / q are powers of two and x / q stays a normal double, so the kernels multiply by 1 / q: the same bits).
+ * S_i = sum over j in N(i) of Q(p_j) per axis, in integers: no order of the sum can matter.
+ * m = (double(S_i) * q) / double(d(i));  p_i' = float32(double(p_i) + w * (m - double(p_i))), every float64 operation
+ * rounded on its own.  An iteration is a lambda pass, then a mu pass when mu != 0; positions are float32 between passes;
+ * each pass takes B from its own input, which the pass before leaves behind as a wave-reduced integer maximum.
+ * Vertex normals: for a face (a, b, c) with u = double(p_b) - double(p_a), v = double(p_c) - double(p_a) the vector
+ * c = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x), every operation rounded on its own (the right-hand normal,
+ * extract_mesh's "towards larger tsdf").  M is the largest |component| over all faces, by an integer maximum on the doubles'
+ * bits; with E the exponent field of M's bits, em = max(E, 1) - 1022 (M < 2^em), qn = 2^(em-32), and qn = 1 when M = 0.
+ * Every face adds (int64) rint(c / qn), 0 for a non-finite component, to its three vertices by integer atomics.  With S
+ * the float64 of a vertex's sums and L = sqrt((S_x^2 + S_y^2) + S_z^2) the normal is float32(S / L), and (0, 0, 0) when
+ * L = 0, which the record counts.
+ * Loops and their bounds: a probe walk of the edge table ends after table_slots steps (table_overflow counts a pair that
+ * found no slot: never, while table_slots >= 2 * 3F); a vertex's gather walks its row of d(i) <= 2E neighbours and never
+ * past the neighbour list's 6F words.  No float atomics, no inter-workgroup waits.  Every launch but the one-workgroup scan
+ * walks tiles of LSF_MESH_SMOOTH_TILE items on a grid of at most max_blocks workgroups with a stride loop behind it.
+ * Workspaces (DEVICE, the caller's, uninitialised; V = vertex_count, F = face_count, tiles(n) = ceil(n / LSF_MESH_SMOOTH_TILE)):
+ *   vertex_work   int32 [LSF_MESH_SMOOTH_VERTEX_WORDS][V]   degree, pinned, row offset, fill cursor
+ *   edge_keys     int64 [table_slots]                       the open-addressing table: (lo << 32) | hi, or -1
+ *   edge_counts   int32 [table_slots]                       faces per edge
+ *   tile_offsets  int32 [tiles(V)]                          the degree scan's tile counts, then exclusive offsets
+ *   neighbours    int32 [max(6F, 1)]                        the compressed-row neighbour list
+ *   scalars       int64 [LSF_MESH_SMOOTH_SCALAR_WORDS]      B's bits of the input, three rotating words for the passes'
+ *                                                           maxima, M's bits */
+typedef struct lsf_mesh_smooth_params {
+    int32_t vertex_count, face_count; /* V and F, each 0 .. LSF_MESH_SMOOTH_MAX_ITEMS */
+    int32_t table_slots;              /* a power of two, 2 * max(3F, 1) .. LSF_MESH_SMOOTH_MAX_SLOTS.  No output depends
+                                         on it */
+    int32_t boundary_fixed;           /* 0 or 1: whether the ends of an edge whose face count is not 2 are pinned */
+    int32_t fresh_record;             /* 0 or 1, lsf_mesh_vertex_normals only: 1 for a call on its own, which begins the
+                                         record and counts invalid vertices and faces; 0 after lsf_mesh_smooth_prepare,
+                                         whose record it keeps and completes */
+    int32_t iterations;               /* 0 .. LSF_MESH_SMOOTH_MAX_ITERATIONS */
+    int32_t max_blocks;               /* the cap of every grid, 1 .. LSF_MESH_SMOOTH_MAX_BLOCKS; 0: that maximum.  No
+                                         output depends on it */
+    int32_t reserved;                 /* 0 */
+    double lam, mu;                   /* lambda: finite, in (0, 1]; mu: finite, <= 0, and 0 leaves the mu passes out */
+} lsf_mesh_smooth_params;
+#define LSF_MESH_SMOOTH_TILE 256
+#define LSF_MESH_SMOOTH_SCAN_THREADS 256
+#define LSF_MESH_SMOOTH_MAX_BLOCKS 512
+#define LSF_MESH_SMOOTH_MAX_ITEMS (1 << 27)
+#define LSF_MESH_SMOOTH_MAX_SLOTS (1 << 30)
+#define LSF_MESH_SMOOTH_MAX_ITERATIONS 1000
+#define LSF_MESH_SMOOTH_VERTEX_WORDS 4
+#define LSF_MESH_SMOOTH_SCALAR_WORDS 5
+/* the record, DEVICE int64 [LSF_MESH_SMOOTH_RECORD_WORDS]: vertices_in, faces_in, invalid_vertices (a non-finite
+ * coordinate), invalid_faces (an index outside [0, V)), edges, boundary_edges (face count 1), nonmanifold_edges (face
+ * count > 2), pinned_vertices, isolated_vertices (d = 0), max_degree, table_overflow, and written by lsf_mesh_smooth_run:
+ * nonfinite_out (the non-finite coordinates the last pass wrote), by lsf_mesh_vertex_normals: zero_normals */
+#define LSF_MESH_SMOOTH_RECORD_WORDS 13
+
+/* vertices: DEVICE float32 [V][3]; faces: DEVICE int32 [F][3], any values (a face with an index outside [0, V) is counted
+ * before any gather and contributes no edge); both read only.  Writes every workspace and the whole record.  Two fills and
+ * eight launches at most, no host wait.  A caller refuses the mesh when the record counts an invalid vertex or face, and
+ * treats table_overflow != 0 as an error.  Refused with LSF_ERR_BAD_ARGUMENT, before any launch: a NULL where a size is not
+ * 0, a count, table_slots, iterations or max_blocks outside its range, a table_slots that is no power of two, a flag that
+ * is not 0 or 1, reserved not 0, lam or mu outside its range, a buffer off 4-byte (int64 buffers: 8-byte) alignment, any
+ * overlap. */
+int lsf_mesh_smooth_prepare(const float *vertices, const int32_t *faces, int32_t *vertex_work, int64_t *edge_keys,
+                            int32_t *edge_counts, int32_t *tile_offsets, int32_t *neighbours, int64_t *scalars,
+                            int64_t *record, const lsf_mesh_smooth_params *params, void *stream);
+
+/* After lsf_mesh_smooth_prepare on the same vertices, workspaces and params.  The passes run ping-pong between
+ * out_vertices and scratch (DEVICE float32 [V][3] each), the first reading vertices, the last writing out_vertices; one
+ * small launch and one launch per pass: iterations passes when mu = 0, else twice as many.  iterations = 0 copies the
+ * positions.  Writes the record's nonfinite_out.  Refused: as above. */
+int lsf_mesh_smooth_run(const float *vertices, const int32_t *vertex_work, const int32_t *neighbours, float *out_vertices,
+                        float *scratch, int64_t *scalars, int64_t *record, const lsf_mesh_smooth_params *params,
+                        void *stream);
+
+/* The area-weighted vertex normals of any mesh.  vertices, faces as above; sums: DEVICE int64 [V][3], a workspace;
+ * normals: DEVICE float32 [V][3].  One fill and four launches (five with fresh_record), none when V = 0 and the record is
+ * kept.  Writes the record's zero_normals, and with fresh_record the whole record (the smoothing's words as 0).
+ * Refused: as above. */
+int lsf_mesh_vertex_normals(const float *vertices, const int32_t *faces, int64_t *sums, float *normals, int64_t *scalars,
+                            int64_t *record, const lsf_mesh_smooth_params *params, void *stream);
+
 /* ---- Euclidean distance field: the exact, capped distance transform of the model's zero crossing ------------------------
  * The reference has no distance transform; the contract is this project's ("Euclidean distance
  * field"; tests/esdf_restatement.py restates it).  observed(v): weight(v) > min_weight.  inside(v): observed and

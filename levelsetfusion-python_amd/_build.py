@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(LIB_DIR, "liblsf_hip.so")
 SOURCES = ["lsf_fields.hip", "lsf_hierarchical.hip", "lsf_slavcheva.hip", "lsf_slavcheva_state.hip",
            "lsf_slavcheva_run.hip", "lsf_slavcheva_box.hip", "lsf_cumulative_warp.hip", "lsf_sobolev_state.hip", "lsf_sobolev_box.hip", "lsf_slab.hip", "lsf_tsdf.hip",
            "lsf_terms.hip", "lsf_rigid.hip", "lsf_rigid3d.hip", "lsf_fusion.hip",
-           "lsf_raycast.hip", "lsf_mesh.hip", "lsf_mesh_simplify.hip", "lsf_mesh_components.hip", "lsf_esdf.hip", "lsf_icp.hip", "lsf_depth_pyramid.hip", "lsf_depth_confidence.hip",
+           "lsf_raycast.hip", "lsf_mesh.hip", "lsf_mesh_simplify.hip", "lsf_mesh_components.hip", "lsf_mesh_smooth.hip", "lsf_esdf.hip", "lsf_icp.hip", "lsf_depth_pyramid.hip", "lsf_depth_confidence.hip",
            "lsf_intensity_pyramid.hip", "lsf_point_sdf.hip", "lsf_volume_shift.hip", "lsf_volume_bricks.hip",
            "lsf_rgbd.hip", "lsf_relocaliser.hip"]
 HEADERS = ["lsf_device.h", "lsf_slavcheva_terms.h", "lsf_slavcheva_state_taps.h", "lsf_tsdf_typed.h",

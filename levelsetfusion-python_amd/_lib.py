@@ -22,7 +22,7 @@ ABI_VERSION = 4
 # time, and tests/test_cabi_and_host.py checks this constant against the header in the tree -- so editing a struct or
 # a prototype in the header without revisiting the binding fails on the CPU, and a stale or variant .so cannot be
 # called through structures of another shape.
-HEADER_ABI_HASH = "5acbbd3dbae5873f"
+HEADER_ABI_HASH = "d176ab41b23512aa"
 
 ERRORS = {-1: "LSF_ERR_BAD_ARGUMENT", -2: "LSF_ERR_BAD_DIMS", -3: "LSF_ERR_KERNEL_TOO_LONG",
           -4: "LSF_ERR_RCCL_UNAVAILABLE", -5: "LSF_ERR_RCCL_FAILED", -6: "LSF_ERR_NOT_RESIDENT"}
@@ -289,6 +289,29 @@ class MeshComponentsParams(ctypes.Structure):
     """lsf_mesh_components_params: connected components of a mesh (lsf_mesh_components_label, _table, _select, _emit)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "has_normals", "has_colours",
                                               "max_blocks")]
+
+
+MESH_SMOOTH_TILE = 256
+MESH_SMOOTH_SCAN_THREADS = 256
+MESH_SMOOTH_MAX_BLOCKS = 512
+MESH_SMOOTH_MAX_ITEMS = 1 << 27
+MESH_SMOOTH_MAX_SLOTS = 1 << 30
+MESH_SMOOTH_MAX_ITERATIONS = 1000
+MESH_SMOOTH_VERTEX_WORDS = 4
+MESH_SMOOTH_SCALAR_WORDS = 5
+MESH_SMOOTH_RECORD_FIELDS = ("vertices_in", "faces_in", "invalid_vertices", "invalid_faces", "edges", "boundary_edges",
+                             "nonmanifold_edges", "pinned_vertices", "isolated_vertices", "max_degree", "table_overflow",
+                             "nonfinite_out", "zero_normals")
+MESH_SMOOTH_RECORD_WORDS = len(MESH_SMOOTH_RECORD_FIELDS)
+MESH_SMOOTH_BOUNDARIES = {"fixed": 1, "free": 0}
+
+
+class MeshSmoothParams(ctypes.Structure):
+    """lsf_mesh_smooth_params: Taubin smoothing and vertex normals of a mesh (lsf_mesh_smooth_prepare, _run,
+    lsf_mesh_vertex_normals)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("vertex_count", "face_count", "table_slots", "boundary_fixed",
+                                              "fresh_record", "iterations", "max_blocks", "reserved")] + \
+        [("lam", ctypes.c_double), ("mu", ctypes.c_double)]
 
 
 ESDF_UNKNOWN = {"free": 0, "occupied": 1}
@@ -616,6 +639,9 @@ PROTOTYPES = {
     "lsf_mesh_components_table": (ctypes.c_int, [_vp] * 7 + [_i64, _P(MeshComponentsParams), _vp]),
     "lsf_mesh_components_select": (ctypes.c_int, [_vp] * 5 + [_i64, _P(MeshComponentsParams), _vp]),
     "lsf_mesh_components_emit": (ctypes.c_int, [_vp] * 11 + [_i64, _i64, _i64, _P(MeshComponentsParams), _vp]),
+    "lsf_mesh_smooth_prepare": (ctypes.c_int, [_vp] * 9 + [_P(MeshSmoothParams), _vp]),
+    "lsf_mesh_smooth_run": (ctypes.c_int, [_vp] * 7 + [_P(MeshSmoothParams), _vp]),
+    "lsf_mesh_vertex_normals": (ctypes.c_int, [_vp] * 6 + [_P(MeshSmoothParams), _vp]),
     "lsf_esdf_compute": (ctypes.c_int, [_vp] * 8 + [_P(EsdfParams), _vp]),
     "lsf_volume_shift": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(VolumeShiftParams), _vp]),
     "lsf_volume_bricks_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(VolumeBricksParams), _vp]),

@@ -83,6 +83,35 @@ min_component_faces=, keep_largest_components=) and the same keywords of Sequenc
 last, after include_streamed, weld and simplify_cell, and add the record to mesh_record / mesh_records under
 "components"; with both None the calls are as they were.  An unwelded seam of streamed meshes splits a component, so
 weld=True is what one wants with them.  Cost: profiles/mesh_components_cost.md.
+smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", recompute_normals=True) removes the surface noise
+that marching cubes copies out of a TSDF fused from real depth, and mesh_vertex_normals(mesh) gives the area-weighted
+vertex normals of any mesh in that layout from its faces alone (INTEGRATION.md section 3, "Mesh smoothing";
+tests/mesh_smooth_restatement.py restates it; csrc/lsf_mesh_smooth.hip).  An iteration is a pass with weight lam and,
+unless mu is 0, a pass with weight mu: Taubin's lambda | mu, which keeps the volume that plain Laplacian passes (mu=0.0)
+lose.  Edges: every face contributes its corner pairs (0,1), (1,2), (2,0); a pair with equal ends is skipped, every
+other pair adds 1 to the face count of its undirected edge.  Two vertices are neighbours when an edge joins them; d(i)
+is the number of distinct neighbours of vertex i.  With boundary="fixed" the ends of every edge whose face count is not
+2 -- open borders, the seams of streamed chunks, non-manifold edges -- are pinned, with "free" none is; a pinned vertex
+and a vertex with d = 0 keep their position bit for bit through every pass, so weld=True closes a seam after smoothing
+as before.  One pass with weight w: B is the largest |coordinate| of the pass's input (an integer maximum on the float
+bits), e = max(E, 1) - 126 with E the exponent field of B's bits, so that B < 2^e, q = 2^(e-32) and q = 1 when B = 0;
+Q(x) = (int64) rint(double(x) / q), ties to even, 0 for a non-finite x; S_i is the sum of Q(p_j) over the neighbours,
+per axis, in integers, so no order of the sum can matter; m = (double(S_i) * q) / double(d(i)); p_i' = float32(double(p_i)
++ w * (m - double(p_i))), every float64 operation rounded on its own.  Positions are float32 between passes and every
+pass takes B from its own input.  Vertex count and order, faces and colours are unchanged; iterations=0 returns the
+positions bit for bit.  Normals: every face (a, b, c) adds c = (p_b - p_a) x (p_c - p_a), computed in float64 and
+quantised to (int64) rint(c / qn) with qn = 2^(em-32), M < 2^em the largest |component| of any face, to its three
+vertices by integer atomics; the normal is float32(S / L) with L = sqrt((S_x^2 + S_y^2) + S_z^2), and (0, 0, 0) when L
+= 0, which the record counts.  It is the right-hand normal, extract_mesh's "towards larger tsdf".  smooth_mesh rebuilds
+the normals of a mesh that has them from the smoothed faces unless recompute_normals=False, which carries them bit for
+bit.  The outputs equal the restatement bit for bit at any launch shape and table size.  ValueError before any launch:
+iterations not a whole number in 0 .. 1000, lam not finite or outside (0, 1], mu not finite or > 0, a boundary other
+than the two names, a layout that is none of extract_mesh's; after the one read of the 13-word record: a non-finite
+vertex or a face index outside [0, V) (return_record=True reads the record a second time and returns it).
+CanonicalVolume.extract_mesh(..., smooth_iterations=, smooth_boundary="fixed") and the same keywords of
+SequenceFusion3d.extract_mesh smooth with the default lambda and mu after simplify_cell / weld and before the component
+filter, which stays last, rebuild the normals with normals=True and add the record to mesh_record / mesh_records under
+"smooth"; with None the calls are as they were.  Cost: profiles/mesh_smooth_cost.md.
 CanonicalVolume.esdf(voxel_size, max_distance_voxels=32, iso=0, min_weight=0, unknown="free", nearest=False) answers
 "how far is this voxel from the nearest surface?", which the model's own values do not: they are projective distances
 along the pixel's ray, truncated at +-1 (INTEGRATION.md section 3, "Euclidean distance field";
@@ -263,7 +292,8 @@ or with icp_iterations summing to > 0 in "icp" mode; in "raycast" and "icp" mode
 count), the non-rigid optimize()'s own (when one is given), and one read of
 the fusion record.  CanonicalVolume.extract_mesh (and SequenceFusion3d.extract_mesh) costs one: the read of the
 vertex and face totals; simplify_cell= and weld= add one each, the read of the simplification's record, min_component_faces= /
-keep_largest_components= two, the reads of the components' record.  A moving
+keep_largest_components= two, the reads of the components' record, smooth_iterations= one, the read of the smoothing's
+record.  A moving
 volume's policy adds none (the twist is on the host already); a shift that streams
 costs extract_mesh's one per leaving box, at most three, and the chunks' copies to the host; a shift with a brick
 store costs one, the read of the brick total, and the copies of the gathered rows to the host and of the re-entering
@@ -288,7 +318,8 @@ image in the prediction, for the RGB-D sensor fisheye and thin-prism lens models
 camera, hole filling, time synchronisation of the two streams, rolling shutter and the reference's XML calibration
 files, marching squares for 2-D models, vertex attributes beyond normals and
 colours, for mesh simplification quadric-error placement of the new vertices, a target face count, welding within a
-tolerance across seams that later frames have moved and per-face attributes, for mesh components edge-adjacency
+tolerance across seams that later frames have moved and per-face attributes, for mesh smoothing cotangent weights, bilateral or
+feature-preserving smoothing, a user pin mask and smoothing the TSDF itself, for mesh components edge-adjacency
 instead of vertex-adjacency, per-component area or volume and components of the volume itself, a mesh extracted without the host read of
 its totals, for the Euclidean distance field an incremental update after a fusion or a shift, a 2-D slice call,
 sub-voxel site positions, z-slab and multi-GPU volumes and feeding the trackers or the level-set term from the field,
@@ -305,6 +336,7 @@ from .canonical_volume import CanonicalVolume
 from .depth_confidence import DepthConfidence
 from .mesh_components import filter_mesh_components, mesh_components
 from .mesh_simplify import simplify_mesh
+from .mesh_smooth import mesh_vertex_normals, smooth_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality
 from .rgbd_sensor import RgbdSensor
@@ -313,6 +345,7 @@ from .sequence import DIRECT_TRACKING_MODES, TRACKING_MODES, TRACKING_REFERENCES
 __all__ = ["CanonicalVolume", "SequenceFusion3d", "DepthConfidence", "MovingVolume", "BrickStore", "RgbdSensor",
            "Relocaliser", "TrackingQuality",
            "merge_meshes", "simplify_mesh", "mesh_components", "filter_mesh_components",
+           "smooth_mesh", "mesh_vertex_normals",
            "unpack_record", "unpack_weighted_record",
            "unpack_colour_record", "unpack_warped_record", "RECORD_FIELDS", "WEIGHTED_RECORD_FIELDS",
            "COLOUR_RECORD_FIELDS", "WARPED_RECORD_FIELDS", "ESDF_RECORD_FIELDS", "unpack_esdf_record",

@@ -5,8 +5,8 @@ import math
 import numpy as np
 import torch
 
-from .. import (device_esdf, device_fusion, device_mesh, device_mesh_components, device_mesh_simplify, device_raycast, device_volume_bricks,
-                device_volume_shift)
+from .. import (device_esdf, device_fusion, device_mesh, device_mesh_components, device_mesh_simplify,
+                device_mesh_smooth, device_raycast, device_volume_bricks, device_volume_shift)
 from ..device_core import require_gpu
 from ..rigid_opt.frame_tracker import device_colour_image
 from ..tsdf.generation import device_depth, offsets_of
@@ -59,6 +59,17 @@ def components_filtered(out, normals, colours, min_component_faces, keep_largest
     v, f, n, c, record = device_mesh_components.filter(out[0], out[1], out[2] if normals else None,
                                                        out[3] if colours else None, min_faces=min_component_faces,
                                                        keep_largest=keep_largest_components)
+    return ((v, f, n, c) if colours else (v, f, n)), record
+
+
+def smoothed(out, normals, colours, smooth_iterations, smooth_boundary):
+    """device_mesh.extract_mesh's tuple after smooth_iterations Taubin iterations with the default lambda and mu (None:
+    as it is), its normals rebuilt from the smoothed faces when they were asked for, and the record or None"""
+    if smooth_iterations is None:
+        return out, None
+    v, f, n, c, record = device_mesh_smooth.smooth(out[0], out[1], out[2] if normals else None,
+                                                   out[3] if colours else None, smooth_iterations,
+                                                   boundary=smooth_boundary)
     return ((v, f, n, c) if colours else (v, f, n)), record
 
 
@@ -151,7 +162,8 @@ class CanonicalVolume:
 
     def extract_mesh(self, array_offset, voxel_size=0.004, iso=0.0, min_weight=0.0, normals=False, as_tensor=False,
                      colours=False, default_colour=device_mesh.DEFAULT_COLOUR, simplify_cell=None,
-                     min_component_faces=None, keep_largest_components=None):
+                     min_component_faces=None, keep_largest_components=None, smooth_iterations=None,
+                     smooth_boundary="fixed"):
         """the level set iso of the model as a triangle mesh, with raycast's conventions (voxel (i, j, k) at
         ((k, j, i) + array_offset) * voxel_size): float32 vertices (V, 3) in world metres, (x, y, z); int32 faces
         (F, 3), their right-hand normal towards larger tsdf; with normals=True also the float32 unit normals (V, 3).
@@ -166,7 +178,12 @@ class CanonicalVolume:
         filter_mesh_components(mesh, min_faces=min_component_faces, keep_largest=keep_largest_components) without the
         copies, for two more host synchronisations; `mesh_record` then is a dict that holds the simplification's fields,
         if that ran, and the components' record under "components".  With both None the call and `mesh_record` are as
-        they were."""
+        they were.
+        smooth_iterations runs that many Taubin iterations after simplify_cell and before the component filter, which
+        stays last: smooth_mesh(mesh, smooth_iterations, boundary=smooth_boundary) with the default lambda and mu and
+        without the copies, the normals rebuilt from the smoothed faces with normals=True, for one more host
+        synchronisation; `mesh_record` then is such a dict with the smoothing's record under "smooth".  With None the
+        call, its launches and `mesh_record` are as they were."""
         if len(self.shape) != 3:
             raise ValueError("mesh extraction needs a 3-D model, this one has shape %s" % (self.shape,))
         if colours and self.colour is None:
@@ -174,6 +191,9 @@ class CanonicalVolume:
         out = device_mesh.extract_mesh(self.tsdf, self.weight, array_offset, voxel_size, iso, min_weight, normals,
                                        *((self.colour, default_colour) if colours else ()))
         out, self.mesh_record = simplified(out, normals, colours, simplify_cell)
+        out, record = smoothed(out, normals, colours, smooth_iterations, smooth_boundary)
+        if record is not None:
+            self.mesh_record = dict(self.mesh_record or {}, smooth=record)
         out, record = components_filtered(out, normals, colours, min_component_faces, keep_largest_components)
         if record is not None:
             self.mesh_record = dict(self.mesh_record or {}, components=record)

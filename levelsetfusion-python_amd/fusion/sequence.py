@@ -16,10 +16,11 @@ from ..rigid_opt.sdf_2_sdf_optimizer3d import unpack_record as unpack_rigid_reco
 from .._lib import DEPTH_F32
 from ..tsdf.generation import DepthCamera, device_depth
 from .brick_store import BrickStore
-from .canonical_volume import CanonicalVolume, components_filtered, mesh_outputs, simplified
+from .canonical_volume import CanonicalVolume, components_filtered, mesh_outputs, simplified, smoothed
 from .depth_confidence import DepthConfidence
 from .mesh_components import filter_mesh_components
 from .mesh_simplify import simplify_mesh
+from .mesh_smooth import smooth_mesh
 from .moving_volume import MovingVolume, merge_meshes
 from .relocaliser import Relocaliser, TrackingQuality, level_stride
 from .rgbd_sensor import RgbdSensor
@@ -410,7 +411,8 @@ class SequenceFusion3d:
 
     def extract_mesh(self, iso=0.0, min_weight=0.0, normals=False, as_tensor=False, colours=False,
                      default_colour=device_mesh.DEFAULT_COLOUR, include_streamed=False, simplify_cell=None, weld=False,
-                     min_component_faces=None, keep_largest_components=None):
+                     min_component_faces=None, keep_largest_components=None, smooth_iterations=None,
+                     smooth_boundary="fixed"):
         """CanonicalVolume.extract_mesh of the model with the sequence's array_offset and voxel_size.  With
         include_streamed (a sequence made with a moving_volume that streams) the window's mesh is followed by the
         streamed chunks, merge_meshes of them all: host arrays only, and only as the chunks were made -- iso 0, the
@@ -425,7 +427,11 @@ class SequenceFusion3d:
         keep_largest_components remove floaters last, after include_streamed, weld and simplify_cell, on every path
         (filter_mesh_components with min_faces and keep_largest); `mesh_records` then also has "components", that
         step's record.  An unwelded seam of streamed meshes splits a component in two, so with include_streamed on a
-        moving_volume that streams meshes weld=True is what one wants with them."""
+        moving_volume that streams meshes weld=True is what one wants with them.  smooth_iterations runs that many
+        Taubin iterations (smooth_mesh with the default lambda and mu and boundary=smooth_boundary) after weld and
+        simplify_cell and before the component filter, on every path, the normals rebuilt when the mesh has them;
+        `mesh_records` then also has "smooth".  With "fixed" an unwelded seam stays bit for bit in place, so welding
+        afterwards still closes it; welded first, the seam is smoothed like the rest."""
         self.mesh_records = dict(weld=None, simplify=None)
         floaters = dict(min_faces=min_component_faces, keep_largest=keep_largest_components)
         filtering = min_component_faces is not None or keep_largest_components is not None
@@ -436,11 +442,13 @@ class SequenceFusion3d:
         if not include_streamed:
             out = self.canonical.extract_mesh(self.array_offset, self.voxel_size, iso, min_weight, normals, as_tensor,
                                               colours, default_colour, simplify_cell, min_component_faces,
-                                              keep_largest_components)
+                                              keep_largest_components, smooth_iterations, smooth_boundary)
             record = self.canonical.mesh_record
-            if filtering:
+            if filtering or smooth_iterations is not None:
                 record = dict(record)  # the volume keeps its own
-                self.mesh_records["components"] = record.pop("components")
+                for step in ("smooth", "components"):
+                    if step in record:
+                        self.mesh_records[step] = record.pop(step)
                 record = record or None
             self.mesh_records["simplify"] = record
             return out
@@ -451,6 +459,9 @@ class SequenceFusion3d:
             out = device_mesh.extract_mesh(tsdf, weight, offset, self.voxel_size, iso, min_weight, normals,
                                            *((colour, default_colour) if colours else ()))
             out, self.mesh_records["simplify"] = simplified(out, normals, colours, simplify_cell)
+            out, record = smoothed(out, normals, colours, smooth_iterations, smooth_boundary)
+            if record is not None:
+                self.mesh_records["smooth"] = record
             out, record = components_filtered(out, normals, colours, min_component_faces, keep_largest_components)
             if filtering:
                 self.mesh_records["components"] = record
@@ -471,6 +482,9 @@ class SequenceFusion3d:
             *merged, self.mesh_records["weld"] = simplify_mesh(merged, return_record=True)
         if simplify_cell is not None:
             *merged, self.mesh_records["simplify"] = simplify_mesh(tuple(merged), simplify_cell, return_record=True)
+        if smooth_iterations is not None:
+            *merged, self.mesh_records["smooth"] = smooth_mesh(tuple(merged), smooth_iterations,
+                                                               boundary=smooth_boundary, return_record=True)
         if filtering:
             *merged, self.mesh_records["components"] = filter_mesh_components(tuple(merged), return_record=True,
                                                                               **floaters)
